@@ -68,7 +68,21 @@ def parse():
                     help="with --gpus N > 1: also time FLUX.2-klein tensor-parallel over the N GPUs (all ranks take part)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / barrier / max-over-ranks plumbing only (gloo, no GPU, no engine): the CPU test of --gpus N")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed decode call returned (its greedy tokens) and the logits of its last "
+                         "step as DIR/tokens.npy (float64) and DIR/logits.npy (float32; per rank's vocabulary shard, logits_rank<r>.npy, at N > 1)")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, rank, world, tokens, logits):
+    """--dump-outputs: the timed path's outputs, for comparing two builds output for output.  The same arguments give the same synthetic
+    weights (engine.Model.synth_weights' fixed seed) and the same prompt, so the inputs are identical from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if rank == 0:
+        np.save(os.path.join(out_dir, "tokens.npy"), np.asarray(tokens, dtype=np.float64))     # (token ids are exact in float64)
+    name = "logits.npy" if world == 1 else f"logits_rank{rank}.npy"
+    np.save(os.path.join(out_dir, name), np.asarray(logits, dtype=np.float32))
 
 
 def self_launch(args):
@@ -636,10 +650,11 @@ def main():
     # the reference's protocol is 3 runs, mean +- sigma (mistral-mlx/examples/benchmark_mistral.rs:62-105): `value` stays the first
     # window of exactly K steps; two more windows of K steps each (the context keeps growing) give the spread
     window_tok_s = [args.steps / elapsed]
+    last_toks = toks
     for _ in range(N_WINDOWS - 1):
         barrier()
         t0 = time.perf_counter()
-        model.decode(args.steps)
+        last_toks = model.decode(args.steps)
         barrier()
         w = time.perf_counter() - t0
         if os.environ.get("OMX_BENCH_DEBUG") == "1":
@@ -651,6 +666,8 @@ def main():
         window_tok_s.append(args.steps / w)
     if peer is not None and peer.aborted():   # a wait inside the peer all-reduce gave up: the tokens of this run are void
         raise SystemExit(f"rank {rank}: the peer-store all-reduce gave up waiting for a peer during the run; no valid measurement")
+    if args.dump_outputs:     # (before anything below runs further decode steps on the model)
+        dump_outputs(args.dump_outputs, rank, world, last_toks, model.last_logits())
 
     # collective secondaries (collective_plan): every rank takes part, rank 0 reports.  The primary model is closed first: Mixtral's
     # shard (93 GB / world + replicated attention) must fit next to nothing else of this size

@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -58,3 +60,36 @@ def test_flagless_multi_gpu_command_covers_all_three_workloads():
     import bench
     class A: no_flux = False; model = "qwen3-8b"
     assert bench.collective_plan(A, 3) == {"secondary": "tp3"} and bench.collective_plan(A, 8) == {"secondary": "tp8", "mixtral": "ep8"}
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    import numpy as np
+    import bench
+    toks = np.array([3, 151935, 7], dtype=np.uint32)
+    logits = np.linspace(-2, 2, 11, dtype=np.float32)
+    bench.dump_outputs(str(tmp_path / "one"), 0, 1, toks, logits)
+    t, lg = np.load(tmp_path / "one" / "tokens.npy"), np.load(tmp_path / "one" / "logits.npy")
+    assert t.dtype == np.float64 and t.tolist() == [3, 151935, 7]
+    assert lg.dtype == np.float32 and np.array_equal(lg, logits)
+    # at N > 1 every rank writes its own vocabulary shard, rank 0 the tokens
+    bench.dump_outputs(str(tmp_path / "two"), 1, 2, toks, logits[:5])
+    assert sorted(os.listdir(tmp_path / "two")) == ["logits_rank1.npy"]
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_steps(tmp_path):
+    """--dump-outputs on the real decode path (2 layers, short prompt): the tokens of the last timed window, and logits of its last
+    step on which that window's last greedy token is a maximum; a second run with the same arguments dumps the same arrays."""
+    import numpy as np
+    flags = ("--steps", "6", "--warmup", "2", "--prompt", "64", "--layers", "2", "--no-flux", "--no-cpu-baseline")
+    dumps = []
+    for i in range(2):
+        rc, lines, err = _run(*flags, "--dump-outputs", str(tmp_path / str(i)))
+        assert rc == 0, err[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 6 and out["ms_per_step"] > 0
+        dumps.append((np.load(tmp_path / str(i) / "tokens.npy"), np.load(tmp_path / str(i) / "logits.npy")))
+    toks, logits = dumps[0]
+    assert toks.dtype == np.float64 and toks.shape == (6,) and logits.dtype == np.float32 and logits.shape == (151936,)
+    assert logits[int(toks[-1])] == logits.max()
+    assert np.array_equal(dumps[1][0], toks) and np.array_equal(dumps[1][1], logits)
