@@ -281,6 +281,15 @@ int omx_dequantize(void* out, const void* packed, const void* scales, const void
  * M <= 16 streams the packed weights (GEMV), larger M dequantises into the library workspace and runs the MFMA GEMM */
 int omx_quantized_matmul(void* out, const void* x, const void* packed, const void* scales, const void* biases, int M, int N,
                          int K, int group_size, int bits, omx_dtype dtype, omx_stream stream);
+/* the compute-bound quantized Linear (qgemm.hip): out [M, N] = x [M, K] . dequant(W)^T with W dequantised INSIDE the matrix-core
+ * kernel (no bf16 copy of W); bf16 x / out / scales / biases, bits 4 or 8, group 32 / 64 / 128, K % 64 == 0, any M >= 1.  Each output
+ * equals omx_dequantize followed by the 16x16x32 bf16 GEMM (omx_linear with OMX_GEMM_TILE=256 OMX_GEMM_MFMA=16) bit for bit.
+ * resid == gate == NULL: plain; both set: out = bf16(resid + acc * gate[col]) (the DiT's gated residual, klein_model.rs:909-925) */
+int omx_quantized_linear_mfma(void* out, const void* x, const void* packed, const void* scales, const void* biases, const void* resid,
+                              const void* gate, int M, int N, int K, int group_size, int bits, omx_stream stream);
+/* omx_linear_swiglu on packed weights: W = [n_plain | half gate | half up] rows; same width rules (n_plain % 4, half % 4, K % 64) */
+int omx_quantized_linear_swiglu(void* out_plain, void* out_act, const void* x, const void* packed, const void* scales, const void* biases,
+                                int M, int n_plain, int half, int K, int group_size, int bits, omx_stream stream);
 /* out [n_rows, N]: row i = x[i / x_div] . dequant(W[rhs_indices[i]])^T over expert-stacked packed weights
  * [n_experts, N, K*bits/32] (QuantizedSwitchLinear::apply, mixtral-mlx/src/model.rs:195-201)                */
 int omx_gather_qmm(void* out, const void* x, const void* packed, const void* scales, const void* biases,
@@ -409,6 +418,15 @@ int omx_klein_destroy(omx_klein m);
 /* `nbytes`: length of the tensor behind `ptr`; every use checks it against the rows x columns it is about to read */
 int omx_klein_set_weight(omx_klein m, const char* name, const void* ptr, size_t nbytes);
 int omx_klein_synth_weights(omx_klein m, uint32_t base_seed);   /* under TP: this rank's shards of the same logical tensors */
+/* quantized DiT (flux-klein-mlx/src/klein_quantized.rs): a Linear's weight as an MLX packed triplet -- packed u32 [rows, cols*bits/32],
+ * bf16 scales / biases [rows, cols/group_size] -- under the `.weight` name omx_klein_set_weight takes (the caller keeps the memory).
+ * bits 4 / 8, group 32 / 64 / 128, cols % group_size == 0; tp_size 1 only.  A model may mix bf16 and packed Linears. */
+int omx_klein_set_quantized_weight(omx_klein m, const char* name, const void* packed, const void* scales, const void* biases, int rows,
+                                   int cols, int group_size, int bits);
+/* QuantizedFluxKlein::from_unquantized (klein_quantized.rs:498): every bf16 Linear weight registered so far becomes a model-owned
+ * packed triplet (omx_quantize); the norms stay bf16.  The forward never reads the bf16 Linear pointers again; synthetic ones are freed. */
+int omx_klein_quantize(omx_klein m, int group_size, int bits);
+int omx_klein_weight_bytes(omx_klein m, size_t* bytes);   /* device bytes of the tensors the forward reads */
 /* comm: ncclComm_t, allreduce_fn: address of ncclAllReduce (RCCL); one bf16 all-reduce after every row-split
  * projection (2 per double-block stream, 1 per single block) */
 int omx_klein_set_comm(omx_klein m, void* comm, void* allreduce_fn);

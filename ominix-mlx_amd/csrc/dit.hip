@@ -21,6 +21,9 @@
 #include <vector>
 
 #include "gemm.hpp"
+#include "qgemm.hpp"
+#include "quant.hpp"
+#include "workspace.hpp"
 
 namespace omx {
 namespace {
@@ -147,6 +150,10 @@ struct omx_klein_ {
     omx_klein_config cfg;
     std::map<std::string, const bf16_t*> w;
     std::map<std::string, size_t> wbytes;      // size of every registered tensor (omx_klein_set_weight / the synthetic generator)
+    // packed Linears (klein_quantized.rs): a name lives in `w` (bf16) or here, never in both
+    struct QLin { QWeight q; int rows, cols; size_t bytes; };
+    std::map<std::string, QLin> qw;
+    bool qgemm = true;                          // OMX_KLEIN_QGEMM (read by every forward; 0 = dequantise into scratch + bf16 kernel)
     std::vector<void*> owned;
     hipStream_t stream = nullptr;      // the stream helpers launch on (switched to stream_txt for the txt half of a double block)
     hipStream_t stream_main = nullptr, stream_txt = nullptr;
@@ -189,10 +196,68 @@ int kalloc(omx_klein m, T** p, size_t n) {
     return 0;
 }
 
+// the packed triplet registered under `name` (null: a bf16 Linear), checked against the [N, K] this forward reads
+int kget_q(omx_klein m, const std::string& name, const omx_klein_::QLin** out, int N, int K) {
+    *out = nullptr;
+    auto it = m->qw.find(name);
+    if (it == m->qw.end()) return 0;
+    OMX_REQUIRE(it->second.rows == N && it->second.cols == K, "ShapeMismatch: %s is a packed [%d, %d], this forward reads [%d, %d]", name.c_str(),
+                it->second.rows, it->second.cols, N, K);
+    OMX_REQUIRE(m->cfg.tp_size == 1 && m->allreduce == nullptr, "omx_klein: packed weights with tensor parallelism are not supported (%s)", name.c_str());
+    *out = &it->second;
+    return 0;
+}
+
+// OMX_KLEIN_QGEMM=0: the A/B route -- each packed matrix dequantised into the stream's scratch right before the bf16 kernel
+int dequant_scratch(omx_klein m, const omx_klein_::QLin& q, const bf16_t** w) {
+    void* ws = nullptr;
+    if (get_workspace_aux(&ws, (size_t)q.rows * q.cols * 2, m->stream)) return 1;
+    if (launch_dequantize_bf16((bf16_t*)ws, q.q.w, q.q.scales, q.q.biases, q.rows, q.cols, q.q.group, q.q.bits, false, m->stream)) return 1;
+    *w = (const bf16_t*)ws;
+    return 0;
+}
+
+// a packed Linear: M <= 16 rows on the packed GEMV (omx_quantized_matmul) where it takes the shape, else the packed-weight MFMA GEMM;
+// resid / gate: the gated residual epilogue
+int qlinear(omx_klein m, bf16_t* out, const bf16_t* x, const omx_klein_::QLin& q, const bf16_t* resid, const bf16_t* gate, int M, int N, int K) {
+    if (!gate && M <= 16 && K % 512 == 0)
+        return omx_quantized_matmul(out, x, q.q.w, q.q.scales, q.q.biases, M, N, K, q.q.group, q.q.bits, OMX_BFLOAT16, m->stream);
+    if (!m->qgemm) {
+        const bf16_t* w = nullptr;
+        if (dequant_scratch(m, q, &w)) return 1;
+        if (gate) return launch_gemm_bf16_gated(out, x, w, resid, gate, M, N, K, m->stream);
+        return omx_linear(out, x, w, nullptr, M, N, K, OMX_BFLOAT16, m->stream);
+    }
+    return launch_qgemm(out, x, q.q, resid, gate, M, N, K, m->stream);
+}
+
 int linear(omx_klein m, bf16_t* out, const bf16_t* x, const char* wname, int M, int N, int K) {
+    const omx_klein_::QLin* q = nullptr;
+    if (kget_q(m, wname, &q, N, K)) return 1;
+    if (q) return qlinear(m, out, x, *q, nullptr, nullptr, M, N, K);
     const bf16_t* w = nullptr;
     if (kget(m, wname, &w, (size_t)N * K)) return 1;
     return omx_linear(out, x, w, nullptr, M, N, K, OMX_BFLOAT16, m->stream);
+}
+
+// W = [n_plain | gate | up] rows with the SwiGLU epilogue (launch_gemm_bf16_swiglu); `name` may be bf16 or packed
+int swiglu_projection(omx_klein m, bf16_t* out_plain, int ld_plain, bf16_t* out_act, int ld_act, const bf16_t* x, const std::string& name,
+                      int M, int n_plain, int half, int K) {
+    const omx_klein_::QLin* q = nullptr;
+    const bf16_t* w = nullptr;
+    if (kget_q(m, name, &q, n_plain + 2 * half, K)) return 1;
+    if (q && m->qgemm) return launch_qgemm_swiglu(out_plain, ld_plain, out_act, ld_act, x, q->q, M, n_plain, half, K, m->stream);
+    if (q) {
+        if (dequant_scratch(m, *q, &w)) return 1;
+    } else if (kget(m, name, &w, (size_t)(n_plain + 2 * half) * K)) {
+        return 1;
+    }
+    return launch_gemm_bf16_swiglu(out_plain, ld_plain, out_act, ld_act, x, w, M, n_plain, half, K, m->stream);
+}
+
+// does the forward take the SwiGLU-epilogue launch for this projection (the packed kernel serves every shape)
+bool swiglu_fused(omx_klein m, const std::string& name, int M, int n_plain, int half, int K) {
+    return (m->qgemm && m->qw.count(name)) || gemm_swiglu_preferred(M, n_plain, half, K);
 }
 
 int ensure_buffers(omx_klein m, int s_txt, int s_img) {
@@ -222,9 +287,14 @@ int attention(omx_klein m, bf16_t* out, int64_t o_ts, const bf16_t* q, const bf1
 
 // out = resid + gate * (x . W^T): one fused GEMM on a single GPU; under tensor parallelism W holds this rank's
 // input columns, the bf16 partial is all-reduced (RCCL sum) and the gated residual is applied afterwards
-int gated_projection(omx_klein m, bf16_t* out, const bf16_t* x, const bf16_t* w, const bf16_t* resid, const bf16_t* gate,
+int gated_projection(omx_klein m, bf16_t* out, const bf16_t* x, const std::string& wname, const bf16_t* resid, const bf16_t* gate,
                      int M, int N, int K) {
     hipStream_t s = m->stream;
+    const omx_klein_::QLin* q = nullptr;
+    if (kget_q(m, wname, &q, N, K)) return 1;
+    if (q) return qlinear(m, out, x, *q, resid, gate, M, N, K);
+    const bf16_t* w = nullptr;
+    if (kget(m, wname, &w, (size_t)N * K)) return 1;
     if (m->cfg.tp_size == 1 && m->allreduce == nullptr) return launch_gemm_bf16_gated(out, x, w, resid, gate, M, N, K, s);
     OMX_REQUIRE(m->allreduce != nullptr, "tp_size > 1 but no communicator set (omx_klein_set_comm)");
     if (launch_gemm_bf16(m->partial, x, w, nullptr, M, N, K, s)) return 1;
@@ -285,6 +355,7 @@ int omx_klein_set_weight(omx_klein m, const char* name, const void* ptr, size_t 
     OMX_REQUIRE(nbytes > 0 && nbytes % 2 == 0, "omx_klein_set_weight: %s: %zu bytes is not a bf16 tensor", name, nbytes);
     m->w[name] = (const bf16_t*)ptr;
     m->wbytes[name] = nbytes;
+    m->qw.erase(name);
     return 0;
 }
 
@@ -292,6 +363,111 @@ int omx_klein_set_comm(omx_klein m, void* comm, void* allreduce_fn) {
     OMX_REQUIRE(m, "omx_klein_set_comm: null model");
     m->comm = comm;
     m->allreduce = (nccl_allreduce_fn)allreduce_fn;
+    return 0;
+}
+
+namespace {
+// the in-features of a Linear weight of the DiT by its name (rows follow from the registered bytes); 0: not a Linear (the q / k RmsNorms)
+int klein_linear_cols(omx_klein m, const std::string& name) {
+    const omx_klein_config& c = m->cfg;
+    const int h = c.hidden_size, hl = m->h_l, mh = m->mh_l;
+    auto ends = [&](const char* suf) { const size_t n = strlen(suf); return name.size() >= n && name.compare(name.size() - n, n, suf) == 0; };
+    if (ends("norm_q.weight") || ends("norm_k.weight")) return 0;
+    if (name == "x_embedder.weight") return c.in_channels;
+    if (name == "context_embedder.weight") return c.txt_embed_dim;
+    if (name == "time_embed_1.weight") return 256;
+    const bool single = name.rfind("single_blocks.", 0) == 0, dbl = name.rfind("double_blocks.", 0) == 0;
+    if (ends("to_out.weight")) return single ? hl + mh : hl;
+    if (dbl && ends("mlp_out.weight")) return mh;
+    return h;   // time_embed_2, the modulations, norm_out, proj_out, q / k / v, mlp_in, to_qkv_mlp
+}
+
+int check_qformat(omx_klein m, const char* who, int cols, int group_size, int bits) {
+    OMX_REQUIRE(m->cfg.tp_size == 1 && m->allreduce == nullptr, "%s: packed weights with tensor parallelism (tp_size %d) are not supported",
+                who, m->cfg.tp_size);
+    return qgemm_check_format(who, cols, group_size, bits);
+}
+
+size_t qbytes(int rows, int cols, int group_size, int bits) {
+    return (size_t)rows * cols * bits / 8 + 2 * (size_t)rows * (cols / group_size) * 2;
+}
+}  // namespace
+
+int omx_klein_set_quantized_weight(omx_klein m, const char* name, const void* packed, const void* scales, const void* biases, int rows,
+                                   int cols, int group_size, int bits) {
+    OMX_REQUIRE(m && name && packed && scales && biases, "omx_klein_set_quantized_weight: null argument");
+    OMX_REQUIRE(rows > 0 && cols > 0, "omx_klein_set_quantized_weight: %s: bad shape [%d, %d]", name, rows, cols);
+    if (check_qformat(m, "omx_klein_set_quantized_weight", cols, group_size, bits)) return 1;
+    OMX_REQUIRE(((reinterpret_cast<uintptr_t>(packed)) & 15u) == 0, "omx_klein_set_quantized_weight: %s: packed words must be 16-byte aligned", name);
+    m->qw[name] = omx_klein_::QLin{QWeight{(const uint32_t*)packed, (const bf16_t*)scales, (const bf16_t*)biases, group_size, bits}, rows, cols,
+                                   qbytes(rows, cols, group_size, bits)};
+    m->w.erase(name);
+    m->wbytes.erase(name);
+    return 0;
+}
+
+int omx_klein_quantize(omx_klein m, int group_size, int bits) {
+    OMX_REQUIRE(m, "omx_klein_quantize: null model");
+    OMX_REQUIRE(m->cfg.tp_size == 1 && m->allreduce == nullptr, "omx_klein_quantize: packed weights with tensor parallelism (tp_size %d) are not supported",
+                m->cfg.tp_size);
+    // check every Linear first: a failure leaves the model as it was
+    std::vector<std::pair<std::string, int>> todo;
+    for (const auto& kv : m->w) {
+        const int cols = klein_linear_cols(m, kv.first);
+        if (cols == 0) continue;
+        if (check_qformat(m, "omx_klein_quantize", cols, group_size, bits)) return 1;
+        const size_t bytes = m->wbytes[kv.first];
+        OMX_REQUIRE(bytes % ((size_t)cols * 2) == 0, "omx_klein_quantize: %s holds %zu bytes, not rows of %d bf16", kv.first.c_str(), bytes, cols);
+        todo.emplace_back(kv.first, cols);
+    }
+    // convert into fresh buffers; only when every matrix succeeded do the maps change (a name stays in `w` or `qw`, never both)
+    std::vector<std::pair<std::string, omx_klein_::QLin>> made;
+    std::vector<void*> bufs;
+    auto convert = [&]() -> int {
+        for (const auto& tc : todo) {
+            const int cols = tc.second, rows = (int)(m->wbytes[tc.first] / ((size_t)cols * 2));
+            const size_t groups = (size_t)rows * (cols / group_size);
+            void *packed = nullptr, *sc = nullptr, *bi = nullptr;
+            OMX_HIP_CHECK(hipMalloc(&packed, (size_t)rows * cols * bits / 8 + 64));
+            bufs.push_back(packed);
+            OMX_HIP_CHECK(hipMalloc(&sc, groups * 2 + 64));
+            bufs.push_back(sc);
+            OMX_HIP_CHECK(hipMalloc(&bi, groups * 2 + 64));
+            bufs.push_back(bi);
+            if (omx_quantize(packed, sc, bi, m->w[tc.first], rows, cols, group_size, bits, OMX_BFLOAT16, m->stream)) return 1;
+            made.emplace_back(tc.first, omx_klein_::QLin{QWeight{(const uint32_t*)packed, (const bf16_t*)sc, (const bf16_t*)bi, group_size, bits},
+                                                         rows, cols, qbytes(rows, cols, group_size, bits)});
+        }
+        OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
+        return 0;
+    };
+    if (convert()) {
+        (void)hipStreamSynchronize(m->stream);
+        for (void* p : bufs) (void)hipFree(p);
+        return 1;
+    }
+    m->owned.insert(m->owned.end(), bufs.begin(), bufs.end());
+    for (const auto& nq : made) {   // the bf16 copies: freed where the model owns them (synthetic weights), forgotten otherwise
+        void* p = (void*)m->w[nq.first];
+        for (size_t i = 0; i < m->owned.size(); ++i)
+            if (m->owned[i] == p) {
+                (void)hipFree(p);
+                m->owned.erase(m->owned.begin() + (long)i);
+                break;
+            }
+        m->w.erase(nq.first);
+        m->wbytes.erase(nq.first);
+        m->qw[nq.first] = nq.second;
+    }
+    return 0;
+}
+
+int omx_klein_weight_bytes(omx_klein m, size_t* bytes) {
+    OMX_REQUIRE(m && bytes, "omx_klein_weight_bytes: null argument");
+    size_t n = 0;
+    for (const auto& kv : m->wbytes) n += kv.second;
+    for (const auto& kv : m->qw) n += kv.second.bytes;
+    *bytes = n;
     return 0;
 }
 
@@ -388,6 +564,8 @@ int omx_klein_forward_with_rope(omx_klein m, void* out, const void* latent, cons
     const omx_klein_config& c = m->cfg;
     if (ensure_buffers(m, s_txt, s_img)) return 1;
     m->stream = m->stream_main;   // an earlier forward that failed inside a txt half may have left the side stream selected
+    const char* qgemm_env = getenv("OMX_KLEIN_QGEMM");
+    m->qgemm = !(qgemm_env && qgemm_env[0] == '0');
     hipStream_t s = m->stream;
     const int h = c.hidden_size, S = s_txt + s_img;
     const int H = m->H_l, hl = m->h_l, mh = m->mh_l;   // this rank's heads / attention width / MLP width
@@ -489,20 +667,17 @@ int omx_klein_forward_with_rope(omx_klein m, void* out, const void* latent, cons
             const bf16_t* mod = st ? m->mod_img : m->mod_txt;
             const int rows = st ? s_img : s_txt;
             const size_t r0 = st ? (size_t)s_txt : 0;
-            if (kget(m, b + sn + "to_out.weight", &w, (size_t)h * hl)) return 1;
-            if (gated_projection(m, x2 + r0 * h, m->att + r0 * hl, w, x + r0 * h, mod + 2 * h /*gate1*/, rows, h, hl)) return 1;
+            if (gated_projection(m, x2 + r0 * h, m->att + r0 * hl, b + sn + "to_out.weight", x + r0 * h, mod + 2 * h /*gate1*/, rows, h, hl)) return 1;
             // ---- MLP half ----
             if (omx_fused_modulate(m->xm + r0 * h, x2 + r0 * h, mod + 3 * h, mod + 4 * h, 1, rows, h, 1e-6f, OMX_BFLOAT16, s)) return 1;
-            if (fuse_act && gemm_swiglu_preferred(rows, 0, mh, h)) {
-                if (kget(m, b + sn + "mlp_in.weight", &w, (size_t)2 * mh * h)) return 1;
-                if (launch_gemm_bf16_swiglu(nullptr, 0, act, mh, m->xm + r0 * h, w, rows, 0, mh, h, s)) return 1;
+            if (fuse_act && swiglu_fused(m, b + sn + "mlp_in.weight", rows, 0, mh, h)) {
+                if (swiglu_projection(m, nullptr, 0, act, mh, m->xm + r0 * h, b + sn + "mlp_in.weight", rows, 0, mh, h)) return 1;
             } else {
                 if (linear(m, proj, m->xm + r0 * h, (b + sn + "mlp_in.weight").c_str(), rows, 2 * mh, h)) return 1;
                 swiglu_strided_kernel<<<2048, 256, 0, s>>>(act, mh, proj /*gate = first half*/, proj + mh /*up*/, 2 * mh, rows, mh);
                 OMX_LAUNCH_CHECK();
             }
-            if (kget(m, b + sn + "mlp_out.weight", &w, (size_t)h * mh)) return 1;
-            if (gated_projection(m, x + r0 * h, act, w, x2 + r0 * h, mod + 5 * h /*gate2*/, rows, h, mh)) return 1;
+            if (gated_projection(m, x + r0 * h, act, b + sn + "mlp_out.weight", x2 + r0 * h, mod + 5 * h /*gate2*/, rows, h, mh)) return 1;
         }
         on_stream(1);
         if (join()) return 1;
@@ -513,10 +688,9 @@ int omx_klein_forward_with_rope(omx_klein m, void* out, const void* latent, cons
         const std::string b = "single_blocks." + std::to_string(i) + ".";
         const bf16_t* mod = m->mod_single;
         if (omx_fused_modulate(m->xm, x, mod, mod + h, 1, S, h, 1e-6f, OMX_BFLOAT16, s)) return 1;
-        const bool fused = fuse_act && gemm_swiglu_preferred(S, 3 * hl, mh, h);
+        const bool fused = fuse_act && swiglu_fused(m, b + "to_qkv_mlp.weight", S, 3 * hl, mh, h);
         if (fused) {   // q/k/v columns -> proj, SwiGLU of the MLP columns straight into comb[:, hl:]
-            if (kget(m, b + "to_qkv_mlp.weight", &w, (size_t)ldp * h)) return 1;
-            if (launch_gemm_bf16_swiglu(m->proj, (int)ldp, m->comb + hl, (int)ldc, m->xm, w, S, 3 * hl, mh, h, s)) return 1;
+            if (swiglu_projection(m, m->proj, (int)ldp, m->comb + hl, (int)ldc, m->xm, b + "to_qkv_mlp.weight", S, 3 * hl, mh, h)) return 1;
         } else if (linear(m, m->proj, m->xm, (b + "to_qkv_mlp.weight").c_str(), S, (int)ldp, h)) return 1;
         const unsigned blocks = (unsigned)(((size_t)S * H + 15) / 16);
         const bf16_t* wkn = nullptr;
@@ -528,8 +702,7 @@ int omx_klein_forward_with_rope(omx_klein m, void* out, const void* latent, cons
             swiglu_strided_kernel<<<2048, 256, 0, s>>>(m->comb + hl, ldc, m->proj + 3 * hl, m->proj + 3 * hl + mh, ldp, S, mh);   // cols [hl, hl+mh)
             OMX_LAUNCH_CHECK();
         }
-        if (kget(m, b + "to_out.weight", &w, (size_t)h * ldc)) return 1;
-        if (gated_projection(m, x2, m->comb, w, x, mod + 2 * h, S, h, (int)ldc)) return 1;
+        if (gated_projection(m, x2, m->comb, b + "to_out.weight", x, mod + 2 * h, S, h, (int)ldc)) return 1;
         bf16_t* t = x; x = x2; x2 = t;
     }
     // final layer: RmsNorm (weight = ones), AdaLN chunks [scale, shift], proj_out (klein_model.rs:845-853)

@@ -1702,6 +1702,7 @@ int ring_splits(int blocks, int nt) {
 // chain: 48 such blocks fit the CUs the img grid leaves idle, 384 tiles of 64^2 queue behind its workgroups)
 static thread_local int g_tile_hint = 0;
 void gemm_tile_hint(int rows) { g_tile_hint = rows; }
+int gemm_tile_hint_get() { return g_tile_hint; }
 // float16 operands / results for this thread's next GEMMs (a float16 checkpoint's prompt pass, engine.hip): the eight-wave kernel's
 // float16 instantiations serve every shape (plain: 256- or 128-row tiles; segmented: 256-row tiles)
 static thread_local bool g_gemm_f16 = false;

@@ -29,6 +29,7 @@ int launch_gemm_bf16_bias_relu(bf16_t* out, const bf16_t* x, const bf16_t* w, co
 // tile preference of this thread's next plain GEMMs (gemm.hip g_tile_hint): 0 none, 128 = the 128 x 256 tile for a GEMM that shares the
 // chip with another stream's grid
 void gemm_tile_hint(int rows);
+int gemm_tile_hint_get();   // this thread's current preference (the packed-weight GEMM, qgemm.hip, honours it too)
 // float16 operands and results for this thread's next GEMMs (the bf16_t pointers then hold float16 bit patterns); a float16
 // checkpoint's batched prompt pass switches it on around its launches
 bool gemm_set_f16(bool on);   // returns the previous state

@@ -7,7 +7,7 @@ import sys
 
 import numpy as np
 
-from . import check, lib, require_device
+from . import BFLOAT16, UINT32, OmxError, check, lib, require_device
 from .ops import Tensor
 
 c_int, c_float, c_void_p, c_uint32, c_size_t = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t
@@ -23,6 +23,9 @@ KLEIN_SIGNATURES = {
     "omx_klein_destroy": (c_int, [c_void_p]),
     "omx_klein_set_weight": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
     "omx_klein_synth_weights": (c_int, [c_void_p, c_uint32]),
+    "omx_klein_set_quantized_weight": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int]),
+    "omx_klein_quantize": (c_int, [c_void_p, c_int, c_int]),
+    "omx_klein_weight_bytes": (c_int, [c_void_p, ctypes.POINTER(c_size_t)]),
     "omx_klein_set_comm": (c_int, [c_void_p, c_void_p, c_void_p]),
     "omx_klein_forward_with_rope": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "omx_klein_euler_step": (c_int, [c_void_p, c_void_p, c_float, c_void_p, ctypes.c_int64, c_void_p]),
@@ -34,6 +37,12 @@ for _n, (_r, _a) in KLEIN_SIGNATURES.items():
     _f.restype, _f.argtypes = _r, _a
 
 AXES_DIM, THETA = (32, 32, 32, 32), 2000.0
+
+
+def is_linear_weight(name: str) -> bool:
+    """The DiT weights QuantizedFluxKlein packs (klein_quantized.rs:498-556): every Linear's `.weight` -- the per-head q / k RmsNorms
+    stay bf16 (`norm_out` is the AdaLN Linear and is packed)."""
+    return name.endswith(".weight") and not name.endswith(("norm_q.weight", "norm_k.weight"))
 
 
 def create_txt_ids(seq_len: int) -> np.ndarray:
@@ -112,6 +121,8 @@ class FluxKlein:
         self._h = c_void_p()
         check(lib.omx_klein_create(ctypes.byref(self._h), ctypes.byref(self.cfg)))
         self._keep = []
+        # weight name -> ("bf16" | "packed", the tensors uploaded for it): what load_weights / load_quantized_weights registered
+        self._keep_of = {}
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h.value:
@@ -130,9 +141,74 @@ class FluxKlein:
         """Logical (unsharded) tensors by the reference's internal names; sliced here under tensor parallelism."""
         weights = shard_state_dict(weights, self.cfg.hidden_size, self.cfg.mlp_hidden, self.cfg.tp_rank, self.cfg.tp_size)
         for name, arr in weights.items():
-            t = Tensor.from_numpy(arr, "bf16")
+            t = arr if isinstance(arr, Tensor) else Tensor.from_numpy(arr, "bf16")   # (a device tensor: single GPU)
             self._keep.append(t)
+            self._keep_of[name] = ("bf16", [t])
             check(lib.omx_klein_set_weight(self._h, name.encode(), t.ptr, t.nbytes))
+
+    def _drop(self, name: str) -> None:
+        ids = {id(t) for t in self._keep_of.pop(name, (None, []))[1]}
+        self._keep = [t for t in self._keep if id(t) not in ids]
+
+    def quantize(self, group_size: int = 64, bits: int = 8) -> None:
+        """QuantizedFluxKlein::from_unquantized(flux, group_size, bits) (klein_quantized.rs:498): every Linear registered so far becomes
+        a model-owned packed triplet; the bf16 copies this object uploaded for them are released.  Triplets registered by
+        load_quantized_weights are already packed: the model keeps reading them, so they stay referenced here."""
+        check(lib.omx_klein_quantize(self._h, group_size, bits))
+        for name in [n for n, (kind, _) in self._keep_of.items() if kind == "bf16" and is_linear_weight(n)]:
+            self._drop(name)
+
+    def load_quantized_weights(self, weights: dict, group_size: int = 64, bits: int = 8) -> None:
+        """A pre-quantized checkpoint under the internal names load_weights takes (what sanitize_klein_quantized_weights produces,
+        weights.rs:599-): `<lin>.weight` packed uint32 [rows, cols * bits / 32] with `<lin>.scales` / `<lin>.biases` [rows, cols / group],
+        and the bf16 norm `.weight`s.  Values are numpy arrays or device Tensors."""
+        if self.cfg.tp_size > 1:
+            raise OmxError("load_quantized_weights: packed weights with tensor parallelism are not supported")
+        if bits not in (4, 8):
+            raise OmxError(f"load_quantized_weights: bits must be 4 or 8 (got {bits})")
+        def dev(a, code, what):
+            if isinstance(a, Tensor):
+                if a.dtype != code:
+                    raise OmxError(f"load_quantized_weights: {what} is a device tensor of dtype {a.dtype}, expected {code}")
+                return a
+            if code == UINT32 and np.asarray(a).dtype != np.uint32:
+                raise OmxError(f"load_quantized_weights: {what} must hold uint32 packed words (got {np.asarray(a).dtype})")
+            return Tensor.from_numpy(a, "u32" if code == UINT32 else "bf16")
+        for name in weights:
+            if not name.endswith((".weight", ".scales", ".biases")):
+                raise OmxError(f"load_quantized_weights: {name}: expected a `.weight`, `.scales` or `.biases` name")
+            if name.endswith((".scales", ".biases")) and name.rsplit(".", 1)[0] + ".weight" not in weights:
+                raise OmxError(f"load_quantized_weights: {name} has no `.weight` beside it")
+        for name, arr in weights.items():
+            if not name.endswith(".weight"):
+                continue
+            base = name[:-len(".weight")]
+            if base + ".scales" not in weights:
+                t = dev(arr, BFLOAT16, name)
+                self._drop(name)
+                self._keep.append(t)
+                self._keep_of[name] = ("bf16", [t])
+                check(lib.omx_klein_set_weight(self._h, name.encode(), t.ptr, t.nbytes))
+                continue
+            if base + ".biases" not in weights:
+                raise OmxError(f"load_quantized_weights: {base}.biases is missing")
+            q = dev(arr, UINT32, name)
+            sc, bi = dev(weights[base + ".scales"], BFLOAT16, base + ".scales"), dev(weights[base + ".biases"], BFLOAT16, base + ".biases")
+            rows, cols = q.shape[0], q.shape[-1] * 32 // bits
+            if (len(q.shape) != 2 or cols % group_size or tuple(sc.shape) != (rows, cols // group_size)
+                    or tuple(bi.shape) != (rows, cols // group_size)):
+                raise OmxError(f"load_quantized_weights: {base}: packed {tuple(q.shape)}, scales {tuple(sc.shape)}, biases {tuple(bi.shape)} "
+                               f"do not form one [{rows}, {cols}] matrix at {bits} bits, group {group_size}")
+            check(lib.omx_klein_set_quantized_weight(self._h, name.encode(), q.ptr, sc.ptr, bi.ptr, rows, cols, group_size, bits))
+            self._drop(name)
+            self._keep += [q, sc, bi]
+            self._keep_of[name] = ("packed", [q, sc, bi])
+
+    def weight_bytes(self) -> int:
+        """Device bytes of the tensors the forward reads (packed words + scales + biases of packed Linears, bf16 tensors)."""
+        v = c_size_t()
+        check(lib.omx_klein_weight_bytes(self._h, ctypes.byref(v)))
+        return v.value
 
     def synth_weights(self, base_seed: int = 0x0C0FFEE5) -> None:
         check(lib.omx_klein_synth_weights(self._h, base_seed & 0xFFFFFFFF))

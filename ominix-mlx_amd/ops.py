@@ -365,6 +365,46 @@ def quantized_matmul(x: Tensor, packed: Tensor, scales: Tensor, biases: Optional
     return out
 
 
+def _packed_k(x: Tensor, packed: Tensor, scales: Tensor, biases: Optional[Tensor], bits: int, who: str) -> int:
+    if bits not in (4, 8):
+        raise OmxError(f"{who}: bits must be 4 or 8 (got {bits})")
+    K = packed.shape[-1] * 32 // bits
+    if x.shape[-1] != K:
+        raise OmxError(f"{who}: input features {x.shape[-1]} != weight in-features {K}")
+    if packed.dtype != UINT32 or x.dtype != BFLOAT16 or scales.dtype != BFLOAT16 or (biases is not None and biases.dtype != BFLOAT16):
+        raise OmxError(f"{who}: bf16 activations, u32 packed words and bf16 scales / biases expected")
+    return K
+
+
+def quantized_linear(x: Tensor, packed: Tensor, scales: Tensor, biases: Optional[Tensor], group_size: int = 64, bits: int = 8,
+                     resid: Optional[Tensor] = None, gate: Optional[Tensor] = None) -> Tensor:
+    """x @ dequant(W)^T on the packed-weight matrix-core GEMM (include/omx.h: omx_quantized_linear_mfma), any number of rows; with
+    resid [M, N] and gate [N]: resid + (x @ dequant(W)^T) * gate (the DiT's gated residual), one rounding."""
+    K = _packed_k(x, packed, scales, biases, bits, "quantized_linear")
+    N = packed.shape[0]
+    out = Tensor(tuple(x.shape[:-1]) + (N,), x.dtype)
+    check(lib.omx_quantized_linear_mfma(out.ptr, x.ptr, packed.ptr, scales.ptr, _p(biases), _p(resid), _p(gate), x.size // K, N, K,
+                                        group_size, bits, None))
+    return out
+
+
+def quantized_linear_swiglu(x: Tensor, packed: Tensor, scales: Tensor, biases: Optional[Tensor], n_plain: int, group_size: int = 64,
+                            bits: int = 8):
+    """linear_swiglu on a packed weight [n_plain | gate | up] (include/omx.h: omx_quantized_linear_swiglu).
+    -> (plain [M, n_plain] or None, act [M, half])."""
+    K = _packed_k(x, packed, scales, biases, bits, "quantized_linear_swiglu")
+    N = packed.shape[0]
+    if (N - n_plain) % 2 or N <= n_plain:
+        raise OmxError(f"quantized_linear_swiglu: {N} weight rows do not split into {n_plain} plain + an even gate/up pair")
+    half = (N - n_plain) // 2
+    M = x.size // K
+    plain = Tensor(tuple(x.shape[:-1]) + (n_plain,), x.dtype) if n_plain else None
+    act = Tensor(tuple(x.shape[:-1]) + (half,), x.dtype)
+    check(lib.omx_quantized_linear_swiglu(_p(plain), act.ptr, x.ptr, packed.ptr, scales.ptr, _p(biases), M, n_plain, half, K, group_size,
+                                          bits, None))
+    return plain, act
+
+
 def gather_qmm(x: Tensor, packed: Tensor, scales: Tensor, biases: Optional[Tensor], rhs_indices: Tensor, x_div: int = 1,
                group_size: int = 64, bits: int = 4) -> Tensor:
     """QuantizedSwitchLinear::apply (mixtral-mlx/src/model.rs:195-201): row i uses expert rhs_indices[i] and

@@ -1,6 +1,7 @@
 """flux-klein-mlx/examples/generate_klein.rs end to end on the MI355X build, with synthetic weights of the real shapes
 (no checkpoints in this environment): Qwen3-4B text encoder (taps 8/17/26 -> 7680) -> FLUX.2-klein DiT, official
-schedule, Euler steps -> latent unpack -> VAE decoder -> PPM.   python tools/generate_klein.py [size] [steps] [out.ppm]"""
+schedule, Euler steps -> latent unpack -> VAE decoder -> PPM.
+    python tools/generate_klein.py [--quantize [4|8]] [size] [steps] [out.ppm]   (--quantize: the DiT packed at group 64, 8-bit by default)"""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -8,9 +9,15 @@ import omx_import
 omx = omx_import.load_package()
 from ominix_mlx_amd import engine, flux_pipeline, klein, vae
 
-size = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
-steps = int(sys.argv[2]) if len(sys.argv) > 2 else 4
-out_path = sys.argv[3] if len(sys.argv) > 3 else None
+argv = sys.argv[1:]
+quantize = 0                                        # generate_klein.rs:53-54, 309-315: --quantize -> from_unquantized(flux, 64, 8)
+if "--quantize" in argv:
+    i = argv.index("--quantize")
+    quantize = int(argv[i + 1]) if i + 1 < len(argv) and argv[i + 1] in ("4", "8") else 8
+    del argv[i:i + (2 if i + 1 < len(argv) and argv[i + 1] in ("4", "8") else 1)]
+size = int(argv[0]) if len(argv) > 0 else 1024
+steps = int(argv[1]) if len(argv) > 1 else 4
+out_path = argv[2] if len(argv) > 2 else None
 T = omx.ops.Tensor
 t0 = time.perf_counter()
 enc = engine.Model(hidden_size=2560, num_hidden_layers=36, intermediate_size=9728, num_attention_heads=32, num_key_value_heads=8,
@@ -18,6 +25,8 @@ enc = engine.Model(hidden_size=2560, num_hidden_layers=36, intermediate_size=972
 enc.synth_weights()
 dit = klein.FluxKlein()
 dit.synth_weights()
+if quantize:
+    dit.quantize(64, quantize)
 dec = vae.VaeDecoder()
 dec.load_weights(vae.random_decoder_weights(1))
 omx.ops.synchronize()
@@ -36,7 +45,7 @@ t = time.perf_counter(); img = dec.decode(T.from_numpy(z.astype(np.float32))); v
 rgb = vae.to_rgb8(img.numpy())
 if out_path:
     vae.write_ppm(out_path, rgb)
-print(json.dumps({"image": f"{size}x{size}", "steps": steps, "model_setup_s": round(load_s, 2), "text_encoder_ms": round(enc_ms, 2),
+print(json.dumps({"image": f"{size}x{size}", "steps": steps, "dit_bits": quantize or 16, "dit_weight_bytes": dit.weight_bytes(), "model_setup_s": round(load_s, 2), "text_encoder_ms": round(enc_ms, 2),
                   "text_encoder_device_ms": round(enc.last_prefill_ms(), 2), "dit_step_ms": step_ms, "denoise_wall_ms": round(den_ms, 2),
                   "vae_ms": round(vae_ms, 2), "vae_device_ms": round(dec.last_ms(), 2),
                   "end_to_end_ms": round(enc_ms + den_ms + vae_ms, 2), "rgb_shape": list(rgb.shape),
