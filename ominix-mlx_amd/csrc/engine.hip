@@ -92,6 +92,31 @@ __global__ __launch_bounds__(256) void qembed_kernel(bf16_t* __restrict__ h, con
     }
 }
 
+// ... 2 / 3 / 5 / 6 bits: one thread per run of 32 elements (BITS words, quant_chunked in quant.hpp), the same element expression
+template <int BITS>
+__global__ __launch_bounds__(256) void qembed_chunk_kernel(bf16_t* __restrict__ h, const uint32_t* __restrict__ w,
+                                                           const bf16_t* __restrict__ scales, const bf16_t* __restrict__ biases,
+                                                           const StepState* st, int hidden, int group, unsigned* seq, float* rope_cur,
+                                                           const float* rope_cos, const float* rope_sin, int half, bool scales_f16) {
+    step_begin(st, seq, rope_cur, rope_cos, rope_sin, half);
+    const size_t row = st->cur_token;
+    const int chunks = hidden / 32;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < chunks; i += gridDim.x * blockDim.x) {
+        uint32_t wd[BITS];
+#pragma unroll
+        for (int k = 0; k < BITS; ++k) wd[k] = w[(row * chunks + i) * BITS + k];
+        const int g = i * 32 / group;
+        const bf16_t sb16 = scales[row * (hidden / group) + g], bb16 = biases ? biases[row * (hidden / group) + g] : (bf16_t)0;
+        const float sc = scales_f16 ? __half2float(__ushort_as_half(sb16)) : bf16_to_f32(sb16);
+        const float bi = scales_f16 ? __half2float(__ushort_as_half(bb16)) : bf16_to_f32(bb16);
+#pragma unroll
+        for (int e = 0; e < 32; ++e) {
+            const float v = (float)qfield<BITS>(wd, e) * sc + bi;
+            h[i * 32 + e] = scales_f16 ? Act16<true>::bits(v) : f32_to_bf16(v);
+        }
+    }
+}
+
 // h = bf16(resid + bf16(all-reduced partial)): the residual of a block whose output arrives as an f32 sum over the ranks
 // (f16: a float16 model -- the same two roundings in float16)
 __global__ void ep_fold_kernel(bf16_t* __restrict__ out, const bf16_t* __restrict__ resid, const float* __restrict__ partial, int64_t n, bool f16 = false) {
@@ -492,8 +517,13 @@ int enqueue_step_quant(omx_qwen3 m, bool with_head) {
     hipStream_t s = m->stream;
     const int hd = c.hidden_size, D = c.head_dim, bits = c.quant_bits, group = c.quant_group;
     const bool sf16 = c.quant_scales_f16 != 0;
+#define OMX_QEMBED_CHUNK(B)                                                                                                          \
+    else if (bits == B) OMX_LAUNCH(qembed_chunk_kernel<B>, 4, 256, 0, s, m->h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->st, hd, group, \
+                                   m->step_seq, m->rope_cur, m->rope_cos, m->rope_sin, D / 2, sf16);
     if (bits == 4) OMX_LAUNCH(qembed_kernel<4>, 4, 256, 0, s, m->h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->st, hd, group, m->step_seq,
                               m->rope_cur, m->rope_cos, m->rope_sin, D / 2, sf16);
+    OMX_QEMBED_CHUNK(2) OMX_QEMBED_CHUNK(3) OMX_QEMBED_CHUNK(5) OMX_QEMBED_CHUNK(6)
+#undef OMX_QEMBED_CHUNK
     else OMX_LAUNCH(qembed_kernel<8>, 4, 256, 0, s, m->h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->st, hd, group, m->step_seq, m->rope_cur,
                     m->rope_cos, m->rope_sin, D / 2, sf16);
     OMX_LAUNCH_CHECK();
@@ -1464,7 +1494,12 @@ int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) {
                     : (c.tp_size % c.num_key_value_heads == 0 &&
                        (c.num_attention_heads / c.num_key_value_heads) % (c.tp_size / c.num_key_value_heads) == 0),
                 "InvalidConfig: %d kv heads cannot be split or replicated over tp_size %d", c.num_key_value_heads, c.tp_size);
-    OMX_REQUIRE(c.quant_bits == 0 || c.quant_bits == 4 || c.quant_bits == 8, "InvalidConfig: quantization bits %d (0 = bf16, 4, 8)", c.quant_bits);
+    OMX_REQUIRE(c.quant_bits == 0 || c.quant_bits == 2 || c.quant_bits == 3 || c.quant_bits == 4 || c.quant_bits == 5 || c.quant_bits == 6 ||
+                    c.quant_bits == 8, "InvalidConfig: quantization bits %d (0 = bf16, 2, 3, 4, 5, 6, 8)", c.quant_bits);
+    // the widths whose packed kernels exist for the dense single-rank model only (no packed expert stacks, no sharded rows / K slices)
+    OMX_REQUIRE(!quant_chunked(c.quant_bits) || (c.num_experts == 0 && c.tp_size <= 1 && c.ep_size <= 1),
+                "InvalidConfig: %d-bit quantization runs on dense single-rank models (num_experts %d, tp_size %d, ep_size %d; experts and "
+                "tensor / expert parallelism take bits 4 or 8)", c.quant_bits, c.num_experts, c.tp_size, c.ep_size);
     // (round 4) quantized checkpoints under tensor parallelism: the packed rows / K slices of the dense model; (round 5) also the packed
     // expert stacks of a sparse-MoE model, expert parallel or expert tensor parallel, with bf16 triplets
     omx_qwen3 m = new omx_qwen3_();

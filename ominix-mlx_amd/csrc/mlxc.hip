@@ -1153,7 +1153,7 @@ int mlx_quantized_matmul(mlx_array* res, const mlx_array x, const mlx_array w, c
     if (biases.ctx) { rec.a[4] = *A(biases); rec.na = 5; }
     rec.i0 = N; rec.i1 = K; rec.i2 = M; rec.i3 = g | (b << 16);
     // the decode form (one bf16 row against a whole packed matrix): what the deferred list may rewrite onto the fused packed-GEMV family
-    rec.flag = M == 1 && x0.dt == MLX_BFLOAT16 && (b == 4 || b == 8) && K % 512 == 0 && is_contig(x0) && is_contig(w0) && is_contig(s0) &&
+    rec.flag = M == 1 && x0.dt == MLX_BFLOAT16 && (b == 2 || b == 3 || b == 4 || b == 5 || b == 6 || b == 8) && K % 512 == 0 && is_contig(x0) && is_contig(w0) && is_contig(s0) &&
                (!biases.ctx || is_contig(*A(biases)));
     rec.run = [](Rec& q) -> int {
         Contig cx, cw, cs, cb;

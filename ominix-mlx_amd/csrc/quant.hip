@@ -5,7 +5,9 @@
 //              nn::QuantizedLinear::forward (mlx-rs/src/nn/quantized.rs:361-385).
 // Format: w [N, K] -> packed u32 [N, K*bits/32] (element j of a row = the `bits`-wide field at bit
 // (j*bits) mod 32 of word floor(j*bits/32), LSB first), scales / biases [N, K/group] in the activation
-// dtype; w ~= q * scale + bias.  bits 4 or 8, group 32 / 64 / 128.
+// dtype; w ~= q * scale + bias.  bits 2, 3, 4, 5, 6 or 8, group 32 / 64 / 128.  At 3 / 5 / 6 bits a field may straddle two words; a
+// run of 32 elements always fills exactly `bits` words (quant_chunked, quant.hpp), the unit every kernel of those widths (and of 2 bits)
+// works in.
 //
 // quantized_matmul (transpose = true: x . dequant(W)^T):
 //   * M <= 16 (decode): weight-streaming GEMV that reads the PACKED weights -- a quarter (4-bit) of the
@@ -64,6 +66,29 @@ __global__ __launch_bounds__(256) void quantize_kernel(uint32_t* __restrict__ pa
     if (lane == 0) {
         Elem<DT>::st(scales + g, scale);
         Elem<DT>::st(biases + g, bias);
+    }
+    if constexpr (32 % BITS != 0) {
+        // 3 / 5 / 6 bits: lane L < group * BITS / 32 assembles word L of the group from the (at most 32 / BITS + 2) elements whose
+        // fields touch its bits [32 L, 32 L + 32): element e sits at lane e / per_lane, slot e % per_lane
+        uint32_t qv[2] = {0u, 0u};
+        for (int i = 0; i < per_lane; ++i) {
+            const int e = lane * per_lane + i;
+            if (e < group) qv[i] = (uint32_t)fminf(fmaxf(rintf((v[i] - bias) / scale), 0.f), n_bins);
+        }
+        const int n_words = group * BITS / 32;
+        const int e_first = (32 * lane) / BITS;
+        uint64_t word = 0;
+#pragma unroll
+        for (int k = 0; k < 32 / BITS + 2; ++k) {
+            const int e = e_first + k;                              // (every lane shuffles: the bpermute reads all lanes' values)
+            const int src = min(e / per_lane, 63);
+            const uint32_t a0 = __shfl(qv[0], src, 64), a1 = __shfl(qv[1], src, 64);
+            const uint32_t q = (e % per_lane) ? a1 : a0;
+            const int bit = e * BITS - 32 * lane;
+            if (e < group && bit < 32) word |= bit >= 0 ? (uint64_t)q << bit : (uint64_t)(q >> -bit);
+        }
+        if (lane < n_words) packed[g * n_words + lane] = (uint32_t)word;
+        return;
     }
     // pack: element e goes to word e / EPW at bit (e % EPW) * BITS; the EPW elements of a word sit in
     // EPW / per_lane consecutive lanes
@@ -126,6 +151,46 @@ __global__ __launch_bounds__(256) void dequantize_any_kernel(typename Elem<DT>::
     }
 }
 
+// 2 / 3 / 5 / 6 bits (quant_chunked): one thread per run of 32 elements = BITS words.  Each element is the expression of the 4 / 8-bit
+// kernels above ((float)q * s + b, one rounding), so a q gives the same bits at every width.  bf16 / f16 out: four 16-byte stores.
+template <int BITS>
+__global__ __launch_bounds__(256) void dequantize_chunk_kernel(bf16_t* __restrict__ out, const uint32_t* __restrict__ packed,
+                                                               const bf16_t* __restrict__ scales, const bf16_t* __restrict__ biases,
+                                                               int64_t n_chunks, int group, bool scales_f16, bool out_f16) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_chunks; i += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t wd[BITS];
+#pragma unroll
+        for (int k = 0; k < BITS; ++k) wd[k] = packed[i * BITS + k];
+        const int64_t g = i * 32 / group;
+        const float s = scales_f16 ? scale_to_f32<true>(scales[g]) : bf16_to_f32(scales[g]);
+        const float b = biases ? (scales_f16 ? scale_to_f32<true>(biases[g]) : bf16_to_f32(biases[g])) : 0.f;
+        bf16_t o[32];
+#pragma unroll
+        for (int e = 0; e < 32; ++e) {
+            const float v = (float)qfield<BITS>(wd, e) * s + b;
+            o[e] = out_f16 ? (bf16_t)__half_as_ushort(__float2half(v)) : f32_to_bf16(v);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) reinterpret_cast<u32x4*>(out + i * 32)[k] = reinterpret_cast<const u32x4*>(o)[k];
+    }
+}
+
+// ... any float dtype (omx_dequantize's float32 form)
+template <int BITS, int DT>
+__global__ __launch_bounds__(256) void dequantize_any_chunk_kernel(typename Elem<DT>::T* __restrict__ out, const uint32_t* __restrict__ packed,
+                                                                   const typename Elem<DT>::T* __restrict__ scales,
+                                                                   const typename Elem<DT>::T* __restrict__ biases, int64_t n_chunks, int group) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_chunks; i += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t wd[BITS];
+#pragma unroll
+        for (int k = 0; k < BITS; ++k) wd[k] = packed[i * BITS + k];
+        const int64_t g = i * 32 / group;
+        const float sc = Elem<DT>::ld(scales + g), b = biases ? Elem<DT>::ld(biases + g) : 0.f;
+#pragma unroll
+        for (int e = 0; e < 32; ++e) Elem<DT>::st(out + i * 32 + e, (float)qfield<BITS>(wd, e) * sc + b);
+    }
+}
+
 __device__ __forceinline__ uint64_t qargmax_key(float v, uint32_t idx) {
     uint32_t u = __float_as_uint(v);
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -134,13 +199,19 @@ __device__ __forceinline__ uint64_t qargmax_key(float v, uint32_t idx) {
 }
 
 // W = u32 words per lane per step; a lane's W*EPW elements lie inside one group.
+// 2 / 3 / 5 / 6 bits (quant_chunked): W == BITS, a lane's chunk is 32 elements (one run of BITS words, streamed with dwordx2 / x3 / x4 + x1 /
+// x4 + x2 non-temporal loads), the activations stay in natural order, and a K that is not a multiple of 64 x 32 masks the tail lanes of the
+// last step.  Element pairs (q0, q1) become the bf16 pair (128 + q0, 128 + q1) by bit assembly -- each field one v_bfe_u32 (v_alignbit for
+// a straddling one) and the pair one v_lshl_or_b32 + one v_or_b32 of the 0x4300 magic -- into the same v_dot2 as the 4-bit branch.
 // PRO / EPI as in gemv.hip (same arithmetic and rounding points): RMSNorm prologue; store, residual add, SwiGLU
 // over (gate, up) row pairs, logits + greedy-argmax partial.
 // SB: scales and biases come interleaved from QMat::sb (one load per row and step instead of two)
 template <int BITS, int W, int PRO, int EPI, int RB, bool SB = false, bool F16S = false>
 __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
     typedef Act16<F16S> A16;                                // activations / outputs: bfloat16, or float16 for a float16 checkpoint (F16S)
-    constexpr int EPW = 32 / BITS, EPL = W * EPW;          // elements per lane per step
+    constexpr bool CH = quant_chunked(BITS);
+    static_assert(!CH || W == BITS, "a chunked width streams one run of BITS words per lane and step");
+    constexpr int EPW = 32 / BITS, EPL = CH ? 32 : W * EPW;          // elements per lane per step
     constexpr int LR = (EPI == EPI_SWIGLU) ? 2 : 1;         // physical rows per logical row
     constexpr int NR = RB * LR;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -157,8 +228,9 @@ __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
     }
     bf16_t* out = a.out + (size_t)by * a.N;
 
-    const int steps = a.K / (64 * EPL);
-    const int words_per_row = a.K / EPW, groups_per_row = a.K / a.group;
+    const int steps = CH ? (a.K + 64 * EPL - 1) / (64 * EPL) : a.K / (64 * EPL);
+    const int nchunks = a.K / EPL;     // (CH: lanes of the last step at chunk >= nchunks load and add nothing)
+    const int words_per_row = CH ? a.K / 32 * BITS : a.K / EPW, groups_per_row = a.K / a.group;
     const int row_begin = (blockIdx.x * 4 + wave) * a.rows_per_wave;
     const int row_end = min(row_begin + a.rows_per_wave, a.N);
     uint64_t best = 0;
@@ -202,10 +274,36 @@ __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
         }
         const int chunk = st * 64 + lane;
         const int g = chunk * EPL / a.group;
+        if constexpr (CH) {
+            if (chunk >= nchunks) return;    // (never consumed: see consume)
+        }
 #pragma unroll
         for (int r = 0; r < NR; ++r) {
             const uint32_t* p = rw[r] + (size_t)chunk * W;
-            if (W == 4) {
+            if constexpr (CH) {
+                // BITS words at a 4-byte aligned address (the x3 / x4 forms need only dword alignment on gfx950)
+                typedef uint32_t v4a __attribute__((ext_vector_type(4), aligned(4)));
+                typedef uint32_t v3a __attribute__((ext_vector_type(3), aligned(4)));
+                typedef uint32_t v2a __attribute__((ext_vector_type(2), aligned(4)));
+                if (W == 2) {
+                    const v2a v = __builtin_nontemporal_load(reinterpret_cast<const v2a*>(p));
+                    u.wd[r][0] = v[0]; u.wd[r][W > 1 ? 1 : 0] = v[1];
+                } else if (W == 3) {
+                    const v3a v = __builtin_nontemporal_load(reinterpret_cast<const v3a*>(p));
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) u.wd[r][k < W ? k : 0] = v[k];
+                } else {
+                    const v4a v = __builtin_nontemporal_load(reinterpret_cast<const v4a*>(p));
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) u.wd[r][k < W ? k : 0] = v[k];
+                    if (W == 5) {
+                        u.wd[r][W > 4 ? 4 : 0] = __builtin_nontemporal_load(p + 4);
+                    } else {
+                        const v2a t = __builtin_nontemporal_load(reinterpret_cast<const v2a*>(p + 4));
+                        u.wd[r][W > 4 ? 4 : 0] = t[0]; u.wd[r][W > 5 ? 5 : 0] = t[1];
+                    }
+                }
+            } else if (W == 4) {
                 const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
                 u.wd[r][0] = v[0]; u.wd[r][W > 1 ? 1 : 0] = v[1]; u.wd[r][W > 2 ? 2 : 0] = v[2]; u.wd[r][W > 3 ? 3 : 0] = v[3];
             } else if (W == 2) {
@@ -228,47 +326,58 @@ __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
     auto consume = [&](const Unit& u, int f) {
         const int r0 = row_begin + (f / steps) * RB, st = f % steps;
         const int chunk = st * 64 + lane;
+        const bool live = !CH || chunk < nchunks;
         uint32_t xp[EPL / 2];   // the lane's activations, still packed bf16 pairs
+        if (live) {
 #pragma unroll
-        for (int j = 0; j < EPL / 8; ++j) {
-            const u32x4 xv = *reinterpret_cast<const u32x4*>(xs + (size_t)chunk * EPL + j * 8);
+            for (int j = 0; j < EPL / 8; ++j) {
+                const u32x4 xv = *reinterpret_cast<const u32x4*>(xs + (size_t)chunk * EPL + j * 8);
 #pragma unroll
-            for (int q = 0; q < 4; ++q) xp[j * 4 + q] = xv[q];
-        }
-        const float xsm = xsum[chunk];
+                for (int q = 0; q < 4; ++q) xp[j * 4 + q] = xv[q];
+            }
+            const float xsm = xsum[chunk];
 #pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            float d = 0.f;
-            const float scl = SB ? (F16S ? scale_to_f32<true>((uint16_t)u.sbv[r]) : bf16lo(u.sbv[r])) : scale_to_f32<F16S>(u.sc[r]);
-            float bia = SB ? (F16S ? scale_to_f32<true>((uint16_t)(u.sbv[r] >> 16)) : bf16hi(u.sbv[r])) : scale_to_f32<F16S>(u.bi[r]);
+            for (int r = 0; r < NR; ++r) {
+                float d = 0.f;
+                const float scl = SB ? (F16S ? scale_to_f32<true>((uint16_t)u.sbv[r]) : bf16lo(u.sbv[r])) : scale_to_f32<F16S>(u.sc[r]);
+                float bia = SB ? (F16S ? scale_to_f32<true>((uint16_t)(u.sbv[r] >> 16)) : bf16hi(u.sbv[r])) : scale_to_f32<F16S>(u.bi[r]);
+                if constexpr (CH) {
 #pragma unroll
-            for (int wi = 0; wi < W; ++wi) {
-                const uint32_t wdw = u.wd[r][wi];
-                if (BITS == 4) {
-                    // nibbles -> bf16 pairs by bit assembly: 0x4300 | q is the bf16 value 128 + q, so each v_dot2c
-                    // accumulates x . (128 + q); the 128 * sum(x) excess is folded into the bias term below
-                    // One v_perm per pair: the 0x43 exponent byte comes from the second source, the two nibble bytes from
-                    // the same masked word -- so a pair is (q0, q2), (q4, q6) of the even nibbles or (q1, q3), (q5, q7) of the
-                    // odd ones, and the activations were stored in LDS in that order (put() below).
-                    const uint32_t lo = wdw & 0x0F0F0F0Fu, hi = (wdw >> 4) & 0x0F0F0F0Fu;
-                    const uint32_t c43 = A16::kMagicBytes;   // bf16: 0x4300 | q = 128 + q; float16: 0x6400 | q = 1024 + q
-                    const uint32_t q0 = __builtin_amdgcn_perm(c43, lo, 0x04010400u), q1 = __builtin_amdgcn_perm(c43, lo, 0x04030402u);
-                    const uint32_t q2 = __builtin_amdgcn_perm(c43, hi, 0x04010400u), q3 = __builtin_amdgcn_perm(c43, hi, 0x04030402u);
-                    d = A16::dot2(xp[wi * 4 + 0], A16::unmagic(q0), d);
-                    d = A16::dot2(xp[wi * 4 + 1], A16::unmagic(q1), d);
-                    d = A16::dot2(xp[wi * 4 + 2], A16::unmagic(q2), d);
-                    d = A16::dot2(xp[wi * 4 + 3], A16::unmagic(q3), d);
-                } else {
-#pragma unroll
-                    for (int b = 0; b < 4; ++b) {
-                        const uint32_t xw = xp[wi * 2 + (b >> 1)];
-                        d = fmaf((b & 1) ? A16::hi(xw) : A16::lo(xw), (float)((wdw >> (8 * b)) & 0xFFu), d);
+                    for (int i = 0; i < 16; ++i) {
+                        const uint32_t q0 = qfield<BITS>(u.wd[r], 2 * i), q1 = qfield<BITS>(u.wd[r], 2 * i + 1);
+                        const uint32_t pr = ((q1 << 16) | q0) | (A16::kMagicBytes & 0xFF00FF00u);
+                        d = A16::dot2(xp[i], A16::unmagic(pr), d);
                     }
                 }
+#pragma unroll
+                for (int wi = 0; wi < (CH ? 0 : W); ++wi) {
+                    const uint32_t wdw = u.wd[r][wi];
+                    if (BITS == 4) {
+                        // nibbles -> bf16 pairs by bit assembly: 0x4300 | q is the bf16 value 128 + q, so each v_dot2c
+                        // accumulates x . (128 + q); the 128 * sum(x) excess is folded into the bias term below
+                        // One v_perm per pair: the 0x43 exponent byte comes from the second source, the two nibble bytes from
+                        // the same masked word -- so a pair is (q0, q2), (q4, q6) of the even nibbles or (q1, q3), (q5, q7) of the
+                        // odd ones, and the activations were stored in LDS in that order (put() below).
+                        const uint32_t lo = wdw & 0x0F0F0F0Fu, hi = (wdw >> 4) & 0x0F0F0F0Fu;
+                        const uint32_t c43 = A16::kMagicBytes;   // bf16: 0x4300 | q = 128 + q; float16: 0x6400 | q = 1024 + q
+                        const uint32_t q0 = __builtin_amdgcn_perm(c43, lo, 0x04010400u), q1 = __builtin_amdgcn_perm(c43, lo, 0x04030402u);
+                        const uint32_t q2 = __builtin_amdgcn_perm(c43, hi, 0x04010400u), q3 = __builtin_amdgcn_perm(c43, hi, 0x04030402u);
+                        d = A16::dot2(xp[wi * 4 + 0], A16::unmagic(q0), d);
+                        d = A16::dot2(xp[wi * 4 + 1], A16::unmagic(q1), d);
+                        d = A16::dot2(xp[wi * 4 + 2], A16::unmagic(q2), d);
+                        d = A16::dot2(xp[wi * 4 + 3], A16::unmagic(q3), d);
+                    } else {
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const uint32_t xw = xp[wi * 2 + (b >> 1)];
+                            d = fmaf((b & 1) ? A16::hi(xw) : A16::lo(xw), (float)((wdw >> (8 * b)) & 0xFFu), d);
+                        }
+                    }
+                }
+                if (BITS == 4 || CH) bia = fmaf(-A16::kMagic, scl, bia);
+                acc[r] = fmaf(scl, d, acc[r]);
+                acc[r] = fmaf(bia, xsm, acc[r]);
             }
-            if (BITS == 4) bia = fmaf(-A16::kMagic, scl, bia);
-            acc[r] = fmaf(scl, d, acc[r]);
-            acc[r] = fmaf(bia, xsm, acc[r]);
         }
         if (st == steps - 1) {   // the batch's rows are complete: reduce, epilogue, restart the accumulators
 #pragma unroll
@@ -433,11 +542,12 @@ int launch_qgemv_w(const QGemvArgs& a, int pro, int epi, hipStream_t s) {
     constexpr int EPW = 32 / BITS;
     const int groups = (a.N + a.rows_per_wave - 1) / a.rows_per_wave;
     const dim3 grid((groups + 3) / 4, a.n_batch > 1 ? a.n_batch : 1), block(256);
-    const size_t shmem = (size_t)a.K * 2 + (size_t)(a.K / (W * EPW)) * 4 + 64;
+    constexpr int EPL = quant_chunked(BITS) ? 32 : W * EPW;
+    const size_t shmem = (size_t)a.K * 2 + (size_t)(a.K / EPL) * 4 + 64;
     // RB = logical rows per unit: 4 for long matrices, 2 when the matrix is small enough that wave count matters more
     // (rows_per_wave == RB there: one batch per wave, twice the waves) and for SwiGLU row pairs
     // interleaved scale/bias words: the engine's K % 2048 == 0 matrices (every member of the stack must carry them)
-    bool sb = W == 4;
+    bool sb = W == 4 || quant_chunked(BITS);
     for (int i = 0; i < 3 && sb; ++i)
         if (a.m[i].w && !a.m[i].sb) sb = false;
 #define OMX_QGEMV_LAUNCH(P, E, SBF, F16)                                                       \
@@ -449,7 +559,7 @@ int launch_qgemv_w(const QGemvArgs& a, int pro, int epi, hipStream_t s) {
     }
 #define OMX_QGEMV_CASE(P, E)                                                                  \
     if (pro == P && epi == E) {                                                               \
-        if constexpr (W == 4) {                                                               \
+        if constexpr (W == 4 || quant_chunked(BITS)) {                                        \
             if (sb) {                                                                         \
                 if (a.scales_f16) OMX_QGEMV_LAUNCH(P, E, true, true)                          \
                 OMX_QGEMV_LAUNCH(P, E, true, false)                                           \
@@ -474,10 +584,15 @@ template <int BITS>
 int launch_qgemv_bits(const QGemvArgs& a_in, int pro, int epi, hipStream_t s) {
     QGemvArgs a = a_in;
     constexpr int EPW = 32 / BITS;
+    if constexpr (quant_chunked(BITS)) {
+        OMX_REQUIRE(a.K > 0 && a.K % 32 == 0 && a.group >= 32, "quantized_matmul: K=%d unsupported for %d-bit group %d", a.K, BITS, a.group);
+    }
     int W = 4;
-    while (W * EPW > 8 && (a.K % (64 * W * EPW) != 0 || W * EPW > a.group)) W >>= 1;
-    OMX_REQUIRE(a.K % (64 * W * EPW) == 0 && W * EPW <= a.group && W * EPW >= 8, "quantized_matmul: K=%d unsupported for %d-bit group %d (K must be a multiple of %d)",
-                a.K, BITS, a.group, 64 * EPW);
+    if constexpr (!quant_chunked(BITS)) {
+        while (W * EPW > 8 && (a.K % (64 * W * EPW) != 0 || W * EPW > a.group)) W >>= 1;
+        OMX_REQUIRE(a.K % (64 * W * EPW) == 0 && W * EPW <= a.group && W * EPW >= 8, "quantized_matmul: K=%d unsupported for %d-bit group %d (K must be a multiple of %d)",
+                    a.K, BITS, a.group, 64 * EPW);
+    }
     if (a.n_batch < 1) a.n_batch = 1;
     if (a.x_div < 1) a.x_div = 1;
     // long streams for the vocabulary matrix, one batch per wave otherwise; small matrices: two rows per wave
@@ -489,17 +604,22 @@ int launch_qgemv_bits(const QGemvArgs& a_in, int pro, int epi, hipStream_t s) {
         if (a.N <= 8192 && a.K > 8192 && epi != EPI_SWIGLU && (atoi(e) == 2 || atoi(e) == 4 || atoi(e) == 8)) a.rows_per_wave = atoi(e);
     if (const char* e = getenv("OMX_QGEMV_RPW_GU"))      // ... of the gate/up pair launch (logical rows: 2, 4, 8)
         if (epi == EPI_SWIGLU && a.N < 65536 && (atoi(e) == 2 || atoi(e) == 4 || atoi(e) == 8)) a.rows_per_wave = atoi(e);
-    if (W == 4) return launch_qgemv_w<BITS, 4>(a, pro, epi, s);
-    if (W == 2) return launch_qgemv_w<BITS, 2>(a, pro, epi, s);
-    if constexpr (BITS == 4) return launch_qgemv_w<BITS, 1>(a, pro, epi, s);
-    return set_error("quantized gemv: K=%d too small for %d-bit weights", a.K, BITS);
+    if constexpr (quant_chunked(BITS)) {
+        return launch_qgemv_w<BITS, BITS>(a, pro, epi, s);
+    } else {
+        if (W == 4) return launch_qgemv_w<BITS, 4>(a, pro, epi, s);
+        if (W == 2) return launch_qgemv_w<BITS, 2>(a, pro, epi, s);
+        if constexpr (BITS == 4) return launch_qgemv_w<BITS, 1>(a, pro, epi, s);
+        return set_error("quantized gemv: K=%d too small for %d-bit weights", a.K, BITS);
+    }
 }
 
-// quantize / dequantize alone take what mlx_rs::ops::quantize takes: 2, 4 or 8 bits on bfloat16 / float16 / float32 (the reference's
-// own value test loops [2, 4, 8] on float32: ops/quantization.rs:289-305); the matmul kernels stay 4 / 8 bit (check_format)
+// quantize / dequantize alone take what mlx_rs::ops::quantize takes: MLX's affine widths 2, 3, 4, 5, 6 and 8 on bfloat16 / float16 /
+// float32 (the reference's own value test loops [2, 4, 8] on float32: ops/quantization.rs:289-305)
+bool quant_bits_ok(int bits) { return bits == 2 || bits == 3 || bits == 4 || bits == 5 || bits == 6 || bits == 8; }
 int check_format_qdq(const char* who, int K, int group, int bits, int dtype) {
     OMX_REQUIRE(dtype == OMX_BFLOAT16 || dtype == OMX_FLOAT16 || dtype == OMX_FLOAT32, "%s: bf16 / f16 / f32 only (got dtype %d)", who, dtype);
-    OMX_REQUIRE(bits == 2 || bits == 4 || bits == 8, "%s: bits must be 2, 4 or 8 (got %d; the 3 / 5 / 6-bit MLX packings are not built)", who, bits);
+    OMX_REQUIRE(quant_bits_ok(bits), "%s: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", who, bits);
     OMX_REQUIRE(group == 32 || group == 64 || group == 128, "%s: group_size must be 32, 64 or 128 (got %d)", who, group);
     OMX_REQUIRE(K > 0 && K % group == 0, "%s: the last dimension (%d) must be divisible by the group size (%d)", who, K, group);
     return 0;
@@ -508,7 +628,7 @@ int check_format_qdq(const char* who, int K, int group, int bits, int dtype) {
 // dtype: OMX_BFLOAT16, or OMX_FLOAT16 where `f16_scales_ok` -- scales / biases of a float16 checkpoint (activations stay bf16)
 int check_format(const char* who, int K, int group, int bits, int dtype, bool f16_scales_ok = false) {
     OMX_REQUIRE(dtype == OMX_BFLOAT16 || (f16_scales_ok && dtype == OMX_FLOAT16), "%s: bf16 activations / scales only (got dtype %d)", who, dtype);
-    OMX_REQUIRE(bits == 4 || bits == 8, "%s: bits must be 4 or 8 (got %d)", who, bits);
+    OMX_REQUIRE(quant_bits_ok(bits), "%s: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", who, bits);
     OMX_REQUIRE(group == 32 || group == 64 || group == 128, "%s: group_size must be 32, 64 or 128 (got %d)", who, group);
     OMX_REQUIRE(K > 0 && K % group == 0, "%s: the last dimension (%d) must be divisible by the group size (%d)", who, K, group);
     return 0;
@@ -556,12 +676,18 @@ int qgemv_grid(int N) {
 }
 
 int launch_qgemv(const QGemvArgs& a, int bits, int pro, int epi, hipStream_t s) {
-    OMX_REQUIRE(bits == 4 || bits == 8, "quantized gemv: bits must be 4 or 8 (got %d)", bits);
+    OMX_REQUIRE(quant_bits_ok(bits), "quantized gemv: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", bits);
     if (bits == 4) {
         const int r = launch_qgemv4m(a, pro, epi, s);
         if (r >= 0) return r;
     }
-    return bits == 4 ? launch_qgemv_bits<4>(a, pro, epi, s) : launch_qgemv_bits<8>(a, pro, epi, s);
+    switch (bits) {
+    case 2: return launch_qgemv_bits<2>(a, pro, epi, s);
+    case 3: return launch_qgemv_bits<3>(a, pro, epi, s);
+    case 5: return launch_qgemv_bits<5>(a, pro, epi, s);
+    case 6: return launch_qgemv_bits<6>(a, pro, epi, s);
+    default: return bits == 4 ? launch_qgemv_bits<4>(a, pro, epi, s) : launch_qgemv_bits<8>(a, pro, epi, s);
+    }
 }
 
 }  // namespace omx
@@ -583,6 +709,9 @@ extern "C" int omx_quantize(void* packed, void* scales, void* biases, const void
     OMX_Q_CASE(2, OMX_BFLOAT16) OMX_Q_CASE(4, OMX_BFLOAT16) OMX_Q_CASE(8, OMX_BFLOAT16)
     OMX_Q_CASE(2, OMX_FLOAT16) OMX_Q_CASE(4, OMX_FLOAT16) OMX_Q_CASE(8, OMX_FLOAT16)
     OMX_Q_CASE(2, OMX_FLOAT32) OMX_Q_CASE(4, OMX_FLOAT32) OMX_Q_CASE(8, OMX_FLOAT32)
+    OMX_Q_CASE(3, OMX_BFLOAT16) OMX_Q_CASE(5, OMX_BFLOAT16) OMX_Q_CASE(6, OMX_BFLOAT16)
+    OMX_Q_CASE(3, OMX_FLOAT16) OMX_Q_CASE(5, OMX_FLOAT16) OMX_Q_CASE(6, OMX_FLOAT16)
+    OMX_Q_CASE(3, OMX_FLOAT32) OMX_Q_CASE(5, OMX_FLOAT32) OMX_Q_CASE(6, OMX_FLOAT32)
 #undef OMX_Q_CASE
     OMX_LAUNCH_CHECK();
     return 0;
@@ -591,6 +720,19 @@ extern "C" int omx_quantize(void* packed, void* scales, void* biases, const void
 static int launch_dequantize_any(void* out, const uint32_t* packed, const void* scales, const void* biases, int64_t rows, int cols,
                                  int group_size, int bits, bool scales_f16, bool out_f16, hipStream_t s) {
     OMX_REQUIRE(out && packed && scales, "omx_dequantize: null tensor");
+    if (quant_chunked(bits)) {
+        const int64_t n_chunks = rows * cols / 32;
+        if (n_chunks == 0) return 0;
+        const unsigned blocks = (unsigned)((n_chunks + 255) / 256 < 16384 ? (n_chunks + 255) / 256 : 16384);
+#define OMX_DQC_CASE(B)                                                                                                         \
+        if (bits == B) dequantize_chunk_kernel<B><<<blocks, 256, 0, s>>>((bf16_t*)out, packed, (const bf16_t*)scales, (const bf16_t*)biases, \
+                                                                          n_chunks, group_size, scales_f16, out_f16);
+        OMX_DQC_CASE(2) OMX_DQC_CASE(3) OMX_DQC_CASE(5) OMX_DQC_CASE(6)
+#undef OMX_DQC_CASE
+        OMX_LAUNCH_CHECK();
+        return 0;
+    }
+    OMX_REQUIRE(bits == 4 || bits == 8, "dequantize: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", bits);
     const int64_t n_words = rows * cols * bits / 32;
     if (n_words == 0) return 0;
     const unsigned blocks = (unsigned)((n_words + 255) / 256 < 16384 ? (n_words + 255) / 256 : 16384);
@@ -613,6 +755,16 @@ extern "C" int omx_dequantize(void* out, const void* packed, const void* scales,
     if (bits != 2 && dtype != OMX_FLOAT32) {   // the 16-bit forms the matmul paths share (vector stores)
         const bool f16 = dtype == OMX_FLOAT16;
         return launch_dequantize_any(out, (const uint32_t*)packed, scales, biases, rows, cols, group_size, bits, f16, f16, (hipStream_t)stream);
+    }
+    if (bits != 2 && quant_chunked(bits)) {   // 3 / 5 / 6 bits, float32 out
+        const int64_t n_chunks = rows * cols / 32;
+        if (n_chunks == 0) return 0;
+        const unsigned blocks = (unsigned)((n_chunks + 255) / 256 < 16384 ? (n_chunks + 255) / 256 : 16384);
+        if (bits == 3) dequantize_any_chunk_kernel<3, OMX_FLOAT32><<<blocks, 256, 0, (hipStream_t)stream>>>((float*)out, (const uint32_t*)packed, (const float*)scales, (const float*)biases, n_chunks, group_size);
+        if (bits == 5) dequantize_any_chunk_kernel<5, OMX_FLOAT32><<<blocks, 256, 0, (hipStream_t)stream>>>((float*)out, (const uint32_t*)packed, (const float*)scales, (const float*)biases, n_chunks, group_size);
+        if (bits == 6) dequantize_any_chunk_kernel<6, OMX_FLOAT32><<<blocks, 256, 0, (hipStream_t)stream>>>((float*)out, (const uint32_t*)packed, (const float*)scales, (const float*)biases, n_chunks, group_size);
+        OMX_LAUNCH_CHECK();
+        return 0;
     }
     const int64_t n_words = rows * cols * bits / 32;
     if (n_words == 0) return 0;

@@ -1,4 +1,4 @@
-// Packed-weight (MLX affine 4/8-bit) GEMV family: the decode-time Linear of a quantized checkpoint
+// Packed-weight (MLX affine 2/3/4/5/6/8-bit) GEMV family: the decode-time Linear of a quantized checkpoint
 // (nn::QuantizedLinear::forward, mlx-rs/src/nn/quantized.rs:361-385; quant.hip for the format).
 #pragma once
 #include "common.hpp"
@@ -61,5 +61,16 @@ bool qgemv4m_shape_ok(int K, int group, int bits);
 size_t qgemv4m_tile_words(int n, int K);            // u32 words of the tile form of an [n, K] matrix
 int launch_qgemv4m_repack(uint32_t* tiles, const uint32_t* wq, const bf16_t* scales, const bf16_t* biases, int n, int K, hipStream_t s);
 int qgemv_grid(int N);          // blocks launch_qgemv uses == argmax partials written
+
+// The widths whose fields do not divide a word (3, 5, 6) and 2: a run of 32 elements is exactly BITS consecutive words, element j the
+// BITS-wide field at bit j * BITS of that little-endian bit string (a field may straddle two words).  j must be a compile-time constant
+// after unrolling: one v_bfe_u32, or v_alignbit + mask for a straddling field.
+constexpr bool quant_chunked(int bits) { return bits == 2 || bits == 3 || bits == 5 || bits == 6; }
+template <int B>
+__device__ __forceinline__ uint32_t qfield(const uint32_t* w, int j) {
+    const int p = j * B, k = p >> 5, o = p & 31;
+    if (o + B <= 32) return (w[k] >> o) & ((1u << B) - 1u);
+    return __builtin_amdgcn_alignbit(w[k + 1], w[k], o) & ((1u << B) - 1u);
+}
 
 }  // namespace omx

@@ -146,7 +146,8 @@ class Model:
                  tie_word_embeddings=False, rope_scaling=None, max_context=4096, tp_rank=0, tp_size=1, quantization=None,
                  num_experts=0, num_experts_per_tok=0, moe_intermediate_size=0, moe_mode="qwen3_moe", norm_topk_prob=False,
                  qk_norm=True, ep_rank=0, ep_size=1, attention_bias=False, **_ignored):
-        """quantization: config.json's {"bits": 4|8, "group_size": 64} (model.rs:63) or None for a bf16 checkpoint; + "scales_dtype":
+        """quantization: config.json's {"bits": 2|3|4|5|6|8, "group_size": 64} (model.rs:63) or None for a bf16 checkpoint (2, 3,
+        5 and 6 bits: dense single-rank models only); + "scales_dtype":
         "float16" when the checkpoint's scales / biases are float16 (loader.load_model reads it off the tensors' dtype).
         num_experts > 0: sparse-MoE feed-forward in every layer -- moe_mode "qwen3_moe" (qwen3_moe.rs ModelArgs :60-87) or
         "mixtral" (mixtral-mlx ModelArgs :54-80, with qk_norm=False and moe_intermediate_size = intermediate_size)."""

@@ -1,4 +1,4 @@
-"""Decode loop of the Qwen3-8B-shaped model as an MLX 4-bit checkpoint (for rocprofv3 / quick timing)."""
+"""Decode loop of the Qwen3-8B-shaped model as an MLX checkpoint (for rocprofv3 / quick timing): quant_decode.py [bits (4; 0 = bf16)] [ctx]."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
