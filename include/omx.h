@@ -244,6 +244,9 @@ int omx_bench_qwen3_per_op(omx_qwen3 model, const omx_qwen3_config* cfg, const u
 /* timing of the last omx_qwen3_decode call measured with HIP events on the engine stream (ms)       */
 int omx_qwen3_last_decode_ms(omx_qwen3 m, float* ms);
 int omx_qwen3_last_prefill_ms(omx_qwen3 m, float* ms);   /* same for the last omx_qwen3_prefill call */
+/* bytes the engine holds for dequantised weights of a packed model: the prompt pass's dequant cache slab plus its scratch (the
+ * verify pass adds none) */
+int omx_qwen3_dequant_bytes(omx_qwen3 m, size_t* bytes);
 /* test hook: copy an internal bf16 buffer ("h","h2","qkv","attn_out","act","k<l>","v<l>") to the host */
 int omx_qwen3_debug_read(omx_qwen3 m, const char* name, void* host, size_t n_elems);
 int omx_qwen3_stream(omx_qwen3 m, omx_stream* s);

@@ -411,6 +411,51 @@ extern "C" int omx_debug_qgemv(void* out, float* out_f32, unsigned long long* ar
 }
 extern "C" int omx_debug_qgemv_grid(int N) { return omx::qgemv_grid(N); }
 
+/* test hook of qgemv_rows.hip: M activation rows x [M, K] against n_members packed matrices (w / sc / bi / n: arrays of n_members; a
+ * q | k | v stack, or gate and up for EPI_SWIGLU), out [M, N] (resid [M, N]).  use_sb: build the interleaved scale | bias words first.
+ * reference != 0 runs what the rows kernel must reproduce bit for bit instead: launch_qgemv's VALU kernel (no matrix-core tiles) with
+ * n_batch = M -- one launch per row for EPI_RESIDUAL, whose batched form shares one residual row. */
+extern "C" int omx_debug_qgemv_rows(void* out, const void* x, const void* norm_w, const void* resid, const void* const* w, const void* const* sc,
+                                    const void* const* bi, const int* n, int n_members, int M, int N, int K, int group, int bits, int pro, int epi,
+                                    float eps, int single_round, int use_sb, int reference, void* stream) {
+    using namespace omx;
+    OMX_REQUIRE(out && x && w && sc && n && n_members >= 1 && n_members <= 3 && M >= 1, "omx_debug_qgemv_rows: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    QRowsArgs ra = {};
+    QGemvArgs& a = ra.g;
+    uint32_t* sb[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < n_members; ++i) {
+        a.m[i] = QMat{(const uint32_t*)w[i], (const bf16_t*)sc[i], bi ? (const bf16_t*)bi[i] : nullptr, n[i]};
+        if (use_sb) {
+            const size_t ng = (size_t)n[i] * (K / group);
+            OMX_HIP_CHECK(hipMalloc((void**)&sb[i], ng * 4));
+            if (launch_quant_interleave(sb[i], a.m[i].scales, a.m[i].biases, ng, s)) return 1;
+            a.m[i].sb = sb[i];
+        }
+    }
+    a.N = N; a.K = K; a.group = group;
+    a.x = (const bf16_t*)x; a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.resid = (const bf16_t*)resid;
+    a.out = (bf16_t*)out; a.swiglu_single_round = single_round;
+    int rc = 0;
+    if (!reference) {
+        ra.M = M;
+        rc = launch_qgemv_rows(ra, bits, pro, epi, s);
+    } else if (epi == EPI_RESIDUAL) {
+        for (int t = 0; t < M && rc == 0; ++t) {
+            QGemvArgs r = a;
+            r.x = a.x + (size_t)t * K; r.resid = a.resid + (size_t)t * N; r.out = a.out + (size_t)t * N;
+            rc = launch_qgemv(r, bits, pro, epi, s);
+        }
+    } else {
+        a.n_batch = M; a.x_div = 1;
+        rc = launch_qgemv(a, bits, pro, epi, s);
+    }
+    OMX_HIP_CHECK(hipStreamSynchronize(s));
+    for (int i = 0; i < 3; ++i)
+        if (sb[i]) (void)hipFree(sb[i]);
+    return rc;
+}
+
 // ---- what does a COLD weight matrix cost a streaming GEMV at its start?  (tools/tlb_probe.py)
 //      mode 0: rotate through n_copies matrices (cold, as in a decode step)
 //      mode 1: before each GEMV, a tiny kernel reads ONE line every `stride` bytes of that matrix from every XCD

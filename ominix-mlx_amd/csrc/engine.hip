@@ -1141,7 +1141,8 @@ __global__ void encoder_mask_kernel(bf16_t* mask, const uint8_t* am, int T) {
 
 // the prompt pass's row buffers (T rows each) and, for a packed model, the scratch its dequantised GEMM operands pass through: grown
 // here, on the host, AHEAD of a prompt's device-timed region (a hipMalloc between the launches leaves the device idle for its duration)
-int prefill_reserve(omx_qwen3 m, int T) {
+// dequant = false: the row buffers only (the verify pass of a packed model dequantises no weight: qgemv_rows.hip)
+int prefill_reserve(omx_qwen3 m, int T, bool dequant = true) {
     const omx_qwen3_config& c = m->cfg;
     const int hd = c.hidden_size, D = c.head_dim, H = m->H, Hkv = m->Hkv, I = m->I;
     if (T > m->pf_cap) {
@@ -1155,7 +1156,7 @@ int prefill_reserve(omx_qwen3 m, int T) {
         }
         m->pf_cap = T;
     }
-    if (c.quant_bits != 0) {
+    if (c.quant_bits != 0 && dequant) {
         const size_t need = std::max((size_t)std::max(std::max(H * D, I), hd) * (size_t)std::max(hd, I),
                                      std::max((size_t)(H + 2 * Hkv) * D * hd, (size_t)2 * I * hd));
         if (need > m->dq_cap) {
@@ -1201,7 +1202,44 @@ __global__ void heads_to_tokens_kernel(bf16_t* __restrict__ out, const bf16_t* _
     }
 }
 
-int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = nullptr, bool full_last = false) {
+// QuantizedEmbedding::forward for the T rows of prompt_dev straight from the packed table (the verify pass of a packed model, which
+// dequantises no matrix): each element (float)q * scale + bias with one rounding, the expression of dequantize_kernel /
+// dequantize_chunk_kernel (quant.hip), so the rows equal the prompt pass's gather-then-dequantise bit for bit.  One block per row.
+template <int BITS>
+__global__ __launch_bounds__(256) void qembed_rows_kernel(bf16_t* __restrict__ out, const uint32_t* __restrict__ table, const bf16_t* __restrict__ scales,
+                                                          const bf16_t* __restrict__ biases, const uint32_t* __restrict__ ids, int hidden, int group) {
+    const size_t id = ids[blockIdx.x];
+    const uint32_t* wrow = table + id * (size_t)(hidden / 32 * BITS);
+    const bf16_t* srow = scales + id * (size_t)(hidden / group);
+    const bf16_t* brow = biases ? biases + id * (size_t)(hidden / group) : nullptr;
+    for (int j = threadIdx.x; j < hidden; j += blockDim.x) {
+        const int p = j * BITS, k = p >> 5, o = p & 31;
+        const uint32_t q = (o + BITS <= 32 ? wrow[k] >> o : __builtin_amdgcn_alignbit(wrow[k + 1], wrow[k], o)) & ((1u << BITS) - 1u);
+        const float sc = bf16_to_f32(srow[j / group]), b = brow ? bf16_to_f32(brow[j / group]) : 0.f;
+        out[(size_t)blockIdx.x * hidden + j] = f32_to_bf16((float)q * sc + b);
+    }
+}
+
+// one packed Linear of the verify pass over T rows: launch_qgemv_rows in blocks of <= 8 rows (x, resid, out and the member outputs
+// advance by the block's rows)
+int packed_rows(const QGemvArgs& g, int T, bf16_t* const* mout, int bits, int pro, int epi, hipStream_t s) {
+    for (int t0 = 0; t0 < T; t0 += 8) {
+        QRowsArgs ra = {};
+        ra.g = g;
+        ra.M = std::min(8, T - t0);
+        ra.g.x = g.x + (size_t)t0 * g.K;
+        if (g.resid) ra.g.resid = g.resid + (size_t)t0 * g.N;
+        if (g.out) ra.g.out = g.out + (size_t)t0 * g.N;
+        for (int i = 0; mout && i < 3; ++i)
+            if (mout[i]) ra.mout[i] = mout[i] + (size_t)t0 * g.m[i].n;
+        if (launch_qgemv_rows(ra, bits, pro, epi, s)) return 1;
+    }
+    return 0;
+}
+
+// packed_rows (omx_qwen3_verify only): every packed Linear of a dense single-rank bf16-triplet model through qgemv_rows.hip -- no weight
+// is dequantised, neither into the dequant cache nor into its scratch
+int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = nullptr, bool full_last = false, bool packed_rows_pass = false) {
     const omx_qwen3_config& c = m->cfg;
     // float16 checkpoints (round 4): the same pass in float16 -- weights dequantised to float16, the eight-wave GEMM kernel's float16
     // form, float16 norms / RoPE / slabs, the flash attention kernel's float16 form -- for
@@ -1217,7 +1255,10 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = 
     const omx_dtype act_dt = f16 ? OMX_FLOAT16 : OMX_BFLOAT16;
     hipStream_t s = m->stream;
     const int hd = c.hidden_size, D = c.head_dim, H = m->H, Hkv = m->Hkv, I = m->I;
-    if (prefill_reserve(m, T)) return 1;   // (omx_qwen3_prefill has called it ahead of its timed region already)
+    const bool prow = packed_rows_pass && c.quant_bits != 0;
+    OMX_REQUIRE(!prow || (!f16 && !enc && c.num_experts == 0 && m->allreduce == nullptr && c.tp_size <= 1 && c.ep_size <= 1),
+                "packed verify pass: dense single-rank models with bf16 scales only");
+    if (prefill_reserve(m, T, !prow)) return 1;   // (omx_qwen3_prefill has called it ahead of its timed region already)
     // tensor parallel: q/k/v/gate/up are this rank's column shards (local H, Hkv, I), o / down are row
     // shards whose [T, hidden] bf16 partial sums are all-reduced -- two collectives per layer -- before the residual add
     const bool tp = m->allreduce != nullptr && c.ep_size <= 1;
@@ -1248,7 +1289,7 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = 
     // quantized checkpoint: each weight is dequantised into one scratch matrix right before its GEMM (MLX's qmm does
     // the same per tile); K is the contraction width of that weight
     // `at`: element offset inside the scratch, so that the members of one segmented launch (q | k | v, gate | up) coexist
-    if (quant) dq_cache_prepare(m);      // (omx_qwen3_prefill has called it ahead of its timed region already)
+    if (quant && !prow) dq_cache_prepare(m);      // (omx_qwen3_prefill has called it ahead of its timed region already)
     auto W = [&](const bf16_t* dense, const QMat* qm, int K, size_t at = 0) -> const bf16_t* {
         if (!quant) return dense;
         if (m->dq_cache_mode == 1) {
@@ -1267,7 +1308,15 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = 
         if (launch_dequantize_bf16(m->dq_buf + at, qm->w, qm->scales, qm->biases, qm->n, K, c.quant_group, c.quant_bits, f16, s, f16)) return nullptr;
         return m->dq_buf + at;
     };
-    if (quant) {
+    if (prow) {
+        const int bits = c.quant_bits;
+#define OMX_QEMB_ROWS(B) \
+        else if (bits == B) OMX_LAUNCH(qembed_rows_kernel<B>, T, 256, 0, s, m->pf_h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->prompt_dev, hd, c.quant_group);
+        if (false) {}
+        OMX_QEMB_ROWS(2) OMX_QEMB_ROWS(3) OMX_QEMB_ROWS(4) OMX_QEMB_ROWS(5) OMX_QEMB_ROWS(6) OMX_QEMB_ROWS(8)
+#undef OMX_QEMB_ROWS
+        OMX_LAUNCH_CHECK();
+    } else if (quant) {
         // QuantizedEmbedding::forward: gather the packed rows, dequantise (quantized.rs:192-203)
         const int wpr = hd * c.quant_bits / 32, gpr = hd / c.quant_group;
         uint32_t* rows_w = (uint32_t*)m->pf_xn;                       // scratch: [T, wpr] u32 fits in [T, hd] bf16
@@ -1301,9 +1350,18 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = 
         qkv.plain[2] = {L.v, L.v_bias, m->pf_v, Hkv * D, Hkv * D, 0};
         // (a handful of rows: the weight-streaming launch normalises its staged copy of the rows itself -- no RMSNorm launch)
         const bool qkv_norm = !f16 && seg_gemm && gemm_segmented_preferred(T, hd, qkv) && gemv_rows_takes_norm(T, hd, qkv);
+        if (prow) {   // q | k | v with the RMSNorm prologue, each member into its own row buffer
+            QGemvArgs a = {};
+            a.m[0] = Q.q; a.m[1] = Q.k; a.m[2] = Q.v;
+            a.N = (H + 2 * Hkv) * D; a.K = hd; a.group = c.quant_group;
+            a.x = h; a.norm_w = L.in_ln; a.eps = c.rms_norm_eps;
+            bf16_t* const outs[3] = {m->pf_q, m->pf_k, m->pf_v};
+            if (packed_rows(a, T, outs, c.quant_bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
+        } else
         if (!qkv_norm && omx_rms_norm(m->pf_xn, h, L.in_ln, T, hd, c.rms_norm_eps, act_dt, s)) return 1;
         if (qkv_norm) { qkv.pre_norm_w = L.in_ln; qkv.pre_norm_eps = c.rms_norm_eps; }
-        if (f16 || (seg_gemm && gemm_segmented_preferred(T, hd, qkv))) {   // (float16: always the segmented 256-row kernel)
+        if (prow) {
+        } else if (f16 || (seg_gemm && gemm_segmented_preferred(T, hd, qkv))) {   // (float16: always the segmented 256-row kernel)
             if (quant) {   // the three dequantised matrices side by side in the scratch
                 const size_t nq = (size_t)H * D * hd, nk = (size_t)Hkv * D * hd;
                 if (!(qkv.plain[0].w = W(nullptr, &Q.q, hd, 0)) || !(qkv.plain[1].w = W(nullptr, &Q.k, hd, nq)) ||
@@ -1357,6 +1415,22 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = 
                                 (int64_t)m->cap * D, scale, enc && enc->mask ? OMX_MASK_ADDITIVE : OMX_MASK_CAUSAL,
                                 enc ? enc->mask : nullptr, s, /*out_token_major=*/true))
             return 1;
+        if (prow) {   // o + residual
+            QGemvArgs a = {};
+            a.m[0] = Q.o; a.N = hd; a.K = H * D; a.group = c.quant_group;
+            a.x = m->pf_attn; a.resid = h; a.out = h2;
+            if (packed_rows(a, T, nullptr, c.quant_bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
+            // gate / up + nn::silu(gate) * up with the RMSNorm prologue, then down + residual
+            a = QGemvArgs{};
+            a.m[0] = Q.gate; a.m[1] = Q.up; a.N = I; a.K = hd; a.group = c.quant_group;
+            a.x = h2; a.norm_w = L.post_ln; a.eps = c.rms_norm_eps; a.out = m->pf_g;
+            if (packed_rows(a, T, nullptr, c.quant_bits, PRO_RMSNORM, EPI_SWIGLU, s)) return 1;
+            a = QGemvArgs{};
+            a.m[0] = Q.down; a.N = hd; a.K = I; a.group = c.quant_group;
+            a.x = m->pf_g; a.resid = h2; a.out = h;
+            if (packed_rows(a, T, nullptr, c.quant_bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
+            continue;
+        }
         if (!(w = W(L.o, &Q.o, H * D)) || row_split(h2, m->pf_attn, w, h, H * D)) return 1;
         GemmSegs gu = {};
         gu.w_gate = L.gate; gu.w_up = L.up; gu.out_act = m->pf_g; gu.half = I; gu.ld_act = I; gu.act_mode = 1;
@@ -2030,14 +2104,21 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
 }
 
 /* Speculative decoding (mlx-rs-core/src/speculative.rs).  `verify` is verify_draft_tokens (:132-161): the target model runs ALL n
- * tokens [last accepted, draft 1 .. draft n-1] in one batched matrix-core pass on top of its cache (their K/V rows are appended) and
- * returns the greedy token of every position -- the lm_head is one [n, V] GEMM, the weights stream once for all rows.  Afterwards the
- * cache holds n more tokens and the next step's input token is greedy_out[n-1]; the caller then drops the rejected tail with
- * omx_qwen3_trim.  Single-rank bf16 weights (a vocabulary-sharded or quantized head has no batched form here). */
+ * tokens [last accepted, draft 1 .. draft n-1] in one batched pass on top of its cache (their K/V rows are appended) and returns the
+ * greedy token of every position -- the weights stream once for all rows: bf16 weights through the matrix-core GEMMs (the lm_head one
+ * [n, V] GEMM), packed weights (2/3/4/5/6/8-bit, bf16 scales) through the few-row packed GEMV of qgemv_rows.hip in blocks of <= 8
+ * rows, lm_head included, with no weight dequantised.  Afterwards the cache holds n more tokens and the next step's input token is
+ * greedy_out[n-1]; the caller then drops the rejected tail with omx_qwen3_trim.  Single-rank dense models (a vocabulary-sharded head
+ * has no batched form here; packed experts and float16 triplets are refused). */
 int omx_qwen3_verify(omx_qwen3 m, const uint32_t* tokens, int n, uint32_t* greedy_out) {
     OMX_REQUIRE(m && tokens && greedy_out, "omx_qwen3_verify: null argument");
     OMX_REQUIRE(n >= 1 && n <= 64, "omx_qwen3_verify: %d tokens (1..64 per call)", n);
-    OMX_REQUIRE(m->allreduce == nullptr && m->cfg.quant_bits == 0, "omx_qwen3_verify: single-rank bf16 models only");
+    OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
+                "omx_qwen3_verify: tensor / expert parallel models are not supported (single-rank models only)");
+    const bool packed = m->cfg.quant_bits != 0;
+    OMX_REQUIRE(!packed || !m->cfg.quant_scales_f16,
+                "omx_qwen3_verify: float16 triplets (scales_dtype float16) are not supported on packed models; bf16 scales only");
+    OMX_REQUIRE(!packed || m->cfg.num_experts == 0, "omx_qwen3_verify: packed models with experts (MoE) are not supported; dense models only");
     for (int i = 0; i < n; ++i) OMX_REQUIRE(tokens[i] < (uint32_t)m->cfg.vocab_size, "omx_qwen3_verify: token id %u out of range (vocab %d)", tokens[i], m->cfg.vocab_size);
     StepState st;
     OMX_HIP_CHECK(hipMemcpyAsync(&st, m->st, sizeof(st), hipMemcpyDeviceToHost, m->stream));
@@ -2058,10 +2139,17 @@ int omx_qwen3_verify(omx_qwen3 m, const uint32_t* tokens, int n, uint32_t* greed
         m->verify_cap = cap;
     }
     OMX_HIP_CHECK(hipMemcpyAsync(m->prompt_dev, tokens, (size_t)n * 4, hipMemcpyHostToDevice, s));
-    if (prefill_prefix_batched(m, n, st.pos, nullptr, /*full_last=*/true)) return 1;
+    if (prefill_prefix_batched(m, n, st.pos, nullptr, /*full_last=*/true, /*packed_rows_pass=*/packed)) return 1;
     // [final RMSNorm rows] -> [lm_head GEMM, n x V] -> [argmax per row]   (model.rs:423, 480-489; sampler.rs:9-18 at temperature 0)
-    if (omx_rms_norm(m->pf_xn, m->pf_h, m->final_norm, n, hd, m->cfg.rms_norm_eps, OMX_BFLOAT16, s)) return 1;
-    if (launch_gemm_bf16(m->verify_logits, m->pf_xn, m->lm_head, nullptr, n, V, hd, s)) return 1;
+    if (packed) {   // the packed head (or the tied q_embed table), the final RMSNorm as its prologue
+        QGemvArgs a = {};
+        a.m[0] = m->q_head; a.m[0].n = V; a.N = V; a.K = hd; a.group = m->cfg.quant_group;
+        a.x = m->pf_h; a.norm_w = m->final_norm; a.eps = m->cfg.rms_norm_eps; a.out = m->verify_logits;
+        if (packed_rows(a, n, nullptr, m->cfg.quant_bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
+    } else {
+        if (omx_rms_norm(m->pf_xn, m->pf_h, m->final_norm, n, hd, m->cfg.rms_norm_eps, OMX_BFLOAT16, s)) return 1;
+        if (launch_gemm_bf16(m->verify_logits, m->pf_xn, m->lm_head, nullptr, n, V, hd, s)) return 1;
+    }
     if (m->temperature == 0.f) {
         if (omx_argmax(m->verify_tokens, m->verify_logits, n, V, OMX_BFLOAT16, s)) return 1;
     } else {
@@ -2108,6 +2196,13 @@ int omx_qwen3_trim(omx_qwen3 m, int n, uint32_t next_token) {
     st.cur_token = next_token;
     OMX_HIP_CHECK(hipMemcpyAsync(m->st, &st, sizeof(st), hipMemcpyHostToDevice, m->stream));
     OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return 0;
+}
+
+/* bytes the engine holds for dequantised weights: the dequant cache's slab plus the scratch of the prompt pass's GEMM operands */
+int omx_qwen3_dequant_bytes(omx_qwen3 m, size_t* bytes) {
+    OMX_REQUIRE(m && bytes, "omx_qwen3_dequant_bytes: null argument");
+    *bytes = (m->dq_slab ? m->dq_slab_bytes : 0) + (m->dq_buf ? m->dq_cap * sizeof(bf16_t) : 0);
     return 0;
 }
 

@@ -62,6 +62,19 @@ size_t qgemv4m_tile_words(int n, int K);            // u32 words of the tile for
 int launch_qgemv4m_repack(uint32_t* tiles, const uint32_t* wq, const bf16_t* scales, const bf16_t* biases, int n, int K, hipStream_t s);
 int qgemv_grid(int N);          // blocks launch_qgemv uses == argmax partials written
 
+// qgemv_rows.hip: M <= 8 activation rows against one packed matrix (or a q | k | v stack, a gate / up pair) with every packed word read
+// once per launch -- the speculative verify pass of a quantized checkpoint.  g carries launch_qgemv's fields with their meaning for ONE
+// row, except that x [M, K], resid [M, N] and out [M, N] hold M rows; bf16 triplets, forms PRO_NONE / PRO_RMSNORM x EPI_STORE,
+// PRO_NONE x EPI_RESIDUAL, PRO_NONE / PRO_RMSNORM x EPI_SWIGLU.  Row t of the result is bit-identical to launch_qgemv on row t alone
+// (no matrix-core tiles).
+struct QRowsArgs {
+    QGemvArgs g;
+    int M;
+    bf16_t* mout[3];     // optional (not SwiGLU): member i's rows go to mout[i] [M, m[i].n] instead of out
+    int nb;              // (set by the launcher)
+};
+int launch_qgemv_rows(const QRowsArgs& a, int bits, int pro, int epi, hipStream_t s);
+
 // The widths whose fields do not divide a word (3, 5, 6) and 2: a run of 32 elements is exactly BITS consecutive words, element j the
 // BITS-wide field at bit j * BITS of that little-endian bit string (a field may straddle two words).  j must be a compile-time constant
 // after unrolling: one v_bfe_u32, or v_alignbit + mask for a straddling field.

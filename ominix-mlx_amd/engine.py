@@ -44,6 +44,7 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_last_logits": (c_int, [c_void_p, c_void_p, c_int]),
     "omx_qwen3_last_decode_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "omx_qwen3_last_prefill_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
+    "omx_qwen3_dequant_bytes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_size_t)]),
     "omx_qwen3_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
     "omx_qwen3_stream": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
     "omx_qwen3_step_bytes": (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_double)]),
@@ -305,6 +306,12 @@ class Model:
         v = c_float()
         check(lib.omx_qwen3_last_decode_ms(self._h, ctypes.byref(v)))
         return v.value
+
+    def dequant_bytes(self) -> int:
+        """Device bytes held for dequantised weights (dequant cache slab + scratch of the prompt pass); 0 for a bf16 model."""
+        v = ctypes.c_size_t()
+        check(lib.omx_qwen3_dequant_bytes(self._h, ctypes.byref(v)))
+        return int(v.value)
 
     def last_prefill_ms(self) -> float:
         v = c_float()
