@@ -94,7 +94,8 @@ int omx_fused_modulate(void* out, const void* x, const void* shift, const void* 
 
 /* ---- a5: Linear.  mlx_matmul ops.h:598-602 / mlx_addmm ops.h:36-43 as used by nn::Linear
  *      (mlx-rs/src/nn/linear.rs:87-92): out[M,N] = x[M,K] . W[N,K]^T (+ bias[N]).
- *      M <= 8 takes the HBM-streaming GEMV path, larger M the MFMA GEMM path.                  */
+ *      M <= 8 takes the HBM-streaming GEMV path, larger M the MFMA GEMM path.
+ *      float16: M <= 8 with K % 8 == 0 (the GEMV's float16 form, bias or not), M > 8 with K % 64 == 0; other shapes fail.  */
 int omx_linear(void* out, const void* x, const void* w, const void* bias, int M, int N, int K,
                omx_dtype dtype, omx_stream stream);
 /* Linear whose trailing 2*half output features are a [gate | up] pair consumed by fused_swiglu
@@ -185,6 +186,10 @@ typedef struct omx_qwen3_config_ {
     /* quantized checkpoints only: scales / biases are float16 (an MLX float16 checkpoint; nn/quantized.rs:361-385 takes any float).
      * They enter the arithmetic as their exact float32 values; activations and outputs stay bf16.  Dense decoders (not with experts). */
     int quant_scales_f16;
+    /* dense (quant_bits 0) checkpoints only: the weights are float16 (MLX keeps a model in the dtype it was saved in), and the model runs
+     * in float16 end to end -- embedding, norms, RoPE, K/V, every rounding point and the logits.  Single rank, no experts, no
+     * attention_bias, head_dim 128; omx_qwen3_verify refuses such a model.  0 = bfloat16 weights. */
+    int float16_weights;
 } omx_qwen3_config;
 typedef struct omx_qwen3_* omx_qwen3;
 
@@ -249,6 +254,13 @@ int omx_qwen3_last_prefill_ms(omx_qwen3 m, float* ms);   /* same for the last om
 int omx_qwen3_dequant_bytes(omx_qwen3 m, size_t* bytes);
 /* test hook: copy an internal bf16 buffer ("h","h2","qkv","attn_out","act","k<l>","v<l>") to the host */
 int omx_qwen3_debug_read(omx_qwen3 m, const char* name, void* host, size_t n_elems);
+/* test hook of the dense decode GEMV (csrc/gemv.hip): ONE launch with prologue `pro` (0 none, 1 RMSNorm) and epilogue `epi` (0 store
+ * [+ bias], 1 residual, 2 SwiGLU over gate w0 / up w1, 3 logits + argmax partials), bf16 (f16 = 0) or float16 (f16 = 1) operands.
+ * w0 | w1 | w2 are row-stacked ([n0 | n1 | rest] rows of K) for the other epilogues.  argmax_slot: omx_debug_gemv_grid(N, K) keys. */
+int omx_debug_gemv(void* out, unsigned long long* argmax_slot, const void* x, const void* norm_w, const void* resid, const void* bias,
+                   const void* w0, const void* w1, const void* w2, int n0, int n1, int N, int K, int pro, int epi, int f16, float eps,
+                   int single_round, omx_stream stream);
+int omx_debug_gemv_grid(int N, int K);
 int omx_qwen3_stream(omx_qwen3 m, omx_stream* s);
 /* algorithmic HBM bytes of ONE decode step at context length ctx (SURVEY.md 8d formula)             */
 int omx_qwen3_step_bytes(omx_qwen3 m, int ctx, double* bytes);

@@ -411,6 +411,31 @@ extern "C" int omx_debug_qgemv(void* out, float* out_f32, unsigned long long* ar
 }
 extern "C" int omx_debug_qgemv_grid(int N) { return omx::qgemv_grid(N); }
 
+/* test hook of the dense decode GEMV (gemv.hip): one launch_gemv of the given prologue / epilogue, bf16 (f16 = 0) or float16 (f16 = 1).
+ * w0 [n0, K] | w1 | w2 row-stacked (q | k | v; N = n0 + n1 + rest), or gate (w0) / up (w1) [N, K] for EPI_SWIGLU.  EPI_ARGMAX writes
+ * omx_debug_gemv_grid(N, K) partial keys to argmax_slot.  Synchronises the stream. */
+extern "C" int omx_debug_gemv(void* out, unsigned long long* argmax_slot, const void* x, const void* norm_w, const void* resid, const void* bias,
+                              const void* w0, const void* w1, const void* w2, int n0, int n1, int N, int K, int pro, int epi, int f16, float eps,
+                              int single_round, void* stream) {
+    using namespace omx;
+    OMX_REQUIRE(out && x && w0 && N > 0, "omx_debug_gemv: bad arguments");
+    GemvArgs a = {};
+    a.w0 = (const bf16_t*)w0; a.w1 = (const bf16_t*)w1; a.w2 = (const bf16_t*)w2;
+    if (epi == EPI_SWIGLU || !w1) {
+        a.n0 = N;
+    } else {
+        a.n0 = n0; a.n1 = w2 ? n1 : N - n0; a.n2 = w2 ? N - n0 - n1 : 0;
+    }
+    a.N = N; a.K = K;
+    a.x = (const bf16_t*)x; a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.resid = (const bf16_t*)resid;
+    a.out = out; a.out_bias = (const bf16_t*)bias; a.argmax_slot = argmax_slot; a.swiglu_single_round = single_round;
+    a.f16 = f16;
+    const int rc = launch_gemv(a, pro, epi, (hipStream_t)stream);
+    OMX_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return rc;
+}
+extern "C" int omx_debug_gemv_grid(int N, int K) { return omx::gemv_grid(N, K, omx::EPI_ARGMAX, 0); }
+
 /* test hook of qgemv_rows.hip: M activation rows x [M, K] against n_members packed matrices (w / sc / bi / n: arrays of n_members; a
  * q | k | v stack, or gate and up for EPI_SWIGLU), out [M, N] (resid [M, N]).  use_sb: build the interleaved scale | bias words first.
  * reference != 0 runs what the rows kernel must reproduce bit for bit instead: launch_qgemv's VALU kernel (no matrix-core tiles) with

@@ -212,6 +212,9 @@ using namespace omx;
 
 struct omx_qwen3_ {
     omx_qwen3_config cfg;
+    // float16 activations: a packed checkpoint with float16 triplets, or a dense float16 one -- the model then runs in float16 end to
+    // end (embedding row, norms, RoPE, K/V slabs, every rounding point, logits, sampler); every float16 branch keys on this
+    bool f16 = false;
     int H, Hkv, I, V;            // local (per-rank) heads / intermediate / vocab
     int cap;                     // KV slab capacity in tokens
     std::map<std::string, const void*> named;
@@ -326,7 +329,7 @@ int add_sampling_noise(omx_qwen3 m, hipStream_t s) {
     const int tp = c.tp_size > 1 ? c.tp_size : 1;
     if (launch_rng_next(m->rng, s)) return 1;
     return launch_sample_noise(m->argmax_partials, m->n_argmax_partials, m->logits, m->rng + 2, m->V, c.tp_rank * m->V,
-                               m->V * tp, 1.0f / m->temperature, c.quant_scales_f16 != 0, s);
+                               m->V * tp, 1.0f / m->temperature, m->f16, s);
 }
 
 int resolve_weights(omx_qwen3 m) {
@@ -462,7 +465,8 @@ bool attention_takes_oproj(omx_qwen3 m) {
     if (c.quant_bits == 4)   // 4-bit checkpoint: the packed O matrix with its interleaved scale | bias words (built at load for K % 2048 == 0)
         return c.ep_size <= 1 && c.tp_size <= 1 && !c.quant_scales_f16 && !m->qlayers.empty() && m->qlayers[0].o.sb != nullptr &&
                attn_step_oproj_q4_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size, c.quant_group);
-    return c.quant_bits == 0 && attn_step_oproj_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size);
+    // (a dense float16 model: the O projection stays its own launch -- the attention launch's O phase is bf16-only)
+    return c.quant_bits == 0 && !m->f16 && attn_step_oproj_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size);
 }
 
 // OMX_PEER_FUSED: a GEMV whose blocks poll their peers' stores must be resident as a whole -- a block waiting for a peer's row while
@@ -497,7 +501,7 @@ int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* resid = n
         a.out = m->attn_out;
         a.abort_flag = m->wait_abort;
         a.trace = m->attn_trace ? m->attn_trace + (size_t)l * m->attn_nsplit * m->Hkv * 8 : nullptr;
-        a.f16 = c.quant_scales_f16;   // a float16 checkpoint runs in float16 end to end
+        a.f16 = m->f16;   // a float16 checkpoint runs in float16 end to end
         if (resid && (out || out_f32)) {
             a.o_resid = resid; a.o_out = out; a.o_out_f32 = out_f32; a.o_rows = c.hidden_size; a.xg = m->attn_xg;
             if (c.quant_bits) {
@@ -656,7 +660,7 @@ int step_engine_mode(omx_qwen3 m) {
     const char* e = getenv("OMX_STEP_ENGINE");         // (read per call: tests flip it between engines of one process)
     const int mode = e ? atoi(e) : 0;
     const omx_qwen3_config& c = m->cfg;
-    const bool ok = mode > 0 && !m->se_disabled && c.quant_bits == 0 && c.num_experts == 0 && c.tp_size == 1 && c.ep_size <= 1 && m->allreduce == nullptr &&
+    const bool ok = mode > 0 && !m->se_disabled && c.quant_bits == 0 && !m->f16 && c.num_experts == 0 && c.tp_size == 1 && c.ep_size <= 1 && m->allreduce == nullptr &&
            !c.attention_bias && m->se_gran != nullptr && m->cus > 0 &&
            step_engine_ok(c.hidden_size, m->H, m->Hkv, c.head_dim, m->I, m->attn_nsplit, m->cus);
     return ok ? (mode == 2 ? 2 : 1) : 0;
@@ -787,6 +791,7 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             a.norm_w = L.in_ln; a.eps = c.rms_norm_eps;
             a.out = m->qkv;
             a.out_bias = L.qkv_bias;
+            a.f16 = m->f16;
             a.rows_per_wave = rpw_env("OMX_GEMV_RPW_QKV");
             time_next_launch(m, l, KC_QKV);
                 if (launch_gemv(a, PRO_RMSNORM, EPI_STORE, s)) return 1;
@@ -805,6 +810,7 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             GemvArgs a = {};
             a.w0 = L.o; a.n0 = hd; a.N = hd; a.K = m->H * D;
             a.x = m->attn_out;
+            a.f16 = m->f16;
             a.rows_per_wave = rpw_env("OMX_GEMV_RPW_O");
             if (!tp) {
                 a.resid = h; a.out = hn;
@@ -870,6 +876,7 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             a.x = h; a.x_partial = pending; a.x_partial_n = pending_n; a.x_out = pending ? hn : nullptr;
             a.norm_w = L.post_ln; a.eps = c.rms_norm_eps;
             a.out = m->act;
+            a.f16 = m->f16;
             a.rows_per_wave = rpw_env("OMX_GEMV_RPW_GU");
             time_next_launch(m, l, KC_GATE_UP);
                 if (launch_gemv(a, PRO_RMSNORM, EPI_SWIGLU, s)) return 1;
@@ -879,6 +886,7 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             GemvArgs a = {};
             a.w0 = L.down; a.n0 = hd; a.N = hd; a.K = m->I;
             a.x = m->act;
+            a.f16 = m->f16;
             a.rows_per_wave = rpw_env("OMX_GEMV_RPW_DOWN");
             if (!tp) {
                 a.resid = h; a.out = hn;
@@ -911,6 +919,7 @@ int enqueue_step_tail(omx_qwen3 m, bool with_head, const bf16_t* h, const float*
         a.out = m->logits;
         a.argmax_slot = m->argmax_partials;
         a.row_offset = c.tp_rank * m->V;
+        a.f16 = m->f16;
         time_next_launch(m, 0, KC_HEAD);
                 if (launch_gemv(a, PRO_RMSNORM, EPI_ARGMAX, s)) return 1;
         if (add_sampling_noise(m, s)) return 1;
@@ -1062,6 +1071,7 @@ int enqueue_head_on_row(omx_qwen3 m, const bf16_t* row, hipStream_t s) {
         a.out = m->logits;
         a.argmax_slot = m->argmax_partials;
         a.row_offset = c.tp_rank * m->V;
+        a.f16 = m->f16;
         if (launch_gemv(a, PRO_RMSNORM, EPI_ARGMAX, s)) return 1;
     }
     if (add_sampling_noise(m, s)) return 1;
@@ -1245,7 +1255,8 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = 
     // form, float16 norms / RoPE / slabs, the flash attention kernel's float16 form -- for
     // plain prompts of a dense model, also on tensor-parallel shards (each rank's float16 partial products summed in f32); encode /
     // verify and the expert forms stay bfloat16-only
-    const bool f16 = c.quant_scales_f16 != 0;
+    // (a dense float16 checkpoint takes the same pass on its own float16 weights: nothing to dequantise)
+    const bool f16 = m->f16;
     // (round 5: the encoder taps and passes of a handful of rows too -- a tap copies 16-bit rows whatever their format, and the 128-row
     //  float16 GEMM tile predicates its rows.  An encoder PADDING mask stays refused: the reference builds it as (1 - keep) * f16(-1e9) =
     //  0 * -inf = NaN on every kept key, flux-klein-mlx/src/qwen3_encoder.rs:196-198 -- there is no finite result to reproduce.)
@@ -1586,6 +1597,15 @@ int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) {
     // (round 5: float16 sparse-MoE checkpoints also expert parallel / expert tensor parallel -- decode form; their prompts go token by token)
     OMX_REQUIRE(!m->cfg.quant_scales_f16 || (m->cfg.quant_bits && m->cfg.head_dim == 128),
                 "InvalidConfig: a float16 checkpoint (quantization scales_dtype float16) runs as a packed model with head_dim 128");
+    // dense float16 weights: single rank, dense MLP, no q/k/v bias, head_dim 128 (the float16 attention kernels' width)
+    OMX_REQUIRE(!c.float16_weights || !c.quant_bits,
+                "InvalidConfig: float16_weights marks a dense checkpoint (quant_bits 0, got %d); a packed float16 checkpoint sets quant_scales_f16", c.quant_bits);
+    OMX_REQUIRE(!c.float16_weights || c.num_experts == 0, "InvalidConfig: float16_weights with experts (dense float16 MoE is not supported)");
+    OMX_REQUIRE(!c.float16_weights || (c.tp_size <= 1 && m->cfg.ep_size <= 1),
+                "InvalidConfig: float16_weights under tensor / expert parallelism (tp_size %d, ep_size %d) is not supported", c.tp_size, m->cfg.ep_size);
+    OMX_REQUIRE(!c.float16_weights || !c.attention_bias, "InvalidConfig: float16_weights with attention_bias (dense float16 Qwen2) is not supported");
+    OMX_REQUIRE(!c.float16_weights || c.head_dim == 128, "InvalidConfig: float16_weights needs head_dim 128 (got %d)", c.head_dim);
+    m->f16 = c.quant_scales_f16 || c.float16_weights;
     m->H = c.num_attention_heads / c.tp_size;
     m->Hkv = c.num_key_value_heads >= c.tp_size ? c.num_key_value_heads / c.tp_size : 1;
     m->I = c.intermediate_size / c.tp_size;
@@ -1779,7 +1799,8 @@ int omx_qwen3_synth_weights(omx_qwen3 m, uint32_t base_seed) { return synth_weig
 int omx_qwen3_synth_weights_peaked(omx_qwen3 m, uint32_t base_seed) { return synth_weights_impl(m, base_seed, true); }
 static int synth_weights_impl(omx_qwen3 m, uint32_t base_seed, bool peaked) {
     OMX_REQUIRE(m, "omx_qwen3_synth_weights: null model");
-    OMX_REQUIRE(!peaked || (m->cfg.quant_bits == 0 && !m->cfg.tie_word_embeddings), "omx_qwen3_synth_weights_peaked: bf16 checkpoints with an untied lm_head only");
+    OMX_REQUIRE(!peaked || (m->cfg.quant_bits == 0 && !m->cfg.float16_weights && !m->cfg.tie_word_embeddings),
+                "omx_qwen3_synth_weights_peaked: bf16 checkpoints with an untied lm_head only");
     OMX_REQUIRE(!m->cfg.quant_scales_f16, "omx_qwen3_synth_weights: the device generator quantises in bf16; a float16-scale model takes uploaded triplets");
     const omx_qwen3_config& c = m->cfg;
     const int D = c.head_dim, hd = c.hidden_size, r = c.tp_rank;
@@ -1790,8 +1811,9 @@ static int synth_weights_impl(omx_qwen3 m, uint32_t base_seed, bool peaked) {
         bf16_t* p = nullptr;
         if (dev_alloc(m, &p, (size_t)rows * cols)) return 1;
         const uint32_t seed = base_seed ^ crc32_str(name.c_str());
+        // (a dense float16 model: the same generator values rounded to float16 -- oracle/synth.py tensor(dt="f16"))
         if (omx_fill_uniform_2d(p, rows, cols, ld_full, row0, col0, seed, is_norm ? amp_n : amp_w, is_norm ? 1.0f : 0.0f,
-                                OMX_BFLOAT16, m->stream))
+                                c.float16_weights ? OMX_FLOAT16 : OMX_BFLOAT16, m->stream))
             return 1;
         m->named[name] = p;
         return 0;
@@ -2056,7 +2078,7 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
     // with one all-reduce of the MoE block's [T, hidden] partial per layer (round 3; token-serial before)
     // (float16 models: the batched pass exists for plain prompts -- dense and sparse-MoE models, on one rank or sharded (round 6: the
     //  float16 form of the sharded MoE block); short prompts go through the decode step)
-    const bool f16_serial = m->cfg.quant_scales_f16 && n_prompt <= 16;
+    const bool f16_serial = m->f16 && n_prompt <= 16;
     const bool serial = (serial_env && serial_env[0] == '1') || n_prompt < 2 || f16_serial;
     if (prepare_step(m, serial ? off : off + n_prompt - 1)) return 1;   // the first step this call will run (graphs are per context bucket)
     if (!serial && m->cfg.quant_bits) dq_cache_prepare(m);             // (a once-per-model allocation: ahead of the timed region)
@@ -2116,6 +2138,8 @@ int omx_qwen3_verify(omx_qwen3 m, const uint32_t* tokens, int n, uint32_t* greed
     OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
                 "omx_qwen3_verify: tensor / expert parallel models are not supported (single-rank models only)");
     const bool packed = m->cfg.quant_bits != 0;
+    OMX_REQUIRE(!m->cfg.float16_weights, "omx_qwen3_verify: dense float16 models (float16_weights) are not supported; speculative verify runs "
+                "on bf16 weights or bf16-scale packed weights");
     OMX_REQUIRE(!packed || !m->cfg.quant_scales_f16,
                 "omx_qwen3_verify: float16 triplets (scales_dtype float16) are not supported on packed models; bf16 scales only");
     OMX_REQUIRE(!packed || m->cfg.num_experts == 0, "omx_qwen3_verify: packed models with experts (MoE) are not supported; dense models only");

@@ -1,6 +1,7 @@
 // See gemv.hpp for the design notes.
 #include "moe_route.hpp"
 #include "gemv.hpp"
+#include "act16.hpp"
 #include "peer.hpp"
 #include "launch_timing.hpp"
 
@@ -24,11 +25,16 @@ __device__ __forceinline__ const bf16_t* row_ptr(const GemvArgs& a, int row) {
     return a.w2 + (size_t)row * a.K;
 }
 
+// F16: float16 weights, widened to f32 (exact) for the same fma chain as bf16 -- not v_dot2_f32_f16, whose two products and the
+// accumulator meet in one unspecified rounding step: the chain keeps one rounding per product-add in a fixed order, the bound the
+// tests check, and the kernel is bound by HBM, not by these VALU ops
+template <bool F16 = false>
 __device__ __forceinline__ float dot8(const u32x4 w, const float (&xf)[8], float acc) {
+    typedef Act16<F16> A;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        acc = fmaf(bf16lo(w[i]), xf[2 * i], acc);
-        acc = fmaf(bf16hi(w[i]), xf[2 * i + 1], acc);
+        acc = fmaf(A::lo(w[i]), xf[2 * i], acc);
+        acc = fmaf(A::hi(w[i]), xf[2 * i + 1], acc);
     }
     return acc;
 }
@@ -40,33 +46,35 @@ __device__ __forceinline__ uint64_t argmax_key(float v, uint32_t idx) {
     return ((uint64_t)u << 32) | (uint32_t)(~idx);
 }
 
-template <int EPI>
+// F16: the same roundings in float16 (the packed float16 GEMV's epilogue, quant.hip)
+template <int EPI, bool F16 = false>
 __device__ __forceinline__ void epilogue(const GemvArgs& a, int row, float v0, float v1, uint64_t& best) {
+    typedef Act16<F16> A;
     if (EPI == EPI_STORE) {
-        reinterpret_cast<bf16_t*>(a.out)[row] = f32_to_bf16(a.out_bias ? v0 + bf16_to_f32(a.out_bias[row]) : v0);
+        reinterpret_cast<bf16_t*>(a.out)[row] = A::bits(a.out_bias ? v0 + A::val(a.out_bias[row]) : v0);
     } else if (EPI == EPI_F32) {
         // (`best` carries the call's tag, read ONCE before the first weight load: a load here would wait behind -- drain -- the
         //  next batch's prefetch; the total is stored by peer_finish_rows)
         if (a.peer) peer_store_word(a.peer, (unsigned)best, row, __float_as_uint(v0));
         else reinterpret_cast<float*>(a.out)[row] = a.out_scale ? round_bf16(round_bf16(v0) * a.out_scale_f) : v0;
     } else if (EPI == EPI_RESIDUAL) {
-        reinterpret_cast<bf16_t*>(a.out)[row] = f32_to_bf16(bf16_to_f32(a.resid[row]) + round_bf16(v0));
+        reinterpret_cast<bf16_t*>(a.out)[row] = A::bits(A::val(a.resid[row]) + A::rnd(v0));
     } else if (EPI == EPI_SWIGLU) {
         // nn::silu(gate) * up, every primitive's result held in bf16
         // (qwen3-mlx/src/model.rs:264-265; mlx-rs/src/nn/activation.rs:876-880)
-        const float g = round_bf16(v0);
-        const float u = round_bf16(v1);
+        const float g = A::rnd(v0);
+        const float u = A::rnd(v1);
         if (a.swiglu_single_round) {
             // mlx_rs_core::fused_swiglu(up, gate) (metal_kernels.rs:11-18): one kernel, one rounding
-            reinterpret_cast<bf16_t*>(a.out)[row] = f32_to_bf16(g / (1.0f + expf(-g)) * u);
+            reinterpret_cast<bf16_t*>(a.out)[row] = A::bits(g / (1.0f + expf(-g)) * u);
         } else {
-            const float sg = round_bf16(1.0f / (1.0f + expf(-g)));
-            reinterpret_cast<bf16_t*>(a.out)[row] = f32_to_bf16(round_bf16(g * sg) * u);
+            const float sg = A::rnd(1.0f / (1.0f + expf(-g)));
+            reinterpret_cast<bf16_t*>(a.out)[row] = A::bits(A::rnd(g * sg) * u);
         }
     } else if (EPI == EPI_ARGMAX) {
-        const bf16_t lb = f32_to_bf16(v0);
+        const bf16_t lb = A::bits(v0);
         reinterpret_cast<bf16_t*>(a.out)[row] = lb;
-        const uint64_t key = argmax_key(bf16_to_f32(lb), (uint32_t)(row + a.row_offset));
+        const uint64_t key = argmax_key(A::val(lb), (uint32_t)(row + a.row_offset));
         best = key > best ? key : best;
     }
 }
@@ -82,13 +90,16 @@ __device__ __forceinline__ void peer_finish_rows(const GemvArgs& a, unsigned tag
 // NVW    = 16-byte vectors per lane per row per wave (compile-time, fully unrolled)
 // KSPLIT = waves sharing one row (1: a wave owns whole rows; 4: each wave owns a K quarter)
 // RB     = logical rows per register batch; LR physical rows per logical row (2 for SwiGLU)
-template <int NVW, int KSPLIT, int RB, int PRO, int EPI, bool TAIL = false>
+// F16    = float16 model (GemvArgs::f16): activation, weights and every rounding point in float16; bf16 otherwise
+template <int NVW, int KSPLIT, int RB, int PRO, int EPI, bool TAIL = false, bool F16 = false>
 #ifndef OMX_GEMV_MINWAVES
 #define OMX_GEMV_MINWAVES 1   // (tuning builds: make VARIANT=w3 VARIANT_FLAGS=-DOMX_GEMV_MINWAVES=3 asks hipcc for <= 168 VGPRs)
 #endif
 __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const GemvArgs a_in) {
     // batched / expert-selected form (MoE decode): blockIdx.y picks the activation row, the output row
     // block and, through a device index array, the expert whose weights are streamed
+    typedef Act16<F16> A;
+    static_assert(!F16 || (PRO != PRO_ROUTE && EPI != EPI_F32), "float16: no routing prologue, no f32 output");
     GemvArgs a = a_in;
     if (EPI == EPI_F32) {
         if (a_in.out_scale) a.out_scale_f = bf16_to_f32(a_in.out_scale[blockIdx.y]);
@@ -163,10 +174,10 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
             const u32x4 xp = xs[koff + j * 64 + lane];                                             \
             float xf[8];                                                                           \
             _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                        \
-                xf[2 * q] = bf16lo(xp[q]);                                                         \
-                xf[2 * q + 1] = bf16hi(xp[q]);                                                     \
+                xf[2 * q] = A::lo(xp[q]);                                                          \
+                xf[2 * q + 1] = A::hi(xp[q]);                                                      \
             }                                                                                      \
-            _Pragma("unroll") for (int r = 0; r < NR; ++r) acc[r] = dot8(WB[r][j], xf, acc[r]);    \
+            _Pragma("unroll") for (int r = 0; r < NR; ++r) acc[r] = dot8<F16>(WB[r][j], xf, acc[r]); \
         }                                                                                          \
         _Pragma("unroll") for (int r = 0; r < NR; ++r) acc[r] = wave_sum(acc[r]);                  \
         if (lane == 0) {                                                                           \
@@ -174,7 +185,7 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
                 const int row = (R0) + r;                                                          \
                 if (row < row_end) {                                                               \
                     if (KSPLIT == 1) {                                                             \
-                        epilogue<EPI>(a, row, acc[LR * r], acc[LR * r + (LR - 1)], best);          \
+                        epilogue<EPI, F16>(a, row, acc[LR * r], acc[LR * r + (LR - 1)], best);     \
                     } else {                                                                       \
                         const int lr = row - row_begin;                                            \
                         part[(lr * LR) * KSPLIT + wave] = acc[LR * r];                             \
@@ -278,7 +289,7 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
         if (a_in.w1) a.w1 = a_in.w1 + e * a_in.w_estride;
         if (active) OMX_ISSUE(wA, row_begin);
     } else
-    // ---- prologue: stage x (bf16) in LDS; optionally x := bf16(x + bf16(partial)); RMS-normalise ----
+    // ---- prologue: stage x (bf16 / float16) in LDS; optionally x := bf16(x + bf16(partial)); RMS-normalise ----
     {
         const bf16_t* xg = a.x + (a.x_row ? (size_t)a.x_row[0] * K : 0);
         float ss = 0.f;
@@ -302,15 +313,15 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
                     }
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        raw[q] = pack_bf16(bf16lo(raw[q]) + round_bf16(pp[2 * q]),
-                                           bf16hi(raw[q]) + round_bf16(pp[2 * q + 1]));
+                        raw[q] = A::pack(A::lo(raw[q]) + A::rnd(pp[2 * q]),
+                                         A::hi(raw[q]) + A::rnd(pp[2 * q + 1]));
                     if (a.x_out && blockIdx.x == 0) *(reinterpret_cast<u32x4*>(a.x_out) + v) = raw;
                 }
                 xv[i] = raw;
                 if (PRO == PRO_RMSNORM) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
-                        const float lo = bf16lo(raw[q]), hi = bf16hi(raw[q]);
+                        const float lo = A::lo(raw[q]), hi = A::hi(raw[q]);
                         ss = fmaf(lo, lo, ss);
                         ss = fmaf(hi, hi, ss);
                     }
@@ -328,8 +339,8 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
                     u32x4 o;
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        o[q] = pack_bf16(bf16lo(xv[i][q]) * rstd * bf16lo(nw[q]),
-                                         bf16hi(xv[i][q]) * rstd * bf16hi(nw[q]));
+                        o[q] = A::pack(A::lo(xv[i][q]) * rstd * A::lo(nw[q]),
+                                       A::hi(xv[i][q]) * rstd * A::hi(nw[q]));
                     xs[v] = o;
                 }
             }
@@ -365,7 +376,7 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
                 v0 += part[(lr * LR) * KSPLIT + w];
                 if (LR == 2) v1 += part[(lr * LR + 1) * KSPLIT + w];
             }
-            epilogue<EPI>(a, row_begin + lr, v0, v1, best);
+            epilogue<EPI, F16>(a, row_begin + lr, v0, v1, best);
         }
     }
     if (EPI == EPI_F32) {
@@ -401,8 +412,10 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
 // ---- any contraction width (K a multiple of 8): the fallback for shapes without a tuned instantiation (Qwen2.5-7B:
 //      K = 3584 / 18944).  Same prologues and epilogues, a runtime loop over the 16-byte vectors of a row, RB rows share
 //      each activation vector; one register set (no double buffer), so it streams at roughly 2/3 of the tuned kernels. ----
-template <int PRO, int EPI>
+template <int PRO, int EPI, bool F16 = false>
 __global__ __launch_bounds__(kBlock) void gemv_generic_kernel(const GemvArgs a_in) {
+    typedef Act16<F16> A;
+    static_assert(!F16 || (PRO != PRO_ROUTE && EPI != EPI_F32), "float16: no routing prologue, no f32 output");
     GemvArgs a = a_in;
     if (EPI == EPI_F32) {
         if (a_in.out_scale) a.out_scale_f = bf16_to_f32(a_in.out_scale[blockIdx.y]);
@@ -446,14 +459,14 @@ __global__ __launch_bounds__(kBlock) void gemv_generic_kernel(const GemvArgs a_i
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    raw[q] = pack_bf16(bf16lo(raw[q]) + round_bf16(pp[2 * q]), bf16hi(raw[q]) + round_bf16(pp[2 * q + 1]));
+                    raw[q] = A::pack(A::lo(raw[q]) + A::rnd(pp[2 * q]), A::hi(raw[q]) + A::rnd(pp[2 * q + 1]));
                 if (a.x_out && blockIdx.x == 0) *(reinterpret_cast<u32x4*>(a.x_out) + v) = raw;
             }
             xs[v] = raw;
             if (PRO == PRO_RMSNORM) {
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
-                    const float lo = bf16lo(raw[q]), hi = bf16hi(raw[q]);
+                    const float lo = A::lo(raw[q]), hi = A::hi(raw[q]);
                     ss = fmaf(lo, lo, ss);
                     ss = fmaf(hi, hi, ss);
                 }
@@ -468,7 +481,7 @@ __global__ __launch_bounds__(kBlock) void gemv_generic_kernel(const GemvArgs a_i
                 u32x4 o;
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    o[q] = pack_bf16(bf16lo(raw[q]) * rstd * bf16lo(nw[q]), bf16hi(raw[q]) * rstd * bf16hi(nw[q]));
+                    o[q] = A::pack(A::lo(raw[q]) * rstd * A::lo(nw[q]), A::hi(raw[q]) * rstd * A::hi(nw[q]));
                 xs[v] = o;
             }
         }
@@ -503,16 +516,16 @@ __global__ __launch_bounds__(kBlock) void gemv_generic_kernel(const GemvArgs a_i
             const u32x4 xp = xs[v];
             float xf[8];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) { xf[2 * q] = bf16lo(xp[q]); xf[2 * q + 1] = bf16hi(xp[q]); }
+            for (int q = 0; q < 4; ++q) { xf[2 * q] = A::lo(xp[q]); xf[2 * q + 1] = A::hi(xp[q]); }
 #pragma unroll
-            for (int r = 0; r < NR; ++r) acc[r] = dot8(w[r], xf, acc[r]);
+            for (int r = 0; r < NR; ++r) acc[r] = dot8<F16>(w[r], xf, acc[r]);
         }
 #pragma unroll
         for (int r = 0; r < NR; ++r) acc[r] = wave_sum(acc[r]);
         if (lane == 0) {
 #pragma unroll
             for (int r = 0; r < RB; ++r)
-                if (r0 + r < row_end) epilogue<EPI>(a, r0 + r, acc[LR * r], acc[LR * r + (LR - 1)], best);
+                if (r0 + r < row_end) epilogue<EPI, F16>(a, r0 + r, acc[LR * r], acc[LR * r + (LR - 1)], best);
         }
     }
     if (EPI == EPI_F32) {
@@ -537,6 +550,7 @@ __global__ __launch_bounds__(kBlock) void gemv_generic_kernel(const GemvArgs a_i
     }
 }
 
+template <bool F16>
 int launch_generic(const GemvArgs& a, int pro, int epi, hipStream_t s) {
     const int groups = (a.N + a.rows_per_wave - 1) / a.rows_per_wave;
     const dim3 grid((groups + kWaves - 1) / kWaves, a.n_batch > 1 ? a.n_batch : 1), block(kBlock);
@@ -544,8 +558,8 @@ int launch_generic(const GemvArgs& a, int pro, int epi, hipStream_t s) {
 #define OMX_GEN_CASE(P, E)                                                                                         \
     if (pro == P && epi == E) {                                                                                    \
         if (shmem > 48 * 1024)                                                                                     \
-            OMX_HIP_CHECK(hipFuncSetAttribute((const void*)gemv_generic_kernel<P, E>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-        OMX_LAUNCH_TIMED((gemv_generic_kernel<P, E>), grid, block, shmem, s, a);                                         \
+            OMX_HIP_CHECK(hipFuncSetAttribute((const void*)gemv_generic_kernel<P, E, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+        OMX_LAUNCH_TIMED((gemv_generic_kernel<P, E, F16>), grid, block, shmem, s, a);                                    \
         OMX_LAUNCH_CHECK();                                                                                        \
         return 0;                                                                                                  \
     }
@@ -555,12 +569,14 @@ int launch_generic(const GemvArgs& a, int pro, int epi, hipStream_t s) {
     OMX_GEN_CASE(PRO_RMSNORM, EPI_SWIGLU)
     OMX_GEN_CASE(PRO_NONE, EPI_SWIGLU)
     OMX_GEN_CASE(PRO_RMSNORM, EPI_ARGMAX)
-    OMX_GEN_CASE(PRO_NONE, EPI_F32)
+    if constexpr (!F16) {
+        OMX_GEN_CASE(PRO_NONE, EPI_F32)
+    }
 #undef OMX_GEN_CASE
     return set_error("gemv: unsupported prologue/epilogue combination %d/%d", pro, epi);
 }
 
-template <int NVW, int KSPLIT, int RB>
+template <int NVW, int KSPLIT, int RB, bool F16>
 int launch_nv(const GemvArgs& a, int pro, int epi, hipStream_t s) {
     const int groups = (a.N + a.rows_per_wave - 1) / a.rows_per_wave;   // row groups (waves or blocks)
     const dim3 grid(KSPLIT == 1 ? (groups + kWaves - 1) / kWaves : groups, a.n_batch > 1 ? a.n_batch : 1), block(kBlock);
@@ -569,9 +585,9 @@ int launch_nv(const GemvArgs& a, int pro, int epi, hipStream_t s) {
 #define OMX_GEMV_CASE(P, E)                                                                          \
     if (pro == P && epi == E) {                                                                      \
         if (tail && P == PRO_NONE)                                                                   \
-            OMX_LAUNCH_TIMED((gemv_kernel<NVW, KSPLIT, (E == EPI_SWIGLU ? (RB > 1 ? RB / 2 : 1) : RB), PRO_NONE, E, true>), grid, block, shmem, s, a); \
+            OMX_LAUNCH_TIMED((gemv_kernel<NVW, KSPLIT, (E == EPI_SWIGLU ? (RB > 1 ? RB / 2 : 1) : RB), PRO_NONE, E, true, F16>), grid, block, shmem, s, a); \
         else                                                                                         \
-            OMX_LAUNCH_TIMED((gemv_kernel<NVW, KSPLIT, (E == EPI_SWIGLU ? (RB > 1 ? RB / 2 : 1) : RB), P, E>), grid, block, shmem, s, a); \
+            OMX_LAUNCH_TIMED((gemv_kernel<NVW, KSPLIT, (E == EPI_SWIGLU ? (RB > 1 ? RB / 2 : 1) : RB), P, E, false, F16>), grid, block, shmem, s, a); \
         OMX_LAUNCH_CHECK();                                                                          \
         return 0;                                                                                    \
     }
@@ -581,12 +597,14 @@ int launch_nv(const GemvArgs& a, int pro, int epi, hipStream_t s) {
     OMX_GEMV_CASE(PRO_RMSNORM, EPI_SWIGLU)
     OMX_GEMV_CASE(PRO_NONE, EPI_SWIGLU)
     OMX_GEMV_CASE(PRO_RMSNORM, EPI_ARGMAX)
-    OMX_GEMV_CASE(PRO_NONE, EPI_F32)
-    if constexpr (KSPLIT == 1 && NVW <= 8) {
-        if (pro == PRO_ROUTE && epi == EPI_SWIGLU && !tail) {
-            OMX_LAUNCH_TIMED((gemv_kernel<NVW, KSPLIT, (RB > 1 ? RB / 2 : 1), PRO_ROUTE, EPI_SWIGLU>), grid, block, shmem, s, a);
-            OMX_LAUNCH_CHECK();
-            return 0;
+    if constexpr (!F16) {   // (bf16 only: the routing prologue and the f32 / peer output)
+        OMX_GEMV_CASE(PRO_NONE, EPI_F32)
+        if constexpr (KSPLIT == 1 && NVW <= 8) {
+            if (pro == PRO_ROUTE && epi == EPI_SWIGLU && !tail) {
+                OMX_LAUNCH_TIMED((gemv_kernel<NVW, KSPLIT, (RB > 1 ? RB / 2 : 1), PRO_ROUTE, EPI_SWIGLU>), grid, block, shmem, s, a);
+                OMX_LAUNCH_CHECK();
+                return 0;
+            }
         }
     }
 #undef OMX_GEMV_CASE
@@ -645,31 +663,47 @@ bool gemv_k_supported(int K, bool needs_full_vectors) {
     return K > 0 && K % 8 == 0 && K <= 65536;   // tuned kernels where they exist, the generic one otherwise
 }
 
+namespace {
+template <bool F16>
+int launch_tuned(const GemvArgs& a, int nv, int pro, int epi, hipStream_t s) {
+    switch (nv) {
+        // RB*NVW ~ 16 x 1-KiB loads in flight per wave per register set
+        case 1: return launch_nv<1, 1, 8, F16>(a, pro, epi, s);
+        case 2: return launch_nv<2, 1, 8, F16>(a, pro, epi, s);
+        case 3: return launch_nv<3, 1, 4, F16>(a, pro, epi, s);
+        case 4: return launch_nv<4, 1, 4, F16>(a, pro, epi, s);
+        case 6: return launch_nv<6, 1, 2, F16>(a, pro, epi, s);
+        case 7: return launch_nv<7, 1, 2, F16>(a, pro, epi, s);
+        case 8: return launch_nv<8, 1, 2, F16>(a, pro, epi, s);
+        case 12: return launch_nv<3, 4, 4, F16>(a, pro, epi, s);
+        case 16: return launch_nv<4, 4, 4, F16>(a, pro, epi, s);
+        case 24: return launch_nv<6, 4, 2, F16>(a, pro, epi, s);
+        case 28: return launch_nv<7, 4, 2, F16>(a, pro, epi, s);
+        case 32: return launch_nv<8, 4, 2, F16>(a, pro, epi, s);
+        case 40: return launch_nv<10, 4, 2, F16>(a, pro, epi, s);
+        default: return set_error("gemv: K=%d (K/512=%d) has no instantiated kernel", a.K, nv);
+    }
+}
+}  // namespace
+
 int launch_gemv(const GemvArgs& a_in, int pro, int epi, hipStream_t s) {
     GemvArgs a = a_in;
     OMX_REQUIRE(a.K > 0 && a.K % 8 == 0 && a.K <= 65536, "gemv: K=%d must be a positive multiple of 8 (at most 65536)", a.K);
     OMX_REQUIRE(a.N > 0, "gemv: N must be positive");
+    if (a.f16) {   // the float16 forms of a plain launch: every other combination is refused by name
+        OMX_REQUIRE(pro == PRO_NONE || pro == PRO_RMSNORM, "gemv: float16 takes PRO_NONE or PRO_RMSNORM (got prologue %d; PRO_ROUTE is bf16-only)", pro);
+        OMX_REQUIRE(epi == EPI_STORE || epi == EPI_RESIDUAL || epi == EPI_SWIGLU || epi == EPI_ARGMAX,
+                    "gemv: float16 takes EPI_STORE, EPI_RESIDUAL, EPI_SWIGLU or EPI_ARGMAX (got epilogue %d; EPI_F32 / peer are bf16-only)", epi);
+        OMX_REQUIRE(!a.peer, "gemv: float16 has no peer (tensor-parallel) output");
+        OMX_REQUIRE(a.n_batch <= 1 && !a.w_sel, "gemv: float16 has no batched or expert-selected launch");
+        OMX_REQUIRE(!a.x_partial, "gemv: float16 takes no x_partial (tensor-parallel / MoE fold)");
+        OMX_REQUIRE(!a.out_bias || epi == EPI_STORE, "gemv: out_bias rides on EPI_STORE only");
+    }
     const int nv = tuned_nv(a.K, pro == PRO_NONE && !a.x_partial);
     const bool t = nv != 0;
     a.rows_per_wave = resolve_rpw(a.N, a.K, epi, a.rows_per_wave, t);
-    if (!t) return launch_generic(a, pro, epi, s);
-    switch (nv) {
-        // RB*NVW ~ 16 x 1-KiB loads in flight per wave per register set
-        case 1: return launch_nv<1, 1, 8>(a, pro, epi, s);
-        case 2: return launch_nv<2, 1, 8>(a, pro, epi, s);
-        case 3: return launch_nv<3, 1, 4>(a, pro, epi, s);
-        case 4: return launch_nv<4, 1, 4>(a, pro, epi, s);
-        case 6: return launch_nv<6, 1, 2>(a, pro, epi, s);
-        case 7: return launch_nv<7, 1, 2>(a, pro, epi, s);
-        case 8: return launch_nv<8, 1, 2>(a, pro, epi, s);
-        case 12: return launch_nv<3, 4, 4>(a, pro, epi, s);
-        case 16: return launch_nv<4, 4, 4>(a, pro, epi, s);
-        case 24: return launch_nv<6, 4, 2>(a, pro, epi, s);
-        case 28: return launch_nv<7, 4, 2>(a, pro, epi, s);
-        case 32: return launch_nv<8, 4, 2>(a, pro, epi, s);
-        case 40: return launch_nv<10, 4, 2>(a, pro, epi, s);
-        default: return set_error("gemv: K=%d (K/512=%d) has no instantiated kernel", a.K, nv);
-    }
+    if (!t) return a.f16 ? launch_generic<true>(a, pro, epi, s) : launch_generic<false>(a, pro, epi, s);
+    return a.f16 ? launch_tuned<true>(a, nv, pro, epi, s) : launch_tuned<false>(a, nv, pro, epi, s);
 }
 
 }  // namespace omx

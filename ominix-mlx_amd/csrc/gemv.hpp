@@ -53,6 +53,11 @@ struct GemvArgs {
     // expert parallelism: only experts [w_sel_lo, w_sel_lo + w_sel_n) live on this rank (w_sel_n == 0: all of them); a batch
     // entry routed elsewhere does no work (its output is never read: the combine skips it too)
     int w_sel_lo, w_sel_n;
+    // float16 model (a dense float16 checkpoint): w*, x, norm_w, resid, out_bias and out hold float16 bits, every rounding point is
+    // float16 (the packed float16 GEMV's, quant.hip).  PRO_NONE / PRO_RMSNORM x EPI_STORE / RESIDUAL / SWIGLU / ARGMAX of a plain
+    // launch only: no routing prologue, no f32 / peer output, no batch / expert selection, no x_partial.  (It sits in the padding
+    // before out_bias: the struct, and so every bf16 kernel's argument layout, keeps its size.)
+    int f16;
     const bf16_t* out_bias;     // EPI_STORE: optional [N] added before the rounding (nn::Linear with bias = addmm, linear.rs:87-92)
     // optional timeline (tools/gemv_trace.py; only in -DOMX_GEMV_TRACE builds): thread 0 of block b stamps the 100 MHz wall clock into trace[b*4 + k] at
     // k = 0 first weight batch issued, 1 activation staged, 2 first batch reduced, 3 last store issued
@@ -77,6 +82,7 @@ struct GemvArgs {
     uint32_t* route_inds;
     bf16_t* route_scores;
 };
+static_assert(sizeof(GemvArgs) == 264, "GemvArgs: a new field changes every GEMV kernel's argument layout");
 bool gemv_route_supported(int K, int n_experts, int top_k);
 
 int launch_gemv(const GemvArgs& a, int pro, int epi, hipStream_t s);

@@ -159,6 +159,9 @@ extern "C" int omx_fill_uniform_2d(void* dst, int64_t rows, int64_t cols, int64_
         case OMX_BFLOAT16:
             fill_uniform_2d_kernel<OMX_BFLOAT16><<<blocks, 256, 0, s>>>((omx::bf16_t*)dst, rows, cols, ld_full, row0, col0, seed, amp, offset);
             break;
+        case OMX_FLOAT16:
+            fill_uniform_2d_kernel<OMX_FLOAT16><<<blocks, 256, 0, s>>>((omx::f16_t*)dst, rows, cols, ld_full, row0, col0, seed, amp, offset);
+            break;
         case OMX_FLOAT32:
             fill_uniform_2d_kernel<OMX_FLOAT32><<<blocks, 256, 0, s>>>((float*)dst, rows, cols, ld_full, row0, col0, seed, amp, offset);
             break;

@@ -248,8 +248,24 @@ int omx_linear(void* out, const void* x, const void* w, const void* bias, int M,
     OMX_REQUIRE(dtype == OMX_BFLOAT16 || dtype == OMX_FLOAT32 || dtype == OMX_FLOAT16, "omx_linear: bfloat16, float16 and float32 are implemented (got dtype %d)", (int)dtype);
     if (M == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
+    if (dtype == OMX_FLOAT16 && M <= 8) {
+        // decode sizes: the HBM-streaming GEMV's float16 form, one launch per row (f32 accumulation, one rounding to float16; the bias
+        // added before it)
+        OMX_REQUIRE(K % 8 == 0 && K <= 65536, "omx_linear: float16 with at most 8 rows takes K %% 8 == 0 and K <= 65536 (M=%d K=%d)", M, K);
+        for (int m = 0; m < M; ++m) {
+            omx::GemvArgs a = {};
+            a.w0 = (const omx::bf16_t*)w;
+            a.n0 = N; a.N = N; a.K = K;
+            a.x = (const omx::bf16_t*)x + (size_t)m * K;
+            a.out = (omx::bf16_t*)out + (size_t)m * N;
+            a.out_bias = (const omx::bf16_t*)bias;
+            a.f16 = 1;
+            if (omx::launch_gemv(a, omx::PRO_NONE, omx::EPI_STORE, s)) return 1;
+        }
+        return 0;
+    }
     if (dtype == OMX_FLOAT16) {   // the eight-wave kernel's float16 form (round 4): float16 operands, f32 accumulation, one rounding to float16
-        OMX_REQUIRE(M > 8 && K % 64 == 0, "omx_linear: float16 takes more than 8 rows and K %% 64 == 0 (M=%d K=%d)", M, K);
+        OMX_REQUIRE(K % 64 == 0, "omx_linear: float16 with more than 8 rows takes K %% 64 == 0 (M=%d K=%d)", M, K);
         const bool was = omx::gemm_set_f16(true);
         const int rc = omx::launch_gemm_bf16((omx::bf16_t*)out, (const omx::bf16_t*)x, (const omx::bf16_t*)w, (const omx::bf16_t*)bias, M, N, K, s);
         omx::gemm_set_f16(was);

@@ -22,7 +22,8 @@ class Qwen3Config(ctypes.Structure):
                 ("tie_word_embeddings", c_int), ("max_context", c_int), ("tp_rank", c_int), ("tp_size", c_int),
                 ("quant_bits", c_int), ("quant_group", c_int), ("num_experts", c_int), ("num_experts_per_tok", c_int),
                 ("moe_intermediate_size", c_int), ("moe_mode", c_int), ("norm_topk_prob", c_int), ("no_qk_norm", c_int),
-                ("ep_rank", c_int), ("ep_size", c_int), ("attention_bias", c_int), ("quant_scales_f16", c_int)]
+                ("ep_rank", c_int), ("ep_size", c_int), ("attention_bias", c_int), ("quant_scales_f16", c_int),
+                ("float16_weights", c_int)]
 
 
 ENGINE_SIGNATURES = {
@@ -56,6 +57,9 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_verify_logits": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "omx_qwen3_trim": (c_int, [c_void_p, c_int, c_uint32]),
     "omx_qwen3_get_weight": (c_int, [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t)]),
+    # test hook of the dense decode GEMV (csrc/gemv.hip): one launch of a prologue / epilogue form, bf16 or float16
+    "omx_debug_gemv": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_float, c_int, c_void_p]),
+    "omx_debug_gemv_grid": (c_int, [c_int, c_int]),
     "omx_bench_qwen3_per_op": (c_int, [c_void_p, ctypes.POINTER(Qwen3Config), ctypes.POINTER(c_uint32), c_int, c_int, ctypes.POINTER(c_uint32),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }
@@ -79,6 +83,16 @@ def rope_scale_from_config(rope_scaling: Optional[dict]) -> float:
         except (TypeError, ValueError):
             raise OmxError('key "factor" is not a valid float')
     raise OmxError(f"Unsupported RoPE type {rope_type!r}")
+
+
+def dense_dtype_is_f16(dtype) -> bool:
+    """engine.Model(dtype=...): True for float16, False for bfloat16; anything else is refused."""
+    d = str(dtype).lower()
+    if d in ("float16", "f16", "half"):
+        return True
+    if d in ("bfloat16", "bf16"):
+        return False
+    raise OmxError(f"Model: dtype {dtype!r} (bfloat16 or float16)")
 
 
 def expected_shape(c: Qwen3Config, name: str):
@@ -146,14 +160,17 @@ class Model:
                  num_key_value_heads, head_dim, vocab_size, rms_norm_eps=1e-6, rope_theta=1e6,
                  tie_word_embeddings=False, rope_scaling=None, max_context=4096, tp_rank=0, tp_size=1, quantization=None,
                  num_experts=0, num_experts_per_tok=0, moe_intermediate_size=0, moe_mode="qwen3_moe", norm_topk_prob=False,
-                 qk_norm=True, ep_rank=0, ep_size=1, attention_bias=False, **_ignored):
+                 qk_norm=True, ep_rank=0, ep_size=1, attention_bias=False, dtype="bfloat16", **_ignored):
         """quantization: config.json's {"bits": 2|3|4|5|6|8, "group_size": 64} (model.rs:63) or None for a bf16 checkpoint (2, 3,
         5 and 6 bits: dense single-rank models only); + "scales_dtype":
         "float16" when the checkpoint's scales / biases are float16 (loader.load_model reads it off the tensors' dtype).
         num_experts > 0: sparse-MoE feed-forward in every layer -- moe_mode "qwen3_moe" (qwen3_moe.rs ModelArgs :60-87) or
-        "mixtral" (mixtral-mlx ModelArgs :54-80, with qk_norm=False and moe_intermediate_size = intermediate_size)."""
+        "mixtral" (mixtral-mlx ModelArgs :54-80, with qk_norm=False and moe_intermediate_size = intermediate_size).
+        dtype: the weight dtype of a dense (unquantised) checkpoint -- "bfloat16" (default) or "float16"; a float16 model runs in
+        float16 end to end, like MLX runs a checkpoint saved in float16 (single rank, dense MLP, head_dim 128)."""
         require_device()
         q = quantization or {}
+        f16_weights = dense_dtype_is_f16(dtype)
         self.cfg = Qwen3Config(hidden_size, num_hidden_layers, intermediate_size, num_attention_heads,
                                num_key_value_heads, head_dim, vocab_size, rms_norm_eps, rope_theta,
                                rope_scale_from_config(rope_scaling), int(bool(tie_word_embeddings)), max_context,
@@ -161,7 +178,8 @@ class Model:
                                int(num_experts), int(num_experts_per_tok), int(moe_intermediate_size),
                                {"mixtral": 0, "qwen3_moe": 1}[moe_mode], int(bool(norm_topk_prob)), int(not qk_norm),
                                int(ep_rank), int(ep_size), int(bool(attention_bias)),
-                               int(str(q.get("scales_dtype", "bfloat16")).lower() in ("float16", "f16", "half")))
+                               int(str(q.get("scales_dtype", "bfloat16")).lower() in ("float16", "f16", "half")),
+                               int(f16_weights))
         self._h = c_void_p()
         check(lib.omx_qwen3_create(ctypes.byref(self._h), ctypes.byref(self.cfg)))
         self._keep = []
@@ -177,6 +195,11 @@ class Model:
         # layered on it) is being torn down
         if sys is not None and not sys.is_finalizing():   # (module globals are already None late in shutdown)
             self.close()
+
+    @property
+    def f16(self) -> bool:
+        """The model runs in float16 (a packed checkpoint with float16 triplets, or dense float16 weights)."""
+        return bool(self.cfg.quant_scales_f16 or self.cfg.float16_weights)
 
     @property
     def vocab_local(self) -> int:
@@ -216,10 +239,10 @@ class Model:
                 raise OmxError(f"{name}: a quantized weight must be packed uint32, found {dt}")
             # quantized checkpoints: "<prefix>.weight" is packed uint32 (ops/quantization.rs:41-84), scales / biases bf16; in a float16
             # checkpoint every other tensor (the norm weights) is float16 too -- the model then runs in float16 end to end, like in MLX
-            if self.cfg.quant_scales_f16 and dt != np.uint32 and type(arr).__name__ == "Bf16Bits":
+            if self.f16 and dt != np.uint32 and type(arr).__name__ == "Bf16Bits":
                 # a BF16 tensor of a checkpoint whose triplets are float16 (loader.read_safetensors hands raw bits): its VALUES go up as float16
                 arr = (np.asarray(arr).astype(np.uint32) << np.uint32(16)).view(np.float32)
-            t = Tensor.from_numpy(arr, "u32" if dt == np.uint32 else "f16" if self.cfg.quant_scales_f16 else "bf16")
+            t = Tensor.from_numpy(arr, "u32" if dt == np.uint32 else "f16" if self.f16 else "bf16")
             self._keep.append(t)
             check(lib.omx_qwen3_set_weight(self._h, name.encode(), t.ptr, t.nbytes))
 
@@ -241,7 +264,7 @@ class Model:
         from .ops import Tensor
         ids = np.ascontiguousarray(np.asarray(input_ids, dtype=np.uint32).ravel())
         taps = (c_int * len(extract_layers))(*[int(t) for t in extract_layers])
-        out = Tensor((ids.size, len(extract_layers) * self.cfg.hidden_size), "f16" if self.cfg.quant_scales_f16 else "bf16")
+        out = Tensor((ids.size, len(extract_layers) * self.cfg.hidden_size), "f16" if self.f16 else "bf16")
         am = None
         if attention_mask is not None:
             am = np.ascontiguousarray(np.asarray(attention_mask).ravel() != 0, dtype=np.uint8)
@@ -350,7 +373,7 @@ class Model:
     def last_logits(self) -> np.ndarray:
         raw = np.empty(self.vocab_local, dtype=np.uint16)
         check(lib.omx_qwen3_last_logits(self._h, raw.ctypes.data, raw.size))
-        if self.cfg.quant_scales_f16:      # a float16 model's logits are float16
+        if self.f16:      # a float16 model's logits are float16
             return raw.view(np.float16).astype(np.float32)
         return (raw.astype(np.uint32) << np.uint32(16)).view(np.float32)
 

@@ -141,11 +141,29 @@ def model_args(model_dir: str) -> dict:
     return args
 
 
-def load_model(model_dir: str, max_context: int = 4096, **overrides):
-    """qwen3_mlx::load_model: config.json + shards -> a ready engine.Model (bf16 or MLX-quantized)."""
+def dense_dtype(weights: Dict[str, np.ndarray], args: dict) -> str:
+    """The dtype engine.Model runs a checkpoint in: "float16" for an unquantised checkpoint whose Linear / embedding weights
+    (the 2-D ".weight" tensors) are all F16 and whose shape the float16 engine runs (single rank, dense MLP, no q/k/v bias,
+    head_dim 128) -- MLX keeps a model in the dtype it was saved in (qwen3-mlx/src/model.rs:509-560); "bfloat16" otherwise
+    (a quantized checkpoint decides its activation dtype by its scales instead)."""
+    if args.get("quantization") is not None:
+        return "bfloat16"
+    mats = [v for k, v in weights.items() if k.endswith(".weight") and np.ndim(v) >= 2]
+    if not mats or any(np.asarray(v).dtype != np.float16 for v in mats):
+        return "bfloat16"
+    if args.get("num_experts", 0) or args.get("attention_bias") or args.get("head_dim") != 128 or args.get("tp_size", 1) > 1:
+        return "bfloat16"   # (the float16 engine refuses these: such a checkpoint keeps the bf16 conversion)
+    return "float16"
+
+
+def load_model(model_dir: str, max_context: int = 4096, dtype=None, **overrides):
+    """qwen3_mlx::load_model: config.json + shards -> a ready engine.Model (bf16, float16 or MLX-quantized).
+    dtype: None = the checkpoint's own (dense_dtype: an F16 checkpoint runs in float16); "bfloat16" converts an F16 checkpoint
+    to bf16 as before."""
     from . import engine
     args = dict(model_args(model_dir), max_context=max_context, **overrides)
     weights = load_all_weights(model_dir)
+    args["dtype"] = dense_dtype(weights, args) if dtype is None else dtype
     if args.get("moe_mode") == "mixtral":
         weights = sanitize_weights(weights, args["num_hidden_layers"], args["num_experts"])
     if args.get("quantization") is not None and any(k.endswith(".scales") and np.asarray(v).dtype == np.float16 for k, v in weights.items()):
