@@ -261,6 +261,39 @@ int omx_debug_gemv(void* out, unsigned long long* argmax_slot, const void* x, co
                    const void* w0, const void* w1, const void* w2, int n0, int n1, int N, int K, int pro, int epi, int f16, float eps,
                    int single_round, omx_stream stream);
 int omx_debug_gemv_grid(int N, int K);
+/* test hook of the dense decode GEMV, every field of a plain or batched launch (no routing prologue, no peer output).  In: the fields
+ * of omx_debug_gemv plus rows_per_wave (0: the tuned choice), row_offset (EPI_ARGMAX), x_partial [x_partial_n][K] f32 with x_out,
+ * out_scale (EPI_F32, [n_batch] bf16), the batch fields (n_batch, x_div, x_bstride elements, out_bstride_bytes, w_sel [n_batch]
+ * expert ids, w_estride elements, w_sel_lo / w_sel_n) and argmax_slot_n (capacity of argmax_slot; a launch needing more blocks is
+ * refused).  Out: the route launch_gemv takes (nv: tuned width class K/512 or 0 for the generic kernel, ksplit waves per row, tail:
+ * masked last vectors), the resolved rows_per_wave and the blocks along x (= argmax partials written).  dry_run != 0: only the route,
+ * nothing is launched (no device needed).  Synchronises the stream. */
+typedef struct omx_gemv_ex_ {
+    void* out; unsigned long long* argmax_slot; int argmax_slot_n;
+    const void* x; const void* norm_w; const void* resid; const void* bias;
+    const void* w0; const void* w1; const void* w2; int n0, n1, N, K, pro, epi, f16; float eps; int single_round;
+    int rows_per_wave, row_offset;
+    const float* x_partial; int x_partial_n; void* x_out; const void* out_scale;
+    int n_batch, x_div; long long x_bstride, out_bstride_bytes; const unsigned* w_sel; long long w_estride; int w_sel_lo, w_sel_n;
+    int dry_run;
+    int route_nv, route_ksplit, route_tail, route_rows_per_wave, route_blocks;   /* out */
+} omx_gemv_ex;
+int omx_debug_gemv_ex(omx_gemv_ex* a, omx_stream stream);
+/* test hook of the step attention (csrc/attn_step.hip): ONE launch_attn_step on caller-owned buffers, without the O projection.
+ * qkv [H*D | Hkv*D | Hkv*D] raw, K / V slabs [Hkv, cap, D], q/k norm weights [D] (both null: no q/k norm), rope_cur [D] f32
+ * cos | sin of `pos`, granules [granules_n] (kept by the caller: leftovers of earlier calls stay, as in the engine), tag
+ * seq * tag_mul + tag_add.  Split plan: chunk / nsplit when both > 0, else attn_step_plan(tk_max) (the engine's rule); refused on the
+ * host when it does not cover pos + 1, when pos >= cap or when the granules do not fit.  Out: out [H*D], the plan used, abort_flag.
+ * Synchronises the stream. */
+typedef struct omx_attn_step_dbg_ {
+    const void* qkv; void* k; void* v; int H, Hkv, D, cap; float scale, eps;
+    const void* q_norm_w; const void* k_norm_w; const float* rope_cur;
+    void* granules; long long granules_n;
+    int pos; unsigned seq, tag_mul, tag_add; int f16;
+    int chunk, nsplit, tk_max;   /* in: plan (or tk_max); out: the plan used */
+    void* out; unsigned abort_flag;   /* out */
+} omx_attn_step_dbg;
+int omx_debug_attn_step(omx_attn_step_dbg* a, omx_stream stream);
 int omx_qwen3_stream(omx_qwen3 m, omx_stream* s);
 /* algorithmic HBM bytes of ONE decode step at context length ctx (SURVEY.md 8d formula)             */
 int omx_qwen3_step_bytes(omx_qwen3 m, int ctx, double* bytes);

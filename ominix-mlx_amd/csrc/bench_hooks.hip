@@ -5,6 +5,7 @@
 
 #include "gemm.hpp"
 #include "gemv.hpp"
+#include "attn.hpp"
 
 extern "C" int omx_bench_gemv(int N, int K, int pro, int epi, int rows_per_wave, int n_copies, int iters,
                               float* avg_ms) {
@@ -435,6 +436,77 @@ extern "C" int omx_debug_gemv(void* out, unsigned long long* argmax_slot, const 
     return rc;
 }
 extern "C" int omx_debug_gemv_grid(int N, int K) { return omx::gemv_grid(N, K, omx::EPI_ARGMAX, 0); }
+
+extern "C" int omx_debug_gemv_ex(omx_gemv_ex* d, void* stream) {
+    using namespace omx;
+    OMX_REQUIRE(d && d->N > 0 && d->K > 0, "omx_debug_gemv_ex: bad arguments");
+    OMX_REQUIRE(d->pro == PRO_NONE || d->pro == PRO_RMSNORM, "omx_debug_gemv_ex: prologue %d (PRO_ROUTE is not taken here)", d->pro);
+    GemvArgs a = {};
+    a.w0 = (const bf16_t*)d->w0; a.w1 = (const bf16_t*)d->w1; a.w2 = (const bf16_t*)d->w2;
+    if (d->epi == EPI_SWIGLU || !d->w1) {
+        a.n0 = d->N;
+    } else {
+        a.n0 = d->n0; a.n1 = d->w2 ? d->n1 : d->N - d->n0; a.n2 = d->w2 ? d->N - d->n0 - d->n1 : 0;
+    }
+    a.N = d->N; a.K = d->K;
+    a.x = (const bf16_t*)d->x; a.norm_w = (const bf16_t*)d->norm_w; a.eps = d->eps; a.resid = (const bf16_t*)d->resid;
+    a.out = d->out; a.out_bias = (const bf16_t*)d->bias; a.argmax_slot = d->argmax_slot; a.swiglu_single_round = d->single_round;
+    a.f16 = d->f16;
+    a.rows_per_wave = d->rows_per_wave; a.row_offset = d->row_offset;
+    a.x_partial = d->x_partial; a.x_partial_n = d->x_partial_n; a.x_out = (bf16_t*)d->x_out; a.out_scale = (const bf16_t*)d->out_scale;
+    a.n_batch = d->n_batch; a.x_div = d->x_div; a.x_bstride = (size_t)d->x_bstride; a.out_bstride_bytes = (size_t)d->out_bstride_bytes;
+    a.w_sel = d->w_sel; a.w_estride = (size_t)d->w_estride; a.w_sel_lo = d->w_sel_lo; a.w_sel_n = d->w_sel_n;
+    const GemvRoute r = gemv_route(a, d->pro, d->epi);
+    d->route_nv = r.nv; d->route_ksplit = r.ksplit; d->route_tail = r.tail; d->route_rows_per_wave = r.rows_per_wave; d->route_blocks = r.blocks;
+    if (d->dry_run) return 0;
+    OMX_REQUIRE(d->out && d->x && d->w0, "omx_debug_gemv_ex: out, x and w0 are required");
+    OMX_REQUIRE(d->epi != EPI_ARGMAX || (d->argmax_slot && r.blocks <= d->argmax_slot_n),
+                "omx_debug_gemv_ex: the launch writes %d argmax partials, the slot holds %d", r.blocks, d->argmax_slot_n);
+    OMX_REQUIRE(!(d->n_batch > 1 || d->w_sel) || (d->x_div >= 1 && d->out_bstride_bytes > 0), "omx_debug_gemv_ex: batched launch needs x_div and out_bstride_bytes");
+    OMX_REQUIRE(!d->x_partial || d->x_partial_n >= 1, "omx_debug_gemv_ex: x_partial needs x_partial_n >= 1");
+    const int rc = launch_gemv(a, d->pro, d->epi, (hipStream_t)stream);
+    OMX_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));
+    return rc;
+}
+
+extern "C" int omx_debug_attn_step(omx_attn_step_dbg* d, void* stream) {
+    using namespace omx;
+    OMX_REQUIRE(d && d->qkv && d->k && d->v && d->rope_cur && d->granules && d->out, "omx_debug_attn_step: missing buffer");
+    OMX_REQUIRE(d->H > 0 && d->Hkv > 0 && d->H % d->Hkv == 0 && (d->D == 64 || d->D == 128) && d->cap > 0,
+                "omx_debug_attn_step: bad geometry (H %d, Hkv %d, D %d, cap %d)", d->H, d->Hkv, d->D, d->cap);
+    OMX_REQUIRE(d->pos >= 0 && d->pos < d->cap, "omx_debug_attn_step: position %d outside the cache of %d rows", d->pos, d->cap);
+    OMX_REQUIRE(!d->q_norm_w == !d->k_norm_w, "omx_debug_attn_step: q and k norm weights go together");
+    const int G = d->H / d->Hkv;
+    if (d->chunk <= 0 || d->nsplit <= 0) {
+        OMX_REQUIRE(d->tk_max > 0, "omx_debug_attn_step: give chunk and nsplit, or tk_max");
+        attn_step_plan(d->tk_max, d->Hkv, G, d->D, &d->chunk, &d->nsplit);
+    }
+    OMX_REQUIRE((long long)d->chunk * d->nsplit >= (long long)d->pos + 1,
+                "omx_debug_attn_step: plan (chunk %d, %d splits) does not cover position %d", d->chunk, d->nsplit, d->pos);
+    OMX_REQUIRE((long long)d->H * d->nsplit * (d->D + 2) <= d->granules_n, "omx_debug_attn_step: %lld granules, the plan needs %lld",
+                d->granules_n, (long long)d->H * d->nsplit * (d->D + 2));
+    hipStream_t s = (hipStream_t)stream;
+    unsigned* st = nullptr;   // pos | seq | abort flag
+    OMX_HIP_CHECK(hipMalloc((void**)&st, 3 * sizeof(unsigned)));
+    const unsigned host[3] = {(unsigned)d->pos, d->seq, 0u};
+    OMX_HIP_CHECK(hipMemcpyAsync(st, host, sizeof(host), hipMemcpyHostToDevice, s));
+    AttnStepArgs a = {};
+    a.qkv = (const bf16_t*)d->qkv; a.k = (bf16_t*)d->k; a.v = (bf16_t*)d->v; a.kv_head_stride = (int64_t)d->cap * d->D;
+    a.H = d->H; a.Hkv = d->Hkv; a.cap = d->cap; a.scale = d->scale; a.eps = d->eps;
+    a.q_norm_w = (const bf16_t*)d->q_norm_w; a.k_norm_w = (const bf16_t*)d->k_norm_w; a.rope_cur = d->rope_cur;
+    a.pos_ptr = (const int*)st; a.seq_ptr = st + 1; a.tag_mul = d->tag_mul; a.tag_add = d->tag_add;
+    a.chunk = d->chunk; a.nsplit = d->nsplit; a.ws = (uint64_t*)d->granules; a.out = (bf16_t*)d->out; a.abort_flag = st + 2;
+    a.f16 = d->f16;
+    int rc = launch_attn_step(a, d->D, s);
+    unsigned back[3] = {0u, 0u, 0u};
+    if (rc == 0) {
+        OMX_HIP_CHECK(hipMemcpyAsync(back, st, sizeof(back), hipMemcpyDeviceToHost, s));
+        OMX_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    d->abort_flag = back[2];
+    OMX_HIP_CHECK(hipFree(st));
+    return rc;
+}
 
 /* test hook of qgemv_rows.hip: M activation rows x [M, K] against n_members packed matrices (w / sc / bi / n: arrays of n_members; a
  * q | k | v stack, or gate and up for EPI_SWIGLU), out [M, N] (resid [M, N]).  use_sb: build the interleaved scale | bias words first.

@@ -658,6 +658,19 @@ int gemv_grid(int N, int K, int epi, int rows_per_wave) {
     return (t && ((K + 511) / 512) > 8) ? groups : (groups + kWaves - 1) / kWaves;
 }
 
+// the kernel launch_gemv picks for `a` (pro, epi), without launching: the tuned width class (0: the generic kernel), the waves per row
+// (4: K split), whether the last vector rows are masked, the resolved rows_per_wave and the block count along x
+GemvRoute gemv_route(const GemvArgs& a, int pro, int epi) {
+    GemvRoute r = {};
+    r.nv = tuned_nv(a.K, pro == PRO_NONE && !a.x_partial);
+    r.ksplit = r.nv > 8 ? 4 : 1;
+    r.tail = r.nv != 0 && a.K < r.nv * 512;
+    r.rows_per_wave = resolve_rpw(a.N, a.K, epi, a.rows_per_wave, r.nv != 0);
+    const int groups = (a.N + r.rows_per_wave - 1) / r.rows_per_wave;
+    r.blocks = r.ksplit > 1 ? groups : (groups + kWaves - 1) / kWaves;
+    return r;
+}
+
 bool gemv_k_supported(int K, bool needs_full_vectors) {
     (void)needs_full_vectors;
     return K > 0 && K % 8 == 0 && K <= 65536;   // tuned kernels where they exist, the generic one otherwise

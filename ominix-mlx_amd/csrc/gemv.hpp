@@ -88,6 +88,10 @@ bool gemv_route_supported(int K, int n_experts, int top_k);
 int launch_gemv(const GemvArgs& a, int pro, int epi, hipStream_t s);
 // number of blocks launch_gemv will use (== entries written to argmax_slot); resolves rows_per_wave
 int gemv_grid(int N, int K, int epi, int rows_per_wave);
+// the kernel launch_gemv would run for a launch (test hooks): tuned width class nv (K/512 vectors per row; 0 = the generic kernel),
+// ksplit waves per row, masked tail, resolved rows_per_wave, blocks along x (== entries written to argmax_slot)
+struct GemvRoute { int nv, ksplit, tail, rows_per_wave, blocks; };
+GemvRoute gemv_route(const GemvArgs& a, int pro, int epi);
 // true when launch_gemv has a kernel for contraction width K (K not a multiple of 512 only without a prologue)
 bool gemv_k_supported(int K, bool needs_full_vectors);
 

@@ -26,6 +26,30 @@ class Qwen3Config(ctypes.Structure):
                 ("float16_weights", c_int)]
 
 
+class GemvEx(ctypes.Structure):
+    """omx_gemv_ex: every field of one dense decode GEMV launch (omx_debug_gemv_ex); route_* are filled in by the call."""
+    _fields_ = [("out", c_void_p), ("argmax_slot", c_void_p), ("argmax_slot_n", c_int),
+                ("x", c_void_p), ("norm_w", c_void_p), ("resid", c_void_p), ("bias", c_void_p),
+                ("w0", c_void_p), ("w1", c_void_p), ("w2", c_void_p), ("n0", c_int), ("n1", c_int), ("N", c_int), ("K", c_int),
+                ("pro", c_int), ("epi", c_int), ("f16", c_int), ("eps", c_float), ("single_round", c_int),
+                ("rows_per_wave", c_int), ("row_offset", c_int),
+                ("x_partial", c_void_p), ("x_partial_n", c_int), ("x_out", c_void_p), ("out_scale", c_void_p),
+                ("n_batch", c_int), ("x_div", c_int), ("x_bstride", ctypes.c_longlong), ("out_bstride_bytes", ctypes.c_longlong),
+                ("w_sel", c_void_p), ("w_estride", ctypes.c_longlong), ("w_sel_lo", c_int), ("w_sel_n", c_int),
+                ("dry_run", c_int),
+                ("route_nv", c_int), ("route_ksplit", c_int), ("route_tail", c_int), ("route_rows_per_wave", c_int), ("route_blocks", c_int)]
+
+
+class AttnStepDbg(ctypes.Structure):
+    """omx_attn_step_dbg: one step-attention launch on caller-owned buffers (omx_debug_attn_step); chunk / nsplit / abort_flag
+    come back filled in."""
+    _fields_ = [("qkv", c_void_p), ("k", c_void_p), ("v", c_void_p), ("H", c_int), ("Hkv", c_int), ("D", c_int), ("cap", c_int),
+                ("scale", c_float), ("eps", c_float), ("q_norm_w", c_void_p), ("k_norm_w", c_void_p), ("rope_cur", c_void_p),
+                ("granules", c_void_p), ("granules_n", ctypes.c_longlong),
+                ("pos", c_int), ("seq", c_uint32), ("tag_mul", c_uint32), ("tag_add", c_uint32), ("f16", c_int),
+                ("chunk", c_int), ("nsplit", c_int), ("tk_max", c_int), ("out", c_void_p), ("abort_flag", c_uint32)]
+
+
 ENGINE_SIGNATURES = {
     "omx_fill_uniform_2d": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64, c_uint32, c_float, c_float, c_int, c_void_p]),
@@ -60,6 +84,10 @@ ENGINE_SIGNATURES = {
     # test hook of the dense decode GEMV (csrc/gemv.hip): one launch of a prologue / epilogue form, bf16 or float16
     "omx_debug_gemv": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_float, c_int, c_void_p]),
     "omx_debug_gemv_grid": (c_int, [c_int, c_int]),
+    # ... every field of the launch (rows_per_wave, argmax row_offset, x_partial fold, EPI_F32 out_scale, batched / expert-selected
+    # entries) and the route it takes; the step attention (csrc/attn_step.hip) on caller-owned buffers
+    "omx_debug_gemv_ex": (c_int, [ctypes.POINTER(GemvEx), c_void_p]),
+    "omx_debug_attn_step": (c_int, [ctypes.POINTER(AttnStepDbg), c_void_p]),
     "omx_bench_qwen3_per_op": (c_int, [c_void_p, ctypes.POINTER(Qwen3Config), ctypes.POINTER(c_uint32), c_int, c_int, ctypes.POINTER(c_uint32),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

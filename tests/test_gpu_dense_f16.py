@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import ref_core as rc
+from oracle import ref_decode as rd
 from oracle import ref_qwen3 as rq
 from oracle import synth
 
@@ -28,12 +29,11 @@ def lib(omx):
 
 def ulp16(v):
     """float16 ulp at |v| (subnormal spacing 2^-24 below 2^-14)."""
-    a = np.maximum(np.abs(np.asarray(v, np.float64)), 2.0 ** -14)
-    return 2.0 ** (np.floor(np.log2(a)) - 10)
+    return rd.ulp16(v, "f16")
 
 
 def f16(v):
-    return np.asarray(v, np.float64).astype(np.float32).astype(np.float16).astype(np.float64)
+    return rd.rnd(v, "f16")
 
 
 def rand_f16(rng, shape, lo_exp=8, hi_exp=14):
@@ -44,23 +44,12 @@ def rand_f16(rng, shape, lo_exp=8, hi_exp=14):
     return bits.view(np.float16)
 
 
-def rows_dot(W, x, chunk=8192):
-    """exact W @ x (float64) and sum |W| |x| per row, chunked (the vocabulary-sized matrix does not fit in float64 at once)"""
-    xd, xa = x.astype(np.float64), np.abs(x.astype(np.float64))
-    out, mag = np.empty(W.shape[0]), np.empty(W.shape[0])
-    for r in range(0, W.shape[0], chunk):
-        Wd = W[r:r + chunk].astype(np.float64)
-        out[r:r + chunk] = Wd @ xd
-        mag[r:r + chunk] = np.abs(Wd) @ xa
-    return out, mag
+rows_dot = rd.rows_dot   # exact W @ x and sum |W| |x| per row (oracle/ref_decode.py, shared with the bf16 GEMV tests)
 
 
 def rmsnorm_f16(x, nw):
     """the kernel's prologue: f32 sum of squares, rstd = 1/sqrt(ss/K + eps), xn = f16((x * rstd) * w) in f32 arithmetic"""
-    x32, w32 = x.astype(np.float32), nw.astype(np.float32)
-    ss = np.float32(np.sum(x32.astype(np.float64) ** 2))
-    rstd = np.float32(1.0) / np.sqrt(ss / np.float32(x.size) + np.float32(EPS))
-    return ((x32 * rstd) * w32).astype(np.float16)
+    return rd.rmsnorm16(x, nw, EPS, "f16").astype(np.float16)
 
 
 def run_gemv(omx, lib, mats, x, pro, epi, nw=None, resid=None, bias=None, single_round=0):
@@ -87,17 +76,12 @@ def run_gemv(omx, lib, mats, x, pro, epi, nw=None, resid=None, bias=None, single
 
 def check_plain(got, exact, mag, K, extra=0.0):
     """|got - f16(exact)| <= 1/2 ulp_f16 + the f32 accumulation bound K 2^-24 sum|x w| (+ the prologue's rounding flips)"""
-    acc = K * U24 * mag + extra
-    err = np.abs(got - exact)
-    tol = 0.5 * ulp16(np.abs(exact) + acc) + acc
-    bad = np.nonzero(err > tol)[0]
-    assert bad.size == 0, f"{bad.size} rows off, e.g. row {bad[0]}: got {got[bad[0]]} exact {exact[bad[0]]} tol {tol[bad[0]]}"
-    assert np.array_equal(got, f16(got)), "outputs must be float16 values"
+    rd.check_plain(got, exact, mag, K, extra, "f16")
 
 
 def flip_slack(W, xn):
     """RMSNorm output rounding may flip a few float16 roundings of xn against the host's f32 rstd: 4 flips of the widest ulp"""
-    return 4.0 * ulp16(np.abs(xn.astype(np.float64)).max()) * np.abs(W.astype(np.float32)).max(axis=1)
+    return rd.flip_slack(W, xn, "f16")
 
 
 SHAPES = {   # Qwen3-8B decode widths, plus shapes that take the generic kernel (K not a multiple of 512 with a prologue) or a tail
