@@ -141,6 +141,40 @@ int omx_random_normal(float* out, const uint32_t* key, int64_t n, float loc, flo
 int omx_random_categorical(uint32_t* out, const void* logits, int64_t rows, int n, int num_samples, float inv_temp,
                            const uint32_t* key, omx_dtype dtype, omx_stream stream);
 
+/* ---- filtered sampling (csrc/sample_filter.hip): what the reference's generation loops do beside the 19-line sampler --
+ *      funasr-qwen4b-mlx/src/model.rs:1333-1383 (sample_top_k_p: presence penalty, top-k), step-audio2-mlx/src/llm.rs:440-474
+ *      (apply_repetition_penalty), gpt-sovits-mlx/src/sampling.rs:122-215 (repetition penalty, top-p, temperature, top-k).
+ *      The rule, one IEEE float32 operation per element and step, for a row of V logits and a set `seen` of token ids:
+ *        1. x = f32(logit)
+ *        2. repetition_penalty r != 1, v seen:  x = x > 0 ? x / r : x * r          (step-audio2)
+ *        3. presence_penalty q != 0, v seen:    x = x - q                          (funasr-qwen4b; with both set: 2 then 3, this
+ *                                                                                   project's choice -- the reference never sets both)
+ *        4. y = x * (1/T), 1/T rounded to f32 first (as omx_random_categorical)
+ *        5. top_k (0 or >= V: off): keep y >= the k-th largest y; ties at the threshold are ALL kept (the reference's `ge`)
+ *        6. top_p (1: off) on the survivors of 5 (temperature, top-k, top-p: the HF / vLLM order): with Z = sum exp(y - max) over
+ *           them, keep v iff the mass of survivors with y STRICTLY greater than y_v is < top_p * Z.  A tie group stays or goes whole,
+ *           the maximum always stays.  (gpt-sovits-mlx/src/sampling.rs:180-203 drops a token when the INCLUSIVE mass exceeds p,
+ *           which depends on the order of equal values and can drop every token: not reproduced, on purpose.)
+ *        7. token = argmax over the kept set of y + gumbel(word r*V + v of a rows*V-word draw from key), first index on ties:
+ *           with every filter and penalty off, omx_random_categorical bit for bit.
+ *      temperature 0: argmax of x after steps 2-3 (no key needed).  Masses are summed exactly (2^-40 fixed point, 64-bit).       */
+typedef struct omx_sampling_ {
+    float temperature;          /* >= 0 */
+    int32_t top_k;              /* 0 = off */
+    float top_p;                /* in (0, 1]; 1 = off */
+    float repetition_penalty;   /* > 0; 1 = off */
+    float presence_penalty;     /* 0 = off */
+} omx_sampling;
+/* seen: V bytes, non-zero = the id was generated (NULL: none).  thr_out [rows] (nullable): the final threshold on y, -inf when
+ * nothing is filtered; kept_out [rows] (nullable): the number of entries with y >= that threshold.
+ * One launch, one block per row; a single row of 16 384 entries or more: a launch per level of the selection over many blocks, with its
+ * histograms in the library's workspace (omx_set_workspace / grown outside graph capture, like the split kernels').              */
+int omx_sample_filtered(uint32_t* out_token, const void* logits, omx_dtype dtype, int64_t rows, int V, const omx_sampling* p,
+                        const uint8_t* seen, const uint32_t* key, float* thr_out, int32_t* kept_out, omx_stream stream);
+/* mlx_topk_axis (ops.h; funasr-qwen4b-mlx/src/model.rs:1357) on the same selection: out [rows, k] = the k largest of x [rows, V] in
+ * ascending order, dtype of x.  k <= 4096.                                                                                      */
+int omx_topk_values(void* out, const void* x, omx_dtype dtype, int64_t rows, int V, int k, omx_stream stream);
+
 /* embedding gather (mlx_take_axis ops.h:1109, nn/embedding.rs): out[r,:] = table[ids[r],:] */
 int omx_take_rows(void* out, const void* table, const uint32_t* ids, int64_t n_ids, int dim, omx_dtype dtype,
                   omx_stream stream);
@@ -213,6 +247,12 @@ int omx_qwen3_set_comm(omx_qwen3 m, void* comm, void* allreduce_fn);
  * otherwise every sampled token is categorical(logits * (1/temperature)) with the next key of a RandomState
  * seeded like mlx_rs::random::seed(seed) (random.rs:21-41, :88-91).  The draw stays on the device, inside the step. */
 int omx_qwen3_set_sampler(omx_qwen3 m, float temperature, uint64_t seed);
+/* filtered sampling inside the step (omx_sample_filtered's rule; `seen` = the tokens sampled since the last prefill / reset, the
+ * prompt excluded, kept on the device and marked by the step itself).  Every sampled token -- prefill's first one and each decode step,
+ * which stays one hipGraph -- goes through [select] [noise over the kept set] [finalize] [mark seen].  omx_qwen3_set_sampler turns
+ * every filter and penalty off again.  Refused: tensor-parallel engines (a sharded vocabulary needs a histogram all-reduce);
+ * omx_qwen3_verify / _trim refuse while a filter or penalty is on (their rows are not part of the history).                      */
+int omx_qwen3_set_sampling(omx_qwen3 m, const omx_sampling* p, uint64_t seed);
 /* text-encoder use of the stack (flux-klein-mlx/src/qwen3_encoder.rs:403-455, `forward_with_hidden_states` + `encode`):
  * all n tokens through layers 0..tap_layers[n_taps-1]; out (DEVICE, bf16) [n, n_taps*hidden] = the raw hidden states
  * after the tapped layers, concatenated on the last axis (FLUX.2-klein: taps 8,17,26 -> 7680 of Qwen3-4B).

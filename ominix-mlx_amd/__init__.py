@@ -39,6 +39,15 @@ c_void_p, c_int, c_int64, c_float, c_size_t, c_uint32 = (
 BOOL, UINT8, UINT16, UINT32, UINT64, INT8, INT16, INT32, INT64, FLOAT16, FLOAT32, FLOAT64, BFLOAT16, COMPLEX64 = range(14)
 MASK_NONE, MASK_CAUSAL, MASK_BOOL, MASK_ADDITIVE = range(4)
 
+class Sampling(ctypes.Structure):
+    """omx_sampling (include/omx.h): the parameters of the filtered sampler; the defaults switch everything off."""
+    _fields_ = [("temperature", ctypes.c_float), ("top_k", ctypes.c_int32), ("top_p", ctypes.c_float),
+                ("repetition_penalty", ctypes.c_float), ("presence_penalty", ctypes.c_float)]
+
+    def __init__(self, temperature=0.0, top_k=0, top_p=1.0, repetition_penalty=1.0, presence_penalty=0.0):
+        super().__init__(float(temperature), int(top_k), float(top_p), float(repetition_penalty), float(presence_penalty))
+
+
 # name -> (restype, argtypes).  Every symbol include/omx.h declares must appear here
 # (tests/test_abi.py cross-checks this table against the header).
 SIGNATURES = {
@@ -88,6 +97,9 @@ SIGNATURES = {
     "omx_random_gumbel": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
     "omx_random_normal": (c_int, [c_void_p, c_void_p, c_int64, ctypes.c_float, ctypes.c_float, c_void_p]),
     "omx_random_categorical": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, ctypes.c_float, c_void_p, c_int, c_void_p]),
+    "omx_sample_filtered": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, ctypes.POINTER(Sampling), c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
+    "omx_topk_values": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_void_p]),
     "omx_take_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "omx_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
 }

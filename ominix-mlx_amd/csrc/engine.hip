@@ -29,6 +29,7 @@
 #include "gemm.hpp"
 #include "gemv.hpp"
 #include "random.hpp"
+#include "sample_filter.hpp"
 #include "prefill.hpp"
 #include "quant.hpp"
 #include "launch_timing.hpp"
@@ -272,6 +273,12 @@ struct omx_qwen3_ {
     // of mlx-rs RandomState kept on the device: rng[0..1] = state, rng[2..3] = the key of the current draw
     float temperature = 0.f;
     uint32_t* rng = nullptr;
+    // filtered sampling (omx_qwen3_set_sampling, sample_filter.hip): penalties / top-k / top-p in front of the draw.  seen [V] bytes = the
+    // tokens sampled since the last prefill, marked inside the step; sel = the selection's scratch (per-level histograms)
+    bool filter_on = false;
+    omx_sampling sampling = {0.f, 0, 1.f, 1.f, 0.f};
+    uint8_t* seen = nullptr;
+    uint8_t* sel = nullptr;
 
     // batched-prefill activations (allocated on first use, sized for pf_cap tokens)
     int pf_cap = 0;
@@ -323,7 +330,26 @@ int dev_alloc(omx_qwen3 m, T** p, size_t n) {
 // temperature sampling: replace the greedy per-block partials by those of logits / T + Gumbel noise, the noise
 // of vocabulary row v being word v of a V-word draw from the step's key (random.hip).  The greedy partials the
 // lm_head epilogue wrote are simply overwritten; sample_finalize_kernel / the TP max all-reduce are unchanged.
+bool sampling_penalised(const omx_sampling& p) { return p.repetition_penalty != 1.f || p.presence_penalty != 0.f; }
+
+// filtered sampling: [key] [select: a launch per level of the descent, histograms in m->sel] [noise over the kept set -> the partials]; temperature 0 with a
+// penalty is the argmax of the penalised logits (the noise launch without noise).  Single rank (omx_qwen3_set_sampling refuses TP).
+int add_filtered_sampling(omx_qwen3 m, hipStream_t s) {
+    const omx_sampling& p = m->sampling;
+    const bool greedy = p.temperature == 0.f;
+    const uint8_t* seen = sampling_penalised(p) ? m->seen : nullptr;
+    if (!greedy && launch_rng_next(m->rng, s)) return 1;
+    if (launch_sample_select(m->sel, m->logits, m->f16, m->V, p, seen, s)) return 1;
+    return launch_sample_filtered_noise(m->argmax_partials, m->n_argmax_partials, m->logits, m->f16, m->V, p, seen, m->sel, m->rng + 2, s);
+}
+// after the finalize: the sampled token joins the history the penalties read
+int mark_sampled_token(omx_qwen3 m, hipStream_t s) {
+    if (!m->filter_on || !sampling_penalised(m->sampling)) return 0;
+    return launch_mark_seen(m->seen, m->V, m->st, s);
+}
+
 int add_sampling_noise(omx_qwen3 m, hipStream_t s) {
+    if (m->filter_on) return add_filtered_sampling(m, s);
     if (m->temperature == 0.f) return 0;
     const omx_qwen3_config& c = m->cfg;
     const int tp = c.tp_size > 1 ? c.tp_size : 1;
@@ -643,6 +669,7 @@ int enqueue_step_quant(omx_qwen3 m, bool with_head) {
         OMX_LAUNCH(sample_finalize_kernel, 1, 256, 0, s, m->st, m->argmax_partials, m->n_argmax_partials, m->out_ring, m->ring_cap,
                    (unsigned long long*)nullptr);
         OMX_LAUNCH_CHECK();
+        if (mark_sampled_token(m, s)) return 1;
         }
     } else {
         feed_prompt_kernel<<<1, 1, 0, s>>>(m->st, m->prompt_dev);
@@ -660,7 +687,7 @@ int step_engine_mode(omx_qwen3 m) {
     const char* e = getenv("OMX_STEP_ENGINE");         // (read per call: tests flip it between engines of one process)
     const int mode = e ? atoi(e) : 0;
     const omx_qwen3_config& c = m->cfg;
-    const bool ok = mode > 0 && !m->se_disabled && c.quant_bits == 0 && !m->f16 && c.num_experts == 0 && c.tp_size == 1 && c.ep_size <= 1 && m->allreduce == nullptr &&
+    const bool ok = mode > 0 && !m->se_disabled && !m->filter_on && c.quant_bits == 0 && !m->f16 && c.num_experts == 0 && c.tp_size == 1 && c.ep_size <= 1 && m->allreduce == nullptr &&
            !c.attention_bias && m->se_gran != nullptr && m->cus > 0 &&
            step_engine_ok(c.hidden_size, m->H, m->Hkv, c.head_dim, m->I, m->attn_nsplit, m->cus);
     return ok ? (mode == 2 ? 2 : 1) : 0;
@@ -927,6 +954,7 @@ int enqueue_step_tail(omx_qwen3 m, bool with_head, const bf16_t* h, const float*
             OMX_LAUNCH(sample_finalize_kernel, 1, 256, 0, s, m->st, m->argmax_partials, m->n_argmax_partials, m->out_ring, m->ring_cap,
                        (unsigned long long*)nullptr);
             OMX_LAUNCH_CHECK();
+            if (mark_sampled_token(m, s)) return 1;
         } else {
             sample_finalize_kernel<<<1, 256, 0, s>>>(m->st, m->argmax_partials, m->n_argmax_partials, m->out_ring,
                                                      m->ring_cap, m->argmax_key);
@@ -954,7 +982,7 @@ int step_aql_mode(omx_qwen3 m) {
     const int mode = e ? atoi(e) : 0;
     const omx_qwen3_config& c = m->cfg;
     if (mode <= 0 || m->aql_disabled || m->eager || m->allreduce != nullptr || c.tp_size > 1 || c.ep_size > 1 || c.num_experts > 0 ||
-        m->temperature != 0.f || step_engine_mode(m) != 0)
+        m->temperature != 0.f || m->filter_on || step_engine_mode(m) != 0)
         return 0;
     return mode;
 }
@@ -1081,6 +1109,8 @@ int enqueue_head_on_row(omx_qwen3 m, const bf16_t* row, hipStream_t s) {
         OMX_REQUIRE(m->allreduce(m->argmax_key, m->argmax_key, 1, kNcclUint64, kNcclMax, m->comm, s) == 0, "ncclAllReduce failed");
         apply_token_kernel<<<1, 1, 0, s>>>(m->st, m->argmax_key, m->out_ring, m->ring_cap);
         OMX_LAUNCH_CHECK();
+    } else if (mark_sampled_token(m, s)) {
+        return 1;
     }
     return 0;
 }
@@ -1108,7 +1138,7 @@ int step_health(omx_qwen3 m) {
 // step state the call started from and let the caller run the steps again (the KV rows they wrote are rewritten).  Returns 0 when a
 // retry is possible.
 int step_fallback(omx_qwen3 m, const StepState& st) {
-    if (m->temperature != 0.f) return 1;                       // the sampler's key sequence advanced: no silent replay
+    if (m->temperature != 0.f || m->filter_on) return 1;       // the sampler's key sequence / token history advanced: no silent replay
     // more than one rank: a local replay would re-enqueue every all-reduce of the n steps (and the argmax one) on THIS rank only -- its
     // peers never issue them, so the collectives would pair with the peers' next call (wrong sums or a hang).  Report the abort instead.
     if (m->allreduce != nullptr || m->cfg.tp_size > 1 || m->cfg.ep_size > 1) return 1;
@@ -2003,6 +2033,49 @@ int omx_qwen3_set_sampler(omx_qwen3 m, float temperature, uint64_t seed) {
         m->eager = false;
         m->temperature = temperature;
     }
+    if (m->filter_on) {   // the plain sampler: every filter and penalty off
+        drop_graphs(m);
+        m->eager = false;
+        m->filter_on = false;
+        m->sampling = {temperature, 0, 1.f, 1.f, 0.f};
+    }
+    return 0;
+}
+
+static bool env_positive(const char* name) {
+    const char* e = getenv(name);
+    return e && atoi(e) > 0;
+}
+
+int omx_qwen3_set_sampling(omx_qwen3 m, const omx_sampling* p, uint64_t seed) {
+    OMX_REQUIRE(m && p, "omx_qwen3_set_sampling: null argument");
+    OMX_REQUIRE(p->temperature >= 0.f && p->temperature == p->temperature, "omx_qwen3_set_sampling: temperature %f must be >= 0", (double)p->temperature);
+    OMX_REQUIRE(p->top_k >= 0, "omx_qwen3_set_sampling: top_k %d must be >= 0 (0 = off)", p->top_k);
+    OMX_REQUIRE(p->top_p > 0.f && p->top_p <= 1.f, "omx_qwen3_set_sampling: top_p %f must be in (0, 1] (1 = off)", (double)p->top_p);
+    OMX_REQUIRE(p->repetition_penalty > 0.f && p->repetition_penalty < INFINITY,
+                "omx_qwen3_set_sampling: repetition_penalty %f must be positive (1 = off)", (double)p->repetition_penalty);
+    OMX_REQUIRE(fabsf(p->presence_penalty) < INFINITY, "omx_qwen3_set_sampling: presence_penalty %f must be finite (0 = off)", (double)p->presence_penalty);
+    const bool on = sampling_penalised(*p) || (p->temperature != 0.f && (p->top_k > 0 || p->top_p < 1.f));
+    if (!on) return omx_qwen3_set_sampler(m, p->temperature, seed);
+    OMX_REQUIRE(m->cfg.tp_size <= 1 && m->allreduce == nullptr,
+                "omx_qwen3_set_sampling: filtered sampling is not supported under tensor parallelism (tp_size %d): each rank holds a "
+                "vocabulary shard, the selection would need a histogram all-reduce", m->cfg.tp_size);
+    OMX_REQUIRE(!env_positive("OMX_STEP_ENGINE") && !env_positive("OMX_STEP_AQL"),
+                "omx_qwen3_set_sampling: filtered sampling is not supported with the OMX_STEP_ENGINE / OMX_STEP_AQL step modes");
+    OMX_REQUIRE(m->V <= (1 << 23), "omx_qwen3_set_sampling: vocabulary %d exceeds 2^23 entries", m->V);
+    if (!m->rng && dev_alloc(m, &m->rng, 4)) return 1;
+    if (!m->seen && dev_alloc(m, &m->seen, (size_t)m->V)) return 1;
+    if (!m->sel && dev_alloc(m, &m->sel, sample_select_ws_bytes())) return 1;
+    if (omx_random_key(m->rng, seed, (omx_stream)m->stream)) return 1;
+    OMX_HIP_CHECK(hipMemsetAsync(m->seen, 0, (size_t)m->V, m->stream));
+    OMX_HIP_CHECK(hipMemsetAsync(m->sel, 0, sample_select_ws_bytes(), m->stream));
+    OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
+    // the parameters are launch arguments inside the captured step: drop the graphs, the next step rebuilds them
+    drop_graphs(m);
+    m->eager = false;
+    m->temperature = p->temperature;
+    m->sampling = *p;
+    m->filter_on = true;
     return 0;
 }
 
@@ -2052,6 +2125,8 @@ int omx_qwen3_encode(omx_qwen3 m, const uint32_t* ids, int n, const uint8_t* att
 int omx_qwen3_reset(omx_qwen3 m) {
     OMX_REQUIRE(m, "omx_qwen3_reset: null model");
     OMX_HIP_CHECK(hipMemsetAsync(m->st, 0, sizeof(StepState), m->stream));
+    if (m->seen) OMX_HIP_CHECK(hipMemsetAsync(m->seen, 0, (size_t)m->V, m->stream));
+    if (m->sel) OMX_HIP_CHECK(hipMemsetAsync(m->sel, 0, sample_select_ws_bytes(), m->stream));
     OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
     return 0;
 }
@@ -2084,6 +2159,8 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
     if (!serial && m->cfg.quant_bits) dq_cache_prepare(m);             // (a once-per-model allocation: ahead of the timed region)
     if (!serial && prefill_reserve(m, n_prompt)) return 1;             // (row buffers / scratch of this prompt size: likewise)
     OMX_HIP_CHECK(hipMemcpyAsync(m->prompt_dev, prompt, (size_t)n_prompt * 4, hipMemcpyHostToDevice, m->stream));
+    if (m->seen) OMX_HIP_CHECK(hipMemsetAsync(m->seen, 0, (size_t)m->V, m->stream));   // the penalties' history: tokens sampled since this prefill
+    if (m->sel) OMX_HIP_CHECK(hipMemsetAsync(m->sel, 0, sample_select_ws_bytes(), m->stream));   // (the selection's histograms start from zero)
     StepState st;
     OMX_HIP_CHECK(hipMemcpyAsync(&st, m->st, sizeof(st), hipMemcpyDeviceToHost, m->stream));
     OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -2135,6 +2212,8 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
 int omx_qwen3_verify(omx_qwen3 m, const uint32_t* tokens, int n, uint32_t* greedy_out) {
     OMX_REQUIRE(m && tokens && greedy_out, "omx_qwen3_verify: null argument");
     OMX_REQUIRE(n >= 1 && n <= 64, "omx_qwen3_verify: %d tokens (1..64 per call)", n);
+    OMX_REQUIRE(!m->filter_on, "omx_qwen3_verify: filtered sampling (top-k / top-p / penalties, omx_qwen3_set_sampling) is on: speculative "
+                "verify draws from unfiltered rows; call omx_qwen3_set_sampler first");
     OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
                 "omx_qwen3_verify: tensor / expert parallel models are not supported (single-rank models only)");
     const bool packed = m->cfg.quant_bits != 0;
@@ -2211,6 +2290,8 @@ int omx_qwen3_verify_logits(omx_qwen3 m, int row, void* host_bf16, int n) {
  * replaces the pending input token. */
 int omx_qwen3_trim(omx_qwen3 m, int n, uint32_t next_token) {
     OMX_REQUIRE(m, "omx_qwen3_trim: null argument");
+    OMX_REQUIRE(!m->filter_on, "omx_qwen3_trim: filtered sampling (top-k / top-p / penalties, omx_qwen3_set_sampling) is on: the token "
+                "history on the device cannot be trimmed; call omx_qwen3_set_sampler first");
     OMX_REQUIRE(next_token < (uint32_t)m->cfg.vocab_size, "omx_qwen3_trim: token id %u out of range (vocab %d)", next_token, m->cfg.vocab_size);
     StepState st;
     OMX_HIP_CHECK(hipMemcpyAsync(&st, m->st, sizeof(st), hipMemcpyDeviceToHost, m->stream));

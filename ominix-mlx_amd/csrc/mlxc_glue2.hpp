@@ -307,6 +307,25 @@ int mlx_topk_axis(mlx_array* res, const mlx_array a, int k, int axis, const mlx_
     if (norm_axis(axis, nd, "mlx_topk_axis", &ax)) return 1;
     const int n = A(a)->shape[ax];
     OMX_REQUIRE(k >= 0 && k <= n, "mlx_topk_axis: k %d out of range for %d elements", k, n);
+    if (n > 65536) {
+        // longer than the sort kernels take (a Qwen vocabulary is 151 936): the sampler's selection kernel (sample_filter.hip) finds the
+        // k-th largest and orders the k values -- funasr-qwen4b-mlx/src/model.rs:1357 (sample_top_k_p).  Shorter axes keep the sort.
+        const Arr& src = *A(a);
+        OMX_REQUIRE(ax == nd - 1, "mlx_topk_axis: %d elements along axis %d: axes longer than 65536 are supported as the last axis only", n, ax);
+        OMX_REQUIRE(src.dt == MLX_BFLOAT16 || src.dt == MLX_FLOAT16 || src.dt == MLX_FLOAT32,
+                    "mlx_topk_axis: %d elements along the axis: axes longer than 65536 are supported for bfloat16 / float16 / float32", n);
+        OMX_REQUIRE(k >= 1, "mlx_topk_axis: k = 0 of %d elements", n);
+        Contig c;
+        if (c.init(src)) return 1;
+        std::vector<int> shape = src.shape;
+        shape[ax] = k;
+        NEW_OR_FAIL(r, shape, src.dt);
+        if (omx_topk_values(r->ptr(), c.a->ptr(), (omx_dtype)src.dt, (int64_t)(src.size() / (size_t)n), n, k, (omx_stream)g_stream)) {
+            delete r;
+            return 1;
+        }
+        return assign(res, r);
+    }
     Tmp sorted;
     if (mlx_sort_axis(&sorted, a, ax, s)) return 1;
     std::vector<int> start((size_t)nd, 0), stop = A(a)->shape, strides((size_t)nd, 1);

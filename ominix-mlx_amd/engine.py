@@ -8,7 +8,7 @@ from typing import Dict, Iterator, Optional
 
 import numpy as np
 
-from . import OmxError, check, lib, require_device
+from . import OmxError, Sampling, check, lib, require_device
 from .ops import Tensor
 
 c_int, c_float, c_void_p, c_uint32 = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32
@@ -60,6 +60,7 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_synth_weights_peaked": (c_int, [c_void_p, c_uint32]),
     "omx_qwen3_set_comm": (c_int, [c_void_p, c_void_p, c_void_p]),
     "omx_qwen3_set_sampler": (c_int, [c_void_p, ctypes.c_float, ctypes.c_uint64]),
+    "omx_qwen3_set_sampling": (c_int, [c_void_p, ctypes.POINTER(Sampling), ctypes.c_uint64]),
     "omx_qwen3_sampler_state": (c_int, [c_void_p, c_void_p, c_int]),
     "omx_qwen3_encode": (c_int, [c_void_p, ctypes.POINTER(c_uint32), c_int, c_void_p, ctypes.POINTER(c_int), c_int, c_void_p]),
     "omx_qwen3_reset": (c_int, [c_void_p]),
@@ -302,10 +303,19 @@ class Model:
                                    am.ctypes.data if am is not None else None, taps, len(extract_layers), out.ptr))
         return out
 
-    def set_sampler(self, temperature: float, seed: int = 0) -> None:
+    def set_sampler(self, temperature: float, seed: int = 0, *, top_k: int = 0, top_p: float = 1.0, repetition_penalty: float = 1.0,
+                    presence_penalty: float = 0.0) -> None:
         """DefaultSampler (mlx-rs-core/src/sampler.rs:9-18): 0 = greedy, otherwise categorical(logits / temperature)
-        drawn on the device with the key sequence of `mlx_rs::random::seed(seed)`."""
-        check(lib.omx_qwen3_set_sampler(self._h, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF))
+        drawn on the device with the key sequence of `mlx_rs::random::seed(seed)`.
+        The keywords put the filters of the reference's generation loops in front of the draw, inside the same device step
+        (omx_sample_filtered's rule): repetition_penalty (step-audio2-mlx/src/llm.rs:440-474) and presence_penalty
+        (funasr-qwen4b-mlx/src/model.rs:1342-1352) on the tokens sampled since the last prefill, top_k (ties kept, :1357-1372), top_p on
+        the survivors.  Their defaults are off: the call is then the plain sampler, bit for bit."""
+        if top_k == 0 and top_p == 1.0 and repetition_penalty == 1.0 and presence_penalty == 0.0:
+            check(lib.omx_qwen3_set_sampler(self._h, float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF))
+            return
+        p = Sampling(temperature, top_k, top_p, repetition_penalty, presence_penalty)
+        check(lib.omx_qwen3_set_sampling(self._h, ctypes.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
     def sampler_state(self) -> tuple:
         """The two words of the sampler's key sequence (after set_sampler): the reference's speculative loop draws both models' tokens from
@@ -436,8 +446,9 @@ class Generate:
     prefills the prompt.  temp == 0 is the greedy path of sample() (model.rs:733-735); temp != 0 draws
     categorical(logits / temp) (model.rs:736-739) from the key sequence seeded with `seed`."""
 
-    def __init__(self, model: Model, temp: float, prompt_token, chunk: int = 16, seed: int = 0):
-        model.set_sampler(temp, seed)
+    def __init__(self, model: Model, temp: float, prompt_token, chunk: int = 16, seed: int = 0, *, top_k: int = 0, top_p: float = 1.0,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0):
+        model.set_sampler(temp, seed, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty)
         self.model, self.prompt, self.chunk = model, np.asarray(prompt_token, dtype=np.uint32).ravel(), chunk
         self._prefilled = False
         self._buf = []

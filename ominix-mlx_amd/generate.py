@@ -85,10 +85,11 @@ def apply_chat_template_and_encode(tokenizer, model_template: str, conversations
 
 def generate_text(model, tokenizer, prompt: str, temperature: float = 0.7, max_tokens: int = 100, seed: int = 0,
                   emit: Optional[Callable[[str], None]] = None, flush_every: int = 10,
-                  stop_token_ids: Optional[Iterable[int]] = None, prompt_ids: Optional[Sequence[int]] = None) -> dict:
+                  stop_token_ids: Optional[Iterable[int]] = None, prompt_ids: Optional[Sequence[int]] = None, *, top_k: int = 0,
+                  top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0) -> dict:
     """generate_qwen3.rs:31-101.  Returns {"text", "tokens", "prompt_tokens", "seconds", "tokens_per_sec"}; `emit` receives
     each decoded chunk as the example prints it.  `stop_token_ids` (not in the example, which always runs max_tokens)
-    ends the stream after such a token."""
+    ends the stream after such a token.  top_k / top_p / repetition_penalty / presence_penalty: Model.set_sampler's filters (off by default)."""
     from .engine import Generate
     ids = list(prompt_ids) if prompt_ids is not None else list(tokenizer.encode(prompt, add_special_tokens=True).ids)
     if not ids:
@@ -107,7 +108,8 @@ def generate_text(model, tokenizer, prompt: str, temperature: float = 0.7, max_t
                 emit(text)
             pending.clear()
 
-    for i, token in enumerate(Generate(model, temperature, ids, chunk=flush_every, seed=seed)):
+    for i, token in enumerate(Generate(model, temperature, ids, chunk=flush_every, seed=seed, top_k=top_k, top_p=top_p,
+                                       repetition_penalty=repetition_penalty, presence_penalty=presence_penalty)):
         token = int(token)
         pending.append(token)
         all_tokens.append(token)

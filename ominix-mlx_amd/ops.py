@@ -326,6 +326,32 @@ def random_categorical(logits: Tensor, key: Tensor, num_samples=None, inv_temp: 
     return out
 
 
+def sample_filtered(logits: Tensor, key: Optional[Tensor], temperature: float, *, top_k: int = 0, top_p: float = 1.0,
+                    repetition_penalty: float = 1.0, presence_penalty: float = 0.0, seen: Optional[Tensor] = None):
+    """omx_sample_filtered over the last axis: penalties on the ids marked in `seen` (uint8 [V]), * (1/T), top-k (ties at the threshold
+    kept), top-p on the survivors, then the keyed categorical draw restricted to the kept set.  Returns (tokens u32, thresholds f32,
+    kept counts), one per row: the kept set of a row is exactly {y >= threshold}."""
+    from . import Sampling
+    n = logits.shape[-1]
+    rows = logits.size // n
+    lead = tuple(logits.shape[:-1])
+    out, thr, kept = Tensor(lead, UINT32), Tensor(lead, FLOAT32), Tensor(lead, UINT32)
+    if seen is not None and (seen.dtype != UINT8 or seen.size != n):
+        raise OmxError(f"sample_filtered: seen must be uint8 [{n}]")
+    p = Sampling(temperature, top_k, top_p, repetition_penalty, presence_penalty)
+    check(lib.omx_sample_filtered(out.ptr, logits.ptr, logits.dtype, rows, n, ctypes.byref(p), seen.ptr if seen is not None else None,
+                                  key.ptr if key is not None else None, thr.ptr, kept.ptr, None))
+    return out, thr, kept
+
+
+def topk_values(x: Tensor, k: int) -> Tensor:
+    """mlx_topk_axis over the last axis on the sampler's selection kernel: the k largest values of every row, ascending."""
+    n = x.shape[-1]
+    out = Tensor(tuple(x.shape[:-1]) + (int(k),), x.dtype)
+    check(lib.omx_topk_values(out.ptr, x.ptr, x.dtype, x.size // n, n, int(k), None))
+    return out
+
+
 def quantize(w: Tensor, group_size: int = 64, bits: int = 4):
     """mlx_rs::ops::quantize (ops/quantization.rs:41-84): w [..., K] -> (packed u32 [..., K*bits/32], scales, biases)."""
     K = w.shape[-1]

@@ -1,16 +1,28 @@
-"""qwen3-mlx/examples/generate_qwen3.rs on the MI355X engine:  python tools/generate_qwen3.py <model_dir> [prompt]"""
-import os, sys
+"""qwen3-mlx/examples/generate_qwen3.rs on the MI355X engine:
+    python tools/generate_qwen3.py <model_dir> [prompt] [--temperature T] [--top-k K] [--top-p P] [--repetition-penalty R]
+                                   [--presence-penalty Q] [--seed S] [--max-tokens N]
+Without flags: the example's plain temperature 0.7.  The Qwen3 model card's settings are --temperature 0.6 --top-k 20 --top-p 0.95."""
+import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import omx_import
 omx_import.load_package()
 from ominix_mlx_amd import generate, loader
 
-if len(sys.argv) < 2:
-    sys.exit(f"Usage: {sys.argv[0]} <model_dir> [prompt]")
-model_dir = sys.argv[1]
-prompt = sys.argv[2] if len(sys.argv) > 2 else "Hello, I am a language model,"
-tokenizer = generate.load_tokenizer(model_dir)
-model = loader.load_model(model_dir)
-print(f"Prompt: {prompt}\n---")
-out = generate.generate_text(model, tokenizer, prompt, temperature=0.7, max_tokens=100, emit=lambda t: print(t, end="", flush=True))
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("model_dir")
+ap.add_argument("prompt", nargs="?", default="Hello, I am a language model,")
+ap.add_argument("--temperature", type=float, default=0.7)
+ap.add_argument("--top-k", type=int, default=0, help="keep the k most likely tokens, ties included (0 = off)")
+ap.add_argument("--top-p", type=float, default=1.0, help="nucleus mass on the survivors of top-k (1 = off)")
+ap.add_argument("--repetition-penalty", type=float, default=1.0, help="x > 0 ? x / r : x * r on generated tokens (1 = off)")
+ap.add_argument("--presence-penalty", type=float, default=0.0, help="x - q on generated tokens (0 = off)")
+ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--max-tokens", type=int, default=100)
+args = ap.parse_args()
+tokenizer = generate.load_tokenizer(args.model_dir)
+model = loader.load_model(args.model_dir)
+print(f"Prompt: {args.prompt}\n---")
+out = generate.generate_text(model, tokenizer, args.prompt, temperature=args.temperature, max_tokens=args.max_tokens, seed=args.seed,
+                             emit=lambda t: print(t, end="", flush=True), top_k=args.top_k, top_p=args.top_p,
+                             repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty)
 print(f"\n---\nGenerated {len(out['tokens'])} tokens in {out['seconds']:.2f}s ({out['tokens_per_sec']:.1f} tok/s)")
