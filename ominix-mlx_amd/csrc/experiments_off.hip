@@ -1,5 +1,5 @@
 // The default build's answer to the entry points of the experimental engines (Makefile: EXPERIMENTS=1 builds step_engine.hip and
-// aql_step.hip instead of this file): "not built".  engine.hip needs no #ifdef: step_engine_ok() == false keeps the persistent step off,
+// aql_step.hip instead of this file): "not built".  engine_step.hip needs no #ifdef: step_engine_ok() == false keeps the persistent step off,
 // aql_build() == nullptr makes the engine mark its AQL replay unavailable and stay on the hipGraph.
 #include "aql_step.hpp"
 #include "step_engine.hpp"

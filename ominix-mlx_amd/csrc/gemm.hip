@@ -1703,7 +1703,7 @@ int ring_splits(int blocks, int nt) {
 static thread_local int g_tile_hint = 0;
 void gemm_tile_hint(int rows) { g_tile_hint = rows; }
 int gemm_tile_hint_get() { return g_tile_hint; }
-// float16 operands / results for this thread's next GEMMs (a float16 checkpoint's prompt pass, engine.hip): the eight-wave kernel's
+// float16 operands / results for this thread's next GEMMs (a float16 checkpoint's prompt pass, engine_prefill.hip): the eight-wave kernel's
 // float16 instantiations serve every shape (plain: 256- or 128-row tiles; segmented: 256-row tiles)
 static thread_local bool g_gemm_f16 = false;
 bool gemm_set_f16(bool on) { const bool was = g_gemm_f16; g_gemm_f16 = on; return was; }   // returns the previous state (nested scopes)

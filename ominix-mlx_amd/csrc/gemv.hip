@@ -387,7 +387,7 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
     }
     if (EPI == EPI_ARGMAX) {
         // one partial per block (no same-address atomics: 150k of them serialise at ~12 ns each);
-        // argmax_finalize in engine.hip reduces the partials
+        // sample_finalize_kernel in engine_step.hip reduces the partials
         uint64_t* bred = reinterpret_cast<uint64_t*>(red);   // 4 x u64 = first 32 B of the scratch
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {

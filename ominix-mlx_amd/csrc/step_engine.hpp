@@ -1,7 +1,7 @@
 // Persistent decode step: every layer of one token in ONE launch, on a loader / consumer engine per CU.
 //   reference: the per-token body of Generate (qwen3-mlx/src/model.rs:314-340 decoder layer, :804-843 decode loop) -- the chain
 //   [RMSNorm + q/k/v Linear] [q/k norm + RoPE + KV append + SDPA] [o Linear + residual] [RMSNorm + gate/up + silu*up] [down + residual]
-//   that engine.hip otherwise enqueues as four launches per layer.
+//   that engine_step.hip otherwise enqueues as four launches per layer.
 //
 // Why: at batch 1 every launch of the step is a weight stream of 5-35 us, and each launch boundary costs ~2.3 us in which no weight
 // byte moves (drain + dispatch + first-byte latency + ramp).  Weights depend on nothing, so a wave that ONLY loads never has to stop at

@@ -126,7 +126,7 @@ def dense_dtype_is_f16(dtype) -> bool:
 
 def expected_shape(c: Qwen3Config, name: str):
     """Shape the engine will read for checkpoint tensor `name` on THIS rank (after the TP / EP slicing), or None for a
-    name the forward does not use.  Mirrors resolve_weights in csrc/engine.hip."""
+    name the forward does not use.  Mirrors resolve_weights in csrc/engine_weights.hip."""
     tp, ep = max(c.tp_size, 1), max(c.ep_size, 1)
     hd, D = c.hidden_size, c.head_dim
     H, Hkv, I, V = c.num_attention_heads // tp, max(1, c.num_key_value_heads // tp), c.intermediate_size // tp, c.vocab_size
