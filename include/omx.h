@@ -345,11 +345,19 @@ int omx_qwen3_decode_path(omx_qwen3 m, int* path);
 int omx_qwen3_debug_trace_step(omx_qwen3 m, unsigned long long* host, size_t n_words, int* blocks);
 /* measurement hook: `steps` real decode steps run eagerly, every launch of the per-layer kernels carrying its own HIP event pair
  * (the dispatch's begin / end timestamps on the step's stream); us[7] = average microseconds of {QKV GEMV, attention, O GEMV,
- * gate/up + SwiGLU GEMV, down GEMV, lm_head, persistent step launch (all layers; the five per-layer figures are 0 then)}.  bench.py's roofline.achieved is the gate/up figure.  Dense bf16 single-rank models. */
+ * gate/up + SwiGLU GEMV, down GEMV, lm_head, persistent step launch (all layers; the five per-layer figures are 0 then)}.  bench.py's roofline.achieved is the gate/up figure.  Dense bf16 single-rank models.
+ * Where down and the next layer's q/k/v are one launch (csrc/gemv_chain.hip), its duration is split between the down and the QKV figure in
+ * proportion to their algorithmic bytes. */
 int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us);
 /* debug hook (tools/step_engine_trace.py): ONE eager decode step on the persistent engine (csrc/step_engine.hip, OMX_STEP_ENGINE=1)
  * with per-CU wall-clock stamps; host receives [CUs][64] words, *cus = CUs of the device */
 int omx_qwen3_debug_trace_engine(omx_qwen3 m, unsigned long long* host, size_t n_words, int* cus);
+/* test hooks of the decode step's forms.  step_forms: what the NEXT step would take -- forms[0] = down + the next layer's q/k/v in one
+ * launch (csrc/gemv_chain.hip, OMX_DOWN_QKV=0 turns it off), forms[1] = the O projection inside the attention launch, forms[2] = the
+ * persistent-step mode, forms[3] = 1 once a give-up switched the first off for this engine.  raise_give_up: sets, from the host, the word
+ * a wait inside a launch raises when it gives up; the next omx_qwen3_decode then replays its steps on the next form of the ladder */
+int omx_qwen3_debug_step_forms(omx_qwen3 m, int* forms);
+int omx_qwen3_debug_raise_give_up(omx_qwen3 m);
 
 /* =====================================================================================
  * MLX affine group quantisation (the reference's flagship checkpoint format).

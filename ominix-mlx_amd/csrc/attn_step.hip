@@ -32,6 +32,7 @@
 
 #include "attn.hpp"
 #include "act16.hpp"
+#include "granule.hpp"
 #include "launch_timing.hpp"
 
 namespace omx {
@@ -41,16 +42,6 @@ namespace {
 constexpr int kBlock = 512;
 constexpr int kWaves = 8;
 constexpr unsigned kSpinLimit = 1u << 15;   // gather passes (~1 us each) before a consumer gives up
-
-typedef __attribute__((address_space(1))) unsigned long long gu64;
-
-__device__ __forceinline__ void st_granule_u32(uint64_t* p, unsigned tag, unsigned v) {
-    __hip_atomic_store((gu64*)p, ((unsigned long long)tag << 32) | (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_granule(uint64_t* p, unsigned tag, float v) { st_granule_u32(p, tag, __float_as_uint(v)); }
-__device__ __forceinline__ unsigned long long ld_granule(const uint64_t* p) {
-    return __hip_atomic_load((gu64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 template <int N>
 __device__ __forceinline__ float swap_halves(float v) {     // value of lane (l ^ N/2) of the aligned N-lane group

@@ -642,3 +642,28 @@ extern "C" int omx_bench_gemv_warm(int N, int K, int pro, int epi, int n_copies,
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipStreamDestroy(s);
     return 0;
 }
+
+// ---- test hooks of the decode step's forms (tests/test_gpu_down_qkv_chain.py) ----
+#include "engine_model.hpp"
+
+/* which in-launch folds the NEXT step of this engine would take, as the step itself decides (environment switches read now):
+ * forms[0] = down + the next layer's q/k/v in one launch, forms[1] = the O projection inside the attention launch, forms[2] = the
+ * persistent-step mode; forms[3] = 1 once a give-up switched the first fold off for this engine */
+extern "C" int omx_qwen3_debug_step_forms(omx_qwen3 m, int* forms) {
+    OMX_REQUIRE(m && forms, "omx_qwen3_debug_step_forms: null argument");
+    forms[0] = omx::down_takes_qkv(m) ? 1 : 0;
+    forms[1] = omx::attention_takes_oproj(m) ? 1 : 0;
+    forms[2] = omx::step_engine_mode(m);
+    forms[3] = m->chain_disabled ? 1 : 0;
+    return 0;
+}
+
+/* raise, from the host, the word a wait inside a launch raises when it gives up: the next omx_qwen3_decode finds its steps void and goes
+ * down the fallback ladder (step_fallback) exactly as after a real give-up -- without starving a launch to provoke one */
+extern "C" int omx_qwen3_debug_raise_give_up(omx_qwen3 m) {
+    OMX_REQUIRE(m, "omx_qwen3_debug_raise_give_up: null argument");
+    const unsigned one = 1u;
+    OMX_HIP_CHECK(hipMemcpyAsync(m->wait_abort, &one, 4, hipMemcpyHostToDevice, m->stream));
+    OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return 0;
+}

@@ -140,7 +140,7 @@ int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) {
             return 1;
     }
     if (dev_alloc(m, &m->rope_cur, (size_t)D) || dev_alloc(m, &m->attn_gran, attn_step_ws_granules(m->H, D)) ||
-        dev_alloc(m, &m->attn_xg, (size_t)m->H * D / 2 + 8))
+        dev_alloc(m, &m->attn_xg, (size_t)m->H * D / 2 + 8) || dev_alloc(m, &m->chain_gran, (size_t)c.hidden_size / 2 + 8))
         return 1;
     if (dev_alloc(m, &m->step_seq, 16) || dev_alloc(m, &m->wait_abort, 16)) return 1;
     {
@@ -604,7 +604,10 @@ int omx_qwen3_debug_trace_step(omx_qwen3 m, unsigned long long* host, size_t n_w
 /* measurement hook (bench.py roofline.achieved): runs `steps` REAL decode steps (they advance the context like any other) eagerly, each
  * launch of the five per-layer kernels and the lm_head carrying its own HIP event pair (hipExtLaunchKernelGGL start / stop events: the
  * dispatch's begin / end timestamps on the step's stream, launch_timing.hpp).  us[6] = average of {QKV GEMV, attention, O GEMV,
- * gate/up + SwiGLU GEMV, down GEMV, lm_head} over layers and steps.  Dense bf16 single-rank models only. */
+ * gate/up + SwiGLU GEMV, down GEMV, lm_head} over layers and steps.  Dense bf16 single-rank models only.
+ * Where down and the next layer's q/k/v are one launch (gemv_chain.hip, layers 0 .. L-2), that launch is booked on the down class of its
+ * layer and its duration is split between `down` and `qkv` in proportion to their algorithmic bytes: the q/k/v pairs of layers 1 .. L-1
+ * are never armed and never read, no class comes back as 0 and the classes still sum to the step. */
 int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
     OMX_REQUIRE(m && us && steps > 0, "omx_qwen3_time_step_kernels: bad arguments");
     OMX_REQUIRE(!m->cfg.quant_bits && m->cfg.num_experts == 0 && m->allreduce == nullptr, "omx_qwen3_time_step_kernels: dense bf16 single-rank models only");
@@ -613,7 +616,8 @@ int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
     for (auto& e : ev) OMX_HIP_CHECK(hipEventCreate(&e));
     double sum[KC_COUNT] = {};
     int rc = 0;
-    bool fused_o = false, engine = false, hybrid = false;
+    bool fused_o = false, engine = false, hybrid = false, chain = false;
+    const double qkv_bytes = (double)(m->H + 2 * m->Hkv) * m->cfg.head_dim * m->cfg.hidden_size, down_bytes = (double)m->cfg.hidden_size * m->I;
     arm_launch_events(nullptr, nullptr);
     for (int it = 0; it < steps && !rc; ++it) {
         StepState st;
@@ -623,6 +627,7 @@ int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
         fused_o = attention_takes_oproj(m);
         engine = step_engine_mode(m) == 1;
         hybrid = step_engine_mode(m) == 2;
+        chain = !engine && !hybrid && down_takes_qkv(m);
         m->kernel_events = &ev;
         rc = enqueue_step(m, true);
         m->kernel_events = nullptr;
@@ -634,7 +639,12 @@ int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
                 const size_t i = ((size_t)l * kLayerClasses + k) * 2;
                 if (l < L && k == KC_O && fused_o) continue;     // that pair was never armed
                 if (hybrid && l < L && (k == KC_GATE_UP || (k == KC_DOWN && l != L - 1))) continue;   // one segment launch covers them
+                if (chain && l > 0 && l < L && k == KC_QKV) continue;   // done inside the previous layer's down launch
                 OMX_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+                if (chain && l < L - 1 && k == KC_DOWN) {   // one launch for two classes: shared by bytes
+                    sum[KC_QKV] += ms * 1e3 * (qkv_bytes / (qkv_bytes + down_bytes));
+                    ms *= (float)(down_bytes / (qkv_bytes + down_bytes));
+                }
                 sum[l == L ? (k == 0 ? KC_HEAD : KC_ENGINE) : k] += ms * 1e3;
             }
         rc = step_health(m);

@@ -88,7 +88,16 @@ __global__ __launch_bounds__(256) void sample_finalize_kernel(StepState* st, con
                                                                unsigned long long* key_out) {
     __shared__ unsigned long long red[4];
     unsigned long long best = 0;
-    for (int i = threadIdx.x; i < n_partials; i += 256) best = partials[i] > best ? partials[i] : best;
+    // a batch of a thread's keys is in flight before the first compare (one load + wait per iteration was 19 dependent round trips at
+    // Qwen3's 4748 partials, in a one-block launch the whole chip waits for); past the end the last key is read again: a maximum
+    constexpr int kInFlight = 20;   // (20 x 256 >= 4748: one round)
+    for (int i0 = threadIdx.x; i0 < n_partials; i0 += 256 * kInFlight) {
+        unsigned long long k[kInFlight];
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) k[u] = partials[min(i0 + u * 256, n_partials - 1)];
+#pragma unroll
+        for (int u = 0; u < kInFlight; ++u) best = k[u] > best ? k[u] : best;
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const unsigned long long other = __shfl_xor(best, o, 64);
@@ -223,6 +232,18 @@ bool attention_takes_oproj(omx_qwen3 m) {
                attn_step_oproj_q4_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size, c.quant_group);
     // (a dense float16 model: the O projection stays its own launch -- the attention launch's O phase is bf16-only)
     return c.quant_bits == 0 && !m->f16 && attn_step_oproj_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size);
+}
+
+// down + residual of a layer and [RMSNorm + q/k/v] of the next one as ONE launch (csrc/gemv_chain.hip): the dense bf16 step of a single rank
+// on its launch-per-op form, no rows-per-wave override of the two GEMVs it stands for, a shape the kernel has a register layout for and a
+// grid that is resident as a whole (every workgroup of that launch waits on all others); OMX_DOWN_QKV=0 keeps the two launches
+bool down_takes_qkv(omx_qwen3 m) {
+    const bool off = env_off("OMX_DOWN_QKV");          // (read per call: tests flip it between engines of one process)
+    const omx_qwen3_config& c = m->cfg;
+    if (off || m->chain_disabled || c.quant_bits != 0 || m->f16 || c.num_experts > 0 || c.tp_size > 1 || c.ep_size > 1 || m->allreduce != nullptr) return false;
+    if (step_engine_mode(m) != 0 || env_int("OMX_GEMV_RPW_QKV", 0) != 0 || env_int("OMX_GEMV_RPW_DOWN", 0) != 0) return false;
+    if (!m->chain_gran || !gemv_chain_ok(c.hidden_size, m->I, (m->H + 2 * m->Hkv) * c.head_dim)) return false;
+    return gemv_chain_grid(c.hidden_size) <= kGemvChainBlocksPerCU * m->cus;
 }
 
 // OMX_PEER_FUSED: a GEMV whose blocks poll their peers' stores must be resident as a whole -- a block waiting for a peer's row while
@@ -528,9 +549,11 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
     // MoE block without its weighted-sum launch (the next GEMV folds the experts' outputs in): every block of that GEMV reads top_k
     // extra f32 vectors, so by default only for top-2 routing (Mixtral-8x7B: 206.4 -> 207.9 tok/s); OMX_MOE_FOLD=1 forces it, 0 disables
     const bool moe_fold = env_on("OMX_MOE_FOLD", c.num_experts_per_tok <= 2) && c.num_experts > 0 && !ep && !tp;
+    // layers 0 .. L-2 end with [down + residual + the next layer's RMSNorm + q/k/v] in one launch: layers 1 .. L-1 find their q/k/v done
+    const bool chain = !engine && down_takes_qkv(m);
     for (int l = 0; l < (engine ? 0 : c.num_hidden_layers); ++l) {
         const LayerW& L = m->layers[l];
-        {   // [RMSNorm + QKV GEMV]  model.rs:168-170,324
+        if (!(chain && l > 0)) {   // [RMSNorm + QKV GEMV]  model.rs:168-170,324
             GemvArgs a = {};
             a.w0 = L.q; a.n0 = m->H * D;
             a.w1 = L.k; a.n1 = m->Hkv * D;
@@ -628,7 +651,24 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             if (launch_gemv(a, PRO_RMSNORM, EPI_SWIGLU, s)) return 1;
             if (pending) { std::swap(h, hn); pending = nullptr; pending_n = 1; }
         }
-        {   // [down GEMV + residual]  model.rs:266,327
+        if (chain && l + 1 < c.num_hidden_layers) {   // [down GEMV + residual] [RMSNorm + QKV GEMV of layer l + 1]: one launch
+            const LayerW& Ln = m->layers[l + 1];
+            GemvChainArgs a = {};
+            a.w_down = L.down; a.N = hd; a.K = m->I;
+            a.x = m->act; a.resid = h; a.out = hn;
+            a.xg = m->chain_gran; a.seq_ptr = m->step_seq; a.abort_flag = m->wait_abort;
+            a.tag_mul = (unsigned)c.num_hidden_layers; a.tag_add = (unsigned)l + 1u;
+            a.w0 = Ln.q; a.n0 = m->H * D;
+            a.w1 = Ln.k; a.n1 = m->Hkv * D;
+            a.w2 = Ln.v; a.n2 = m->Hkv * D;
+            a.NQ = (m->H + 2 * m->Hkv) * D;
+            a.norm_w = Ln.in_ln; a.eps = c.rms_norm_eps;
+            a.out_bias = Ln.qkv_bias;
+            a.qkv_out = m->qkv;
+            time_next_launch(m, l, KC_DOWN);              // (the timing hook splits the figure between the two classes by their bytes)
+            if (launch_gemv_chain(a, s)) return 1;
+            std::swap(h, hn);
+        } else {   // [down GEMV + residual]  model.rs:266,327
             GemvArgs a = {};
             a.w0 = L.down; a.n0 = hd; a.N = hd; a.K = m->I;
             a.x = m->act;
@@ -766,7 +806,7 @@ int step_health(omx_qwen3 m) {
     return 0;
 }
 
-// A launch whose workgroups wait on each other (the persistent step, the O projection inside the attention launch) gave up: some
+// A launch whose workgroups wait on each other (down + q/k/v in one launch, the persistent step, the O projection inside the attention launch) gave up: some
 // workgroup was not resident -- another process or stream holds CUs.  Drop to the next form that needs less co-residency, restore the
 // step state the call started from and let the caller run the steps again (the KV rows they wrote are rewritten).  Returns 0 when a
 // retry is possible.
@@ -775,7 +815,8 @@ int step_fallback(omx_qwen3 m, const StepState& st) {
     // more than one rank: a local replay would re-enqueue every all-reduce of the n steps (and the argmax one) on THIS rank only -- its
     // peers never issue them, so the collectives would pair with the peers' next call (wrong sums or a hang).  Report the abort instead.
     if (m->allreduce != nullptr || m->cfg.tp_size > 1 || m->cfg.ep_size > 1) return 1;
-    if (!m->se_disabled && step_engine_takes(m)) m->se_disabled = true;
+    if (!m->chain_disabled && down_takes_qkv(m)) m->chain_disabled = true;
+    else if (!m->se_disabled && step_engine_takes(m)) m->se_disabled = true;
     else if (!m->oproj_disabled && attention_takes_oproj(m)) m->oproj_disabled = true;
     else return 1;
     drop_graphs(m);

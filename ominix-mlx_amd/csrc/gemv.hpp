@@ -95,4 +95,32 @@ GemvRoute gemv_route(const GemvArgs& a, int pro, int epi);
 // true when launch_gemv has a kernel for contraction width K (K not a multiple of 512 only without a prologue)
 bool gemv_k_supported(int K, bool needs_full_vectors);
 
+// ---- down GEMV + residual of a layer and [RMSNorm + q/k/v GEMV] of the NEXT layer as one launch (gemv_chain.hip) ----
+// Phase A is gemv_kernel<NVW, 4, 2, PRO_NONE, EPI_RESIDUAL> on (w_down, x, resid) -> out; the same bf16 row also leaves as tagged
+// granules (granule.hpp).  Every wave then requests its rows of the stacked q/k/v matrices, the block awaits and sweeps the row and
+// finishes with the arithmetic of gemv_kernel<NVW, 1, 2, PRO_RMSNORM, EPI_STORE> on (w0 | w1 | w2, norm_w, eps, out_bias) -> qkv_out.
+struct GemvChainArgs {
+    const bf16_t* w_down;       // [N, K]
+    int N, K;                   // hidden rows, intermediate columns
+    const bf16_t* x;            // [K] the SwiGLU output
+    const bf16_t* resid;        // [N]
+    bf16_t* out;                // [N] the new residual row
+    uint64_t* xg;               // [N / 2] granules {two packed bf16 of the row, tag}; one buffer serves every layer (a launch boundary between them)
+    const unsigned* seq_ptr;    // step sequence number; tag = seq * tag_mul + tag_add (tag_add = layer + 1)
+    unsigned tag_mul, tag_add;
+    unsigned* abort_flag;       // raised when a wait gives up
+    const bf16_t *w0, *w1, *w2; // the next layer's q / k / v, [n*, N]
+    int n0, n1, n2, NQ;         // NQ = n0 + n1 + n2
+    const bf16_t* norm_w;       // [N] the next layer's input RMSNorm weight
+    float eps;
+    const bf16_t* out_bias;     // optional [NQ]
+    bf16_t* qkv_out;            // [NQ]
+};
+// a register layout exists: hidden 4096, intermediate 12288 (Qwen3-8B), 4097..6144 q/k/v rows (three per wave)
+bool gemv_chain_ok(int hidden, int inter, int n_qkv);
+// workgroups of the launch -- each waits on all others, so all of them must be resident: two per CU (<= 256 VGPRs, 25 KB of LDS)
+int gemv_chain_grid(int hidden);
+constexpr int kGemvChainBlocksPerCU = 2;
+int launch_gemv_chain(const GemvChainArgs& a, hipStream_t s);
+
 }  // namespace omx

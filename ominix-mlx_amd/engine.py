@@ -78,6 +78,8 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_debug_trace_step": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, ctypes.POINTER(c_int)]),
     "omx_qwen3_time_step_kernels": (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_float)]),
     "omx_qwen3_debug_trace_engine": (c_int, [c_void_p, c_void_p, ctypes.c_size_t, ctypes.POINTER(c_int)]),
+    "omx_qwen3_debug_step_forms": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "omx_qwen3_debug_raise_give_up": (c_int, [c_void_p]),
     "omx_qwen3_verify": (c_int, [c_void_p, ctypes.POINTER(c_uint32), c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_verify_logits": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "omx_qwen3_trim": (c_int, [c_void_p, c_int, c_uint32]),
@@ -434,6 +436,16 @@ class Model:
         us = (ctypes.c_float * 7)()
         check(lib.omx_qwen3_time_step_kernels(self._h, steps, us))
         return dict(zip(self.KERNEL_CLASSES, (float(v) for v in us)))
+
+    def step_forms(self) -> dict:
+        """Which in-launch folds the next decode step would take (test hook, omx_qwen3_debug_step_forms)."""
+        f = (c_int * 4)()
+        check(lib.omx_qwen3_debug_step_forms(self._h, f))
+        return {"down_qkv": bool(f[0]), "attn_oproj": bool(f[1]), "step_engine": int(f[2]), "down_qkv_gave_up": bool(f[3])}
+
+    def raise_give_up(self) -> None:
+        """Set, from the host, the word a wait inside a launch raises when it gives up (test hook of the fallback ladder)."""
+        check(lib.omx_qwen3_debug_raise_give_up(self._h))
 
     def step_bytes(self, ctx: int) -> float:
         v = ctypes.c_double()
