@@ -281,6 +281,38 @@ int omx_qwen3_verify(omx_qwen3 m, const uint32_t* tokens, int n, uint32_t* greed
 int omx_qwen3_sampler_state(omx_qwen3 m, uint32_t* state2, int set);
 int omx_qwen3_verify_logits(omx_qwen3 m, int row, void* host_bf16, int n);
 int omx_qwen3_trim(omx_qwen3 m, int n, uint32_t next_token);
+/* Batched decode (csrc/engine_batch.hip): up to 8 independent sequences on ONE loaded model.  The reference's Model::forward and KVCache
+ * carry a batch dimension ([B, L] ids, [B, Hkv, T, D] cache, mlx-rs-core/src/cache.rs); a batch object is its ragged form: every slot is a
+ * sequence with its own K/V slabs, position, pending token and sampler, and one decode step advances any chosen subset of the slots with
+ * ONE weight stream per Linear (the rows launches of omx_qwen3_verify).  The model's own sequence (omx_qwen3_prefill / _decode / _verify,
+ * its graphs, slabs and state) is untouched and both may be used on the same model -- but a batch shares the model's stream and its
+ * prompt-pass scratch: calls on a model and on its batches must be SERIALISED by the caller, and a batch must be destroyed before its model.
+ *   create:  n_slots 1..8; max_context 0 = the model's (not above it; rounded up to the 256 step like the model's).  Accepts the models
+ *            omx_qwen3_verify accepts: single rank, dense MLP, bf16 weights or packed weights with bf16 scales, no filtered sampling.
+ *   set_sampler: per slot, the rule of omx_qwen3_set_sampler -- 0 = greedy (default), else categorical(logits / T) with the slot's OWN key
+ *            sequence seeded from `seed` (top-k / top-p / penalties are not available per slot).
+ *   prefill: the prompt through the batched prompt pass onto the slot's slabs at the slot's offset (a second prefill appends), then the
+ *            first token from the slot's sampler, which becomes the slot's pending token.
+ *   decode:  `slots` = 1..n_slots distinct prefilled slots in any order; each advances n_steps (<= 1024) tokens; tokens_out is HOST memory
+ *            [n_steps][n_slots], columns in the listed order; slots not listed are untouched.  Every listed slot needs offset + n_steps <=
+ *            capacity (checked before anything runs).  The steps are enqueued back to back and the host waits once, at the end: positions,
+ *            pending tokens and sampler keys live in device memory.  A sequence's tokens and logits do not depend on which other slots
+ *            are listed beside it, nor on their contents.
+ *   logits:  bf16 logits [V] of the last prefill or step the slot took part in.   offset: tokens in the slot's cache.
+ *   trim:    omx_qwen3_trim per slot: forget the last n cached tokens and make next_token the pending token (n = 0: only the token).
+ *   reset:   the slot is empty again (its sampler's key sequence goes on).                                                              */
+typedef struct omx_qwen3_batch_* omx_qwen3_batch;
+int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int max_context);
+int omx_qwen3_batch_destroy(omx_qwen3_batch b);
+int omx_qwen3_batch_set_sampler(omx_qwen3_batch b, int slot, float temperature, uint64_t seed);
+int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, uint32_t* first_token);
+int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out);
+int omx_qwen3_batch_logits(omx_qwen3_batch b, int slot, void* host_bf16, int n);
+int omx_qwen3_batch_offset(omx_qwen3_batch b, int slot, int* offset);
+int omx_qwen3_batch_trim(omx_qwen3_batch b, int slot, int n, uint32_t next_token);
+int omx_qwen3_batch_reset(omx_qwen3_batch b, int slot);
+/* device time of the steps of the last omx_qwen3_batch_decode call (HIP events on the model's stream), ms */
+int omx_qwen3_batch_last_decode_ms(omx_qwen3_batch b, float* ms);
 /* measurement hook (csrc/per_op_route.hip): qwen3-mlx's Model::forward + Generate::next replayed call for call through the mlx-c handle ABI
  * on this engine's weights (borrowed) -- what an UNMODIFIED crate gets.  tokens_out [n_new + 1]: the token sampled from the prompt, then n_new
  * greedy tokens; host wall-clock per decoded token and mlx_* calls per token. */

@@ -1,0 +1,686 @@
+// Batched decode of up to 8 independent sequences on one loaded Qwen3 model (include/omx.h "Batched decode").
+//
+// The reference's Model::forward and KVCache carry a batch dimension ([B, L] ids, [B, Hkv, T, D] cache, mlx-rs-core/src/cache.rs); the
+// engine's own step pins B = 1.  A batch object adds the ragged form: n_slots sequences, each with its own K/V slabs, position, pending
+// token and sampler, of which one step advances any subset as the M rows of ONE weight stream per Linear -- the rows launches of the
+// speculative verify pass (gemv_rows.hip, qgemv_rows.hip), called through the same batched pass (engine_prefill.hip).  What differs
+// from a verify pass is here: the rows are M different sequences, so the embedding gather, the cache append and the attention take
+// their position, token and slab per row from a slot table in device memory, and the sampler advances that table -- n steps of a call
+// are enqueued back to back and the host waits once.
+//
+// Attention splits are kChunk tokens wide whatever the batch holds: a sequence's partials, and the order its merge adds them in,
+// depend on its own length only, so a sequence's bits do not depend on its neighbours (attn_decode_kernel derives its chunk from the
+// launch's split count, which follows the longest sequence).
+#include "engine_model.hpp"
+
+namespace omx {
+namespace {
+
+constexpr int kMaxSlots = 8;
+constexpr int kChunk = 256;        // tokens per attention split: a multiple of the block step of both head widths (64 / 128 tokens)
+constexpr int kRingSteps = 1024;   // steps of one decode call the token ring holds
+
+constexpr int kBlock = 256;
+constexpr int kWaves = 4;
+constexpr int kUnroll = 4;
+
+// ---- embedding rows of the pending tokens.  BITS = 0: a bf16 table, rows copied; else the packed table, each element
+// (float)q * scale + bias with one rounding -- the expression of qembed_rows_kernel (engine_prefill.hip).  One block per row.
+template <int BITS>
+__global__ __launch_bounds__(256) void batch_embed_kernel(bf16_t* __restrict__ out, const void* __restrict__ table_, const bf16_t* __restrict__ scales,
+                                                          const bf16_t* __restrict__ biases, const BatchSlot* __restrict__ slots,
+                                                          const int* __restrict__ row_slot, int hidden, int group) {
+    const size_t id = slots[row_slot[blockIdx.x]].pending;
+    if constexpr (BITS == 0) {
+        const u32x4* src = reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(table_) + id * (size_t)hidden);
+        u32x4* dst = reinterpret_cast<u32x4*>(out + (size_t)blockIdx.x * hidden);
+        for (int j = threadIdx.x; j < hidden / 8; j += blockDim.x) dst[j] = src[j];
+    } else {
+        const uint32_t* wrow = reinterpret_cast<const uint32_t*>(table_) + id * (size_t)(hidden / 32 * BITS);
+        const bf16_t* srow = scales + id * (size_t)(hidden / group);
+        const bf16_t* brow = biases ? biases + id * (size_t)(hidden / group) : nullptr;
+        for (int j = threadIdx.x; j < hidden; j += blockDim.x) {
+            const int p = j * BITS, k = p >> 5, o = p & 31;
+            const uint32_t q = (o + BITS <= 32 ? wrow[k] >> o : __builtin_amdgcn_alignbit(wrow[k + 1], wrow[k], o)) & ((1u << BITS) - 1u);
+            const float sc = bf16_to_f32(srow[j / group]), b = brow ? bf16_to_f32(brow[j / group]) : 0.f;
+            out[(size_t)blockIdx.x * hidden + j] = f32_to_bf16((float)q * sc + b);
+        }
+    }
+}
+
+// ---- q/k norm + RoPE + cache append, the arithmetic of qk_norm_rope_scatter_kernel (prefill.hip) with the position and the slab of
+// every row taken from its slot: q rows -> q_out[r][h][:], k / v rows -> slot s's slabs at pos[s]
+template <int D>
+__global__ __launch_bounds__(256) void batch_scatter_kernel(
+    const bf16_t* __restrict__ q_lin, const bf16_t* __restrict__ k_lin, const bf16_t* __restrict__ v_lin,
+    const bf16_t* __restrict__ q_norm_w, const bf16_t* __restrict__ k_norm_w, const float* __restrict__ rope_cos,
+    const float* __restrict__ rope_sin, bf16_t* __restrict__ q_out, bf16_t* __restrict__ kbase, bf16_t* __restrict__ vbase,
+    size_t slot_stride, const BatchSlot* __restrict__ slots, const int* __restrict__ row_slot, int T, int H, int Hkv, int cap, float eps) {
+    constexpr int LPR = D / 8;
+    const int lane = threadIdx.x & 63;
+    const int c = lane % LPR;
+    const int rows_per_block = 256 / LPR;
+    const int64_t row = (int64_t)blockIdx.x * rows_per_block + threadIdx.x / LPR;
+    const int per_tok = H + 2 * Hkv;
+    if (row >= (int64_t)T * per_tok) return;
+    const int t = (int)(row / per_tok), hh = (int)(row % per_tok);
+    const int slot = row_slot[t];
+    const int pos = min(slots[slot].pos, cap - 1);   // (the host refuses a step past the slab's end before it launches anything)
+    bf16_t* kcache = kbase + (size_t)slot * slot_stride;
+    bf16_t* vcache = vbase + (size_t)slot * slot_stride;
+    if (hh >= H + Hkv) {   // v: plain copy into the slab
+        const int kvh = hh - H - Hkv;
+        *reinterpret_cast<u32x4*>(vcache + ((size_t)kvh * cap + pos) * D + c * 8) =
+            *reinterpret_cast<const u32x4*>(v_lin + ((size_t)t * Hkv + kvh) * D + c * 8);
+        return;
+    }
+    const bool is_q = hh < H;
+    const bf16_t* src = is_q ? q_lin + ((size_t)t * H + hh) * D : k_lin + ((size_t)t * Hkv + (hh - H)) * D;
+    const bf16_t* w = is_q ? q_norm_w : k_norm_w;
+    const u32x4 r = *reinterpret_cast<const u32x4*>(src + c * 8);
+    const u32x4 wr = w ? *reinterpret_cast<const u32x4*>(w + c * 8) : u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};   // no q/k norm: weight 1
+    float x[8], wv[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        x[2 * e] = bf16lo(r[e]); x[2 * e + 1] = bf16hi(r[e]);
+        wv[2 * e] = bf16lo(wr[e]); wv[2 * e + 1] = bf16hi(wr[e]);
+    }
+    float ss = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) ss = fmaf(x[e], x[e], ss);
+    ss = group_sum<LPR>(ss);
+    const float rstd = w ? 1.0f / sqrtf(ss / (float)D + eps) : 1.0f;   // without a norm the projection goes to RoPE as it is
+    const int i0 = (c % (LPR / 2)) * 8;
+    const bool first_half = c < LPR / 2;
+    float y[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float xn = round_bf16(x[e] * rstd * wv[e]);
+        // partner element i +- D/2 lives in lane c ^ (LPR/2)
+        const float other = (LPR == 16) ? dpp_f<0x128>(xn) : dpp_f<0x1B>(dpp_f<kDppHalfMirror>(xn));
+        const float cs = rope_cos[(size_t)pos * (D / 2) + i0 + e], sn = rope_sin[(size_t)pos * (D / 2) + i0 + e];
+        y[e] = first_half ? xn * cs - other * sn : other * sn + xn * cs;
+    }
+    u32x4 o;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) o[e] = pack_bf16(y[2 * e], y[2 * e + 1]);
+    bf16_t* dst = is_q ? q_out + ((size_t)t * H + hh) * D : kcache + ((size_t)(hh - H) * cap + pos) * D;
+    *reinterpret_cast<u32x4*>(dst + c * 8) = o;
+}
+
+// ---- ragged split-KV decode attention.  The mapping of attn_decode_kernel (attn_decode.hip): K/V rows straight to registers, 16 bytes
+// per lane, the G query heads of a KV head together, one running max per head and wave, the waves' partials merged through LDS.
+// grid = (T * Hkv) x nsplit; block (r, kvh, split) covers tokens [split * chunk, min(len, (split + 1) * chunk)) of row r's slot, len =
+// pos + 1 read from the slot table; a block past its sequence's end writes nothing and the merge never reads its partial.
+struct BatchAttnArgs {
+    const bf16_t* q;           // [T, H, D]
+    const bf16_t *kbase, *vbase;
+    size_t slot_stride, head_stride;
+    const BatchSlot* slots;
+    const int* row_slot;
+    int H, Hkv, cap, chunk, nsplit_cap;
+    float scale;
+    float *ws_o, *ws_ml;       // [T * H][nsplit_cap][D], [T * H][nsplit_cap][2]
+    bf16_t* out;               // [T, H * D]
+};
+
+__device__ __forceinline__ void unpack8(const u32x4 r, float (&x)[8]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        x[2 * e] = bf16lo(r[e]);
+        x[2 * e + 1] = bf16hi(r[e]);
+    }
+}
+
+template <int D, int GT>
+__global__ __launch_bounds__(kBlock) void batch_attn_kernel(const BatchAttnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int bk = blockIdx.x, split = blockIdx.y;
+    constexpr int LPR = D / 8;          // lanes per K/V row
+    constexpr int TPW = 64 / LPR;       // tokens per wave-instruction == token sub-groups per wave
+    constexpr int STEP = TPW * kUnroll; // tokens per wave per step
+    float* sm_o = reinterpret_cast<float*>(smem);                 // [kWaves][TPW][GT][D]
+    float* sm_m = sm_o + kWaves * TPW * GT * D;                   // [kWaves][GT]
+    float* sm_l = sm_m + kWaves * GT;                             // [kWaves][GT]
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int c = lane % LPR;           // 8-element chunk of the head dim owned by this lane
+    const int sg = lane / LPR;          // token sub-group inside the wave
+    const int r = bk / a.Hkv, kvh = bk % a.Hkv;
+    const int G = a.H / a.Hkv;
+    const int slot = a.row_slot[r];
+    const int Tk = min(a.slots[slot].pos + 1, a.cap);
+    const int t_begin = split * a.chunk;
+    if (t_begin >= Tk) return;          // (block-uniform: past this sequence's end)
+    const int t_end = min(Tk, t_begin + a.chunk);
+
+    const bf16_t* Kb = a.kbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride;
+    const bf16_t* Vb = a.vbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride;
+
+    u32x4 kr[kUnroll], vr[kUnroll];
+    int t0 = t_begin + wave * STEP;
+    auto issue_kv = [&](int tbase) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int tc = max(min(tbase + u * TPW + sg, t_end - 1), 0);
+            kr[u] = *reinterpret_cast<const u32x4*>(Kb + (size_t)tc * D + c * 8);
+            vr[u] = *reinterpret_cast<const u32x4*>(Vb + (size_t)tc * D + c * 8);
+        }
+    };
+    if (t0 < t_end) issue_kv(t0);
+
+    float q[GT][8];
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+        const int h = kvh * G + min(g, G - 1);
+        float x[8];
+        unpack8(*reinterpret_cast<const u32x4*>(a.q + ((size_t)r * a.H + h) * D + c * 8), x);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) q[g][e] = x[e] * a.scale;
+    }
+
+    float m[GT], l[GT], o[GT][8];
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+        m[g] = -INFINITY;
+        l[g] = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+    }
+
+    for (; t0 < t_end; t0 += STEP * kWaves) {
+        float s[kUnroll][GT];
+        float vf[kUnroll][8];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int tok = t0 + u * TPW + sg;
+            float kf[8];
+            unpack8(kr[u], kf);
+            unpack8(vr[u], vf[u]);
+            if (tok >= t_end) {   // clamped duplicate row: its p is 0, but 0 * garbage must stay 0
+#pragma unroll
+                for (int e = 0; e < 8; ++e) vf[u][e] = 0.f;
+            }
+#pragma unroll
+            for (int g = 0; g < GT; ++g) {
+                float d = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) d = fmaf(q[g][e], kf[e], d);
+                d = group_sum<LPR>(d);
+                s[u][g] = tok < t_end ? d : -INFINITY;
+            }
+        }
+        if (t0 + STEP * kWaves < t_end) issue_kv(t0 + STEP * kWaves);
+#pragma unroll
+        for (int g = 0; g < GT; ++g) {
+            float mx = s[0][g];
+#pragma unroll
+            for (int u = 1; u < kUnroll; ++u) mx = fmaxf(mx, s[u][g]);
+            float wmx = readlane_f(mx, 0);
+#pragma unroll
+            for (int rr = 1; rr < TPW; ++rr) wmx = fmaxf(wmx, readlane_f(mx, rr * LPR));
+            const float mn = fmaxf(m[g], wmx);
+            const float alpha = (mn == -INFINITY) ? 1.f : __expf(m[g] - mn);
+            m[g] = mn;
+            l[g] *= alpha;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[g][e] *= alpha;
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const float p = (mn == -INFINITY) ? 0.f : __expf(s[u][g] - mn);
+                l[g] += p;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[g][e] = fmaf(p, vf[u][e], o[g][e]);
+            }
+        }
+    }
+
+    // every token sub-group parks its partial in LDS (same m inside a wave: plain sums)
+#pragma unroll
+    for (int g = 0; g < GT; ++g) {
+        float* dst = sm_o + (((size_t)(wave * TPW + sg) * GT + g) * D + c * 8);
+        *reinterpret_cast<f32x4*>(dst) = f32x4{o[g][0], o[g][1], o[g][2], o[g][3]};
+        *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[g][4], o[g][5], o[g][6], o[g][7]};
+        float lw = readlane_f(l[g], 0);
+#pragma unroll
+        for (int rr = 1; rr < TPW; ++rr) lw += readlane_f(l[g], rr * LPR);
+        if (lane == 0) {
+            sm_m[wave * GT + g] = m[g];
+            sm_l[wave * GT + g] = lw;
+        }
+    }
+    __syncthreads();
+    // merge the 4 waves x TPW sub-groups, write the split's partial
+    for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {
+        const int g = idx / D, d = idx % D;
+        float M = sm_m[g];
+#pragma unroll
+        for (int w = 1; w < kWaves; ++w) M = fmaxf(M, sm_m[w * GT + g]);
+        float L = 0.f, O = 0.f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const float mw = sm_m[w * GT + g];
+            const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+            float ow = 0.f;
+#pragma unroll
+            for (int rr = 0; rr < TPW; ++rr) ow += sm_o[((size_t)(w * TPW + rr) * GT + g) * D + d];
+            L = fmaf(f, sm_l[w * GT + g], L);
+            O = fmaf(f, ow, O);
+        }
+        const size_t head = (size_t)r * a.H + kvh * G + g;
+        a.ws_o[(head * a.nsplit_cap + split) * D + d] = O;
+        if (d == 0) {
+            a.ws_ml[(head * a.nsplit_cap + split) * 2] = M;
+            a.ws_ml[(head * a.nsplit_cap + split) * 2 + 1] = L;
+        }
+    }
+}
+
+// merge of a (row, head)'s splits: out[d] = sum_i e^{m_i - M} o_i[d] / sum_i e^{m_i - M} l_i over the ceil(len / chunk) splits of ITS
+// sequence, added in split order, rounded once to bf16.  One block per (row, head), one thread per d.
+template <int D>
+__global__ __launch_bounds__(D) void batch_attn_merge_kernel(const BatchAttnArgs a) {
+    const size_t head = blockIdx.x;
+    const int r = (int)(head / a.H), d = threadIdx.x;
+    const int Tk = min(a.slots[a.row_slot[r]].pos + 1, a.cap);
+    const int ns = (Tk + a.chunk - 1) / a.chunk;
+    const float* ml = a.ws_ml + head * a.nsplit_cap * 2;
+    const float* src = a.ws_o + head * a.nsplit_cap * D + d;
+    float M = -INFINITY;
+    for (int i = 0; i < ns; ++i) M = fmaxf(M, ml[2 * i]);
+    float L = 0.f, acc = 0.f;
+    for (int i = 0; i < ns; ++i) {
+        const float mi = ml[2 * i];
+        const float f = (mi == -INFINITY) ? 0.f : __expf(mi - M);
+        L = fmaf(f, ml[2 * i + 1], L);
+        acc = fmaf(f, src[(size_t)i * D], acc);
+    }
+    a.out[head * D + d] = f32_to_bf16(acc / L);
+}
+
+// ---- per-row sampler + state advance.  One block per row: the row's logits are kept as its slot's last logits, the token is the
+// argmax (inv_temp 0) or categorical(logits / T) -- logits * (1/T) + Gumbel noise, the noise of vocabulary entry v being word v of a
+// V-word draw from the NEXT key of the slot's own sequence (RandomState::next, the rule of rng_next_kernel + sample_noise_kernel,
+// random.hip) -- first index winning a tie; then ring[step][row] = token, pending[s] = token, pos[s] += 1.
+struct BatchSampleArgs {
+    const bf16_t* rows;        // [T, V] logits of this step
+    bf16_t* slot_logits;       // [n_slots, V]
+    BatchSlot* slots;
+    const int* row_slot;
+    uint32_t* ring;            // this step's [T] entries
+    int V;
+    float inv_temp[kMaxSlots]; // per row; 0 = greedy
+};
+
+__global__ __launch_bounds__(1024) void batch_sample_kernel(const BatchSampleArgs a) {
+    __shared__ unsigned long long red[16];
+    const int r = blockIdx.x, slot = a.row_slot[r];
+    BatchSlot* S = a.slots + slot;
+    const float it = a.inv_temp[r];
+    const bf16_t* row = a.rows + (size_t)r * a.V;
+    bf16_t* keep = a.slot_logits + (size_t)slot * a.V;
+    uint32_t s0 = 0, s1 = 0, k0 = 0, k1 = 0;
+    if (it != 0.f) {   // (state, key) = split(state, 2)
+        const uint32_t c0 = S->rng[0], c1 = S->rng[1];
+        threefry2x32(c0, c1, 0u, 2u, s0, k0);
+        threefry2x32(c0, c1, 1u, 3u, s1, k1);
+    }
+    __syncthreads();   // every thread has read the state before thread 0 replaces it
+    unsigned long long best = 0;
+    for (int v = threadIdx.x; v < a.V; v += blockDim.x) {
+        const bf16_t raw = row[v];
+        keep[v] = raw;
+        float x = bf16_to_f32(raw);
+        if (it != 0.f) x = x * it + gumbel_from_word(random_word(k0, k1, (uint64_t)v, (uint64_t)a.V));
+        const unsigned long long kx = sample_key(x, (uint32_t)v);
+        best = kx > best ? kx : best;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(best, o, 64);
+        best = other > best ? other : best;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (unsigned w = 1; w < blockDim.x / 64; ++w) best = red[w] > best ? red[w] : best;
+        const uint32_t token = ~(uint32_t)(best & 0xFFFFFFFFull);
+        a.ring[r] = token;
+        S->pending = token;
+        S->pos += 1;
+        if (it != 0.f) { S->rng[0] = s0; S->rng[1] = s1; S->rng[2] = k0; S->rng[3] = k1; }
+    }
+}
+
+}  // namespace
+
+int launch_batch_embed(omx_qwen3 m, const RaggedRows& rag, int T, hipStream_t s) {
+    const omx_qwen3_config& c = m->cfg;
+    const int hd = c.hidden_size;
+#define OMX_BATCH_EMB(B) \
+    case B: batch_embed_kernel<B><<<T, 256, 0, s>>>(m->pf_h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, rag.slots, rag.row_slot, hd, c.quant_group); break;
+    switch (c.quant_bits) {
+        case 0: batch_embed_kernel<0><<<T, 256, 0, s>>>(m->pf_h, m->embed, nullptr, nullptr, rag.slots, rag.row_slot, hd, 0); break;
+        OMX_BATCH_EMB(2) OMX_BATCH_EMB(3) OMX_BATCH_EMB(4) OMX_BATCH_EMB(5) OMX_BATCH_EMB(6) OMX_BATCH_EMB(8)
+        default: return set_error("batch embed: quantization bits %d unsupported", c.quant_bits);
+    }
+#undef OMX_BATCH_EMB
+    OMX_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_batch_scatter(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s) {
+    const omx_qwen3_config& c = m->cfg;
+    const LayerW& L = m->layers[layer];
+    const int D = c.head_dim, H = m->H, Hkv = m->Hkv;
+    const int64_t rows = (int64_t)T * (H + 2 * Hkv);
+    const int rpb = 256 / (D / 8);
+    const unsigned blocks = (unsigned)((rows + rpb - 1) / rpb);
+    if (D == 128)
+        batch_scatter_kernel<128><<<blocks, 256, 0, s>>>(m->pf_q, m->pf_k, m->pf_v, L.q_norm, L.k_norm, m->rope_cos, m->rope_sin, m->pf_qt,
+                                                         rag.kbase[layer], rag.vbase[layer], rag.slot_stride, rag.slots, rag.row_slot, T, H, Hkv,
+                                                         rag.cap, c.rms_norm_eps);
+    else
+        batch_scatter_kernel<64><<<blocks, 256, 0, s>>>(m->pf_q, m->pf_k, m->pf_v, L.q_norm, L.k_norm, m->rope_cos, m->rope_sin, m->pf_qt,
+                                                        rag.kbase[layer], rag.vbase[layer], rag.slot_stride, rag.slots, rag.row_slot, T, H, Hkv,
+                                                        rag.cap, c.rms_norm_eps);
+    OMX_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s) {
+    const int D = m->cfg.head_dim, H = m->H, Hkv = m->Hkv, G = H / Hkv;
+    OMX_REQUIRE(G >= 1 && G <= 8, "batch attention: %d query heads per KV head unsupported (max 8)", G);
+    OMX_REQUIRE(rag.nsplit >= 1 && rag.nsplit <= rag.nsplit_cap, "batch attention: %d splits of %d", rag.nsplit, rag.nsplit_cap);
+    BatchAttnArgs a = {};
+    a.q = m->pf_qt;
+    a.kbase = rag.kbase[layer]; a.vbase = rag.vbase[layer];
+    a.slot_stride = rag.slot_stride; a.head_stride = (size_t)rag.cap * D;
+    a.slots = rag.slots; a.row_slot = rag.row_slot;
+    a.H = H; a.Hkv = Hkv; a.cap = rag.cap; a.chunk = rag.chunk; a.nsplit_cap = rag.nsplit_cap;
+    a.scale = 1.0f / sqrtf((float)D);
+    a.ws_o = rag.ws_o; a.ws_ml = rag.ws_ml;
+    a.out = m->pf_attn;
+    const dim3 grid(T * Hkv, rag.nsplit), block(kBlock);
+    const int gt = G <= 1 ? 1 : G <= 2 ? 2 : G <= 4 ? 4 : 8;
+#define OMX_BATCH_ATTN_CASE(DD, GG)                                                                     \
+    if (D == DD && gt == GG) {                                                                          \
+        const size_t shmem = ((size_t)kWaves * (64 / (DD / 8)) * GG * DD + 2 * kWaves * GG + 4) * sizeof(float); \
+        if (shmem > 48 * 1024)                                                                          \
+            OMX_HIP_CHECK(hipFuncSetAttribute((const void*)batch_attn_kernel<DD, GG>,                   \
+                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+        batch_attn_kernel<DD, GG><<<grid, block, shmem, s>>>(a);                                        \
+        OMX_LAUNCH_CHECK();                                                                             \
+        batch_attn_merge_kernel<DD><<<T * H, DD, 0, s>>>(a);                                            \
+        OMX_LAUNCH_CHECK();                                                                             \
+        return 0;                                                                                       \
+    }
+    OMX_BATCH_ATTN_CASE(128, 1) OMX_BATCH_ATTN_CASE(128, 2) OMX_BATCH_ATTN_CASE(128, 4) OMX_BATCH_ATTN_CASE(128, 8)
+    OMX_BATCH_ATTN_CASE(64, 1) OMX_BATCH_ATTN_CASE(64, 2) OMX_BATCH_ATTN_CASE(64, 4) OMX_BATCH_ATTN_CASE(64, 8)
+#undef OMX_BATCH_ATTN_CASE
+    return set_error("batch attention: head_dim %d unsupported (64 or 128)", D);
+}
+
+}  // namespace omx
+
+struct omx_qwen3_batch_ {
+    omx_qwen3 m = nullptr;
+    int n_slots = 0, cap = 0;
+    std::vector<bf16_t*> kbase, vbase;                 // per layer: [n_slots][Hkv, cap, D]
+    std::vector<bf16_t*> slot_k[kMaxSlots], slot_v[kMaxSlots];   // the same slabs per slot, as the prompt pass takes them (KvSlabs)
+    size_t slot_stride = 0;
+    BatchSlot* slots = nullptr;                        // device [n_slots]
+    int* row_slot = nullptr;                           // device [kMaxSlots]: the rows of the call in flight
+    bf16_t *step_logits = nullptr, *slot_logits = nullptr;   // [kMaxSlots, V] rows of a step; [n_slots, V] kept per slot
+    uint32_t* ring = nullptr;                          // [kRingSteps][kMaxSlots]
+    float *ws_o = nullptr, *ws_ml = nullptr;           // attention partials
+    int nsplit_cap = 0;
+    // host mirror: a step advances every listed slot by exactly one token, so the positions never have to be read back
+    int pos[kMaxSlots] = {};
+    bool prefilled[kMaxSlots] = {};
+    float temperature[kMaxSlots] = {};
+    float last_decode_ms = 0.f;                        // device time of the last decode call's steps (the model's event pair)
+    std::vector<void*> owned;
+};
+
+namespace {
+
+template <class T>
+int batch_alloc(omx_qwen3_batch b, T** p, size_t n) {
+    void* q = nullptr;
+    OMX_HIP_CHECK(hipMalloc(&q, n * sizeof(T) + 64));
+    OMX_HIP_CHECK(hipMemsetAsync(q, 0, n * sizeof(T) + 64, b->m->stream));
+    *p = (T*)q;
+    b->owned.push_back(q);
+    return 0;
+}
+
+// [final RMSNorm] -> [lm_head over M rows] -> [per-row sample + advance]: rows x[M, hidden] of slots row_slot[0..M) (already on the device)
+int batch_head_and_sample(omx_qwen3_batch b, const bf16_t* x, const int* rows, int M, uint32_t* ring_at) {
+    omx_qwen3 m = b->m;
+    hipStream_t s = m->stream;
+    const int hd = m->cfg.hidden_size, V = m->V;
+    if (m->cfg.quant_bits) {   // the packed head (or the tied q_embed table), the final RMSNorm as its prologue
+        QGemvArgs a = {};
+        a.m[0] = m->q_head; a.m[0].n = V; a.N = V; a.K = hd; a.group = m->cfg.quant_group;
+        a.x = x; a.norm_w = m->final_norm; a.eps = m->cfg.rms_norm_eps; a.out = b->step_logits;
+        if (packed_rows(a, M, nullptr, m->cfg.quant_bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
+    } else {
+        if (omx_rms_norm(m->pf_xn, x, m->final_norm, M, hd, m->cfg.rms_norm_eps, OMX_BFLOAT16, s)) return 1;
+        if (launch_gemm_bf16(b->step_logits, m->pf_xn, m->lm_head, nullptr, M, V, hd, s)) return 1;
+    }
+    BatchSampleArgs a = {};
+    a.rows = b->step_logits; a.slot_logits = b->slot_logits; a.slots = b->slots; a.row_slot = b->row_slot; a.ring = ring_at; a.V = V;
+    for (int r = 0; r < M; ++r) a.inv_temp[r] = b->temperature[rows[r]] == 0.f ? 0.f : 1.0f / b->temperature[rows[r]];
+    batch_sample_kernel<<<M, 1024, 0, s>>>(a);
+    OMX_LAUNCH_CHECK();
+    return 0;
+}
+
+int write_slot(omx_qwen3_batch b, int slot, const BatchSlot& v, size_t bytes) {   // the leading `bytes` of the entry: pos | pending
+    OMX_HIP_CHECK(hipMemcpyAsync(b->slots + slot, &v, bytes, hipMemcpyHostToDevice, b->m->stream));
+    OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
+    return 0;
+}
+
+}  // namespace
+
+#define OMX_BATCH_SLOT(fn)                                                                                \
+    OMX_REQUIRE(b, fn ": null batch");                                                                    \
+    OMX_REQUIRE(slot >= 0 && slot < b->n_slots, fn ": slot %d out of range (0..%d)", slot, b->n_slots - 1)
+
+extern "C" {
+
+int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int max_context) {
+    OMX_REQUIRE(out && m, "omx_qwen3_batch_create: null argument");
+    OMX_REQUIRE(n_slots >= 1 && n_slots <= kMaxSlots, "omx_qwen3_batch_create: %d slots (1..%d)", n_slots, kMaxSlots);
+    const omx_qwen3_config& c = m->cfg;
+    OMX_REQUIRE(c.num_experts == 0, "omx_qwen3_batch_create: models with experts (MoE) are not supported; dense models only");
+    OMX_REQUIRE(m->allreduce == nullptr && c.tp_size <= 1 && c.ep_size <= 1,
+                "omx_qwen3_batch_create: tensor / expert parallel models are not supported (single-rank models only)");
+    OMX_REQUIRE(!c.float16_weights, "omx_qwen3_batch_create: dense float16 models (float16_weights) are not supported; batched decode runs "
+                "on bf16 weights or bf16-scale packed weights");
+    OMX_REQUIRE(!c.quant_scales_f16,
+                "omx_qwen3_batch_create: float16 triplets (scales_dtype float16) are not supported on packed models; bf16 scales only");
+    OMX_REQUIRE(!m->filter_on, "omx_qwen3_batch_create: filtered sampling (top-k / top-p / penalties, omx_qwen3_set_sampling) is on: a batch "
+                "slot draws from unfiltered rows; call omx_qwen3_set_sampler first");
+    OMX_REQUIRE(m->H / m->Hkv <= 8, "omx_qwen3_batch_create: %d query heads per KV head unsupported (max 8)", m->H / m->Hkv);
+    OMX_REQUIRE(max_context >= 0, "omx_qwen3_batch_create: max_context %d must be >= 0 (0 = the model's)", max_context);
+    const int step = 256;   // cache.rs:110-117
+    const int cap = max_context > 0 ? (max_context + step - 1) / step * step : m->cap;
+    OMX_REQUIRE(cap <= m->cap, "omx_qwen3_batch_create: max_context %d exceeds the model's %d (its RoPE tables end there)", max_context, m->cap);
+    omx_qwen3_batch b = new omx_qwen3_batch_();
+    b->m = m;
+    b->n_slots = n_slots;
+    b->cap = cap;
+    const int D = c.head_dim, L = c.num_hidden_layers, V = m->V;
+    b->slot_stride = (size_t)m->Hkv * cap * D;
+    b->kbase.resize(L);
+    b->vbase.resize(L);
+    int rc = 0;
+    for (int l = 0; l < L && !rc; ++l) {
+        rc = batch_alloc(b, &b->kbase[l], b->slot_stride * n_slots) || batch_alloc(b, &b->vbase[l], b->slot_stride * n_slots);
+        for (int s = 0; s < n_slots && !rc; ++s) {
+            b->slot_k[s].push_back(b->kbase[l] + (size_t)s * b->slot_stride);
+            b->slot_v[s].push_back(b->vbase[l] + (size_t)s * b->slot_stride);
+        }
+    }
+    b->nsplit_cap = cap / kChunk;
+    rc = rc || batch_alloc(b, &b->slots, (size_t)n_slots) || batch_alloc(b, &b->row_slot, (size_t)kMaxSlots) ||
+         batch_alloc(b, &b->step_logits, (size_t)kMaxSlots * V) || batch_alloc(b, &b->slot_logits, (size_t)n_slots * V) ||
+         batch_alloc(b, &b->ring, (size_t)kRingSteps * kMaxSlots) ||
+         batch_alloc(b, &b->ws_o, (size_t)kMaxSlots * m->H * b->nsplit_cap * D) || batch_alloc(b, &b->ws_ml, (size_t)kMaxSlots * m->H * b->nsplit_cap * 2);
+    // every slot starts with the key sequence of seed 0, like a model whose sampler was set to (T, 0)
+    for (int s = 0; s < n_slots && !rc; ++s) rc = omx_random_key(b->slots[s].rng, 0, (omx_stream)m->stream);
+    if (!rc && hipStreamSynchronize(m->stream) != hipSuccess) rc = set_error("omx_qwen3_batch_create: stream synchronise failed");
+    if (rc) {
+        omx_qwen3_batch_destroy(b);
+        return 1;
+    }
+    *out = b;
+    return 0;
+}
+
+int omx_qwen3_batch_destroy(omx_qwen3_batch b) {
+    if (!b) return 0;
+    if (b->m && b->m->stream) (void)hipStreamSynchronize(b->m->stream);
+    for (void* p : b->owned) (void)hipFree(p);
+    delete b;
+    return 0;
+}
+
+int omx_qwen3_batch_set_sampler(omx_qwen3_batch b, int slot, float temperature, uint64_t seed) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_set_sampler");
+    OMX_REQUIRE(temperature >= 0.f && temperature == temperature, "omx_qwen3_batch_set_sampler: temperature %f must be >= 0", (double)temperature);
+    if (omx_random_key(b->slots[slot].rng, seed, (omx_stream)b->m->stream)) return 1;
+    OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
+    b->temperature[slot] = temperature;
+    return 0;
+}
+
+int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, uint32_t* first_token) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_prefill");
+    OMX_REQUIRE(prompt && first_token, "omx_qwen3_batch_prefill: null argument");
+    OMX_REQUIRE(n_prompt >= 1, "omx_qwen3_batch_prefill: empty prompt");
+    omx_qwen3 m = b->m;
+    const int off = b->pos[slot];
+    OMX_REQUIRE(off + n_prompt + 1 <= b->cap, "omx_qwen3_batch_prefill: %d cached + %d prompt tokens exceed max_context %d", off, n_prompt, b->cap);
+    for (int i = 0; i < n_prompt; ++i)
+        OMX_REQUIRE(prompt[i] < (uint32_t)m->cfg.vocab_size, "omx_qwen3_batch_prefill: token id %u out of range (vocab %d)", prompt[i], m->cfg.vocab_size);
+    OMX_REQUIRE(n_prompt <= m->prompt_cap, "omx_qwen3_batch_prefill: prompt of %d tokens exceeds the model's prompt buffer (%d)", n_prompt, m->prompt_cap);
+    OMX_REQUIRE(!m->filter_on, "omx_qwen3_batch_prefill: filtered sampling (omx_qwen3_set_sampling) is on; call omx_qwen3_set_sampler first");
+    if (resolve_weights(m)) return 1;
+    hipStream_t s = m->stream;
+    // a handful of rows of a packed model: the packed rows launches, as the verify pass (nothing dequantised); else the prompt pass's GEMMs
+    const bool prow = m->cfg.quant_bits != 0 && n_prompt <= 8;
+    if (m->cfg.quant_bits && !prow) dq_cache_prepare(m);
+    if (prefill_reserve(m, n_prompt, !prow)) return 1;
+    OMX_HIP_CHECK(hipMemcpyAsync(m->prompt_dev, prompt, (size_t)n_prompt * 4, hipMemcpyHostToDevice, s));
+    const KvSlabs kv = {b->slot_k[slot].data(), b->slot_v[slot].data(), b->cap};
+    if (prefill_prefix_batched(m, n_prompt, off, nullptr, /*full_last=*/true, prow, &kv)) return 1;
+    // the last row through the head and the slot's sampler: the sample launch turns pos = off + n - 1 into off + n
+    BatchSlot v = {};
+    v.pos = off + n_prompt - 1;
+    v.pending = prompt[n_prompt - 1];
+    OMX_HIP_CHECK(hipMemcpyAsync(b->slots + slot, &v, 8, hipMemcpyHostToDevice, s));
+    OMX_HIP_CHECK(hipMemcpyAsync(b->row_slot, &slot, 4, hipMemcpyHostToDevice, s));
+    if (batch_head_and_sample(b, m->pf_h + (size_t)(n_prompt - 1) * m->cfg.hidden_size, &slot, 1, b->ring)) return 1;
+    OMX_HIP_CHECK(hipMemcpyAsync(first_token, b->ring, 4, hipMemcpyDeviceToHost, s));
+    OMX_HIP_CHECK(hipStreamSynchronize(s));
+    b->pos[slot] = off + n_prompt;
+    b->prefilled[slot] = true;
+    return 0;
+}
+
+int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out) {
+    OMX_REQUIRE(b && slots && tokens_out, "omx_qwen3_batch_decode: null argument");
+    OMX_REQUIRE(n_slots >= 1 && n_slots <= b->n_slots, "omx_qwen3_batch_decode: %d slots listed (1..%d)", n_slots, b->n_slots);
+    OMX_REQUIRE(n_steps >= 0 && n_steps <= kRingSteps, "omx_qwen3_batch_decode: n_steps=%d out of range (0..%d per call)", n_steps, kRingSteps);
+    omx_qwen3 m = b->m;
+    int rows[kMaxSlots];
+    int longest = 0;
+    for (int r = 0; r < n_slots; ++r) {
+        const int slot = slots[r];
+        OMX_REQUIRE(slot >= 0 && slot < b->n_slots, "omx_qwen3_batch_decode: slot %d out of range (0..%d)", slot, b->n_slots - 1);
+        for (int q = 0; q < r; ++q) OMX_REQUIRE(slots[q] != slot, "omx_qwen3_batch_decode: slot %d listed twice", slot);
+        OMX_REQUIRE(b->prefilled[slot], "omx_qwen3_batch_decode: slot %d has not been prefilled", slot);
+        OMX_REQUIRE(b->pos[slot] + n_steps <= b->cap, "omx_qwen3_batch_decode: slot %d: %d cached + %d new tokens exceed max_context %d", slot,
+                    b->pos[slot], n_steps, b->cap);
+        rows[r] = slot;
+        longest = std::max(longest, b->pos[slot] + n_steps);
+    }
+    OMX_REQUIRE(!m->filter_on, "omx_qwen3_batch_decode: filtered sampling (omx_qwen3_set_sampling) is on; call omx_qwen3_set_sampler first");
+    if (n_steps == 0) return 0;
+    if (resolve_weights(m)) return 1;
+    hipStream_t s = m->stream;
+    const bool packed = m->cfg.quant_bits != 0;
+    if (prefill_reserve(m, n_slots, false)) return 1;
+    OMX_HIP_CHECK(hipMemcpyAsync(b->row_slot, rows, (size_t)n_slots * 4, hipMemcpyHostToDevice, s));
+    RaggedRows rag = {};
+    rag.slots = b->slots; rag.row_slot = b->row_slot;
+    rag.kbase = b->kbase.data(); rag.vbase = b->vbase.data();
+    rag.slot_stride = b->slot_stride; rag.cap = b->cap;
+    rag.chunk = kChunk; rag.nsplit_cap = b->nsplit_cap;
+    rag.nsplit = (longest + kChunk - 1) / kChunk;   // the longest listed sequence at the end of the call
+    rag.ws_o = b->ws_o; rag.ws_ml = b->ws_ml;
+    OMX_HIP_CHECK(hipEventRecord(m->ev0, s));
+    for (int i = 0; i < n_steps; ++i) {
+        if (prefill_prefix_batched(m, n_slots, 0, nullptr, /*full_last=*/true, packed, nullptr, &rag)) return 1;
+        if (batch_head_and_sample(b, m->pf_h, rows, n_slots, b->ring + (size_t)i * n_slots)) return 1;
+    }
+    OMX_HIP_CHECK(hipEventRecord(m->ev1, s));
+    OMX_HIP_CHECK(hipMemcpyAsync(tokens_out, b->ring, (size_t)n_steps * n_slots * 4, hipMemcpyDeviceToHost, s));
+    OMX_HIP_CHECK(hipStreamSynchronize(s));
+    OMX_HIP_CHECK(hipEventElapsedTime(&b->last_decode_ms, m->ev0, m->ev1));
+    for (int r = 0; r < n_slots; ++r) b->pos[rows[r]] += n_steps;
+    return 0;
+}
+
+int omx_qwen3_batch_last_decode_ms(omx_qwen3_batch b, float* ms) {
+    OMX_REQUIRE(b && ms, "omx_qwen3_batch_last_decode_ms: null argument");
+    *ms = b->last_decode_ms;
+    return 0;
+}
+
+int omx_qwen3_batch_logits(omx_qwen3_batch b, int slot, void* host_bf16, int n) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_logits");
+    OMX_REQUIRE(host_bf16, "omx_qwen3_batch_logits: null argument");
+    OMX_REQUIRE(n == b->m->V, "omx_qwen3_batch_logits: expected %d entries, got %d", b->m->V, n);
+    OMX_HIP_CHECK(hipMemcpyAsync(host_bf16, b->slot_logits + (size_t)slot * b->m->V, (size_t)n * 2, hipMemcpyDeviceToHost, b->m->stream));
+    OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
+    return 0;
+}
+
+int omx_qwen3_batch_offset(omx_qwen3_batch b, int slot, int* offset) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_offset");
+    OMX_REQUIRE(offset, "omx_qwen3_batch_offset: null argument");
+    BatchSlot v;   // the device's word, not the host's count of it
+    OMX_HIP_CHECK(hipMemcpyAsync(&v, b->slots + slot, sizeof(v), hipMemcpyDeviceToHost, b->m->stream));
+    OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
+    *offset = v.pos;
+    return 0;
+}
+
+int omx_qwen3_batch_trim(omx_qwen3_batch b, int slot, int n, uint32_t next_token) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_trim");
+    OMX_REQUIRE(next_token < (uint32_t)b->m->cfg.vocab_size, "omx_qwen3_batch_trim: token id %u out of range (vocab %d)", next_token, b->m->cfg.vocab_size);
+    OMX_REQUIRE(n >= 0 && n <= b->pos[slot], "omx_qwen3_batch_trim: cannot drop %d of %d cached tokens", n, b->pos[slot]);
+    BatchSlot v = {};
+    v.pos = b->pos[slot] - n;
+    v.pending = next_token;
+    if (write_slot(b, slot, v, 8)) return 1;
+    b->pos[slot] = v.pos;
+    return 0;
+}
+
+int omx_qwen3_batch_reset(omx_qwen3_batch b, int slot) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_reset");
+    const BatchSlot v = {};
+    if (write_slot(b, slot, v, 8)) return 1;   // (the sampler's key sequence goes on, as omx_qwen3_reset leaves the model's)
+    b->pos[slot] = 0;
+    b->prefilled[slot] = false;
+    return 0;
+}
+
+}  // extern "C"

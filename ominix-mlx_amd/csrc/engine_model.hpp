@@ -60,6 +60,35 @@ struct EncodeOpts {
     const bf16_t* mask;       // optional additive [T, T] (causal + padding), nullptr = causal
 };
 
+// One slot of a batch object (engine_batch.hip) in device memory: the step's kernels read and advance it there, so that the steps of
+// one omx_qwen3_batch_decode call follow each other without the host.
+struct BatchSlot {
+    int pos;               // tokens in the slot's cache == RoPE offset of the pending token
+    uint32_t pending;      // token the slot's next step feeds to the embedding
+    uint32_t rng[4];       // the slot's sampler: [0..1] key-sequence state, [2..3] key of the current draw (as omx_qwen3_::rng)
+    int pad[2];
+};
+
+// KV slabs [Hkv, cap, D] per layer a batched pass appends to and attends over instead of the model's own (a batch slot's)
+struct KvSlabs {
+    bf16_t* const* k;
+    bf16_t* const* v;
+    int cap;
+};
+
+// The ragged form of the batched pass: row r is the pending token of slot row_slot[r], at that slot's position, on that slot's slabs
+// (slot s of layer l at kbase[l] + s * slot_stride).  Attention splits are `chunk` tokens wide whatever the other rows' lengths;
+// ws_o / ws_ml hold nsplit_cap partials per (row, head), of which a launch fills the first `nsplit` at most.
+struct RaggedRows {
+    BatchSlot* slots;         // device
+    const int* row_slot;      // device [T]
+    bf16_t* const* kbase;
+    bf16_t* const* vbase;
+    size_t slot_stride;
+    int cap, chunk, nsplit, nsplit_cap;
+    float *ws_o, *ws_ml;
+};
+
 }  // namespace omx
 
 using namespace omx;
@@ -230,7 +259,14 @@ int launch_ep_fold(int grid, bf16_t* out, const bf16_t* resid, const float* part
 int prefill_reserve(omx_qwen3 m, int T, bool dequant = true);
 void dq_cache_prepare(omx_qwen3 m);
 int packed_rows(const QGemvArgs& g, int T, bf16_t* const* mout, int bits, int pro, int epi, hipStream_t s);
-int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = nullptr, bool full_last = false, bool packed_rows_pass = false);
+int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = nullptr, bool full_last = false, bool packed_rows_pass = false,
+                           const KvSlabs* kv = nullptr, const RaggedRows* rag = nullptr);
 void launch_encoder_mask(bf16_t* mask, const uint8_t* am, int T, hipStream_t s);
+
+// engine_batch.hip: the ragged launches of a batched decode step over T <= 8 rows (RaggedRows); q rows go to pf_qt as [T, H, D], the
+// attention output to pf_attn as [T, H * D]
+int launch_batch_embed(omx_qwen3 m, const RaggedRows& rag, int T, hipStream_t s);
+int launch_batch_scatter(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s);
+int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s);
 
 }  // namespace omx

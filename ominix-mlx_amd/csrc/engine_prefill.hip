@@ -155,7 +155,11 @@ int packed_rows(const QGemvArgs& g, int T, bf16_t* const* mout, int bits, int pr
 // The last layer stops after its cache scatter: nothing downstream of it is consumed for these tokens.
 // packed_rows_pass (omx_qwen3_verify only): every packed Linear of a dense single-rank bf16-triplet model through qgemv_rows.hip -- no weight
 // is dequantised, neither into the dequant cache nor into its scratch
-int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, bool full_last, bool packed_rows_pass) {
+// kv: the slabs the rows are appended to and attend over (default: the model's own).
+// rag (omx_qwen3_batch_decode only): the T rows are T different sequences -- embedding, cache append and attention take their ragged
+// form (engine_batch.hip), every Linear is the launch the verify pass makes for T rows
+int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, bool full_last, bool packed_rows_pass, const KvSlabs* kv,
+                           const RaggedRows* rag) {
     const omx_qwen3_config& c = m->cfg;
     // float16 checkpoints (round 4): the same pass in float16 -- weights dequantised to float16, the eight-wave GEMM kernel's float16
     // form, float16 norms / RoPE / slabs, the flash attention kernel's float16 form -- for
@@ -175,6 +179,10 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
     const bool prow = packed_rows_pass && c.quant_bits != 0;
     OMX_REQUIRE(!prow || (!f16 && !enc && c.num_experts == 0 && m->allreduce == nullptr && c.tp_size <= 1 && c.ep_size <= 1),
                 "packed verify pass: dense single-rank models with bf16 scales only");
+    OMX_REQUIRE(!rag || (T <= 8 && full_last && !f16 && !enc && !kv && (prow || !c.quant_bits) && c.num_experts == 0 && m->allreduce == nullptr &&
+                         c.tp_size <= 1 && c.ep_size <= 1),
+                "ragged pass: up to 8 rows of a dense single-rank model with bf16 weights or bf16-scale packed weights");
+    const int cap = kv ? kv->cap : m->cap;
     if (prefill_reserve(m, T, !prow)) return 1;   // (omx_qwen3_prefill has called it ahead of its timed region already)
     // tensor parallel: q/k/v/gate/up are this rank's column shards (local H, Hkv, I), o / down are row
     // shards whose [T, hidden] bf16 partial sums are all-reduced -- two collectives per layer -- before the residual add
@@ -218,7 +226,9 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
         if (launch_dequantize_bf16(m->dq_buf + at, qm->w, qm->scales, qm->biases, qm->n, K, c.quant_group, c.quant_bits, f16, s, f16)) return nullptr;
         return m->dq_buf + at;
     };
-    if (prow) {
+    if (rag) {
+        if (launch_batch_embed(m, *rag, T, s)) return 1;
+    } else if (prow) {
         const int bits = c.quant_bits;
 #define OMX_QEMB_ROWS(B) \
         case B: OMX_LAUNCH(qembed_rows_kernel<B>, T, 256, 0, s, m->pf_h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->prompt_dev, hd, c.quant_group); break;
@@ -290,8 +300,13 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
             if (!(w = W(L.k, &Q.k, hd)) || launch_gemm_bf16(m->pf_k, m->pf_xn, w, L.k_bias, T, Hkv * D, hd, s)) return 1;
             if (!(w = W(L.v, &Q.v, hd)) || launch_gemm_bf16(m->pf_v, m->pf_xn, w, L.v_bias, T, Hkv * D, hd, s)) return 1;
         }
+        bf16_t* const kc = kv ? kv->k[l] : m->kcache[l];
+        bf16_t* const vc = kv ? kv->v[l] : m->vcache[l];
+        if (rag) {
+            if (launch_batch_scatter(m, l, *rag, T, s)) return 1;
+        } else
         if (launch_qk_norm_rope_scatter(m->pf_q, m->pf_k, m->pf_v, L.q_norm, L.k_norm, m->rope_cos, m->rope_sin, m->pf_qt,
-                                        m->kcache[l], m->vcache[l], T, H, Hkv, D, m->cap, off, c.rms_norm_eps, s, f16))
+                                        kc, vc, T, H, Hkv, D, cap, off, c.rms_norm_eps, s, f16))
             return 1;
         if (!enc && !full_last && l == c.num_hidden_layers - 1) break;   // a prefix only has to leave its K/V rows behind
         const bool skv_off = env_off("OMX_PREFILL_SPLITKV");
@@ -300,14 +315,17 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
             // product, one rounding of the output) -- MLX's fast SDPA accumulates in f32 the same way
             // (OMX_F16_ATTN=explicit: f32 on widened copies through omx_sdpa, then heads back next to each other per token: the A/B form)
             if (env_is("OMX_F16_ATTN", "explicit")) {
-                if (omx_sdpa(m->pf_q, m->pf_qt, m->kcache[l], m->vcache[l], 1, H, Hkv, T, off + T, D, 0, (int64_t)m->cap * D, scale, OMX_MASK_CAUSAL,
+                if (omx_sdpa(m->pf_q, m->pf_qt, kc, vc, 1, H, Hkv, T, off + T, D, 0, (int64_t)cap * D, scale, OMX_MASK_CAUSAL,
                              nullptr, OMX_FLOAT16, s))
                     return 1;
                 heads_to_tokens_kernel<<<1024, 256, 0, s>>>(m->pf_attn, m->pf_q, H, T, D);
                 OMX_LAUNCH_CHECK();
-            } else if (launch_attn_prefill(m->pf_attn, m->pf_qt, m->kcache[l], m->vcache[l], 1, H, Hkv, T, off + T, D, 0, (int64_t)m->cap * D, scale,
+            } else if (launch_attn_prefill(m->pf_attn, m->pf_qt, kc, vc, 1, H, Hkv, T, off + T, D, 0, (int64_t)cap * D, scale,
                                            OMX_MASK_CAUSAL, nullptr, s, /*out_token_major=*/true, nullptr, /*f16=*/true))
                 return 1;
+        } else
+        if (rag) {   // row r over the first pos + 1 keys of its own slot's slabs
+            if (launch_batch_attention(m, l, *rag, T, s)) return 1;
         } else
         if (!enc && T <= 8 && H / Hkv <= 8 && !skv_off) {
             // a handful of new rows over a long cache (speculative verify, a short follow-up prompt): the flash kernel gives them
@@ -315,8 +333,8 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
             // kernel takes the T rows as batch entries over the ONE cache, row i seeing the first off + i + 1 keys
             AttnDecodeArgs a = {};
             a.q = m->pf_qt; a.q_bs = D; a.q_hs = (int64_t)T * D;                    // q_out[h][t][:] of the scatter kernel
-            a.k = m->kcache[l]; a.v = m->vcache[l];
-            a.kv_batch_stride = 0; a.kv_head_stride = (int64_t)m->cap * D;
+            a.k = kc; a.v = vc;
+            a.kv_batch_stride = 0; a.kv_head_stride = (int64_t)cap * D;
             a.B = T; a.H = H; a.Hkv = Hkv; a.Tk = off + T;
             a.scale = scale; a.mask_mode = OMX_MASK_NONE; a.causal_tail = 1;
             a.nsplit = decode_nsplit(off + T, T * Hkv);
@@ -326,8 +344,8 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
             a.ws_ml = a.ws_o + (size_t)T * H * a.nsplit * D;
             a.out = m->pf_attn;                                                       // [T, H * D]
             if (launch_attn_decode(a, D, s)) return 1;
-        } else if (launch_attn_prefill(m->pf_attn, m->pf_qt, m->kcache[l], m->vcache[l], 1, H, Hkv, T, off + T, D, 0,
-                                (int64_t)m->cap * D, scale, enc && enc->mask ? OMX_MASK_ADDITIVE : OMX_MASK_CAUSAL,
+        } else if (launch_attn_prefill(m->pf_attn, m->pf_qt, kc, vc, 1, H, Hkv, T, off + T, D, 0,
+                                (int64_t)cap * D, scale, enc && enc->mask ? OMX_MASK_ADDITIVE : OMX_MASK_CAUSAL,
                                 enc ? enc->mask : nullptr, s, /*out_token_major=*/true))
             return 1;
         if (prow) {   // o + residual

@@ -84,6 +84,17 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_verify_logits": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "omx_qwen3_trim": (c_int, [c_void_p, c_int, c_uint32]),
     "omx_qwen3_get_weight": (c_int, [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t)]),
+    # batched decode: up to 8 independent sequences per step on one loaded model (csrc/engine_batch.hip)
+    "omx_qwen3_batch_create": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int]),
+    "omx_qwen3_batch_destroy": (c_int, [c_void_p]),
+    "omx_qwen3_batch_set_sampler": (c_int, [c_void_p, c_int, ctypes.c_float, ctypes.c_uint64]),
+    "omx_qwen3_batch_prefill": (c_int, [c_void_p, c_int, ctypes.POINTER(c_uint32), c_int, ctypes.POINTER(c_uint32)]),
+    "omx_qwen3_batch_decode": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_uint32)]),
+    "omx_qwen3_batch_logits": (c_int, [c_void_p, c_int, c_void_p, c_int]),
+    "omx_qwen3_batch_offset": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "omx_qwen3_batch_trim": (c_int, [c_void_p, c_int, c_int, c_uint32]),
+    "omx_qwen3_batch_reset": (c_int, [c_void_p, c_int]),
+    "omx_qwen3_batch_last_decode_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     # test hook of the dense decode GEMV (csrc/gemv.hip): one launch of a prologue / epilogue form, bf16 or float16
     "omx_debug_gemv": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_float, c_int, c_void_p]),
     "omx_debug_gemv_grid": (c_int, [c_int, c_int]),
@@ -450,6 +461,76 @@ class Model:
     def step_bytes(self, ctx: int) -> float:
         v = ctypes.c_double()
         check(lib.omx_qwen3_step_bytes(self._h, ctx, ctypes.byref(v)))
+        return v.value
+
+    def batch(self, n_slots: int, max_context: int = 0) -> "Batch":
+        """Up to 8 independent sequences decoded together on this model's weights (omx_qwen3_batch_*)."""
+        return Batch(self, n_slots, max_context)
+
+
+class Batch:
+    """n_slots independent sequences on one loaded Model, each with its own KV slabs, position, pending token and sampler; `decode`
+    advances any subset of them with one weight stream per Linear.  The model's own prefill / decode / verify keep working beside it;
+    calls on a model and its batches must not overlap (they share the model's stream and prompt scratch)."""
+
+    def __init__(self, model: Model, n_slots: int, max_context: int = 0):
+        self.model, self.n_slots = model, int(n_slots)
+        self._h = c_void_p()
+        check(lib.omx_qwen3_batch_create(ctypes.byref(self._h), model._h, int(n_slots), int(max_context)))
+
+    def close(self) -> None:
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            m = getattr(self.model, "_h", None)
+            if m is not None and m.value:     # (a closed model has freed the stream the batch would wait on)
+                lib.omx_qwen3_batch_destroy(h)
+            self._h = c_void_p()
+
+    def __del__(self):
+        if sys is not None and not sys.is_finalizing():
+            self.close()
+
+    def set_sampler(self, slot: int, temperature: float, seed: int = 0) -> None:
+        """Model.set_sampler's plain rule for one slot: 0 = greedy, else categorical(logits / temperature) from the slot's own key sequence."""
+        check(lib.omx_qwen3_batch_set_sampler(self._h, int(slot), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF))
+
+    def prefill(self, slot: int, prompt) -> int:
+        """The prompt onto the slot's cache (appended to what the slot holds); returns the slot's first sampled token."""
+        p = np.ascontiguousarray(prompt, dtype=np.uint32)
+        first = c_uint32()
+        check(lib.omx_qwen3_batch_prefill(self._h, int(slot), p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, ctypes.byref(first)))
+        return first.value
+
+    def decode(self, n: int, slots=None) -> np.ndarray:
+        """n tokens for each of `slots` (default: all; distinct, prefilled) -> [n, len(slots)], columns in the listed order."""
+        ids = np.ascontiguousarray(list(range(self.n_slots)) if slots is None else slots, dtype=np.int32).ravel()
+        out = np.empty((int(n), ids.size), dtype=np.uint32)
+        check(lib.omx_qwen3_batch_decode(self._h, ids.ctypes.data_as(ctypes.POINTER(c_int)), ids.size, int(n),
+                                         out.ctypes.data_as(ctypes.POINTER(c_uint32))))
+        return out
+
+    def logits(self, slot: int) -> np.ndarray:
+        """float32-widened bf16 logits of the last prefill or step the slot took part in."""
+        raw = np.empty(self.model.vocab_local, dtype=np.uint16)
+        check(lib.omx_qwen3_batch_logits(self._h, int(slot), raw.ctypes.data, raw.size))
+        return (raw.astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+    def offset(self, slot: int) -> int:
+        v = c_int()
+        check(lib.omx_qwen3_batch_offset(self._h, int(slot), ctypes.byref(v)))
+        return v.value
+
+    def trim(self, slot: int, n: int, next_token: int) -> None:
+        """Model.trim for one slot: forget the last n cached tokens; next_token becomes the pending token (n = 0: only that)."""
+        check(lib.omx_qwen3_batch_trim(self._h, int(slot), int(n), int(next_token)))
+
+    def reset(self, slot: int) -> None:
+        check(lib.omx_qwen3_batch_reset(self._h, int(slot)))
+
+    def last_decode_ms(self) -> float:
+        """Device time of the steps of the last decode call (HIP events on the model's stream)."""
+        v = c_float()
+        check(lib.omx_qwen3_batch_last_decode_ms(self._h, ctypes.byref(v)))
         return v.value
 
 

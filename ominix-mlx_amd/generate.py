@@ -7,7 +7,10 @@
     generate_text                        qwen3-mlx/examples/generate_qwen3.rs:31-101 (encode with special tokens,
                                          Generate at `temperature`, decode + emit every 10 tokens, flush the rest)
 
-The model side is `engine.Model` / `engine.Generate` (the HIP decode engine); nothing here touches the GPU."""
+    generate_batch                       many prompts over the slots of an `engine.Batch` (the reference batches through the [B, L]
+                                         ids of Model::forward; here the sequences are ragged and retire one by one)
+
+The model side is `engine.Model` / `engine.Generate` / `engine.Batch` (the HIP decode engine); nothing here touches the GPU."""
 from __future__ import annotations
 
 import json
@@ -121,3 +124,48 @@ def generate_text(model, tokenizer, prompt: str, temperature: float = 0.7, max_t
     seconds = time.perf_counter() - start
     return {"text": "".join(pieces), "tokens": all_tokens, "prompt_tokens": len(ids), "seconds": seconds,
             "tokens_per_sec": len(all_tokens) / seconds if seconds > 0 else 0.0}
+
+
+def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_ids: Iterable[int] = (), chunk: int = 16) -> List[List[int]]:
+    """Any number of token-id prompts over the slots of an `engine.Batch`: free slots are prefilled with waiting prompts, the active
+    slots decode together `chunk` tokens at a time, a sequence retires at its first token in `eos_ids` (which it keeps) or at
+    max_new_tokens -- what its slot decoded past that point inside the chunk is dropped -- and its slot is reset and handed to the next
+    waiting prompt.  Returns the generated tokens per prompt, in prompt order.  Drives `batch` through prefill / decode / reset only."""
+    if max_new_tokens < 1 or chunk < 1:
+        raise ValueError("generate_batch: max_new_tokens and chunk must be positive")
+    eos = set(int(t) for t in eos_ids)
+    outputs: List[List[int]] = [[] for _ in prompts]
+    waiting = list(range(len(prompts)))
+    free = list(range(batch.n_slots))
+    active = {}                                   # slot -> prompt index
+
+    def finished(i):
+        return len(outputs[i]) >= max_new_tokens or (outputs[i] and outputs[i][-1] in eos)
+
+    while waiting or active:
+        while waiting and free:
+            slot, i = free.pop(0), waiting.pop(0)
+            if len(prompts[i]) == 0:
+                raise ValueError(f"generate_batch: prompt {i} is empty")
+            outputs[i].append(int(batch.prefill(slot, prompts[i])))
+            if finished(i):                       # EOS as the first token, or max_new_tokens == 1
+                batch.reset(slot)
+                free.append(slot)
+            else:
+                active[slot] = i
+        if not active:
+            continue
+        slots = sorted(active)
+        n = min(chunk, min(max_new_tokens - len(outputs[active[s]]) for s in slots))
+        tokens = batch.decode(n, slots)
+        for col, slot in enumerate(slots):
+            i = active[slot]
+            for step in range(n):
+                outputs[i].append(int(tokens[step][col]))
+                if finished(i):
+                    break
+            if finished(i):
+                del active[slot]
+                batch.reset(slot)
+                free.append(slot)
+    return outputs

@@ -1,0 +1,103 @@
+"""Batched decode (engine.Batch) of the Qwen3-8B-shaped synthetic model: aggregate tokens per second against the batch size.
+
+    python tools/batch_decode.py [--bits 0 4] [--ctx 2048] [--steps 128] [--windows 3]
+        per weight format (0 = bf16, 4 = 4-bit group 64): the single-sequence Model.decode rate, then B = 1, 2, 4, 8 slots each prefilled
+        with --ctx tokens, then 8 slots with ragged contexts (ctx/8 .. ctx); every figure is the median of --windows windows of --steps
+        steps after a warm-up, timed with device events on the engine's stream (Model.last_decode_ms / Batch.last_decode_ms).
+        One JSON line per row, then the table.
+    rocprofv3 --kernel-trace --stats -f csv -d DIR -- python tools/batch_decode.py --trace --bits 0 [--ctx 2048] [--steps 16]
+        8 slots prefilled, --steps steps at B = 8 and nothing else at that row count: the trace's last steps give the per-launch times
+        of a B = 8 step (python tools/batch_decode.py --stats DIR [--steps 32] prints them; pass rocprofv3 -f csv)."""
+import argparse, csv, glob, json, os, sys
+import numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+ap.add_argument("--bits", type=int, nargs="+", default=[0, 4])
+ap.add_argument("--ctx", type=int, default=2048)
+ap.add_argument("--steps", type=int, default=128)
+ap.add_argument("--windows", type=int, default=3)
+ap.add_argument("--layers", type=int, default=36)
+ap.add_argument("--trace", action="store_true", help="only prefill 8 slots and run --steps steps at B = 8 (for a kernel trace)")
+ap.add_argument("--stats", metavar="DIR", help="print the per-launch times of the last --steps steps of a --trace run's kernel_trace.csv under DIR")
+args = ap.parse_args()
+
+if args.stats:
+    # the dispatches of the last --steps steps of the trace: a step begins with its embedding gather
+    import re, statistics
+    f = glob.glob(args.stats + "/**/*kernel_trace.csv", recursive=True)[0]
+    rows = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(f))))
+    starts = [i for i, r in enumerate(rows) if "batch_embed_kernel" in r[2]]
+    steps = min(args.steps, len(starts) - 1)
+    rows = rows[starts[-steps - 1]:starts[-1]]        # (the very last step is left out: it has no successor to end it)
+    by = {}
+    for s0, e0, name in rows:
+        name = re.sub(r"\(anonymous namespace\)::|omx::|^void ", "", name)
+        by.setdefault(re.sub(r"\(.*\)$", "", name)[:78], []).append((e0 - s0) / 1e3)
+    print(f"{'kernel':<78} {'launches/step':>13} {'median us':>10} {'us/step':>9}")
+    for name, v in sorted(by.items(), key=lambda kv: -sum(kv[1])):
+        print(f"{name:<78} {len(v) / steps:>13.1f} {statistics.median(v):>10.2f} {sum(v) / steps:>9.1f}")
+    busy = sum(sum(v) for v in by.values()) / steps
+    print(f"{steps} steps: {len(rows) / steps:.0f} launches per step, kernel time {busy:.1f} us per step, "
+          f"first start to last end {(rows[-1][1] - rows[0][0]) / 1e3 / steps:.1f} us per step")
+    sys.exit(0)
+
+import omx_import
+omx = omx_import.load_package()
+from ominix_mlx_amd import engine
+
+V = 151936
+
+
+def prompt(n, shift):
+    return ((np.arange(n, dtype=np.int64) * 7919 + 13 + shift) % V).astype(np.uint32)
+
+
+def median_ms(run, read_ms, steps, windows):
+    ms = []
+    for _ in range(windows):
+        run(steps)
+        ms.append(read_ms() / steps)
+    return float(np.median(ms)), ms
+
+
+table = []
+for bits in args.bits:
+    room = 8 + args.steps * args.windows + 16
+    m = engine.Model(hidden_size=4096, num_hidden_layers=args.layers, intermediate_size=12288, num_attention_heads=32, num_key_value_heads=8,
+                     head_dim=128, vocab_size=V, max_context=args.ctx + room, quantization={"bits": bits, "group_size": 64} if bits else None)
+    m.synth_weights()
+    fmt = f"{bits}-bit g64" if bits else "bf16"
+    b = m.batch(8)
+    if args.trace:
+        for s in range(8):
+            b.prefill(s, prompt(args.ctx, s))
+        b.decode(args.steps)
+        print(f"{fmt}: {args.steps} steps at B = 8, {b.last_decode_ms() / args.steps:.3f} ms per step", flush=True)
+        b.close(); m.close()
+        continue
+    m.prefill(prompt(args.ctx, 100))
+    m.decode(8)
+    base, raw = median_ms(m.decode, m.last_decode_ms, args.steps, args.windows)
+    row = {"format": fmt, "B": "single", "ctx": args.ctx, "ms_per_step": base, "tok_s": 1e3 / base, "ratio": 1.0, "windows_ms": raw}
+    print(json.dumps(row), flush=True)
+    table.append(row)
+    runs = [(B, [args.ctx] * B) for B in (1, 2, 4, 8)] + [(8, [args.ctx * (i + 1) // 8 for i in range(8)])]
+    for B, ctxs in runs:
+        slots = list(range(B))
+        for s in slots:
+            b.reset(s)
+            b.prefill(s, prompt(ctxs[s], s))
+        b.decode(8, slots)
+        ms, raw = median_ms(lambda n: b.decode(n, slots), b.last_decode_ms, args.steps, args.windows)
+        ragged = len(set(ctxs)) > 1
+        row = {"format": fmt, "B": B, "ctx": f"{ctxs[0]}..{ctxs[-1]}" if ragged else args.ctx, "ms_per_step": ms, "tok_s": B * 1e3 / ms,
+               "ratio": B * base / ms, "windows_ms": raw}
+        print(json.dumps(row), flush=True)
+        table.append(row)
+    b.close(); m.close()
+
+if table:
+    print(f"\n{'format':<12} {'B':>6} {'context':>10} {'ms/step':>9} {'tok/s':>9} {'x single':>9}")
+    for r in table:
+        print(f"{r['format']:<12} {str(r['B']):>6} {str(r['ctx']):>10} {r['ms_per_step']:>9.3f} {r['tok_s']:>9.1f} {r['ratio']:>9.2f}")

@@ -1,6 +1,8 @@
 """qwen3-mlx/examples/generate_qwen3.rs on the MI355X engine:
     python tools/generate_qwen3.py <model_dir> [prompt] [--temperature T] [--top-k K] [--top-p P] [--repetition-penalty R]
                                    [--presence-penalty Q] [--seed S] [--max-tokens N]
+    python tools/generate_qwen3.py <model_dir> --prompts-file FILE [--slots N] [--temperature T] [--seed S] [--max-tokens N]
+--prompts-file: one prompt per line, decoded together over N slots of one loaded model (engine.Batch; plain temperature sampling).
 Without flags: the example's plain temperature 0.7.  The Qwen3 model card's settings are --temperature 0.6 --top-k 20 --top-p 0.95."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,9 +20,32 @@ ap.add_argument("--repetition-penalty", type=float, default=1.0, help="x > 0 ? x
 ap.add_argument("--presence-penalty", type=float, default=0.0, help="x - q on generated tokens (0 = off)")
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--max-tokens", type=int, default=100)
+ap.add_argument("--prompts-file", help="one prompt per line: all of them through generate_batch over --slots slots")
+ap.add_argument("--slots", type=int, default=8, help="sequences decoded together (1..8)")
 args = ap.parse_args()
 tokenizer = generate.load_tokenizer(args.model_dir)
 model = loader.load_model(args.model_dir)
+if args.prompts_file:
+    import json, time
+    with open(args.prompts_file, encoding="utf-8") as fh:
+        texts = [ln.rstrip("\n") for ln in fh if ln.strip()]
+    prompts = [list(tokenizer.encode(t, add_special_tokens=True).ids) for t in texts]
+    eos = []
+    gen_cfg = os.path.join(args.model_dir, "generation_config.json")
+    if os.path.exists(gen_cfg):
+        e = json.load(open(gen_cfg)).get("eos_token_id", [])
+        eos = [int(t) for t in (e if isinstance(e, list) else [e])]
+    batch = model.batch(max(1, min(args.slots, len(prompts))))
+    for slot in range(batch.n_slots):
+        batch.set_sampler(slot, args.temperature, args.seed + slot)
+    start = time.perf_counter()
+    outs = generate.generate_batch(batch, prompts, args.max_tokens, eos_ids=eos)
+    seconds = time.perf_counter() - start
+    for text, toks in zip(texts, outs):
+        print(f"Prompt: {text}\n---\n{tokenizer.decode(toks, skip_special_tokens=True)}\n===")
+    total = sum(len(t) for t in outs)
+    print(f"Generated {total} tokens for {len(prompts)} prompts over {batch.n_slots} slots in {seconds:.2f}s ({total / seconds:.1f} tok/s)")
+    sys.exit(0)
 print(f"Prompt: {args.prompt}\n---")
 out = generate.generate_text(model, tokenizer, args.prompt, temperature=args.temperature, max_tokens=args.max_tokens, seed=args.seed,
                              emit=lambda t: print(t, end="", flush=True), top_k=args.top_k, top_p=args.top_p,
