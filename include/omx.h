@@ -300,7 +300,19 @@ int omx_qwen3_trim(omx_qwen3 m, int n, uint32_t next_token);
  *            are listed beside it, nor on their contents.
  *   logits:  bf16 logits [V] of the last prefill or step the slot took part in.   offset: tokens in the slot's cache.
  *   trim:    omx_qwen3_trim per slot: forget the last n cached tokens and make next_token the pending token (n = 0: only the token).
- *   reset:   the slot is empty again (its sampler's key sequence goes on).                                                              */
+ *   reset:   the slot is empty again (its sampler's key sequence goes on).
+ *   fork:    the EMPTY slot dst becomes what it would be had it been fed src's tokens itself: src's position, src's kept logits row, and a
+ *            copy of rows [0, position) of src's K/V slabs in dst's own.  resample != 0: dst's pending token is drawn from that row with
+ *            dst's own sampler and key sequence (the draw a prefill of the same prompt would have made); 0: it is src's.  *first_token is
+ *            that token.  Refused: src not prefilled, src == dst, dst not empty (reset it first), a slot out of range.  Siblings share
+ *            the whole 256-token chunks below the fork, one level deep (a fork of a fork shares the root's span): the slot table keeps,
+ *            per slot, the `owner` whose slabs hold the same bits in rows [0, shared_len), and a decode step MAY read those chunks once per
+ *            group of listed rows with the same owner instead of once per row -- to the bit the partials the rows' own slabs give, whatever
+ *            the group (OMX_BATCH_SHARE_MIN=2..8: groups from that many rows on; by default none, the grouped block being the slower
+ *            one at every size measured).  Every other call works on the slot's own copy; trim / reset / a prefill from position 0 of a slot lower the
+ *            shared_len of that slot and of the slots that share with it to the chunk boundary they leave intact.  OMX_BATCH_SHARE=0
+ *            (read by create): forks copy, shared_len stays 0, every row reads its own slab.
+ *   shared:  owner and shared_len of a slot, from the device's table.                                                                  */
 typedef struct omx_qwen3_batch_* omx_qwen3_batch;
 int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int max_context);
 int omx_qwen3_batch_destroy(omx_qwen3_batch b);
@@ -311,6 +323,8 @@ int omx_qwen3_batch_logits(omx_qwen3_batch b, int slot, void* host_bf16, int n);
 int omx_qwen3_batch_offset(omx_qwen3_batch b, int slot, int* offset);
 int omx_qwen3_batch_trim(omx_qwen3_batch b, int slot, int n, uint32_t next_token);
 int omx_qwen3_batch_reset(omx_qwen3_batch b, int slot);
+int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint32_t* first_token);
+int omx_qwen3_batch_shared(omx_qwen3_batch b, int slot, int* owner, int* shared_len);
 /* device time of the steps of the last omx_qwen3_batch_decode call (HIP events on the model's stream), ms */
 int omx_qwen3_batch_last_decode_ms(omx_qwen3_batch b, float* ms);
 /* measurement hook (csrc/per_op_route.hip): qwen3-mlx's Model::forward + Generate::next replayed call for call through the mlx-c handle ABI

@@ -123,6 +123,12 @@ struct BatchAttnArgs {
     float *ws_o, *ws_ml;       // [T * H][nsplit_cap][D], [T * H][nsplit_cap][2]
     bf16_t* out;               // [T, H * D]
 };
+// ... and of the grouped form (batch_attn_shared_kernel): the call's rows, their shared spans (RaggedRows) and the tuning
+struct BatchSharedArgs {
+    BatchAttnArgs a;
+    int T, group_min, group_rows;
+    int grp_owner[kMaxSlots], grp_shared[kMaxSlots];
+};
 
 __device__ __forceinline__ void unpack8(const u32x4 r, float (&x)[8]) {
 #pragma unroll
@@ -132,6 +138,177 @@ __device__ __forceinline__ void unpack8(const u32x4 r, float (&x)[8]) {
     }
 }
 
+// The per-row arithmetic of a split, in the pieces both kernels below are made of: what a (row, KV head, split) partial is, to the bit,
+// is written here once.  A lane owns 8 elements (c) of the head dim of token sub-group sg of its wave.
+template <int D, int GT>
+struct AttnRow {
+    static constexpr int LPR = D / 8;          // lanes per K/V row
+    static constexpr int TPW = 64 / LPR;       // tokens per wave-instruction == token sub-groups per wave
+    static constexpr int STEP = TPW * kUnroll; // tokens per wave per step
+    float q[GT][8], m[GT], l[GT], o[GT][8];
+
+    __device__ __forceinline__ void begin(const BatchAttnArgs& a, int r, int kvh, int G, int c) {
+#pragma unroll
+        for (int g = 0; g < GT; ++g) {
+            const int h = kvh * G + min(g, G - 1);
+            float x[8];
+            unpack8(*reinterpret_cast<const u32x4*>(a.q + ((size_t)r * a.H + h) * D + c * 8), x);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) q[g][e] = x[e] * a.scale;
+        }
+#pragma unroll
+        for (int g = 0; g < GT; ++g) {
+            m[g] = -INFINITY;
+            l[g] = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
+        }
+    }
+
+    // scores of the wave's STEP tokens from t0 on against the K rows in kr; the V rows unpacked
+    __device__ __forceinline__ void scores(const u32x4 (&kr)[kUnroll], const u32x4 (&vr)[kUnroll], int t0, int t_end, int sg,
+                                           float (&s)[kUnroll][GT], float (&vf)[kUnroll][8]) const {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int tok = t0 + u * TPW + sg;
+            float kf[8];
+            unpack8(kr[u], kf);
+            unpack8(vr[u], vf[u]);
+            if (tok >= t_end) {   // clamped duplicate row: its p is 0, but 0 * garbage must stay 0
+#pragma unroll
+                for (int e = 0; e < 8; ++e) vf[u][e] = 0.f;
+            }
+#pragma unroll
+            for (int g = 0; g < GT; ++g) {
+                float d = 0.f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) d = fmaf(q[g][e], kf[e], d);
+                d = group_sum<LPR>(d);
+                s[u][g] = tok < t_end ? d : -INFINITY;
+            }
+        }
+    }
+
+    // running max / sum / output of the wave over those tokens
+    __device__ __forceinline__ void update(const float (&s)[kUnroll][GT], const float (&vf)[kUnroll][8]) {
+#pragma unroll
+        for (int g = 0; g < GT; ++g) {
+            float mx = s[0][g];
+#pragma unroll
+            for (int u = 1; u < kUnroll; ++u) mx = fmaxf(mx, s[u][g]);
+            float wmx = readlane_f(mx, 0);
+#pragma unroll
+            for (int rr = 1; rr < TPW; ++rr) wmx = fmaxf(wmx, readlane_f(mx, rr * LPR));
+            const float mn = fmaxf(m[g], wmx);
+            const float alpha = (mn == -INFINITY) ? 1.f : __expf(m[g] - mn);
+            m[g] = mn;
+            l[g] *= alpha;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[g][e] *= alpha;
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) {
+                const float p = (mn == -INFINITY) ? 0.f : __expf(s[u][g] - mn);
+                l[g] += p;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) o[g][e] = fmaf(p, vf[u][e], o[g][e]);
+            }
+        }
+    }
+
+    // every token sub-group parks its partial in LDS (same m inside a wave: plain sums); the 4 waves x TPW sub-groups are merged and
+    // the split's partial of row r written.  smem: [kWaves][TPW][GT][D] o, [kWaves][GT] m, [kWaves][GT] l
+    __device__ __forceinline__ void finish(const BatchAttnArgs& a, unsigned char* smem, int r, int kvh, int G, int split) const {
+        float* sm_o = reinterpret_cast<float*>(smem);
+        float* sm_m = sm_o + kWaves * TPW * GT * D;
+        float* sm_l = sm_m + kWaves * GT;
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int c = lane % LPR, sg = lane / LPR;
+#pragma unroll
+        for (int g = 0; g < GT; ++g) {
+            float* dst = sm_o + (((size_t)(wave * TPW + sg) * GT + g) * D + c * 8);
+            *reinterpret_cast<f32x4*>(dst) = f32x4{o[g][0], o[g][1], o[g][2], o[g][3]};
+            *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[g][4], o[g][5], o[g][6], o[g][7]};
+            float lw = readlane_f(l[g], 0);
+#pragma unroll
+            for (int rr = 1; rr < TPW; ++rr) lw += readlane_f(l[g], rr * LPR);
+            if (lane == 0) {
+                sm_m[wave * GT + g] = m[g];
+                sm_l[wave * GT + g] = lw;
+            }
+        }
+        __syncthreads();
+        for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {
+            const int g = idx / D, d = idx % D;
+            float M = sm_m[g];
+#pragma unroll
+            for (int w = 1; w < kWaves; ++w) M = fmaxf(M, sm_m[w * GT + g]);
+            float L = 0.f, O = 0.f;
+#pragma unroll
+            for (int w = 0; w < kWaves; ++w) {
+                const float mw = sm_m[w * GT + g];
+                const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
+                float ow = 0.f;
+#pragma unroll
+                for (int rr = 0; rr < TPW; ++rr) ow += sm_o[((size_t)(w * TPW + rr) * GT + g) * D + d];
+                L = fmaf(f, sm_l[w * GT + g], L);
+                O = fmaf(f, ow, O);
+            }
+            const size_t head = (size_t)r * a.H + kvh * G + g;
+            a.ws_o[(head * a.nsplit_cap + split) * D + d] = O;
+            if (d == 0) {
+                a.ws_ml[(head * a.nsplit_cap + split) * 2] = M;
+                a.ws_ml[(head * a.nsplit_cap + split) * 2 + 1] = L;
+            }
+        }
+    }
+};
+
+// block (r, kvh, split) on row r's own slab: K/V rows of the next step in flight while this step's are applied
+template <int D, int GT>
+__device__ __forceinline__ void attn_own_row(const BatchAttnArgs& a, unsigned char* smem, int r, int kvh, int split) {
+    using Row = AttnRow<D, GT>;
+    constexpr int LPR = Row::LPR, TPW = Row::TPW, STEP = Row::STEP;
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int c = lane % LPR;           // 8-element chunk of the head dim owned by this lane
+    const int sg = lane / LPR;          // token sub-group inside the wave
+    const int G = a.H / a.Hkv;
+    const int slot = a.row_slot[r];
+    const int Tk = min(a.slots[slot].pos + 1, a.cap);
+    const int t_begin = split * a.chunk;
+    if (t_begin >= Tk) return;          // (block-uniform: past this sequence's end)
+    const int t_end = min(Tk, t_begin + a.chunk);
+
+    const bf16_t* Kb = a.kbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride;
+    const bf16_t* Vb = a.vbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride;
+
+    u32x4 kr[kUnroll], vr[kUnroll];
+    int t0 = t_begin + wave * STEP;
+    auto issue_kv = [&](int tbase) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int tc = max(min(tbase + u * TPW + sg, t_end - 1), 0);
+            kr[u] = *reinterpret_cast<const u32x4*>(Kb + (size_t)tc * D + c * 8);
+            vr[u] = *reinterpret_cast<const u32x4*>(Vb + (size_t)tc * D + c * 8);
+        }
+    };
+    if (t0 < t_end) issue_kv(t0);
+
+    Row row;
+    row.begin(a, r, kvh, G, c);
+    for (; t0 < t_end; t0 += STEP * kWaves) {
+        float s[kUnroll][GT];
+        float vf[kUnroll][8];
+        row.scores(kr, vr, t0, t_end, sg, s, vf);
+        if (t0 + STEP * kWaves < t_end) issue_kv(t0 + STEP * kWaves);
+        row.update(s, vf);
+    }
+    row.finish(a, smem, r, kvh, G, split);
+}
+
+// The ungrouped launch, every row on its own slab.  Its body is attn_own_row's text written out: the kernel a batch without forks runs is
+// kept instruction for instruction what it was before AttnRow existed (the two forms are held to each other by the bit-equality tests of
+// tests/test_gpu_batch_fork.py).
 template <int D, int GT>
 __global__ __launch_bounds__(kBlock) void batch_attn_kernel(const BatchAttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -277,6 +454,76 @@ __global__ __launch_bounds__(kBlock) void batch_attn_kernel(const BatchAttnArgs 
     }
 }
 
+// ---- the same launch when listed rows share a prefix (omx_qwen3_batch_fork).  The rows whose owner is row r's and whose shared span
+// reaches past split `split` form a group, in row order; with group_min members or more, every group_rows-th member's block takes
+// that member and the next group_rows - 1: it loads the split's 256 K and 256 V rows of the KV head from the OWNER's slab into
+// registers once -- a shared split is a whole chunk below every member's position -- and runs AttnRow over them once per member row,
+// token -> (wave, sub-group, unroll slot) as in attn_own_row, so that each partial is the one batch_attn_kernel writes for that
+// (row, KV head, split); the other members' blocks leave at once.  Every other block is attn_own_row.
+template <int D, int GT>
+__global__ __launch_bounds__(kBlock) void batch_attn_shared_kernel(const BatchSharedArgs sa) {
+    const BatchAttnArgs& a = sa.a;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    using Row = AttnRow<D, GT>;
+    constexpr int LPR = Row::LPR, TPW = Row::TPW, STEP = Row::STEP;
+    constexpr int NIT = kChunk / (STEP * kWaves);   // steps of a wave over a whole chunk
+    const int bk = blockIdx.x, split = blockIdx.y;
+    const int r = bk / a.Hkv, kvh = bk % a.Hkv;
+    const int t_begin = split * kChunk;
+    unsigned members = 0;
+    int before = 0;
+    if (sa.grp_shared[r] > t_begin) {
+        const int owner = sa.grp_owner[r];
+        for (int r2 = 0; r2 < sa.T; ++r2)
+            if (sa.grp_owner[r2] == owner && sa.grp_shared[r2] > t_begin) {
+                members |= 1u << r2;
+                before += r2 < r;
+            }
+    }
+    if (__builtin_popcount(members) < sa.group_min) {
+        attn_own_row<D, GT>(a, smem, r, kvh, split);
+        return;
+    }
+    if (before % sa.group_rows) return;   // an earlier member's block takes this row
+
+    const int lane = threadIdx.x & 63;
+    const int wave = threadIdx.x >> 6;
+    const int c = lane % LPR, sg = lane / LPR;
+    const int G = a.H / a.Hkv;
+    const int oslot = sa.grp_owner[r];
+    const bf16_t* Kb = a.kbase + (size_t)oslot * a.slot_stride + (size_t)kvh * a.head_stride;
+    const bf16_t* Vb = a.vbase + (size_t)oslot * a.slot_stride + (size_t)kvh * a.head_stride;
+    const int t_end = t_begin + kChunk;  // <= shared_len <= pos of every member
+    u32x4 kr[NIT][kUnroll], vr[NIT][kUnroll];
+#pragma unroll
+    for (int it = 0; it < NIT; ++it)
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int tc = t_begin + (it * kWaves + wave) * STEP + u * TPW + sg;
+            kr[it][u] = *reinterpret_cast<const u32x4*>(Kb + (size_t)tc * D + c * 8);
+            vr[it][u] = *reinterpret_cast<const u32x4*>(Vb + (size_t)tc * D + c * 8);
+        }
+    int take = sa.group_rows;
+    for (int r2 = r; r2 < sa.T && take > 0; ++r2) {
+        if (!((members >> r2) & 1u)) continue;
+        --take;
+        Row row;
+        row.begin(a, r2, kvh, G, c);
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            // (the rows stay packed between the member rows: unpacked once for all of them they would not fit the register file)
+#pragma unroll
+            for (int u = 0; u < kUnroll; ++u) asm volatile("" : "+v"(kr[it][u]), "+v"(vr[it][u]));
+            float s[kUnroll][GT];
+            float vf[kUnroll][8];
+            row.scores(kr[it], vr[it], t_begin + (it * kWaves + wave) * STEP, t_end, sg, s, vf);
+            row.update(s, vf);
+        }
+        row.finish(a, smem, r2, kvh, G, split);
+        __syncthreads();   // the merge has read the LDS area before the next row parks in it
+    }
+}
+
 // merge of a (row, head)'s splits: out[d] = sum_i e^{m_i - M} o_i[d] / sum_i e^{m_i - M} l_i over the ceil(len / chunk) splits of ITS
 // sequence, added in split order, rounded once to bf16.  One block per (row, head), one thread per d.
 template <int D>
@@ -402,15 +649,27 @@ int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T,
     a.scale = 1.0f / sqrtf((float)D);
     a.ws_o = rag.ws_o; a.ws_ml = rag.ws_ml;
     a.out = m->pf_attn;
+    BatchSharedArgs sa = {};
+    sa.a = a;
+    sa.T = T; sa.group_min = rag.group_min; sa.group_rows = rag.group_rows;
+    for (int r = 0; r < kMaxSlots; ++r) {
+        sa.grp_owner[r] = r < T ? rag.grp_owner[r] : -1;
+        sa.grp_shared[r] = r < T ? rag.grp_shared[r] : 0;
+    }
+    OMX_REQUIRE(!rag.grouped || (rag.chunk == kChunk && rag.group_min >= 2 && rag.group_rows >= 1), "batch attention: grouped splits of %d tokens, "
+                "groups from %d members, %d rows per block", rag.chunk, rag.group_min, rag.group_rows);
     const dim3 grid(T * Hkv, rag.nsplit), block(kBlock);
     const int gt = G <= 1 ? 1 : G <= 2 ? 2 : G <= 4 ? 4 : 8;
 #define OMX_BATCH_ATTN_CASE(DD, GG)                                                                     \
     if (D == DD && gt == GG) {                                                                          \
         const size_t shmem = ((size_t)kWaves * (64 / (DD / 8)) * GG * DD + 2 * kWaves * GG + 4) * sizeof(float); \
+        const void* fn = rag.grouped ? (const void*)batch_attn_shared_kernel<DD, GG> : (const void*)batch_attn_kernel<DD, GG>; \
         if (shmem > 48 * 1024)                                                                          \
-            OMX_HIP_CHECK(hipFuncSetAttribute((const void*)batch_attn_kernel<DD, GG>,                   \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-        batch_attn_kernel<DD, GG><<<grid, block, shmem, s>>>(a);                                        \
+            OMX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+        if (rag.grouped) /* rows that share a prefix: the same grid, grouped blocks over the shared splits */ \
+            batch_attn_shared_kernel<DD, GG><<<grid, block, shmem, s>>>(sa);                            \
+        else                                                                                            \
+            batch_attn_kernel<DD, GG><<<grid, block, shmem, s>>>(a);                                    \
         OMX_LAUNCH_CHECK();                                                                             \
         batch_attn_merge_kernel<DD><<<T * H, DD, 0, s>>>(a);                                            \
         OMX_LAUNCH_CHECK();                                                                             \
@@ -440,6 +699,14 @@ struct omx_qwen3_batch_ {
     int pos[kMaxSlots] = {};
     bool prefilled[kMaxSlots] = {};
     float temperature[kMaxSlots] = {};
+    // shared prefixes (omx_qwen3_batch_fork), the host's copy of the slot table's owner / shared_len: rows [0, shared_len[s]) of slot s
+    // and of slot owner[s] hold the same bits, and shared_len[s] <= pos[s] rounded down to kChunk
+    int owner[kMaxSlots] = {}, shared_len[kMaxSlots] = {};
+    int share_stage[kMaxSlots][2] = {};                // what set_share copies to the table from: alive until the caller synchronises
+    bool share_on = true;                              // OMX_BATCH_SHARE=0: forks copy, nothing is read through an owner
+    // OMX_BATCH_SHARE_MIN / _ROWS: grouped blocks from this many members on; member rows per grouped block.  The grouped block lost to
+    // the rows' own blocks at every group size measured (2, 4, 8 members), so by default no group is large enough
+    int group_min = kMaxSlots + 1, group_rows = 8;
     float last_decode_ms = 0.f;                        // device time of the last decode call's steps (the model's event pair)
     std::vector<void*> owned;
 };
@@ -482,6 +749,33 @@ int write_slot(omx_qwen3_batch b, int slot, const BatchSlot& v, size_t bytes) { 
     OMX_HIP_CHECK(hipMemcpyAsync(b->slots + slot, &v, bytes, hipMemcpyHostToDevice, b->m->stream));
     OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
     return 0;
+}
+
+// owner | shared_len of a slot, host copy and device table (the caller synchronises)
+int set_share(omx_qwen3_batch b, int slot, int owner, int shared_len) {
+    if (b->owner[slot] == owner && b->shared_len[slot] == shared_len) return 0;
+    b->owner[slot] = owner;
+    b->shared_len[slot] = shared_len;
+    b->share_stage[slot][0] = owner;
+    b->share_stage[slot][1] = shared_len;
+    OMX_HIP_CHECK(hipMemcpyAsync(&b->slots[slot].owner, b->share_stage[slot], 8, hipMemcpyHostToDevice, b->m->stream));
+    return 0;
+}
+
+// slot's cache now ends at `pos` (trim; 0: reset, or a prompt from position 0): what it shares, and what others share with it, ends
+// at the chunk boundary at or below -- the rows above are about to be overwritten in ONE of the copies
+int lower_share(omx_qwen3_batch b, int slot, int pos) {
+    const int lim = pos / kChunk * kChunk;
+    if (b->shared_len[slot] > lim && set_share(b, slot, lim ? b->owner[slot] : slot, lim)) return 1;
+    for (int c = 0; c < b->n_slots; ++c)
+        if (c != slot && b->owner[c] == slot && b->shared_len[c] > lim && set_share(b, c, lim ? slot : c, lim)) return 1;
+    return 0;
+}
+
+int env_int(const char* name, int dflt, int lo, int hi) {
+    const char* e = getenv(name);
+    if (!e || !*e) return dflt;
+    return std::min(hi, std::max(lo, atoi(e)));
 }
 
 }  // namespace
@@ -533,6 +827,13 @@ int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int m
          batch_alloc(b, &b->ws_o, (size_t)kMaxSlots * m->H * b->nsplit_cap * D) || batch_alloc(b, &b->ws_ml, (size_t)kMaxSlots * m->H * b->nsplit_cap * 2);
     // every slot starts with the key sequence of seed 0, like a model whose sampler was set to (T, 0)
     for (int s = 0; s < n_slots && !rc; ++s) rc = omx_random_key(b->slots[s].rng, 0, (omx_stream)m->stream);
+    for (int s = 0; s < n_slots && !rc; ++s) {
+        b->owner[s] = -1;
+        rc = set_share(b, s, s, 0);
+    }
+    b->share_on = env_int("OMX_BATCH_SHARE", 1, 0, 1) != 0;
+    b->group_min = env_int("OMX_BATCH_SHARE_MIN", b->group_min, 2, kMaxSlots + 1);
+    b->group_rows = env_int("OMX_BATCH_SHARE_ROWS", b->group_rows, 1, kMaxSlots);
     if (!rc && hipStreamSynchronize(m->stream) != hipSuccess) rc = set_error("omx_qwen3_batch_create: stream synchronise failed");
     if (rc) {
         omx_qwen3_batch_destroy(b);
@@ -571,6 +872,7 @@ int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt,
     OMX_REQUIRE(n_prompt <= m->prompt_cap, "omx_qwen3_batch_prefill: prompt of %d tokens exceeds the model's prompt buffer (%d)", n_prompt, m->prompt_cap);
     OMX_REQUIRE(!m->filter_on, "omx_qwen3_batch_prefill: filtered sampling (omx_qwen3_set_sampling) is on; call omx_qwen3_set_sampler first");
     if (resolve_weights(m)) return 1;
+    if (off == 0 && lower_share(b, slot, 0)) return 1;   // rows from 0 on are rewritten: nobody shares them any more
     hipStream_t s = m->stream;
     // a handful of rows of a packed model: the packed rows launches, as the verify pass (nothing dequantised); else the prompt pass's GEMMs
     const bool prow = m->cfg.quant_bits != 0 && n_prompt <= 8;
@@ -590,6 +892,68 @@ int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt,
     OMX_HIP_CHECK(hipStreamSynchronize(s));
     b->pos[slot] = off + n_prompt;
     b->prefilled[slot] = true;
+    return 0;
+}
+
+int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint32_t* first_token) {
+    OMX_REQUIRE(b && first_token, "omx_qwen3_batch_fork: null argument");
+    OMX_REQUIRE(src >= 0 && src < b->n_slots, "omx_qwen3_batch_fork: source slot %d out of range (0..%d)", src, b->n_slots - 1);
+    OMX_REQUIRE(dst >= 0 && dst < b->n_slots, "omx_qwen3_batch_fork: destination slot %d out of range (0..%d)", dst, b->n_slots - 1);
+    OMX_REQUIRE(src != dst, "omx_qwen3_batch_fork: source and destination are the same slot %d", src);
+    OMX_REQUIRE(b->prefilled[src] && b->pos[src] >= 1, "omx_qwen3_batch_fork: source slot %d has not been prefilled", src);
+    OMX_REQUIRE(!b->prefilled[dst] && b->pos[dst] == 0, "omx_qwen3_batch_fork: destination slot %d is not empty (reset it first)", dst);
+    omx_qwen3 m = b->m;
+    OMX_REQUIRE(!m->filter_on, "omx_qwen3_batch_fork: filtered sampling (omx_qwen3_set_sampling) is on; call omx_qwen3_set_sampler first");
+    hipStream_t s = m->stream;
+    const int pos = b->pos[src], D = m->cfg.head_dim, V = m->V;
+    // rows [0, pos) of every KV head, layer by layer: the heads of a slab lie cap rows apart
+    const size_t pitch = (size_t)b->cap * D * sizeof(bf16_t), width = (size_t)pos * D * sizeof(bf16_t);
+    for (size_t l = 0; l < b->kbase.size(); ++l) {
+        OMX_HIP_CHECK(hipMemcpy2DAsync(b->slot_k[dst][l], pitch, b->slot_k[src][l], pitch, width, (size_t)m->Hkv, hipMemcpyDeviceToDevice, s));
+        OMX_HIP_CHECK(hipMemcpy2DAsync(b->slot_v[dst][l], pitch, b->slot_v[src][l], pitch, width, (size_t)m->Hkv, hipMemcpyDeviceToDevice, s));
+    }
+    BatchSlot v = {};
+    if (resample) {
+        // src's kept row through dst's sampler: the sample launch keeps the row as dst's, draws with dst's next key and turns
+        // pos - 1 into pos, as at the end of a prefill
+        v.pos = pos - 1;
+        OMX_HIP_CHECK(hipMemcpyAsync(b->slots + dst, &v, 8, hipMemcpyHostToDevice, s));
+        OMX_HIP_CHECK(hipMemcpyAsync(b->row_slot, &dst, 4, hipMemcpyHostToDevice, s));
+        BatchSampleArgs a = {};
+        a.rows = b->slot_logits + (size_t)src * V; a.slot_logits = b->slot_logits; a.slots = b->slots; a.row_slot = b->row_slot;
+        a.ring = b->ring; a.V = V;
+        a.inv_temp[0] = b->temperature[dst] == 0.f ? 0.f : 1.0f / b->temperature[dst];
+        batch_sample_kernel<<<1, 1024, 0, s>>>(a);
+        OMX_LAUNCH_CHECK();
+        OMX_HIP_CHECK(hipMemcpyAsync(first_token, b->ring, 4, hipMemcpyDeviceToHost, s));
+    } else {
+        v.pos = pos;
+        OMX_HIP_CHECK(hipMemcpyAsync(b->slots + dst, &v, 4, hipMemcpyHostToDevice, s));
+        OMX_HIP_CHECK(hipMemcpyAsync(&b->slots[dst].pending, &b->slots[src].pending, 4, hipMemcpyDeviceToDevice, s));
+        OMX_HIP_CHECK(hipMemcpyAsync(b->slot_logits + (size_t)dst * V, b->slot_logits + (size_t)src * V, (size_t)V * sizeof(bf16_t),
+                                     hipMemcpyDeviceToDevice, s));
+        OMX_HIP_CHECK(hipMemcpyAsync(first_token, &b->slots[src].pending, 4, hipMemcpyDeviceToHost, s));
+    }
+    // one level deep: a fork of a child shares what the child shares with the root, and holds the rest in its own copy alone
+    const bool child = b->shared_len[src] > 0 && b->owner[src] != src;
+    const int root = child ? b->owner[src] : src;
+    const int sh = !b->share_on ? 0 : child ? b->shared_len[src] : pos / kChunk * kChunk;
+    if (set_share(b, dst, root, sh)) return 1;
+    if (!child && sh > b->shared_len[src] && set_share(b, src, src, sh)) return 1;
+    OMX_HIP_CHECK(hipStreamSynchronize(s));
+    b->pos[dst] = pos;
+    b->prefilled[dst] = true;
+    return 0;
+}
+
+int omx_qwen3_batch_shared(omx_qwen3_batch b, int slot, int* owner, int* shared_len) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_shared");
+    OMX_REQUIRE(owner && shared_len, "omx_qwen3_batch_shared: null argument");
+    BatchSlot v;   // the device's table, as omx_qwen3_batch_offset
+    OMX_HIP_CHECK(hipMemcpyAsync(&v, b->slots + slot, sizeof(v), hipMemcpyDeviceToHost, b->m->stream));
+    OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
+    *owner = v.owner;
+    *shared_len = v.shared_len;
     return 0;
 }
 
@@ -624,6 +988,16 @@ int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int
     rag.chunk = kChunk; rag.nsplit_cap = b->nsplit_cap;
     rag.nsplit = (longest + kChunk - 1) / kChunk;   // the longest listed sequence at the end of the call
     rag.ws_o = b->ws_o; rag.ws_ml = b->ws_ml;
+    // the groups of the call: positions only grow inside it, so a row that may read a split from its owner now may do so at every step
+    rag.group_min = b->group_min; rag.group_rows = b->group_rows;
+    for (int r = 0; r < n_slots; ++r) {
+        const int sh = std::min(b->shared_len[rows[r]], b->pos[rows[r]] / kChunk * kChunk);
+        rag.grp_owner[r] = sh > 0 ? b->owner[rows[r]] : -1;
+        rag.grp_shared[r] = sh;
+        int same = 0;
+        for (int q = 0; q <= r; ++q) same += sh > 0 && rag.grp_shared[q] > 0 && rag.grp_owner[q] == rag.grp_owner[r];
+        rag.grouped = rag.grouped || same >= b->group_min;
+    }
     OMX_HIP_CHECK(hipEventRecord(m->ev0, s));
     for (int i = 0; i < n_steps; ++i) {
         if (prefill_prefix_batched(m, n_slots, 0, nullptr, /*full_last=*/true, packed, nullptr, &rag)) return 1;
@@ -669,6 +1043,7 @@ int omx_qwen3_batch_trim(omx_qwen3_batch b, int slot, int n, uint32_t next_token
     BatchSlot v = {};
     v.pos = b->pos[slot] - n;
     v.pending = next_token;
+    if (lower_share(b, slot, v.pos)) return 1;
     if (write_slot(b, slot, v, 8)) return 1;
     b->pos[slot] = v.pos;
     return 0;
@@ -677,6 +1052,7 @@ int omx_qwen3_batch_trim(omx_qwen3_batch b, int slot, int n, uint32_t next_token
 int omx_qwen3_batch_reset(omx_qwen3_batch b, int slot) {
     OMX_BATCH_SLOT("omx_qwen3_batch_reset");
     const BatchSlot v = {};
+    if (lower_share(b, slot, 0) || set_share(b, slot, slot, 0)) return 1;
     if (write_slot(b, slot, v, 8)) return 1;   // (the sampler's key sequence goes on, as omx_qwen3_reset leaves the model's)
     b->pos[slot] = 0;
     b->prefilled[slot] = false;

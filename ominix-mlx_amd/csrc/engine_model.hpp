@@ -66,7 +66,8 @@ struct BatchSlot {
     int pos;               // tokens in the slot's cache == RoPE offset of the pending token
     uint32_t pending;      // token the slot's next step feeds to the embedding
     uint32_t rng[4];       // the slot's sampler: [0..1] key-sequence state, [2..3] key of the current draw (as omx_qwen3_::rng)
-    int pad[2];
+    int owner;             // the slot whose slabs hold the span this slot shares (omx_qwen3_batch_fork); itself when it shares nothing
+    int shared_len;        // rows [0, shared_len) of this slot's slabs and of owner's hold the same bits; a multiple of the split width
 };
 
 // KV slabs [Hkv, cap, D] per layer a batched pass appends to and attends over instead of the model's own (a batch slot's)
@@ -87,6 +88,12 @@ struct RaggedRows {
     size_t slot_stride;
     int cap, chunk, nsplit, nsplit_cap;
     float *ws_o, *ws_ml;
+    // shared prefixes (omx_qwen3_batch_fork), per listed row and fixed for the call: row r may read tokens [0, grp_shared[r]) from
+    // slot grp_owner[r]'s slabs.  grouped = some split has a group worth a grouped block; group_min / group_rows: the tuning of
+    // launch_batch_attention (from how many members a split's rows are grouped, and how many member rows one block takes)
+    int grp_owner[8], grp_shared[8];
+    bool grouped;
+    int group_min, group_rows;
 };
 
 }  // namespace omx

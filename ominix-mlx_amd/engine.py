@@ -95,6 +95,8 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_batch_trim": (c_int, [c_void_p, c_int, c_int, c_uint32]),
     "omx_qwen3_batch_reset": (c_int, [c_void_p, c_int]),
     "omx_qwen3_batch_last_decode_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
+    "omx_qwen3_batch_fork": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_uint32)]),
+    "omx_qwen3_batch_shared": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     # test hook of the dense decode GEMV (csrc/gemv.hip): one launch of a prologue / epilogue form, bf16 or float16
     "omx_debug_gemv": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_float, c_int, c_void_p]),
     "omx_debug_gemv_grid": (c_int, [c_int, c_int]),
@@ -500,6 +502,22 @@ class Batch:
         first = c_uint32()
         check(lib.omx_qwen3_batch_prefill(self._h, int(slot), p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, ctypes.byref(first)))
         return first.value
+
+    def fork(self, src: int, dst: int, resample: bool = True) -> int:
+        """The empty slot `dst` becomes what it would be had it been fed `src`'s tokens itself: src's position, kept logits and a copy
+        of its K/V rows.  Its pending token is drawn from those logits with dst's own sampler (resample), or is src's.  Returns it.
+        The slot table records the whole 256-token chunks siblings have in common (`shared`); OMX_BATCH_SHARE_MIN=2..8 makes the decode
+        attention read them once per group (bit-identical; slower than the default at every size measured)."""
+        first = c_uint32()
+        check(lib.omx_qwen3_batch_fork(self._h, int(src), int(dst), int(bool(resample)), ctypes.byref(first)))
+        return first.value
+
+    def shared(self, slot: int):
+        """(owner, shared_len) of the device's slot table: the decode attention may read tokens [0, shared_len) of `slot` from
+        slot `owner`'s slabs, which hold the same bits there."""
+        owner, n = c_int(), c_int()
+        check(lib.omx_qwen3_batch_shared(self._h, int(slot), ctypes.byref(owner), ctypes.byref(n)))
+        return owner.value, n.value
 
     def decode(self, n: int, slots=None) -> np.ndarray:
         """n tokens for each of `slots` (default: all; distinct, prefilled) -> [n, len(slots)], columns in the listed order."""

@@ -126,46 +126,75 @@ def generate_text(model, tokenizer, prompt: str, temperature: float = 0.7, max_t
             "tokens_per_sec": len(all_tokens) / seconds if seconds > 0 else 0.0}
 
 
-def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_ids: Iterable[int] = (), chunk: int = 16) -> List[List[int]]:
+def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_ids: Iterable[int] = (), chunk: int = 16,
+                   n: int = 1, before_sibling=None) -> List[List[int]]:
     """Any number of token-id prompts over the slots of an `engine.Batch`: free slots are prefilled with waiting prompts, the active
     slots decode together `chunk` tokens at a time, a sequence retires at its first token in `eos_ids` (which it keeps) or at
     max_new_tokens -- what its slot decoded past that point inside the chunk is dropped -- and its slot is reset and handed to the next
-    waiting prompt.  Returns the generated tokens per prompt, in prompt order.  Drives `batch` through prefill / decode / reset only."""
+    waiting prompt.  Returns the generated tokens per prompt, in prompt order.  Drives `batch` through prefill / decode / reset and,
+    with n > 1, fork.
+    n > 1: n completions of every prompt.  A prompt starts when n slots are free; it is prefilled ONCE and its slot forked n - 1 times,
+    every sibling drawing its first token from the prompt's logits with its own slot's sampler (`Batch.fork`).  A forked sibling's
+    slot is reset and free again as soon as it retires.  The prompt's own slot stops decoding when its sequence retires but is reset
+    only after its last sibling has: resetting the owner ends what its children share with it (`Batch.shared`).  Returns n lists per
+    prompt, prompt-major: completion k of prompt i is [i * n + k].
+    before_sibling(i, k, slot), if given, is called before completion k of prompt i is prefilled (k = 0) or forked into `slot` --
+    the place to give the slot its sampler (`Batch.set_sampler(slot, temperature, seed + k)`)."""
     if max_new_tokens < 1 or chunk < 1:
         raise ValueError("generate_batch: max_new_tokens and chunk must be positive")
+    if n < 1 or n > batch.n_slots:
+        raise ValueError(f"generate_batch: n = {n} completions per prompt need 1..{batch.n_slots} slots")
     eos = set(int(t) for t in eos_ids)
-    outputs: List[List[int]] = [[] for _ in prompts]
+    outputs: List[List[int]] = [[] for _ in range(len(prompts) * n)]
     waiting = list(range(len(prompts)))
     free = list(range(batch.n_slots))
-    active = {}                                   # slot -> prompt index
+    active = {}                                   # slot -> output index
+    owner = {}                                    # prompt index -> the slot it was prefilled in, until its last sibling retires
+    left = {}                                     # prompt index -> siblings still decoding
 
     def finished(i):
         return len(outputs[i]) >= max_new_tokens or (outputs[i] and outputs[i][-1] in eos)
 
+    def release(slot):
+        batch.reset(slot)
+        free.append(slot)
+
+    def retire(slot, i):
+        del active[slot]
+        p = i // n
+        if slot != owner[p]:
+            release(slot)
+        left[p] -= 1
+        if left[p] == 0:
+            release(owner.pop(p))
+
     while waiting or active:
-        while waiting and free:
-            slot, i = free.pop(0), waiting.pop(0)
-            if len(prompts[i]) == 0:
-                raise ValueError(f"generate_batch: prompt {i} is empty")
-            outputs[i].append(int(batch.prefill(slot, prompts[i])))
-            if finished(i):                       # EOS as the first token, or max_new_tokens == 1
-                batch.reset(slot)
-                free.append(slot)
-            else:
-                active[slot] = i
+        while waiting and len(free) >= n:
+            p = waiting.pop(0)
+            if len(prompts[p]) == 0:
+                raise ValueError(f"generate_batch: prompt {p} is empty")
+            slots = [free.pop(0) for _ in range(n)]
+            owner[p], left[p] = slots[0], n
+            for k, slot in enumerate(slots):
+                if before_sibling is not None:
+                    before_sibling(p, k, slot)
+                first = batch.prefill(slot, prompts[p]) if k == 0 else batch.fork(slots[0], slot, True)
+                outputs[p * n + k].append(int(first))
+                active[slot] = p * n + k
+            for k, slot in reversed(list(enumerate(slots))):   # (the owner last: it is released with its last sibling)
+                if finished(p * n + k):           # EOS as the first token, or max_new_tokens == 1
+                    retire(slot, p * n + k)
         if not active:
             continue
         slots = sorted(active)
-        n = min(chunk, min(max_new_tokens - len(outputs[active[s]]) for s in slots))
-        tokens = batch.decode(n, slots)
+        steps = min(chunk, min(max_new_tokens - len(outputs[active[s]]) for s in slots))
+        tokens = batch.decode(steps, slots)
         for col, slot in enumerate(slots):
             i = active[slot]
-            for step in range(n):
+            for step in range(steps):
                 outputs[i].append(int(tokens[step][col]))
                 if finished(i):
                     break
             if finished(i):
-                del active[slot]
-                batch.reset(slot)
-                free.append(slot)
+                retire(slot, i)
     return outputs

@@ -7,8 +7,13 @@
         One JSON line per row, then the table.
     rocprofv3 --kernel-trace --stats -f csv -d DIR -- python tools/batch_decode.py --trace --bits 0 [--ctx 2048] [--steps 16]
         8 slots prefilled, --steps steps at B = 8 and nothing else at that row count: the trace's last steps give the per-launch times
-        of a B = 8 step (python tools/batch_decode.py --stats DIR [--steps 32] prints them; pass rocprofv3 -f csv)."""
-import argparse, csv, glob, json, os, sys
+        of a B = 8 step (python tools/batch_decode.py --stats DIR [--steps 32] prints them; pass rocprofv3 -f csv).
+    python tools/batch_decode.py --fork [--fork-ctx 2048 8192] [--steps 128] [--windows 3]
+        bf16: eight slots forked from one prompt (Batch.fork) against eight slots prefilled independently with prompts of the same
+        length, at every --fork-ctx, each with the grouped read of the shared span on and off (OMX_BATCH_SHARE=1 / 0) in a child
+        process of its own; same windows, same device events.  One JSON line per row, then the table.  With --trace: one
+        configuration only (--fork-ctx C, OMX_BATCH_SHARE from the environment), eight forked slots, for a kernel trace."""
+import argparse, csv, glob, json, os, subprocess, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -20,7 +25,29 @@ ap.add_argument("--windows", type=int, default=3)
 ap.add_argument("--layers", type=int, default=36)
 ap.add_argument("--trace", action="store_true", help="only prefill 8 slots and run --steps steps at B = 8 (for a kernel trace)")
 ap.add_argument("--stats", metavar="DIR", help="print the per-launch times of the last --steps steps of a --trace run's kernel_trace.csv under DIR")
+ap.add_argument("--fork", action="store_true", help="eight forked slots against eight independent ones, shared-span read on and off")
+ap.add_argument("--fork-ctx", type=int, nargs="+", default=[2048, 8192])
+ap.add_argument("--fork-child", type=int, metavar="CTX", help=argparse.SUPPRESS)
 args = ap.parse_args()
+
+if args.fork and not args.trace:
+    # every (context, switch) in a process of its own: the switch is read when the batch is created, and no run inherits another's state
+    table = []
+    for ctx in args.fork_ctx:
+        for share in ("1", "0"):
+            p = subprocess.run([sys.executable, os.path.abspath(__file__), "--fork-child", str(ctx), "--steps", str(args.steps), "--windows",
+                                str(args.windows), "--layers", str(args.layers)], env=dict(os.environ, OMX_BATCH_SHARE=share),
+                               stdout=subprocess.PIPE, text=True, stdin=subprocess.DEVNULL)
+            if p.returncode:
+                sys.exit(f"--fork-child {ctx} (OMX_BATCH_SHARE={share}) failed with status {p.returncode}")
+            for ln in p.stdout.splitlines():
+                if ln.startswith("{"):
+                    print(ln, flush=True)
+                    table.append(json.loads(ln))
+    print(f"\n{'slots':<14} {'prompt':>7} {'share':>6} {'ms/step':>9} {'tok/s':>9} {'fork / prefill ms':>18}")
+    for r in table:
+        print(f"{r['slots']:<14} {r['ctx']:>7} {r['share']:>6} {r['ms_per_step']:>9.3f} {r['tok_s']:>9.1f} {r['setup_ms']:>18.1f}")
+    sys.exit(0)
 
 if args.stats:
     # the dispatches of the last --steps steps of the trace: a step begins with its embedding gather
@@ -60,6 +87,33 @@ def median_ms(run, read_ms, steps, windows):
         ms.append(read_ms() / steps)
     return float(np.median(ms)), ms
 
+
+if args.fork_child or (args.fork and args.trace):
+    import time
+    ctx = args.fork_child or args.fork_ctx[0]
+    share = os.environ.get("OMX_BATCH_SHARE", "1")
+    m = engine.Model(hidden_size=4096, num_hidden_layers=args.layers, intermediate_size=12288, num_attention_heads=32, num_key_value_heads=8,
+                     head_dim=128, vocab_size=V, max_context=ctx + 8 + args.steps * args.windows + 16)
+    m.synth_weights()
+    b = m.batch(8)
+    for forked in ((True,) if args.trace else (True, False)):
+        for s in range(8):
+            b.reset(s)
+        b.prefill(0, prompt(ctx, 0))
+        t0 = time.perf_counter()
+        for s in range(1, 8):
+            b.fork(0, s) if forked else b.prefill(s, prompt(ctx, s))
+        setup = (time.perf_counter() - t0) * 1e3 / 7          # (both calls wait for the device)
+        if args.trace:
+            b.decode(args.steps)
+            print(f"bf16, 8 forked slots of {ctx} tokens, OMX_BATCH_SHARE={share}: {b.last_decode_ms() / args.steps:.3f} ms per step", flush=True)
+            break
+        b.decode(8)
+        ms, raw = median_ms(b.decode, b.last_decode_ms, args.steps, args.windows)
+        print(json.dumps({"slots": "8 forked" if forked else "8 independent", "ctx": ctx, "share": int(share), "shared_len": b.shared(1)[1],
+                          "ms_per_step": ms, "tok_s": 8e3 / ms, "setup_ms": setup, "windows_ms": raw}), flush=True)
+    b.close(); m.close()
+    sys.exit(0)
 
 table = []
 for bits in args.bits:

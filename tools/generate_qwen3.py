@@ -2,7 +2,10 @@
     python tools/generate_qwen3.py <model_dir> [prompt] [--temperature T] [--top-k K] [--top-p P] [--repetition-penalty R]
                                    [--presence-penalty Q] [--seed S] [--max-tokens N]
     python tools/generate_qwen3.py <model_dir> --prompts-file FILE [--slots N] [--temperature T] [--seed S] [--max-tokens N]
+    python tools/generate_qwen3.py <model_dir> [prompt] --samples N [--temperature T] [--seed S] [--max-tokens N]
 --prompts-file: one prompt per line, decoded together over N slots of one loaded model (engine.Batch; plain temperature sampling).
+--samples N: N completions (1..8) of the prompt -- or of every line of --prompts-file -- from ONE prefill: the prompt's slot is forked
+N - 1 times (Batch.fork); sibling i of every prompt draws with a fresh key sequence of seed S + i (Batch.set_sampler before its fork).
 Without flags: the example's plain temperature 0.7.  The Qwen3 model card's settings are --temperature 0.6 --top-k 20 --top-p 0.95."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -22,27 +25,39 @@ ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--max-tokens", type=int, default=100)
 ap.add_argument("--prompts-file", help="one prompt per line: all of them through generate_batch over --slots slots")
 ap.add_argument("--slots", type=int, default=8, help="sequences decoded together (1..8)")
+ap.add_argument("--samples", type=int, default=1, help="completions per prompt from one prefill (1..8; plain temperature sampling)")
 args = ap.parse_args()
+if not 1 <= args.samples <= 8:
+    ap.error("--samples must be 1..8")
 tokenizer = generate.load_tokenizer(args.model_dir)
 model = loader.load_model(args.model_dir)
-if args.prompts_file:
+if args.prompts_file or args.samples > 1:
     import json, time
-    with open(args.prompts_file, encoding="utf-8") as fh:
-        texts = [ln.rstrip("\n") for ln in fh if ln.strip()]
+    if args.prompts_file:
+        with open(args.prompts_file, encoding="utf-8") as fh:
+            texts = [ln.rstrip("\n") for ln in fh if ln.strip()]
+    else:
+        texts = [args.prompt]
     prompts = [list(tokenizer.encode(t, add_special_tokens=True).ids) for t in texts]
     eos = []
     gen_cfg = os.path.join(args.model_dir, "generation_config.json")
     if os.path.exists(gen_cfg):
         e = json.load(open(gen_cfg)).get("eos_token_id", [])
         eos = [int(t) for t in (e if isinstance(e, list) else [e])]
-    batch = model.batch(max(1, min(args.slots, len(prompts))))
-    for slot in range(batch.n_slots):
-        batch.set_sampler(slot, args.temperature, args.seed + slot)
+    n = args.samples
+    batch = model.batch(max(n, min(args.slots, len(prompts) * n)))
+    if n == 1:
+        for slot in range(batch.n_slots):
+            batch.set_sampler(slot, args.temperature, args.seed + slot)
     start = time.perf_counter()
-    outs = generate.generate_batch(batch, prompts, args.max_tokens, eos_ids=eos)
+    # --samples: sibling i of EVERY prompt starts a fresh key sequence of seed + i, set on its slot right before its prefill / fork, so
+    # a prompt's samples do not depend on where it stands in the file or on which slots were free
+    outs = generate.generate_batch(batch, prompts, args.max_tokens, eos_ids=eos, n=n, before_sibling=None if n == 1 else
+                                   lambda p, k, slot: batch.set_sampler(slot, args.temperature, args.seed + k))
     seconds = time.perf_counter() - start
-    for text, toks in zip(texts, outs):
-        print(f"Prompt: {text}\n---\n{tokenizer.decode(toks, skip_special_tokens=True)}\n===")
+    for i, toks in enumerate(outs):
+        head = f"Prompt: {texts[i // n]}" + (f"  [sample {i % n}]" if n > 1 else "")
+        print(f"{head}\n---\n{tokenizer.decode(toks, skip_special_tokens=True)}\n===")
     total = sum(len(t) for t in outs)
     print(f"Generated {total} tokens for {len(prompts)} prompts over {batch.n_slots} slots in {seconds:.2f}s ({total / seconds:.1f} tok/s)")
     sys.exit(0)
