@@ -288,9 +288,20 @@ int omx_qwen3_trim(omx_qwen3 m, int n, uint32_t next_token);
  * its graphs, slabs and state) is untouched and both may be used on the same model -- but a batch shares the model's stream and its
  * prompt-pass scratch: calls on a model and on its batches must be SERIALISED by the caller, and a batch must be destroyed before its model.
  *   create:  n_slots 1..8; max_context 0 = the model's (not above it; rounded up to the 256 step like the model's).  Accepts the models
- *            omx_qwen3_verify accepts: single rank, dense MLP, bf16 weights or packed weights with bf16 scales, no filtered sampling.
+ *            omx_qwen3_verify accepts: single rank, dense MLP, bf16 weights or packed weights with bf16 scales, and the MODEL's filtered
+ *            sampling off (omx_qwen3_set_sampling; create / prefill / fork / decode refuse while it is on -- the slots' filters below are
+ *            the batch's own state and never touch the model's).
  *   set_sampler: per slot, the rule of omx_qwen3_set_sampler -- 0 = greedy (default), else categorical(logits / T) with the slot's OWN key
- *            sequence seeded from `seed` (top-k / top-p / penalties are not available per slot).
+ *            sequence seeded from `seed`.  Turns the slot's filters and penalties off and clears its history.
+ *   set_sampling: per slot, the rule of omx_sample_filtered / omx_qwen3_set_sampling (parameter ranges as there): penalties on the ids
+ *            in the slot's history, * (1/T), top-k with ties kept, top-p on the survivors, then the draw over the kept set with the NEXT key
+ *            of the slot's own sequence (restarted from `seed`); temperature 0 with a penalty = argmax of the penalised logits, without
+ *            one the plain argmax.  The history is a byte per vocabulary entry and slot on the device: the tokens the slot SAMPLED since
+ *            its last prefill (the prompt excluded), marked by the step itself for slots with a penalty on; cleared by set_sampling,
+ *            set_sampler, reset and every prefill (an appending one too).  A step in which no listed slot filters is the plain step,
+ *            launch for launch; otherwise every listed row goes through the filtered sampler (a plain slot draws the same token there)
+ *            -- one launch for short rows, the launch-per-level selection with one grid row per sequence at vocabulary sizes.  A slot's
+ *            tokens do not depend on its neighbours' settings.
  *   prefill: the prompt through the batched prompt pass onto the slot's slabs at the slot's offset (a second prefill appends), then the
  *            first token from the slot's sampler, which becomes the slot's pending token.
  *   decode:  `slots` = 1..n_slots distinct prefilled slots in any order; each advances n_steps (<= 1024) tokens; tokens_out is HOST memory
@@ -300,11 +311,15 @@ int omx_qwen3_trim(omx_qwen3 m, int n, uint32_t next_token);
  *            are listed beside it, nor on their contents.
  *   logits:  bf16 logits [V] of the last prefill or step the slot took part in.   offset: tokens in the slot's cache.
  *   trim:    omx_qwen3_trim per slot: forget the last n cached tokens and make next_token the pending token (n = 0: only the token).
+ *            Refused on a slot with a repetition / presence penalty on (a byte history cannot be rewound, as omx_qwen3_trim).
  *   reset:   the slot is empty again (its sampler's key sequence goes on).
  *   fork:    the EMPTY slot dst becomes what it would be had it been fed src's tokens itself: src's position, src's kept logits row, and a
  *            copy of rows [0, position) of src's K/V slabs in dst's own.  resample != 0: dst's pending token is drawn from that row with
  *            dst's own sampler and key sequence (the draw a prefill of the same prompt would have made); 0: it is src's.  *first_token is
- *            that token.  Refused: src not prefilled, src == dst, dst not empty (reset it first), a slot out of range.  Siblings share
+ *            that token.  The history: resample = 0 copies src's to dst (the sibling continues src's sequence); resample != 0 starts dst
+ *            with an EMPTY one, draws under dst's own settings and marks the token -- right only at the token after the prompt, so it is
+ *            refused when dst has a penalty on and src has decoded past its prefill.
+ *            Refused: src not prefilled, src == dst, dst not empty (reset it first), a slot out of range.  Siblings share
  *            the whole 256-token chunks below the fork, one level deep (a fork of a fork shares the root's span): the slot table keeps,
  *            per slot, the `owner` whose slabs hold the same bits in rows [0, shared_len), and a decode step MAY read those chunks once per
  *            group of listed rows with the same owner instead of once per row -- to the bit the partials the rows' own slabs give, whatever
@@ -317,6 +332,7 @@ typedef struct omx_qwen3_batch_* omx_qwen3_batch;
 int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int max_context);
 int omx_qwen3_batch_destroy(omx_qwen3_batch b);
 int omx_qwen3_batch_set_sampler(omx_qwen3_batch b, int slot, float temperature, uint64_t seed);
+int omx_qwen3_batch_set_sampling(omx_qwen3_batch b, int slot, const omx_sampling* p, uint64_t seed);
 int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, uint32_t* first_token);
 int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out);
 int omx_qwen3_batch_logits(omx_qwen3_batch b, int slot, void* host_bf16, int n);

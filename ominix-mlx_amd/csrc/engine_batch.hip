@@ -699,6 +699,14 @@ struct omx_qwen3_batch_ {
     int pos[kMaxSlots] = {};
     bool prefilled[kMaxSlots] = {};
     float temperature[kMaxSlots] = {};
+    // per-slot filters (omx_qwen3_batch_set_sampling): the settings, and `filtered` = they prune or penalise (else the plain sampler).
+    // seen [n_slots, V] bytes, there from the first penalty on: the tokens a slot sampled since its last prefill, marked by the step
+    // for slots with a penalty on.  sel: one selection scratch per ROW of a step.  decoded: steps a slot took since its last prefill
+    omx_sampling sampling[kMaxSlots];
+    bool filtered[kMaxSlots] = {};
+    uint8_t* seen = nullptr;
+    uint8_t* sel = nullptr;
+    int decoded[kMaxSlots] = {};
     // shared prefixes (omx_qwen3_batch_fork), the host's copy of the slot table's owner / shared_len: rows [0, shared_len[s]) of slot s
     // and of slot owner[s] hold the same bits, and shared_len[s] <= pos[s] rounded down to kChunk
     int owner[kMaxSlots] = {}, shared_len[kMaxSlots] = {};
@@ -723,6 +731,36 @@ int batch_alloc(omx_qwen3_batch b, T** p, size_t n) {
     return 0;
 }
 
+uint8_t* seen_row(omx_qwen3_batch b, int slot) {
+    return b->seen && sampling_penalised(b->sampling[slot]) ? b->seen + (size_t)slot * b->m->V : nullptr;
+}
+
+int clear_history(omx_qwen3_batch b, int slot) {
+    if (b->seen) OMX_HIP_CHECK(hipMemsetAsync(b->seen + (size_t)slot * b->m->V, 0, (size_t)b->m->V, b->m->stream));
+    return 0;
+}
+
+// [per-row sample + advance] of logits[M, V] for slots rows[0..M) (row_slot already on the device): the plain kernel while no listed
+// slot filters, else every row under its own slot's rule (launch_batch_filtered; a plain row draws the same token there)
+int batch_sample(omx_qwen3_batch b, const bf16_t* logits, const int* rows, int M, uint32_t* ring_at) {
+    hipStream_t s = b->m->stream;
+    const int V = b->m->V;
+    bool any = false;
+    for (int r = 0; r < M; ++r) any = any || b->filtered[rows[r]];
+    if (!any) {
+        BatchSampleArgs a = {};
+        a.rows = logits; a.slot_logits = b->slot_logits; a.slots = b->slots; a.row_slot = b->row_slot; a.ring = ring_at; a.V = V;
+        for (int r = 0; r < M; ++r) a.inv_temp[r] = b->temperature[rows[r]] == 0.f ? 0.f : 1.0f / b->temperature[rows[r]];
+        batch_sample_kernel<<<M, 1024, 0, s>>>(a);
+        OMX_LAUNCH_CHECK();
+        return 0;
+    }
+    BatchFilterArgs a = {};
+    a.rows = logits; a.slot_logits = b->slot_logits; a.slots = b->slots; a.row_slot = b->row_slot; a.ring = ring_at; a.ws = b->sel; a.V = V;
+    for (int r = 0; r < M; ++r) a.row[r] = batch_filter_row(b->sampling[rows[r]], V, seen_row(b, rows[r]));
+    return launch_batch_filtered(a, M, s);
+}
+
 // [final RMSNorm] -> [lm_head over M rows] -> [per-row sample + advance]: rows x[M, hidden] of slots row_slot[0..M) (already on the device)
 int batch_head_and_sample(omx_qwen3_batch b, const bf16_t* x, const int* rows, int M, uint32_t* ring_at) {
     omx_qwen3 m = b->m;
@@ -737,12 +775,7 @@ int batch_head_and_sample(omx_qwen3_batch b, const bf16_t* x, const int* rows, i
         if (omx_rms_norm(m->pf_xn, x, m->final_norm, M, hd, m->cfg.rms_norm_eps, OMX_BFLOAT16, s)) return 1;
         if (launch_gemm_bf16(b->step_logits, m->pf_xn, m->lm_head, nullptr, M, V, hd, s)) return 1;
     }
-    BatchSampleArgs a = {};
-    a.rows = b->step_logits; a.slot_logits = b->slot_logits; a.slots = b->slots; a.row_slot = b->row_slot; a.ring = ring_at; a.V = V;
-    for (int r = 0; r < M; ++r) a.inv_temp[r] = b->temperature[rows[r]] == 0.f ? 0.f : 1.0f / b->temperature[rows[r]];
-    batch_sample_kernel<<<M, 1024, 0, s>>>(a);
-    OMX_LAUNCH_CHECK();
-    return 0;
+    return batch_sample(b, b->step_logits, rows, M, ring_at);
 }
 
 int write_slot(omx_qwen3_batch b, int slot, const BatchSlot& v, size_t bytes) {   // the leading `bytes` of the entry: pos | pending
@@ -808,6 +841,7 @@ int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int m
     b->m = m;
     b->n_slots = n_slots;
     b->cap = cap;
+    for (int s = 0; s < kMaxSlots; ++s) b->sampling[s] = {0.f, 0, 1.f, 1.f, 0.f};
     const int D = c.head_dim, L = c.num_hidden_layers, V = m->V;
     b->slot_stride = (size_t)m->Hkv * cap * D;
     b->kbase.resize(L);
@@ -855,8 +889,27 @@ int omx_qwen3_batch_set_sampler(omx_qwen3_batch b, int slot, float temperature, 
     OMX_BATCH_SLOT("omx_qwen3_batch_set_sampler");
     OMX_REQUIRE(temperature >= 0.f && temperature == temperature, "omx_qwen3_batch_set_sampler: temperature %f must be >= 0", (double)temperature);
     if (omx_random_key(b->slots[slot].rng, seed, (omx_stream)b->m->stream)) return 1;
+    if (clear_history(b, slot)) return 1;
     OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
     b->temperature[slot] = temperature;
+    b->sampling[slot] = {temperature, 0, 1.f, 1.f, 0.f};   // the plain sampler: every filter and penalty off
+    b->filtered[slot] = false;
+    return 0;
+}
+
+int omx_qwen3_batch_set_sampling(omx_qwen3_batch b, int slot, const omx_sampling* p, uint64_t seed) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_set_sampling");
+    const int V = b->m->V;
+    if (check_sampling("omx_qwen3_batch_set_sampling", p, V)) return 1;
+    const bool on = sampling_filters(*p, V);
+    if (on && sampling_penalised(*p) && !b->seen && batch_alloc(b, &b->seen, (size_t)b->n_slots * V)) return 1;
+    if (on && !b->sel && batch_alloc(b, &b->sel, (size_t)kMaxSlots * sample_select_ws_bytes())) return 1;
+    if (omx_random_key(b->slots[slot].rng, seed, (omx_stream)b->m->stream)) return 1;
+    if (clear_history(b, slot)) return 1;
+    OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
+    b->temperature[slot] = p->temperature;
+    b->sampling[slot] = *p;
+    b->filtered[slot] = on;
     return 0;
 }
 
@@ -873,6 +926,7 @@ int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt,
     OMX_REQUIRE(!m->filter_on, "omx_qwen3_batch_prefill: filtered sampling (omx_qwen3_set_sampling) is on; call omx_qwen3_set_sampler first");
     if (resolve_weights(m)) return 1;
     if (off == 0 && lower_share(b, slot, 0)) return 1;   // rows from 0 on are rewritten: nobody shares them any more
+    if (clear_history(b, slot)) return 1;                // the penalties see the tokens sampled since THIS prefill (as omx_qwen3_prefill)
     hipStream_t s = m->stream;
     // a handful of rows of a packed model: the packed rows launches, as the verify pass (nothing dequantised); else the prompt pass's GEMMs
     const bool prow = m->cfg.quant_bits != 0 && n_prompt <= 8;
@@ -892,6 +946,7 @@ int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt,
     OMX_HIP_CHECK(hipStreamSynchronize(s));
     b->pos[slot] = off + n_prompt;
     b->prefilled[slot] = true;
+    b->decoded[slot] = 0;
     return 0;
 }
 
@@ -904,6 +959,11 @@ int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint
     OMX_REQUIRE(!b->prefilled[dst] && b->pos[dst] == 0, "omx_qwen3_batch_fork: destination slot %d is not empty (reset it first)", dst);
     omx_qwen3 m = b->m;
     OMX_REQUIRE(!m->filter_on, "omx_qwen3_batch_fork: filtered sampling (omx_qwen3_set_sampling) is on; call omx_qwen3_set_sampler first");
+    // a resampled sibling starts the history a prefill of its own would have started: only right at the token after the prompt
+    OMX_REQUIRE(!(resample && sampling_penalised(b->sampling[dst]) && b->decoded[src] > 0),
+                "omx_qwen3_batch_fork: destination slot %d has a repetition / presence penalty on and source slot %d has decoded %d tokens past "
+                "its prefill: the history of a resampled sibling would miss them (fork right after the prefill, or with resample = 0)",
+                dst, src, b->decoded[src]);
     hipStream_t s = m->stream;
     const int pos = b->pos[src], D = m->cfg.head_dim, V = m->V;
     // rows [0, pos) of every KV head, layer by layer: the heads of a slab lie cap rows apart
@@ -919,12 +979,8 @@ int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint
         v.pos = pos - 1;
         OMX_HIP_CHECK(hipMemcpyAsync(b->slots + dst, &v, 8, hipMemcpyHostToDevice, s));
         OMX_HIP_CHECK(hipMemcpyAsync(b->row_slot, &dst, 4, hipMemcpyHostToDevice, s));
-        BatchSampleArgs a = {};
-        a.rows = b->slot_logits + (size_t)src * V; a.slot_logits = b->slot_logits; a.slots = b->slots; a.row_slot = b->row_slot;
-        a.ring = b->ring; a.V = V;
-        a.inv_temp[0] = b->temperature[dst] == 0.f ? 0.f : 1.0f / b->temperature[dst];
-        batch_sample_kernel<<<1, 1024, 0, s>>>(a);
-        OMX_LAUNCH_CHECK();
+        if (clear_history(b, dst)) return 1;   // an EMPTY history: the launch marks the token it draws
+        if (batch_sample(b, b->slot_logits + (size_t)src * V, &dst, 1, b->ring)) return 1;
         OMX_HIP_CHECK(hipMemcpyAsync(first_token, b->ring, 4, hipMemcpyDeviceToHost, s));
     } else {
         v.pos = pos;
@@ -933,6 +989,8 @@ int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint
         OMX_HIP_CHECK(hipMemcpyAsync(b->slot_logits + (size_t)dst * V, b->slot_logits + (size_t)src * V, (size_t)V * sizeof(bf16_t),
                                      hipMemcpyDeviceToDevice, s));
         OMX_HIP_CHECK(hipMemcpyAsync(first_token, &b->slots[src].pending, 4, hipMemcpyDeviceToHost, s));
+        if (b->seen)   // the sibling continues src's sequence: src's history with it
+            OMX_HIP_CHECK(hipMemcpyAsync(b->seen + (size_t)dst * V, b->seen + (size_t)src * V, (size_t)V, hipMemcpyDeviceToDevice, s));
     }
     // one level deep: a fork of a child shares what the child shares with the root, and holds the rest in its own copy alone
     const bool child = b->shared_len[src] > 0 && b->owner[src] != src;
@@ -943,6 +1001,7 @@ int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint
     OMX_HIP_CHECK(hipStreamSynchronize(s));
     b->pos[dst] = pos;
     b->prefilled[dst] = true;
+    b->decoded[dst] = resample ? 0 : b->decoded[src];
     return 0;
 }
 
@@ -1007,7 +1066,10 @@ int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int
     OMX_HIP_CHECK(hipMemcpyAsync(tokens_out, b->ring, (size_t)n_steps * n_slots * 4, hipMemcpyDeviceToHost, s));
     OMX_HIP_CHECK(hipStreamSynchronize(s));
     OMX_HIP_CHECK(hipEventElapsedTime(&b->last_decode_ms, m->ev0, m->ev1));
-    for (int r = 0; r < n_slots; ++r) b->pos[rows[r]] += n_steps;
+    for (int r = 0; r < n_slots; ++r) {
+        b->pos[rows[r]] += n_steps;
+        b->decoded[rows[r]] += n_steps;
+    }
     return 0;
 }
 
@@ -1040,6 +1102,8 @@ int omx_qwen3_batch_trim(omx_qwen3_batch b, int slot, int n, uint32_t next_token
     OMX_BATCH_SLOT("omx_qwen3_batch_trim");
     OMX_REQUIRE(next_token < (uint32_t)b->m->cfg.vocab_size, "omx_qwen3_batch_trim: token id %u out of range (vocab %d)", next_token, b->m->cfg.vocab_size);
     OMX_REQUIRE(n >= 0 && n <= b->pos[slot], "omx_qwen3_batch_trim: cannot drop %d of %d cached tokens", n, b->pos[slot]);
+    OMX_REQUIRE(!sampling_penalised(b->sampling[slot]), "omx_qwen3_batch_trim: slot %d has a repetition / presence penalty on: the token "
+                "history on the device cannot be trimmed; call omx_qwen3_batch_set_sampler first", slot);
     BatchSlot v = {};
     v.pos = b->pos[slot] - n;
     v.pending = next_token;
@@ -1053,9 +1117,11 @@ int omx_qwen3_batch_reset(omx_qwen3_batch b, int slot) {
     OMX_BATCH_SLOT("omx_qwen3_batch_reset");
     const BatchSlot v = {};
     if (lower_share(b, slot, 0) || set_share(b, slot, slot, 0)) return 1;
+    if (clear_history(b, slot)) return 1;
     if (write_slot(b, slot, v, 8)) return 1;   // (the sampler's key sequence goes on, as omx_qwen3_reset leaves the model's)
     b->pos[slot] = 0;
     b->prefilled[slot] = false;
+    b->decoded[slot] = 0;
     return 0;
 }
 

@@ -32,10 +32,6 @@ constexpr int kSelThreads = 1024;
 constexpr int kCopies = 16;
 constexpr float kMassOne = 1099511627776.0f;   // 2^40
 
-struct RowRule {
-    float inv_temp, rep, pres;
-};
-
 // order-preserving image of y: a > b <=> key(a) > key(b); -0 and +0 share a key (they compare equal); NaN = 0, below everything
 __device__ __forceinline__ uint32_t y_key(float y) {
     uint32_t u = __float_as_uint(y);
@@ -339,7 +335,7 @@ struct ScanLds {
 __device__ __forceinline__ int level_bits(int level) { return level == 2 ? 10 : 11; }
 
 // this thread's eight bins of a level's histogram, and the count / mass of every bin above them (256 threads, all call)
-__device__ void scan_level(ScanLds& S, const uint32_t* __restrict__ gcnt, const unsigned long long* __restrict__ gmass, int nbins,
+__device__ __forceinline__ void scan_level(ScanLds& S, const uint32_t* __restrict__ gcnt, const unsigned long long* __restrict__ gmass, int nbins,
                            uint32_t (&c)[8], unsigned long long (&m)[8], uint32_t& ac, unsigned long long& am) {
     const int tid = threadIdx.x;
     uint32_t tc = 0;
@@ -381,7 +377,7 @@ __device__ void scan_level(ScanLds& S, const uint32_t* __restrict__ gcnt, const 
 }
 
 // one level of top-k's descent: the bin holding the k-th largest.  Returns the carry after it (to every thread).
-__device__ SelCarry decide_k(ScanLds& S, const SelWs* ws, int slot, int level, const SelCarry& in, uint32_t top_k) {
+__device__ __forceinline__ SelCarry decide_k(ScanLds& S, const SelWs* ws, int slot, int level, const SelCarry& in, uint32_t top_k) {
     uint32_t c[8], ac;
     unsigned long long m[8], am;
     scan_level(S, ws->cnt[slot], ws->mass[slot], 1 << level_bits(level), c, m, ac, am);
@@ -407,14 +403,14 @@ __device__ SelCarry decide_k(ScanLds& S, const SelWs* ws, int slot, int level, c
 }
 
 // one level of top-p's descent: the lowest non-empty bin whose strictly-greater mass is < pz
-__device__ SelCarry decide_p(ScanLds& S, const SelWs* ws, int slot, int level, const SelCarry& in, double pz, unsigned long long* total) {
+__device__ __forceinline__ SelCarry decide_p(ScanLds& S, const SelWs* ws, int slot, int level, const SelCarry& in, double pz, bool whole_row, unsigned long long& total) {
     uint32_t c[8], ac;
     unsigned long long m[8], am;
     scan_level(S, ws->cnt[slot], ws->mass[slot], 1 << level_bits(level), c, m, ac, am);
-    if (total) {   // Z of the whole row (no top-k): pz follows from it
+    if (whole_row) {   // Z of the whole row (no top-k): pz follows from it
         unsigned long long t = 0;
         for (int g = 0; g < 16; ++g) t += S.gm[g];
-        *total = t;
+        total = t;
         pz = pz * (double)t;
     }
     uint32_t run = in.above_cnt + ac;
@@ -439,10 +435,18 @@ __device__ SelCarry decide_p(ScanLds& S, const SelWs* ws, int slot, int level, c
     if ((b >> 3) == threadIdx.x) {
         SelCarry o;
         const int j = (int)(b & 7u);
+        uint32_t rcj = 0, cj = 0;   // (picked by a chain of selects: an index known only at run time would put the arrays in scratch)
+        unsigned long long rmj = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            rcj = i == j ? rc[i] : rcj;
+            rmj = i == j ? rm[i] : rmj;
+            cj = i == j ? c[i] : cj;
+        }
         o.prefix = (in.prefix << level_bits(level)) | b;
-        o.above_cnt = rc[j];
-        o.above_mass = rm[j];
-        o.kept = rc[j] + c[j];
+        o.above_cnt = rcj;
+        o.above_mass = rmj;
+        o.kept = rcj + cj;
         o.z = in.z;
         o.none = in.none;
         S.out = o;
@@ -453,10 +457,11 @@ __device__ SelCarry decide_p(ScanLds& S, const SelWs* ws, int slot, int level, c
 
 // the descent up to the state the launch of `slot` needs (slot == kSlots: to the end -> out.prefix = threshold key, out.kept);
 // block 0 leaves what it derived in ws->carry for the later launches
-__device__ SelCarry resolve(ScanLds& S, SelWs* ws, int slot, uint32_t top_k, float top_p, int V, bool k_on, bool p_on) {
+__device__ __forceinline__ SelCarry resolve(ScanLds& S, SelWs* ws, int slot, uint32_t top_k, float top_p, int V, bool k_on, bool p_on) {
     const SelCarry zero = {0u, 0u, 0u, 0u, 0ull, 0ull};
     const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
     SelCarry o = zero;
+    unsigned long long unused = 0;
     if (slot == 1) {
         o = decide_k(S, ws, 0, 0, zero, top_k);
         if (lead) ws->carry[1] = o;
@@ -472,7 +477,7 @@ __device__ SelCarry resolve(ScanLds& S, SelWs* ws, int slot, uint32_t top_k, flo
             kend = decide_k(S, ws, 2, 2, ws->carry[2], top_k);
             pz = pz * (double)kend.z;
         }
-        o = decide_p(S, ws, 0, 0, zero, pz, k_on ? nullptr : &total);
+        o = decide_p(S, ws, 0, 0, zero, pz, !k_on, total);
         if (!k_on) kend.z = total;
         o.z = kend.z;
         if (lead) {
@@ -481,12 +486,12 @@ __device__ SelCarry resolve(ScanLds& S, SelWs* ws, int slot, uint32_t top_k, flo
         }
     } else if (slot == 4) {
         const SelCarry in = ws->carry[4];
-        o = decide_p(S, ws, 3, 1, in, (double)top_p * (double)in.z, nullptr);
+        o = decide_p(S, ws, 3, 1, in, (double)top_p * (double)in.z, false, unused);
         if (lead) ws->carry[5] = o;
     } else if (slot == kSlots) {
         if (p_on) {
             const SelCarry in = ws->carry[5], kend = ws->carry[3];
-            o = decide_p(S, ws, 4, 2, in, (double)top_p * (double)in.z, nullptr);
+            o = decide_p(S, ws, 4, 2, in, (double)top_p * (double)in.z, false, unused);
             if (o.none || o.prefix <= kend.prefix) {   // the higher of the two thresholds
                 o.prefix = kend.prefix;
                 o.kept = kend.kept;
@@ -500,9 +505,11 @@ __device__ SelCarry resolve(ScanLds& S, SelWs* ws, int slot, uint32_t top_k, flo
     return o;
 }
 
+// The bodies of the launches, written once: the one-row kernels below call them as they are, the row-batched ones of a batch step
+// (grid.y = the row) with the row's own arguments.  Blocks and threads are counted along x.
 template <int DT>
-__global__ __launch_bounds__(kHistThreads) void select_max_kernel(SelWs* __restrict__ ws, const typename Elem<DT>::T* __restrict__ row,
-                                                                  const uint8_t* __restrict__ seen, int V, RowRule rule) {
+__device__ __forceinline__ void select_max_body(SelWs* __restrict__ ws, const typename Elem<DT>::T* __restrict__ row,
+                                                const uint8_t* __restrict__ seen, int V, const RowRule& rule) {
     __shared__ uint32_t red[kHistThreads / 64];
     uint32_t best = 0;
     for_each_y<DT>(row, seen, V, rule, blockIdx.x * kHistThreads + threadIdx.x, gridDim.x * kHistThreads, [&](int, float y) {
@@ -521,11 +528,16 @@ __global__ __launch_bounds__(kHistThreads) void select_max_kernel(SelWs* __restr
         atomicMax(&ws->maxkey, best);
     }
 }
+template <int DT>
+__global__ __launch_bounds__(kHistThreads) void select_max_kernel(SelWs* __restrict__ ws, const typename Elem<DT>::T* __restrict__ row,
+                                                                  const uint8_t* __restrict__ seen, int V, RowRule rule) {
+    select_max_body<DT>(ws, row, seen, V, rule);
+}
 
 template <int DT>
-__global__ __launch_bounds__(kHistThreads) void select_hist_kernel(SelWs* __restrict__ ws, const typename Elem<DT>::T* __restrict__ row,
-                                                                   const uint8_t* __restrict__ seen, int V, RowRule rule, int slot,
-                                                                   uint32_t top_k, float top_p, int k_on, int p_on) {
+__device__ __forceinline__ void select_hist_body(SelWs* __restrict__ ws, const typename Elem<DT>::T* __restrict__ row,
+                                                 const uint8_t* __restrict__ seen, int V, const RowRule& rule, int slot, uint32_t top_k,
+                                                 float top_p, int k_on, int p_on) {
     __shared__ ScanLds S;
     __shared__ uint32_t cnt[kBins];
     __shared__ unsigned long long mass[kBins];
@@ -562,11 +574,16 @@ __global__ __launch_bounds__(kHistThreads) void select_hist_kernel(SelWs* __rest
         }
     }
 }
+template <int DT>
+__global__ __launch_bounds__(kHistThreads) void select_hist_kernel(SelWs* __restrict__ ws, const typename Elem<DT>::T* __restrict__ row,
+                                                                   const uint8_t* __restrict__ seen, int V, RowRule rule, int slot,
+                                                                   uint32_t top_k, float top_p, int k_on, int p_on) {
+    select_hist_body<DT>(ws, row, seen, V, rule, slot, top_k, top_p, k_on, p_on);
+}
 
 // [resolve], one block: the last level's decision -> ws->thr (key image of the final threshold), ws->kept; then (zero != 0) the
 // histograms are cleared for the next selection -- a memset node costs a launch of its own (7.6 us traced)
-__global__ __launch_bounds__(kHistThreads) void select_resolve_kernel(SelWs* __restrict__ ws, uint32_t top_k, float top_p, int V, int k_on,
-                                                                      int p_on, int zero) {
+__device__ __forceinline__ void select_resolve_body(SelWs* __restrict__ ws, uint32_t top_k, float top_p, int V, int k_on, int p_on, int zero) {
     __shared__ ScanLds S;
     const SelCarry end = resolve(S, ws, kSlots, top_k, top_p, V, k_on, p_on);
     __syncthreads();
@@ -583,18 +600,18 @@ __global__ __launch_bounds__(kHistThreads) void select_resolve_kernel(SelWs* __r
         ws->kept = end.kept;
     }
 }
+__global__ __launch_bounds__(kHistThreads) void select_resolve_kernel(SelWs* __restrict__ ws, uint32_t top_k, float top_p, int V, int k_on,
+                                                                      int p_on, int zero) {
+    select_resolve_body(ws, top_k, top_p, V, k_on, p_on, zero);
+}
 
 // [noise]: sample_noise_kernel (random.hip) restricted to the kept set {key(y) >= ws->thr}, penalties applied (ws == nullptr: nothing
 // filtered).  n_words: the size of the draw the row's words belong to.
 template <int DT>
-__global__ __launch_bounds__(256) void sample_filtered_noise_kernel(unsigned long long* __restrict__ partials,
-                                                                    const typename Elem<DT>::T* __restrict__ logits,
-                                                                    const uint8_t* __restrict__ seen, const SelWs* __restrict__ ws,
-                                                                    const uint32_t* __restrict__ sub_key, int V, uint64_t n_words,
-                                                                    RowRule rule, int greedy) {
+__device__ __forceinline__ void filtered_noise_body(unsigned long long* __restrict__ partials, const typename Elem<DT>::T* __restrict__ logits,
+                                                    const uint8_t* __restrict__ seen, uint32_t thr, uint32_t k0, uint32_t k1, int V,
+                                                    uint64_t n_words, const RowRule& rule, int greedy) {
     __shared__ unsigned long long red[4];
-    const uint32_t thr = ws ? ws->thr : 0u;
-    const uint32_t k0 = greedy ? 0u : sub_key[0], k1 = greedy ? 0u : sub_key[1];
     unsigned long long best = 0;
     for (int v = blockIdx.x * 256 + threadIdx.x; v < V; v += gridDim.x * 256) {
         const float y = apply_rule(Elem<DT>::ld(logits + v), seen && seen[v], rule);
@@ -615,6 +632,15 @@ __global__ __launch_bounds__(256) void sample_filtered_noise_kernel(unsigned lon
         for (int w = 1; w < 4; ++w) best = red[w] > best ? red[w] : best;
         partials[blockIdx.x] = best;
     }
+}
+template <int DT>
+__global__ __launch_bounds__(256) void sample_filtered_noise_kernel(unsigned long long* __restrict__ partials,
+                                                                    const typename Elem<DT>::T* __restrict__ logits,
+                                                                    const uint8_t* __restrict__ seen, const SelWs* __restrict__ ws,
+                                                                    const uint32_t* __restrict__ sub_key, int V, uint64_t n_words,
+                                                                    RowRule rule, int greedy) {
+    filtered_noise_body<DT>(partials, logits, seen, ws ? ws->thr : 0u, greedy ? 0u : sub_key[0], greedy ? 0u : sub_key[1], V, n_words, rule,
+                            greedy);
 }
 
 // omx_sample_filtered's last launch on this path: the partials' maximum, the threshold and the kept count
@@ -683,6 +709,8 @@ __global__ __launch_bounds__(kSelThreads) void topk_values_kernel(typename Elem<
     }
 }
 
+}  // namespace
+
 int check_sampling(const char* who, const omx_sampling* p, int V) {
     OMX_REQUIRE(p, "%s: null sampling parameters", who);
     OMX_REQUIRE(p->temperature >= 0.f && p->temperature == p->temperature, "%s: temperature %f must be >= 0", who, (double)p->temperature);
@@ -695,6 +723,8 @@ int check_sampling(const char* who, const omx_sampling* p, int V) {
     OMX_REQUIRE(V > 0 && V <= (1 << 23), "%s: %d entries per row (1 .. 2^23: the 64-bit fixed-point mass sums)", who, V);
     return 0;
 }
+
+namespace {
 
 RowRule rule_of(const omx_sampling& p) {
     RowRule r;
@@ -733,7 +763,171 @@ int noise_launch(unsigned long long* partials, int n_partials, const typename El
     return 0;
 }
 
+// ---- the rows of a batch step, each under its own slot's rule (BatchFilterArgs, sample_filter.hpp) ----
+// (state, key) = split(state, 2) of the slot's key sequence, RandomState::next: the words batch_sample_kernel derives
+__device__ __forceinline__ void slot_next_key(const BatchSlot* S, uint32_t& s0, uint32_t& s1, uint32_t& k0, uint32_t& k1) {
+    const uint32_t c0 = S->rng[0], c1 = S->rng[1];
+    threefry2x32(c0, c1, 0u, 2u, s0, k0);
+    threefry2x32(c0, c1, 1u, 3u, s1, k1);
+}
+
+// what thread 0 of a row's last block leaves: the token in the ring and as the slot's pending token, the position and (temperature != 0)
+// the key sequence advanced, the token marked in the history the slot's penalties read
+__device__ __forceinline__ void batch_row_advance(const BatchFilterArgs& a, int r, BatchSlot* S, unsigned long long best, bool greedy,
+                                                  uint32_t s0, uint32_t s1, uint32_t k0, uint32_t k1) {
+    const uint32_t token = ~(uint32_t)(best & 0xFFFFFFFFull);
+    a.ring[r] = token;
+    S->pending = token;
+    S->pos += 1;
+    if (!greedy) { S->rng[0] = s0; S->rng[1] = s1; S->rng[2] = k0; S->rng[3] = k1; }
+    uint8_t* seen = a.row[r].seen;
+    if (seen && token < (uint32_t)a.V) seen[token] = 1;
+}
+
+// short rows: one block per row selects (row_select), draws over the kept set and advances the slot
+__global__ __launch_bounds__(kSelThreads) void batch_filtered_kernel(const BatchFilterArgs a) {
+    __shared__ SelectLds L;
+    __shared__ unsigned long long red[kSelThreads / 64];
+    const int r = blockIdx.x, slot = a.row_slot[r], V = a.V;
+    const BatchFilterRow& R = a.row[r];
+    BatchSlot* S = a.slots + slot;
+    const bool greedy = R.greedy != 0;
+    const bf16_t* row = a.rows + (size_t)r * V;
+    bf16_t* keep = a.slot_logits + (size_t)slot * V;
+    const uint8_t* seen = R.seen;
+    uint32_t s0 = 0, s1 = 0, k0 = 0, k1 = 0;
+    if (!greedy) slot_next_key(S, s0, s1, k0, k1);
+    for (int v = threadIdx.x; v < V; v += kSelThreads) keep[v] = row[v];
+    uint32_t thr, kept;
+    row_select<OMX_BFLOAT16>(L, row, seen, V, R.rule, greedy ? 0 : R.top_k, greedy ? 1.f : R.top_p, thr, kept);
+    unsigned long long best = 0;
+    for_each_y<OMX_BFLOAT16>(row, seen, V, R.rule, threadIdx.x, kSelThreads, [&](int v, float y) {
+        if (y_key(y) >= thr) {
+            const float g = greedy ? 0.f : gumbel_from_word(random_word(k0, k1, (uint64_t)v, (uint64_t)V));
+            const unsigned long long kx = sample_key(greedy ? y : y + g, (uint32_t)v);
+            best = kx > best ? kx : best;
+        }
+    });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(best, o, 64);
+        best = other > best ? other : best;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();   // every thread has read the key state and the history before thread 0 replaces them
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kSelThreads / 64; ++w) best = red[w] > best ? red[w] : best;
+        batch_row_advance(a, r, S, best, greedy, s0, s1, k0, k1);
+    }
+}
+
+// vocabulary-sized rows: the launch-per-level selection with grid.y = the row, every row on its own SelWs.  A launch is there for the
+// union of the rows' settings; a row whose own settings do not need it leaves at once (the exit is uniform over the block).
+__device__ __forceinline__ bool row_selects(const BatchFilterRow& R) { return !R.greedy && (R.k_on || R.p_on); }
+static_assert(sizeof(SelWs) % 16 == 0, "the rows' scratch lies back to back: [resolve] clears it with 16-byte stores");
+__device__ __forceinline__ SelWs* row_ws(const BatchFilterArgs& a, int r) { return (SelWs*)a.ws + r; }
+
+__global__ __launch_bounds__(kHistThreads) void batch_select_max_kernel(const BatchFilterArgs a) {
+    const int r = blockIdx.y;
+    const BatchFilterRow& R = a.row[r];
+    if (!row_selects(R) || !R.p_on) return;
+    select_max_body<OMX_BFLOAT16>(row_ws(a, r), a.rows + (size_t)r * a.V, R.seen, a.V, R.rule);
+}
+
+__global__ __launch_bounds__(kHistThreads) void batch_select_hist_kernel(const BatchFilterArgs a, int slot) {
+    const int r = blockIdx.y;
+    const BatchFilterRow& R = a.row[r];
+    if (!row_selects(R) || ((slot == 1 || slot == 2) && !R.k_on) || ((slot == 3 || slot == 4) && !R.p_on)) return;
+    select_hist_body<OMX_BFLOAT16>(row_ws(a, r), a.rows + (size_t)r * a.V, R.seen, a.V, R.rule, slot, (uint32_t)R.top_k, R.top_p, R.k_on, R.p_on);
+}
+
+__global__ __launch_bounds__(kHistThreads) void batch_select_resolve_kernel(const BatchFilterArgs a) {
+    const int r = blockIdx.y;
+    const BatchFilterRow& R = a.row[r];
+    if (!row_selects(R)) return;
+    select_resolve_body(row_ws(a, r), (uint32_t)R.top_k, R.top_p, a.V, R.k_on, R.p_on, 1);
+}
+
+// [noise] grid (kOpPartials, M): the row kept as the slot's logits, then the partials of the draw over the kept set with the slot's NEXT key
+__global__ __launch_bounds__(256) void batch_noise_kernel(const BatchFilterArgs a) {
+    const int r = blockIdx.y, slot = a.row_slot[r], V = a.V;
+    const BatchFilterRow& R = a.row[r];
+    const bf16_t* row = a.rows + (size_t)r * V;
+    bf16_t* keep = a.slot_logits + (size_t)slot * V;
+    uint32_t s0 = 0, s1 = 0, k0 = 0, k1 = 0;
+    if (!R.greedy) slot_next_key(a.slots + slot, s0, s1, k0, k1);
+    for (int v = blockIdx.x * 256 + threadIdx.x; v < V; v += gridDim.x * 256) keep[v] = row[v];
+    SelWs* ws = row_ws(a, r);
+    filtered_noise_body<OMX_BFLOAT16>(ws->partials, row, R.seen, row_selects(R) ? ws->thr : 0u, k0, k1, V, (uint64_t)V, R.rule, R.greedy);
+}
+
+// [finalize] grid (1, M): the partials' maximum is the row's token; the slot advances
+__global__ __launch_bounds__(kOpPartials) void batch_finalize_kernel(const BatchFilterArgs a) {
+    __shared__ unsigned long long red[kOpPartials / 64];
+    const int r = blockIdx.y;
+    unsigned long long best = row_ws(a, r)->partials[threadIdx.x];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(best, o, 64);
+        best = other > best ? other : best;
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < kOpPartials / 64; ++w) best = red[w] > best ? red[w] : best;
+        BatchSlot* S = a.slots + a.row_slot[r];
+        const bool greedy = a.row[r].greedy != 0;
+        uint32_t s0 = 0, s1 = 0, k0 = 0, k1 = 0;
+        if (!greedy) slot_next_key(S, s0, s1, k0, k1);
+        batch_row_advance(a, r, S, best, greedy, s0, s1, k0, k1);
+    }
+}
+
 }  // namespace
+
+bool sampling_filters(const omx_sampling& p, int V) { return p.repetition_penalty != 1.f || p.presence_penalty != 0.f || selects(p, V); }
+
+BatchFilterRow batch_filter_row(const omx_sampling& p, int V, uint8_t* seen_row) {
+    BatchFilterRow R = {};
+    R.rule = rule_of(p);
+    R.top_k = p.top_k;
+    R.top_p = p.top_p;
+    R.seen = seen_row;
+    R.k_on = p.top_k > 0 && p.top_k < V;
+    R.p_on = p.top_p < 1.f;
+    R.greedy = p.temperature == 0.f;
+    return R;
+}
+
+int launch_batch_filtered(const BatchFilterArgs& a, int M, hipStream_t s) {
+    OMX_REQUIRE(M >= 1 && M <= kBatchFilterRows, "batch sampler: %d rows (1..%d)", M, kBatchFilterRows);
+    if (a.V < kMultiLaunchMin) {
+        batch_filtered_kernel<<<M, kSelThreads, 0, s>>>(a);
+        OMX_LAUNCH_CHECK();
+        return 0;
+    }
+    OMX_REQUIRE(a.ws, "batch sampler: no selection scratch");
+    bool any = false, any_k = false, any_p = false;
+    for (int r = 0; r < M; ++r) {
+        const BatchFilterRow& R = a.row[r];
+        const bool sel = !R.greedy && (R.k_on || R.p_on);
+        any = any || sel;
+        any_k = any_k || (sel && R.k_on);
+        any_p = any_p || (sel && R.p_on);
+    }
+    const dim3 grid(kHistBlocks, M);
+    if (any_p) batch_select_max_kernel<<<grid, kHistThreads, 0, s>>>(a);
+    for (int slot = 0; slot < kSlots && any; ++slot) {
+        if ((slot == 1 || slot == 2) && !any_k) continue;
+        if ((slot == 3 || slot == 4) && !any_p) continue;
+        batch_select_hist_kernel<<<grid, kHistThreads, 0, s>>>(a, slot);
+    }
+    if (any) batch_select_resolve_kernel<<<dim3(1, M), kHistThreads, 0, s>>>(a);
+    batch_noise_kernel<<<dim3(kOpPartials, M), 256, 0, s>>>(a);
+    batch_finalize_kernel<<<dim3(1, M), kOpPartials, 0, s>>>(a);
+    OMX_LAUNCH_CHECK();
+    return 0;
+}
 
 size_t sample_select_ws_bytes() { return sizeof(SelWs); }
 

@@ -88,6 +88,7 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_batch_create": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int]),
     "omx_qwen3_batch_destroy": (c_int, [c_void_p]),
     "omx_qwen3_batch_set_sampler": (c_int, [c_void_p, c_int, ctypes.c_float, ctypes.c_uint64]),
+    "omx_qwen3_batch_set_sampling": (c_int, [c_void_p, c_int, ctypes.POINTER(Sampling), ctypes.c_uint64]),
     "omx_qwen3_batch_prefill": (c_int, [c_void_p, c_int, ctypes.POINTER(c_uint32), c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_batch_decode": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_batch_logits": (c_int, [c_void_p, c_int, c_void_p, c_int]),
@@ -492,9 +493,17 @@ class Batch:
         if sys is not None and not sys.is_finalizing():
             self.close()
 
-    def set_sampler(self, slot: int, temperature: float, seed: int = 0) -> None:
-        """Model.set_sampler's plain rule for one slot: 0 = greedy, else categorical(logits / temperature) from the slot's own key sequence."""
-        check(lib.omx_qwen3_batch_set_sampler(self._h, int(slot), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF))
+    def set_sampler(self, slot: int, temperature: float, seed: int = 0, *, top_k: int = 0, top_p: float = 1.0,
+                    repetition_penalty: float = 1.0, presence_penalty: float = 0.0) -> None:
+        """Model.set_sampler for one slot: 0 = greedy, else categorical(logits / temperature) from the slot's own key sequence.  The
+        keywords are Model.set_sampler's filters (omx_sample_filtered's rule) inside the batched step, per slot: the penalties act on
+        the tokens THIS slot sampled since its last prefill, top_k keeps ties, top_p acts on the survivors.  Their defaults are off:
+        the call is then the plain sampler, bit for bit.  Either form restarts the slot's key sequence and clears its history."""
+        if top_k == 0 and top_p == 1.0 and repetition_penalty == 1.0 and presence_penalty == 0.0:
+            check(lib.omx_qwen3_batch_set_sampler(self._h, int(slot), float(temperature), int(seed) & 0xFFFFFFFFFFFFFFFF))
+            return
+        p = Sampling(temperature, top_k, top_p, repetition_penalty, presence_penalty)
+        check(lib.omx_qwen3_batch_set_sampling(self._h, int(slot), ctypes.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
     def prefill(self, slot: int, prompt) -> int:
         """The prompt onto the slot's cache (appended to what the slot holds); returns the slot's first sampled token."""
@@ -506,6 +515,7 @@ class Batch:
     def fork(self, src: int, dst: int, resample: bool = True) -> int:
         """The empty slot `dst` becomes what it would be had it been fed `src`'s tokens itself: src's position, kept logits and a copy
         of its K/V rows.  Its pending token is drawn from those logits with dst's own sampler (resample), or is src's.  Returns it.
+        With a penalty on, a resampled sibling starts an empty history (fork right after the prefill); resample=False copies src's.
         The slot table records the whole 256-token chunks siblings have in common (`shared`); OMX_BATCH_SHARE_MIN=2..8 makes the decode
         attention read them once per group (bit-identical; slower than the default at every size measured)."""
         first = c_uint32()

@@ -139,7 +139,10 @@ def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int,
     only after its last sibling has: resetting the owner ends what its children share with it (`Batch.shared`).  Returns n lists per
     prompt, prompt-major: completion k of prompt i is [i * n + k].
     before_sibling(i, k, slot), if given, is called before completion k of prompt i is prefilled (k = 0) or forked into `slot` --
-    the place to give the slot its sampler (`Batch.set_sampler(slot, temperature, seed + k)`)."""
+    the place to give the slot its sampler (`Batch.set_sampler(slot, temperature, seed + k)`).
+    Samplers are the caller's: whatever `Batch.set_sampler` was given per slot -- its top_k / top_p / repetition_penalty /
+    presence_penalty filters included -- applies to the prefill's first token, to a fork's and to every decoded one; a slot's penalty
+    history starts empty at its prefill or fork and is cleared by the reset that frees the slot."""
     if max_new_tokens < 1 or chunk < 1:
         raise ValueError("generate_batch: max_new_tokens and chunk must be positive")
     if n < 1 or n > batch.n_slots:

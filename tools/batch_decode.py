@@ -4,7 +4,10 @@
         per weight format (0 = bf16, 4 = 4-bit group 64): the single-sequence Model.decode rate, then B = 1, 2, 4, 8 slots each prefilled
         with --ctx tokens, then 8 slots with ragged contexts (ctx/8 .. ctx); every figure is the median of --windows windows of --steps
         steps after a warm-up, timed with device events on the engine's stream (Model.last_decode_ms / Batch.last_decode_ms).
-        One JSON line per row, then the table.
+        One JSON line per row, then the table.  --batch-sizes 1 8 keeps those rows only (and drops the single-sequence and ragged rows).
+        --temperature T [--top-k K] [--top-p P] [--presence-penalty Q]: every slot samples with these settings (Batch.set_sampler,
+        seed = its slot) instead of greedily -- the cost of the per-slot filters is the difference between two such runs.  They
+        apply to --trace too.
     rocprofv3 --kernel-trace --stats -f csv -d DIR -- python tools/batch_decode.py --trace --bits 0 [--ctx 2048] [--steps 16]
         8 slots prefilled, --steps steps at B = 8 and nothing else at that row count: the trace's last steps give the per-launch times
         of a B = 8 step (python tools/batch_decode.py --stats DIR [--steps 32] prints them; pass rocprofv3 -f csv).
@@ -28,6 +31,11 @@ ap.add_argument("--stats", metavar="DIR", help="print the per-launch times of th
 ap.add_argument("--fork", action="store_true", help="eight forked slots against eight independent ones, shared-span read on and off")
 ap.add_argument("--fork-ctx", type=int, nargs="+", default=[2048, 8192])
 ap.add_argument("--fork-child", type=int, metavar="CTX", help=argparse.SUPPRESS)
+ap.add_argument("--batch-sizes", type=int, nargs="+", help="only these slot counts (1..8), no single-sequence and no ragged row")
+ap.add_argument("--temperature", type=float, default=0.0, help="every slot's sampler (0 = greedy)")
+ap.add_argument("--top-k", type=int, default=0)
+ap.add_argument("--top-p", type=float, default=1.0)
+ap.add_argument("--presence-penalty", type=float, default=0.0)
 args = ap.parse_args()
 
 if args.fork and not args.trace:
@@ -123,6 +131,11 @@ for bits in args.bits:
     m.synth_weights()
     fmt = f"{bits}-bit g64" if bits else "bf16"
     b = m.batch(8)
+    sampler = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, presence_penalty=args.presence_penalty)
+    filters = {k: v for k, v, off in (("top_k", args.top_k, 0), ("top_p", args.top_p, 1.0), ("presence_penalty", args.presence_penalty, 0.0)) if v != off}
+    if args.temperature != 0.0 or filters:
+        for s in range(8):
+            b.set_sampler(s, args.temperature, s, **filters)
     if args.trace:
         for s in range(8):
             b.prefill(s, prompt(args.ctx, s))
@@ -130,13 +143,17 @@ for bits in args.bits:
         print(f"{fmt}: {args.steps} steps at B = 8, {b.last_decode_ms() / args.steps:.3f} ms per step", flush=True)
         b.close(); m.close()
         continue
-    m.prefill(prompt(args.ctx, 100))
-    m.decode(8)
-    base, raw = median_ms(m.decode, m.last_decode_ms, args.steps, args.windows)
-    row = {"format": fmt, "B": "single", "ctx": args.ctx, "ms_per_step": base, "tok_s": 1e3 / base, "ratio": 1.0, "windows_ms": raw}
-    print(json.dumps(row), flush=True)
-    table.append(row)
+    base = float("nan")
+    if not args.batch_sizes:
+        m.prefill(prompt(args.ctx, 100))
+        m.decode(8)
+        base, raw = median_ms(m.decode, m.last_decode_ms, args.steps, args.windows)
+        row = {"format": fmt, "B": "single", "ctx": args.ctx, "ms_per_step": base, "tok_s": 1e3 / base, "ratio": 1.0, "windows_ms": raw}
+        print(json.dumps(row), flush=True)
+        table.append(row)
     runs = [(B, [args.ctx] * B) for B in (1, 2, 4, 8)] + [(8, [args.ctx * (i + 1) // 8 for i in range(8)])]
+    if args.batch_sizes:
+        runs = [(B, [args.ctx] * B) for B in args.batch_sizes]
     for B, ctxs in runs:
         slots = list(range(B))
         for s in slots:
@@ -146,7 +163,7 @@ for bits in args.bits:
         ms, raw = median_ms(lambda n: b.decode(n, slots), b.last_decode_ms, args.steps, args.windows)
         ragged = len(set(ctxs)) > 1
         row = {"format": fmt, "B": B, "ctx": f"{ctxs[0]}..{ctxs[-1]}" if ragged else args.ctx, "ms_per_step": ms, "tok_s": B * 1e3 / ms,
-               "ratio": B * base / ms, "windows_ms": raw}
+               "ratio": B * base / ms, "windows_ms": raw, "sampler": sampler}
         print(json.dumps(row), flush=True)
         table.append(row)
     b.close(); m.close()

@@ -3,7 +3,8 @@
                                    [--presence-penalty Q] [--seed S] [--max-tokens N]
     python tools/generate_qwen3.py <model_dir> --prompts-file FILE [--slots N] [--temperature T] [--seed S] [--max-tokens N]
     python tools/generate_qwen3.py <model_dir> [prompt] --samples N [--temperature T] [--seed S] [--max-tokens N]
---prompts-file: one prompt per line, decoded together over N slots of one loaded model (engine.Batch; plain temperature sampling).
+(the filter flags --top-k / --top-p / --repetition-penalty / --presence-penalty apply to all three forms)
+--prompts-file: one prompt per line, decoded together over N slots of one loaded model (engine.Batch), every slot with these settings.
 --samples N: N completions (1..8) of the prompt -- or of every line of --prompts-file -- from ONE prefill: the prompt's slot is forked
 N - 1 times (Batch.fork); sibling i of every prompt draws with a fresh key sequence of seed S + i (Batch.set_sampler before its fork).
 Without flags: the example's plain temperature 0.7.  The Qwen3 model card's settings are --temperature 0.6 --top-k 20 --top-p 0.95."""
@@ -25,7 +26,7 @@ ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--max-tokens", type=int, default=100)
 ap.add_argument("--prompts-file", help="one prompt per line: all of them through generate_batch over --slots slots")
 ap.add_argument("--slots", type=int, default=8, help="sequences decoded together (1..8)")
-ap.add_argument("--samples", type=int, default=1, help="completions per prompt from one prefill (1..8; plain temperature sampling)")
+ap.add_argument("--samples", type=int, default=1, help="completions per prompt from one prefill (1..8)")
 args = ap.parse_args()
 if not 1 <= args.samples <= 8:
     ap.error("--samples must be 1..8")
@@ -45,15 +46,16 @@ if args.prompts_file or args.samples > 1:
         e = json.load(open(gen_cfg)).get("eos_token_id", [])
         eos = [int(t) for t in (e if isinstance(e, list) else [e])]
     n = args.samples
+    filters = dict(top_k=args.top_k, top_p=args.top_p, repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty)
     batch = model.batch(max(n, min(args.slots, len(prompts) * n)))
     if n == 1:
         for slot in range(batch.n_slots):
-            batch.set_sampler(slot, args.temperature, args.seed + slot)
+            batch.set_sampler(slot, args.temperature, args.seed + slot, **filters)
     start = time.perf_counter()
     # --samples: sibling i of EVERY prompt starts a fresh key sequence of seed + i, set on its slot right before its prefill / fork, so
     # a prompt's samples do not depend on where it stands in the file or on which slots were free
     outs = generate.generate_batch(batch, prompts, args.max_tokens, eos_ids=eos, n=n, before_sibling=None if n == 1 else
-                                   lambda p, k, slot: batch.set_sampler(slot, args.temperature, args.seed + k))
+                                   lambda p, k, slot: batch.set_sampler(slot, args.temperature, args.seed + k, **filters))
     seconds = time.perf_counter() - start
     for i, toks in enumerate(outs):
         head = f"Prompt: {texts[i // n]}" + (f"  [sample {i % n}]" if n > 1 else "")
