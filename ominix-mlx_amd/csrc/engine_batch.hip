@@ -145,6 +145,9 @@ struct AttnRow {
     static constexpr int LPR = D / 8;          // lanes per K/V row
     static constexpr int TPW = 64 / LPR;       // tokens per wave-instruction == token sub-groups per wave
     static constexpr int STEP = TPW * kUnroll; // tokens per wave per step
+    // the block's LDS, what finish() merges through: [kWaves][TPW][GT][D] o, [kWaves][GT] m, [kWaves][GT] l (+ 4 floats of slack)
+    static constexpr int SM_O = kWaves * TPW * GT * D, SM_ML = kWaves * GT;
+    static constexpr size_t SMEM_BYTES = (size_t)(SM_O + 2 * SM_ML + 4) * sizeof(float);
     float q[GT][8], m[GT], l[GT], o[GT][8];
 
     __device__ __forceinline__ void begin(const BatchAttnArgs& a, int r, int kvh, int G, int c) {
@@ -216,11 +219,11 @@ struct AttnRow {
     }
 
     // every token sub-group parks its partial in LDS (same m inside a wave: plain sums); the 4 waves x TPW sub-groups are merged and
-    // the split's partial of row r written.  smem: [kWaves][TPW][GT][D] o, [kWaves][GT] m, [kWaves][GT] l
+    // the split's partial of row r written
     __device__ __forceinline__ void finish(const BatchAttnArgs& a, unsigned char* smem, int r, int kvh, int G, int split) const {
         float* sm_o = reinterpret_cast<float*>(smem);
-        float* sm_m = sm_o + kWaves * TPW * GT * D;
-        float* sm_l = sm_m + kWaves * GT;
+        float* sm_m = sm_o + SM_O;
+        float* sm_l = sm_m + SM_ML;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const int c = lane % LPR, sg = lane / LPR;
 #pragma unroll
@@ -306,152 +309,12 @@ __device__ __forceinline__ void attn_own_row(const BatchAttnArgs& a, unsigned ch
     row.finish(a, smem, r, kvh, G, split);
 }
 
-// The ungrouped launch, every row on its own slab.  Its body is attn_own_row's text written out: the kernel a batch without forks runs is
-// kept instruction for instruction what it was before AttnRow existed (the two forms are held to each other by the bit-equality tests of
-// tests/test_gpu_batch_fork.py).
+// The ungrouped launch, every row on its own slab: what a batch without forks runs
 template <int D, int GT>
 __global__ __launch_bounds__(kBlock) void batch_attn_kernel(const BatchAttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int bk = blockIdx.x, split = blockIdx.y;
-    constexpr int LPR = D / 8;          // lanes per K/V row
-    constexpr int TPW = 64 / LPR;       // tokens per wave-instruction == token sub-groups per wave
-    constexpr int STEP = TPW * kUnroll; // tokens per wave per step
-    float* sm_o = reinterpret_cast<float*>(smem);                 // [kWaves][TPW][GT][D]
-    float* sm_m = sm_o + kWaves * TPW * GT * D;                   // [kWaves][GT]
-    float* sm_l = sm_m + kWaves * GT;                             // [kWaves][GT]
-
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int c = lane % LPR;           // 8-element chunk of the head dim owned by this lane
-    const int sg = lane / LPR;          // token sub-group inside the wave
-    const int r = bk / a.Hkv, kvh = bk % a.Hkv;
-    const int G = a.H / a.Hkv;
-    const int slot = a.row_slot[r];
-    const int Tk = min(a.slots[slot].pos + 1, a.cap);
-    const int t_begin = split * a.chunk;
-    if (t_begin >= Tk) return;          // (block-uniform: past this sequence's end)
-    const int t_end = min(Tk, t_begin + a.chunk);
-
-    const bf16_t* Kb = a.kbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride;
-    const bf16_t* Vb = a.vbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride;
-
-    u32x4 kr[kUnroll], vr[kUnroll];
-    int t0 = t_begin + wave * STEP;
-    auto issue_kv = [&](int tbase) {
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const int tc = max(min(tbase + u * TPW + sg, t_end - 1), 0);
-            kr[u] = *reinterpret_cast<const u32x4*>(Kb + (size_t)tc * D + c * 8);
-            vr[u] = *reinterpret_cast<const u32x4*>(Vb + (size_t)tc * D + c * 8);
-        }
-    };
-    if (t0 < t_end) issue_kv(t0);
-
-    float q[GT][8];
-#pragma unroll
-    for (int g = 0; g < GT; ++g) {
-        const int h = kvh * G + min(g, G - 1);
-        float x[8];
-        unpack8(*reinterpret_cast<const u32x4*>(a.q + ((size_t)r * a.H + h) * D + c * 8), x);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) q[g][e] = x[e] * a.scale;
-    }
-
-    float m[GT], l[GT], o[GT][8];
-#pragma unroll
-    for (int g = 0; g < GT; ++g) {
-        m[g] = -INFINITY;
-        l[g] = 0.f;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
-    }
-
-    for (; t0 < t_end; t0 += STEP * kWaves) {
-        float s[kUnroll][GT];
-        float vf[kUnroll][8];
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const int tok = t0 + u * TPW + sg;
-            float kf[8];
-            unpack8(kr[u], kf);
-            unpack8(vr[u], vf[u]);
-            if (tok >= t_end) {   // clamped duplicate row: its p is 0, but 0 * garbage must stay 0
-#pragma unroll
-                for (int e = 0; e < 8; ++e) vf[u][e] = 0.f;
-            }
-#pragma unroll
-            for (int g = 0; g < GT; ++g) {
-                float d = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) d = fmaf(q[g][e], kf[e], d);
-                d = group_sum<LPR>(d);
-                s[u][g] = tok < t_end ? d : -INFINITY;
-            }
-        }
-        if (t0 + STEP * kWaves < t_end) issue_kv(t0 + STEP * kWaves);
-#pragma unroll
-        for (int g = 0; g < GT; ++g) {
-            float mx = s[0][g];
-#pragma unroll
-            for (int u = 1; u < kUnroll; ++u) mx = fmaxf(mx, s[u][g]);
-            float wmx = readlane_f(mx, 0);
-#pragma unroll
-            for (int rr = 1; rr < TPW; ++rr) wmx = fmaxf(wmx, readlane_f(mx, rr * LPR));
-            const float mn = fmaxf(m[g], wmx);
-            const float alpha = (mn == -INFINITY) ? 1.f : __expf(m[g] - mn);
-            m[g] = mn;
-            l[g] *= alpha;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[g][e] *= alpha;
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const float p = (mn == -INFINITY) ? 0.f : __expf(s[u][g] - mn);
-                l[g] += p;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[g][e] = fmaf(p, vf[u][e], o[g][e]);
-            }
-        }
-    }
-
-    // every token sub-group parks its partial in LDS (same m inside a wave: plain sums)
-#pragma unroll
-    for (int g = 0; g < GT; ++g) {
-        float* dst = sm_o + (((size_t)(wave * TPW + sg) * GT + g) * D + c * 8);
-        *reinterpret_cast<f32x4*>(dst) = f32x4{o[g][0], o[g][1], o[g][2], o[g][3]};
-        *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[g][4], o[g][5], o[g][6], o[g][7]};
-        float lw = readlane_f(l[g], 0);
-#pragma unroll
-        for (int rr = 1; rr < TPW; ++rr) lw += readlane_f(l[g], rr * LPR);
-        if (lane == 0) {
-            sm_m[wave * GT + g] = m[g];
-            sm_l[wave * GT + g] = lw;
-        }
-    }
-    __syncthreads();
-    // merge the 4 waves x TPW sub-groups, write the split's partial
-    for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {
-        const int g = idx / D, d = idx % D;
-        float M = sm_m[g];
-#pragma unroll
-        for (int w = 1; w < kWaves; ++w) M = fmaxf(M, sm_m[w * GT + g]);
-        float L = 0.f, O = 0.f;
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) {
-            const float mw = sm_m[w * GT + g];
-            const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
-            float ow = 0.f;
-#pragma unroll
-            for (int rr = 0; rr < TPW; ++rr) ow += sm_o[((size_t)(w * TPW + rr) * GT + g) * D + d];
-            L = fmaf(f, sm_l[w * GT + g], L);
-            O = fmaf(f, ow, O);
-        }
-        const size_t head = (size_t)r * a.H + kvh * G + g;
-        a.ws_o[(head * a.nsplit_cap + split) * D + d] = O;
-        if (d == 0) {
-            a.ws_ml[(head * a.nsplit_cap + split) * 2] = M;
-            a.ws_ml[(head * a.nsplit_cap + split) * 2 + 1] = L;
-        }
-    }
+    const int r = blockIdx.x / a.Hkv, kvh = blockIdx.x % a.Hkv;
+    attn_own_row<D, GT>(a, smem, r, kvh, blockIdx.y);
 }
 
 // ---- the same launch when listed rows share a prefix (omx_qwen3_batch_fork).  The rows whose owner is row r's and whose shared span
@@ -650,11 +513,13 @@ int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T,
     a.ws_o = rag.ws_o; a.ws_ml = rag.ws_ml;
     a.out = m->pf_attn;
     BatchSharedArgs sa = {};
-    sa.a = a;
-    sa.T = T; sa.group_min = rag.group_min; sa.group_rows = rag.group_rows;
-    for (int r = 0; r < kMaxSlots; ++r) {
-        sa.grp_owner[r] = r < T ? rag.grp_owner[r] : -1;
-        sa.grp_shared[r] = r < T ? rag.grp_shared[r] : 0;
+    if (rag.grouped) {
+        sa.a = a;
+        sa.T = T; sa.group_min = rag.group_min; sa.group_rows = rag.group_rows;
+        for (int r = 0; r < kMaxSlots; ++r) {
+            sa.grp_owner[r] = r < T ? rag.grp_owner[r] : -1;
+            sa.grp_shared[r] = r < T ? rag.grp_shared[r] : 0;
+        }
     }
     OMX_REQUIRE(!rag.grouped || (rag.chunk == kChunk && rag.group_min >= 2 && rag.group_rows >= 1), "batch attention: grouped splits of %d tokens, "
                 "groups from %d members, %d rows per block", rag.chunk, rag.group_min, rag.group_rows);
@@ -662,7 +527,7 @@ int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T,
     const int gt = G <= 1 ? 1 : G <= 2 ? 2 : G <= 4 ? 4 : 8;
 #define OMX_BATCH_ATTN_CASE(DD, GG)                                                                     \
     if (D == DD && gt == GG) {                                                                          \
-        const size_t shmem = ((size_t)kWaves * (64 / (DD / 8)) * GG * DD + 2 * kWaves * GG + 4) * sizeof(float); \
+        const size_t shmem = AttnRow<DD, GG>::SMEM_BYTES;                                               \
         const void* fn = rag.grouped ? (const void*)batch_attn_shared_kernel<DD, GG> : (const void*)batch_attn_kernel<DD, GG>; \
         if (shmem > 48 * 1024)                                                                          \
             OMX_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \

@@ -76,6 +76,57 @@ def test_ragged_batch_matches_the_oracle_teacher_forced(omx, name):
     b.close(); m.close()
 
 
+# ---- 1b. every instantiation of the split kernel against the oracle ----
+
+WIDTH_CTX = 1024
+WIDTH_LENS = [5, 250, 255, 600]
+# (head_dim, query heads, KV heads): batch_attn_kernel<D, GT> for D = 64 / 128 and GT = 1 / 2 / 4 / 8, and 3 query heads per KV head
+WIDTHS = [(128, 8, 2), (128, 4, 4), (128, 4, 2), (128, 8, 1), (64, 4, 4), (64, 4, 2), (64, 8, 2), (64, 8, 1), (64, 6, 2)]
+
+
+@pytest.mark.parametrize("D,H,Hkv", WIDTHS, ids=lambda v: str(v))
+def test_every_width_matches_the_oracle(omx, D, H, Hkv):
+    """batch_attn_kernel<D, GT> at both head widths and 1 / 2 / 4 / 8 query heads per KV head, and at 3 (GT = 4 with the last head
+    repeated in the spare column, a merge loop of 3 D elements), on one-layer models of hidden 512: four slots whose prompts are the
+    ways a split can end -- 5 tokens (three of the four waves see no token and merge with m = -inf), 250 (a clamped ragged tail,
+    and the sequence grows into a second split while decoding), 255 (pos + 1 lands exactly on the chunk boundary), 600 (three splits, the
+    last one ragged) -- 12 positions each, the oracle's token forced after every step.  The rules of
+    test_ragged_batch_matches_the_oracle_teacher_forced with L = 1: logits within 1.5 bound, the engine's token the oracle's unless
+    the oracle's margin is <= 2 bound, at most half of the 48 positions such near-ties (the oracle alone, in WIDTHS' order:
+    11, 9, 10, 13, 11, 8, 8, 14, 6)."""
+    cfg = rq.Qwen3Config(512, 1, 1024, H, Hkv, D, 2048, 1e-6, 1e6, False)
+    m, oracle = _engine(cfg, WIDTH_CTX), rq.Qwen3Oracle(cfg, rq.synth_weights(cfg))
+    V, n_pos, n = cfg.vocab_size, 12, len(WIDTH_LENS)
+    prompts = [_prompt(k, V) for k in WIDTH_LENS]
+    refs = [oracle.generate(p, n_pos, return_logits=True) for p in prompts]
+    b = m.batch(n, WIDTH_CTX)
+    got = [[int(b.prefill(s, prompts[s]))] for s in range(n)]
+    logits = [[b.logits(s)] for s in range(n)]
+    for i in range(1, n_pos):
+        for s in range(n):
+            b.trim(s, 0, int(refs[s][0][i - 1]))
+        step = b.decode(1)
+        for s in range(n):
+            got[s].append(int(step[0, s]))
+            logits[s].append(b.logits(s))
+    near, worst = 0, 0.0
+    for s in range(n):
+        assert b.offset(s) == WIDTH_LENS[s] + n_pos - 1
+        ref_tokens, ref_logits = refs[s]
+        bound = _bound(cfg, ref_logits)
+        margins = rc.argmax_margin(ref_logits)
+        for i in range(n_pos):
+            err = float(np.abs(logits[s][i] - ref_logits[i]).max())
+            worst = max(worst, err / bound)
+            print(f"({D}, {H}, {Hkv}) slot {s} pos {i}: err {err:.4f} bound {bound:.4f} margin {margins[i]:.4f} token {got[s][i]} ref {int(ref_tokens[i])}")
+            assert err <= 1.5 * bound, f"slot {s} position {i}: logits off by {err:.4f} (1.5 x bound = {1.5 * bound:.4f})"
+            assert got[s][i] == int(ref_tokens[i]) or margins[i] <= 2 * bound, f"slot {s} position {i}: token {got[s][i]} vs {int(ref_tokens[i])}"
+            near += int(margins[i] <= 2 * bound)
+    print(f"({D}, {H}, {Hkv}): worst error {worst:.3f} x bound, {near} of {n * n_pos} positions are near-ties of the oracle")
+    assert near <= n * n_pos // 2
+    b.close(); m.close()
+
+
 # ---- 2. neighbours do not change a sequence ----
 
 def _run_a(b, slot_a, prompt_a, neighbours, order, steps=16, disturb=None):
