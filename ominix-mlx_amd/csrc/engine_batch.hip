@@ -11,6 +11,7 @@
 // Attention splits are kChunk tokens wide whatever the batch holds: a sequence's partials, and the order its merge adds them in,
 // depend on its own length only, so a sequence's bits do not depend on its neighbours (attn_decode_kernel derives its chunk from the
 // launch's split count, which follows the longest sequence).
+#include "attn_row.hpp"
 #include "engine_model.hpp"
 
 namespace omx {
@@ -20,12 +21,8 @@ constexpr int kMaxSlots = 8;
 constexpr int kChunk = 256;        // tokens per attention split: a multiple of the block step of both head widths (64 / 128 tokens)
 constexpr int kRingSteps = 1024;   // steps of one decode call the token ring holds
 
-constexpr int kBlock = 256;
-constexpr int kWaves = 4;
-constexpr int kUnroll = 4;
-
 // ---- embedding rows of the pending tokens.  BITS = 0: a bf16 table, rows copied; else the packed table, each element
-// (float)q * scale + bias with one rounding -- the expression of qembed_rows_kernel (engine_prefill.hip).  One block per row.
+// (float)q * scale + bias with one rounding -- qembed_row (quant.hpp), what qembed_rows_kernel (engine_prefill.hip) runs.  One block per row.
 template <int BITS>
 __global__ __launch_bounds__(256) void batch_embed_kernel(bf16_t* __restrict__ out, const void* __restrict__ table_, const bf16_t* __restrict__ scales,
                                                           const bf16_t* __restrict__ biases, const BatchSlot* __restrict__ slots,
@@ -36,80 +33,12 @@ __global__ __launch_bounds__(256) void batch_embed_kernel(bf16_t* __restrict__ o
         u32x4* dst = reinterpret_cast<u32x4*>(out + (size_t)blockIdx.x * hidden);
         for (int j = threadIdx.x; j < hidden / 8; j += blockDim.x) dst[j] = src[j];
     } else {
-        const uint32_t* wrow = reinterpret_cast<const uint32_t*>(table_) + id * (size_t)(hidden / 32 * BITS);
-        const bf16_t* srow = scales + id * (size_t)(hidden / group);
-        const bf16_t* brow = biases ? biases + id * (size_t)(hidden / group) : nullptr;
-        for (int j = threadIdx.x; j < hidden; j += blockDim.x) {
-            const int p = j * BITS, k = p >> 5, o = p & 31;
-            const uint32_t q = (o + BITS <= 32 ? wrow[k] >> o : __builtin_amdgcn_alignbit(wrow[k + 1], wrow[k], o)) & ((1u << BITS) - 1u);
-            const float sc = bf16_to_f32(srow[j / group]), b = brow ? bf16_to_f32(brow[j / group]) : 0.f;
-            out[(size_t)blockIdx.x * hidden + j] = f32_to_bf16((float)q * sc + b);
-        }
+        qembed_row<BITS>(out + (size_t)blockIdx.x * hidden, reinterpret_cast<const uint32_t*>(table_), scales, biases, id, hidden, group);
     }
 }
 
-// ---- q/k norm + RoPE + cache append, the arithmetic of qk_norm_rope_scatter_kernel (prefill.hip) with the position and the slab of
-// every row taken from its slot: q rows -> q_out[r][h][:], k / v rows -> slot s's slabs at pos[s]
-template <int D>
-__global__ __launch_bounds__(256) void batch_scatter_kernel(
-    const bf16_t* __restrict__ q_lin, const bf16_t* __restrict__ k_lin, const bf16_t* __restrict__ v_lin,
-    const bf16_t* __restrict__ q_norm_w, const bf16_t* __restrict__ k_norm_w, const float* __restrict__ rope_cos,
-    const float* __restrict__ rope_sin, bf16_t* __restrict__ q_out, bf16_t* __restrict__ kbase, bf16_t* __restrict__ vbase,
-    size_t slot_stride, const BatchSlot* __restrict__ slots, const int* __restrict__ row_slot, int T, int H, int Hkv, int cap, float eps) {
-    constexpr int LPR = D / 8;
-    const int lane = threadIdx.x & 63;
-    const int c = lane % LPR;
-    const int rows_per_block = 256 / LPR;
-    const int64_t row = (int64_t)blockIdx.x * rows_per_block + threadIdx.x / LPR;
-    const int per_tok = H + 2 * Hkv;
-    if (row >= (int64_t)T * per_tok) return;
-    const int t = (int)(row / per_tok), hh = (int)(row % per_tok);
-    const int slot = row_slot[t];
-    const int pos = min(slots[slot].pos, cap - 1);   // (the host refuses a step past the slab's end before it launches anything)
-    bf16_t* kcache = kbase + (size_t)slot * slot_stride;
-    bf16_t* vcache = vbase + (size_t)slot * slot_stride;
-    if (hh >= H + Hkv) {   // v: plain copy into the slab
-        const int kvh = hh - H - Hkv;
-        *reinterpret_cast<u32x4*>(vcache + ((size_t)kvh * cap + pos) * D + c * 8) =
-            *reinterpret_cast<const u32x4*>(v_lin + ((size_t)t * Hkv + kvh) * D + c * 8);
-        return;
-    }
-    const bool is_q = hh < H;
-    const bf16_t* src = is_q ? q_lin + ((size_t)t * H + hh) * D : k_lin + ((size_t)t * Hkv + (hh - H)) * D;
-    const bf16_t* w = is_q ? q_norm_w : k_norm_w;
-    const u32x4 r = *reinterpret_cast<const u32x4*>(src + c * 8);
-    const u32x4 wr = w ? *reinterpret_cast<const u32x4*>(w + c * 8) : u32x4{0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u};   // no q/k norm: weight 1
-    float x[8], wv[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        x[2 * e] = bf16lo(r[e]); x[2 * e + 1] = bf16hi(r[e]);
-        wv[2 * e] = bf16lo(wr[e]); wv[2 * e + 1] = bf16hi(wr[e]);
-    }
-    float ss = 0.f;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ss = fmaf(x[e], x[e], ss);
-    ss = group_sum<LPR>(ss);
-    const float rstd = w ? 1.0f / sqrtf(ss / (float)D + eps) : 1.0f;   // without a norm the projection goes to RoPE as it is
-    const int i0 = (c % (LPR / 2)) * 8;
-    const bool first_half = c < LPR / 2;
-    float y[8];
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float xn = round_bf16(x[e] * rstd * wv[e]);
-        // partner element i +- D/2 lives in lane c ^ (LPR/2)
-        const float other = (LPR == 16) ? dpp_f<0x128>(xn) : dpp_f<0x1B>(dpp_f<kDppHalfMirror>(xn));
-        const float cs = rope_cos[(size_t)pos * (D / 2) + i0 + e], sn = rope_sin[(size_t)pos * (D / 2) + i0 + e];
-        y[e] = first_half ? xn * cs - other * sn : other * sn + xn * cs;
-    }
-    u32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = pack_bf16(y[2 * e], y[2 * e + 1]);
-    bf16_t* dst = is_q ? q_out + ((size_t)t * H + hh) * D : kcache + ((size_t)(hh - H) * cap + pos) * D;
-    *reinterpret_cast<u32x4*>(dst + c * 8) = o;
-}
-
-// ---- ragged split-KV decode attention.  The mapping of attn_decode_kernel (attn_decode.hip): K/V rows straight to registers, 16 bytes
-// per lane, the G query heads of a KV head together, one running max per head and wave, the waves' partials merged through LDS.
+// ---- ragged split-KV decode attention, built from AttnRow (attn_row.hpp: the per-split arithmetic and its lane mapping, the text of
+// attn_decode_kernel as well).
 // grid = (T * Hkv) x nsplit; block (r, kvh, split) covers tokens [split * chunk, min(len, (split + 1) * chunk)) of row r's slot, len =
 // pos + 1 read from the slot table; a block past its sequence's end writes nothing and the merge never reads its partial.
 struct BatchAttnArgs {
@@ -130,147 +59,11 @@ struct BatchSharedArgs {
     int grp_owner[kMaxSlots], grp_shared[kMaxSlots];
 };
 
-__device__ __forceinline__ void unpack8(const u32x4 r, float (&x)[8]) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        x[2 * e] = bf16lo(r[e]);
-        x[2 * e + 1] = bf16hi(r[e]);
-    }
-}
-
-// The per-row arithmetic of a split, in the pieces both kernels below are made of: what a (row, KV head, split) partial is, to the bit,
-// is written here once.  A lane owns 8 elements (c) of the head dim of token sub-group sg of its wave.
-template <int D, int GT>
-struct AttnRow {
-    static constexpr int LPR = D / 8;          // lanes per K/V row
-    static constexpr int TPW = 64 / LPR;       // tokens per wave-instruction == token sub-groups per wave
-    static constexpr int STEP = TPW * kUnroll; // tokens per wave per step
-    // the block's LDS, what finish() merges through: [kWaves][TPW][GT][D] o, [kWaves][GT] m, [kWaves][GT] l (+ 4 floats of slack)
-    static constexpr int SM_O = kWaves * TPW * GT * D, SM_ML = kWaves * GT;
-    static constexpr size_t SMEM_BYTES = (size_t)(SM_O + 2 * SM_ML + 4) * sizeof(float);
-    float q[GT][8], m[GT], l[GT], o[GT][8];
-
-    __device__ __forceinline__ void begin(const BatchAttnArgs& a, int r, int kvh, int G, int c) {
-#pragma unroll
-        for (int g = 0; g < GT; ++g) {
-            const int h = kvh * G + min(g, G - 1);
-            float x[8];
-            unpack8(*reinterpret_cast<const u32x4*>(a.q + ((size_t)r * a.H + h) * D + c * 8), x);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) q[g][e] = x[e] * a.scale;
-        }
-#pragma unroll
-        for (int g = 0; g < GT; ++g) {
-            m[g] = -INFINITY;
-            l[g] = 0.f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[g][e] = 0.f;
-        }
-    }
-
-    // scores of the wave's STEP tokens from t0 on against the K rows in kr; the V rows unpacked
-    __device__ __forceinline__ void scores(const u32x4 (&kr)[kUnroll], const u32x4 (&vr)[kUnroll], int t0, int t_end, int sg,
-                                           float (&s)[kUnroll][GT], float (&vf)[kUnroll][8]) const {
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const int tok = t0 + u * TPW + sg;
-            float kf[8];
-            unpack8(kr[u], kf);
-            unpack8(vr[u], vf[u]);
-            if (tok >= t_end) {   // clamped duplicate row: its p is 0, but 0 * garbage must stay 0
-#pragma unroll
-                for (int e = 0; e < 8; ++e) vf[u][e] = 0.f;
-            }
-#pragma unroll
-            for (int g = 0; g < GT; ++g) {
-                float d = 0.f;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) d = fmaf(q[g][e], kf[e], d);
-                d = group_sum<LPR>(d);
-                s[u][g] = tok < t_end ? d : -INFINITY;
-            }
-        }
-    }
-
-    // running max / sum / output of the wave over those tokens
-    __device__ __forceinline__ void update(const float (&s)[kUnroll][GT], const float (&vf)[kUnroll][8]) {
-#pragma unroll
-        for (int g = 0; g < GT; ++g) {
-            float mx = s[0][g];
-#pragma unroll
-            for (int u = 1; u < kUnroll; ++u) mx = fmaxf(mx, s[u][g]);
-            float wmx = readlane_f(mx, 0);
-#pragma unroll
-            for (int rr = 1; rr < TPW; ++rr) wmx = fmaxf(wmx, readlane_f(mx, rr * LPR));
-            const float mn = fmaxf(m[g], wmx);
-            const float alpha = (mn == -INFINITY) ? 1.f : __expf(m[g] - mn);
-            m[g] = mn;
-            l[g] *= alpha;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[g][e] *= alpha;
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const float p = (mn == -INFINITY) ? 0.f : __expf(s[u][g] - mn);
-                l[g] += p;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) o[g][e] = fmaf(p, vf[u][e], o[g][e]);
-            }
-        }
-    }
-
-    // every token sub-group parks its partial in LDS (same m inside a wave: plain sums); the 4 waves x TPW sub-groups are merged and
-    // the split's partial of row r written
-    __device__ __forceinline__ void finish(const BatchAttnArgs& a, unsigned char* smem, int r, int kvh, int G, int split) const {
-        float* sm_o = reinterpret_cast<float*>(smem);
-        float* sm_m = sm_o + SM_O;
-        float* sm_l = sm_m + SM_ML;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int c = lane % LPR, sg = lane / LPR;
-#pragma unroll
-        for (int g = 0; g < GT; ++g) {
-            float* dst = sm_o + (((size_t)(wave * TPW + sg) * GT + g) * D + c * 8);
-            *reinterpret_cast<f32x4*>(dst) = f32x4{o[g][0], o[g][1], o[g][2], o[g][3]};
-            *reinterpret_cast<f32x4*>(dst + 4) = f32x4{o[g][4], o[g][5], o[g][6], o[g][7]};
-            float lw = readlane_f(l[g], 0);
-#pragma unroll
-            for (int rr = 1; rr < TPW; ++rr) lw += readlane_f(l[g], rr * LPR);
-            if (lane == 0) {
-                sm_m[wave * GT + g] = m[g];
-                sm_l[wave * GT + g] = lw;
-            }
-        }
-        __syncthreads();
-        for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {
-            const int g = idx / D, d = idx % D;
-            float M = sm_m[g];
-#pragma unroll
-            for (int w = 1; w < kWaves; ++w) M = fmaxf(M, sm_m[w * GT + g]);
-            float L = 0.f, O = 0.f;
-#pragma unroll
-            for (int w = 0; w < kWaves; ++w) {
-                const float mw = sm_m[w * GT + g];
-                const float f = (mw == -INFINITY) ? 0.f : __expf(mw - M);
-                float ow = 0.f;
-#pragma unroll
-                for (int rr = 0; rr < TPW; ++rr) ow += sm_o[((size_t)(w * TPW + rr) * GT + g) * D + d];
-                L = fmaf(f, sm_l[w * GT + g], L);
-                O = fmaf(f, ow, O);
-            }
-            const size_t head = (size_t)r * a.H + kvh * G + g;
-            a.ws_o[(head * a.nsplit_cap + split) * D + d] = O;
-            if (d == 0) {
-                a.ws_ml[(head * a.nsplit_cap + split) * 2] = M;
-                a.ws_ml[(head * a.nsplit_cap + split) * 2 + 1] = L;
-            }
-        }
-    }
-};
-
 // block (r, kvh, split) on row r's own slab: K/V rows of the next step in flight while this step's are applied
 template <int D, int GT>
 __device__ __forceinline__ void attn_own_row(const BatchAttnArgs& a, unsigned char* smem, int r, int kvh, int split) {
     using Row = AttnRow<D, GT>;
-    constexpr int LPR = Row::LPR, TPW = Row::TPW, STEP = Row::STEP;
+    constexpr int LPR = Row::LPR, STEP = Row::STEP;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int c = lane % LPR;           // 8-element chunk of the head dim owned by this lane
@@ -287,26 +80,18 @@ __device__ __forceinline__ void attn_own_row(const BatchAttnArgs& a, unsigned ch
 
     u32x4 kr[kUnroll], vr[kUnroll];
     int t0 = t_begin + wave * STEP;
-    auto issue_kv = [&](int tbase) {
-#pragma unroll
-        for (int u = 0; u < kUnroll; ++u) {
-            const int tc = max(min(tbase + u * TPW + sg, t_end - 1), 0);
-            kr[u] = *reinterpret_cast<const u32x4*>(Kb + (size_t)tc * D + c * 8);
-            vr[u] = *reinterpret_cast<const u32x4*>(Vb + (size_t)tc * D + c * 8);
-        }
-    };
-    if (t0 < t_end) issue_kv(t0);
+    if (t0 < t_end) Row::issue_kv(kr, vr, Kb, Vb, t0, t_end, sg, c);
 
     Row row;
-    row.begin(a, r, kvh, G, c);
+    row.begin(a.q + (size_t)r * a.H * D, D, a.scale, kvh, G, c);
     for (; t0 < t_end; t0 += STEP * kWaves) {
         float s[kUnroll][GT];
         float vf[kUnroll][8];
-        row.scores(kr, vr, t0, t_end, sg, s, vf);
-        if (t0 + STEP * kWaves < t_end) issue_kv(t0 + STEP * kWaves);
+        row.scores(kr, vr, t0, t_end, sg, NoMask{}, s, vf);
+        if (t0 + STEP * kWaves < t_end) Row::issue_kv(kr, vr, Kb, Vb, t0 + STEP * kWaves, t_end, sg, c);
         row.update(s, vf);
     }
-    row.finish(a, smem, r, kvh, G, split);
+    row.finish(smem, a.ws_o, a.ws_ml, a.nsplit_cap, (size_t)r * a.H + kvh * G, G, split);
 }
 
 // The ungrouped launch, every row on its own slab: what a batch without forks runs
@@ -371,7 +156,7 @@ __global__ __launch_bounds__(kBlock) void batch_attn_shared_kernel(const BatchSh
         if (!((members >> r2) & 1u)) continue;
         --take;
         Row row;
-        row.begin(a, r2, kvh, G, c);
+        row.begin(a.q + (size_t)r2 * a.H * D, D, a.scale, kvh, G, c);
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             // (the rows stay packed between the member rows: unpacked once for all of them they would not fit the register file)
@@ -379,10 +164,10 @@ __global__ __launch_bounds__(kBlock) void batch_attn_shared_kernel(const BatchSh
             for (int u = 0; u < kUnroll; ++u) asm volatile("" : "+v"(kr[it][u]), "+v"(vr[it][u]));
             float s[kUnroll][GT];
             float vf[kUnroll][8];
-            row.scores(kr[it], vr[it], t_begin + (it * kWaves + wave) * STEP, t_end, sg, s, vf);
+            row.scores(kr[it], vr[it], t_begin + (it * kWaves + wave) * STEP, t_end, sg, NoMask{}, s, vf);
             row.update(s, vf);
         }
-        row.finish(a, smem, r2, kvh, G, split);
+        row.finish(smem, a.ws_o, a.ws_ml, a.nsplit_cap, (size_t)r2 * a.H + kvh * G, G, split);
         __syncthreads();   // the merge has read the LDS area before the next row parks in it
     }
 }
@@ -476,25 +261,6 @@ int launch_batch_embed(omx_qwen3 m, const RaggedRows& rag, int T, hipStream_t s)
         default: return set_error("batch embed: quantization bits %d unsupported", c.quant_bits);
     }
 #undef OMX_BATCH_EMB
-    OMX_LAUNCH_CHECK();
-    return 0;
-}
-
-int launch_batch_scatter(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s) {
-    const omx_qwen3_config& c = m->cfg;
-    const LayerW& L = m->layers[layer];
-    const int D = c.head_dim, H = m->H, Hkv = m->Hkv;
-    const int64_t rows = (int64_t)T * (H + 2 * Hkv);
-    const int rpb = 256 / (D / 8);
-    const unsigned blocks = (unsigned)((rows + rpb - 1) / rpb);
-    if (D == 128)
-        batch_scatter_kernel<128><<<blocks, 256, 0, s>>>(m->pf_q, m->pf_k, m->pf_v, L.q_norm, L.k_norm, m->rope_cos, m->rope_sin, m->pf_qt,
-                                                         rag.kbase[layer], rag.vbase[layer], rag.slot_stride, rag.slots, rag.row_slot, T, H, Hkv,
-                                                         rag.cap, c.rms_norm_eps);
-    else
-        batch_scatter_kernel<64><<<blocks, 256, 0, s>>>(m->pf_q, m->pf_k, m->pf_v, L.q_norm, L.k_norm, m->rope_cos, m->rope_sin, m->pf_qt,
-                                                        rag.kbase[layer], rag.vbase[layer], rag.slot_stride, rag.slots, rag.row_slot, T, H, Hkv,
-                                                        rag.cap, c.rms_norm_eps);
     OMX_LAUNCH_CHECK();
     return 0;
 }

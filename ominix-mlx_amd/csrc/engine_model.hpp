@@ -262,8 +262,8 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = 
                            const KvSlabs* kv = nullptr, const RaggedRows* rag = nullptr);
 void launch_encoder_mask(bf16_t* mask, const uint8_t* am, int T, hipStream_t s);
 
-// engine_batch.hip: the ragged launches of a batched decode step over T <= 8 rows (RaggedRows); q rows go to pf_qt as [T, H, D], the
-// attention output to pf_attn as [T, H * D]
+// the ragged launches of a batched decode step over T <= 8 rows (RaggedRows; engine_batch.hip, the scatter beside its prompt form in
+// prefill.hip); q rows go to pf_qt as [T, H, D], the attention output to pf_attn as [T, H * D]
 int launch_batch_embed(omx_qwen3 m, const RaggedRows& rag, int T, hipStream_t s);
 int launch_batch_scatter(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s);
 int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s);

@@ -44,21 +44,11 @@ __global__ void heads_to_tokens_kernel(bf16_t* __restrict__ out, const bf16_t* _
 }
 
 // QuantizedEmbedding::forward for the T rows of prompt_dev straight from the packed table (the verify pass of a packed model, which
-// dequantises no matrix): each element (float)q * scale + bias with one rounding, the expression of dequantize_kernel /
-// dequantize_chunk_kernel (quant.hip), so the rows equal the prompt pass's gather-then-dequantise bit for bit.  One block per row.
+// dequantises no matrix): qembed_row (quant.hpp), so the rows equal the prompt pass's gather-then-dequantise bit for bit.  One block per row.
 template <int BITS>
 __global__ __launch_bounds__(256) void qembed_rows_kernel(bf16_t* __restrict__ out, const uint32_t* __restrict__ table, const bf16_t* __restrict__ scales,
                                                           const bf16_t* __restrict__ biases, const uint32_t* __restrict__ ids, int hidden, int group) {
-    const size_t id = ids[blockIdx.x];
-    const uint32_t* wrow = table + id * (size_t)(hidden / 32 * BITS);
-    const bf16_t* srow = scales + id * (size_t)(hidden / group);
-    const bf16_t* brow = biases ? biases + id * (size_t)(hidden / group) : nullptr;
-    for (int j = threadIdx.x; j < hidden; j += blockDim.x) {
-        const int p = j * BITS, k = p >> 5, o = p & 31;
-        const uint32_t q = (o + BITS <= 32 ? wrow[k] >> o : __builtin_amdgcn_alignbit(wrow[k + 1], wrow[k], o)) & ((1u << BITS) - 1u);
-        const float sc = bf16_to_f32(srow[j / group]), b = brow ? bf16_to_f32(brow[j / group]) : 0.f;
-        out[(size_t)blockIdx.x * hidden + j] = f32_to_bf16((float)q * sc + b);
-    }
+    qembed_row<BITS>(out + (size_t)blockIdx.x * hidden, table, scales, biases, ids[blockIdx.x], hidden, group);
 }
 
 }  // namespace

@@ -1,22 +1,43 @@
 // Glue kernels of the batched (T > 1) prefill step of the decode engine; each fuses what the
 // reference issues as several lazy ops.
-#include "prefill.hpp"
-#include "act16.hpp"
+#include "engine_model.hpp"
 
 namespace omx {
 namespace {
 
-// One D/8-lane group per (token, head) row.  q rows: per-head RMSNorm -> RoPE -> q_out[h][t][:]
-// (the [B,H,T,D] operand of SDPA); k rows: same, written straight into the KV slab at offset+t
-// (KVCache::update_and_fetch, cache.rs:183-188); v rows: copied into the slab.
+// Where the rows of a qk_norm_rope_scatter_kernel launch live: row t's position and K/V slabs, and the q_out row of (t, head h).
+// A prompt: token t at position offset + t of one pair of slabs; q_out[h][t][:] (the [B,H,T,D] operand of SDPA)
+struct PromptRows {
+    bf16_t *kcache, *vcache;
+    int offset;
+    __device__ __forceinline__ void at(int t, int cap, int& pos, bf16_t*& k, bf16_t*& v) const { pos = offset + t; k = kcache; v = vcache; }
+    static __device__ __forceinline__ size_t q_row(int t, int h, int T, int H) { return (size_t)h * T + t; }
+};
+// The ragged rows of a batched decode step (engine_batch.hip): row t is the pending token of slot row_slot[t], at that slot's position
+// in that slot's slabs; q_out[t][h][:]
+struct SlotRows {
+    bf16_t *kbase, *vbase;
+    size_t slot_stride;
+    const BatchSlot* slots;
+    const int* row_slot;
+    __device__ __forceinline__ void at(int t, int cap, int& pos, bf16_t*& k, bf16_t*& v) const {
+        const int slot = row_slot[t];
+        pos = min(slots[slot].pos, cap - 1);   // (the host refuses a step past the slab's end before it launches anything)
+        k = kbase + (size_t)slot * slot_stride;
+        v = vbase + (size_t)slot * slot_stride;
+    }
+    static __device__ __forceinline__ size_t q_row(int t, int h, int T, int H) { return (size_t)t * H + h; }
+};
+
+// One D/8-lane group per (token, head) row.  q rows: per-head RMSNorm -> RoPE -> q_out; k rows: same, written straight into the KV
+// slab at the row's position (KVCache::update_and_fetch, cache.rs:183-188); v rows: copied into the slab.
 //   reference: qwen3-mlx/src/model.rs:172-196 (reshape/transpose, q_norm/k_norm, rope, cache update).
-// F16: a float16 model (float16 rows, norm weights, cache slabs and rounding points: act16.hpp)
-template <int D, bool F16 = false>
+// Rows: PromptRows / SlotRows.  F16: a float16 model (float16 rows, norm weights, cache slabs and rounding points: act16.hpp)
+template <int D, class Rows, bool F16 = false>
 __global__ __launch_bounds__(256) void qk_norm_rope_scatter_kernel(
     const bf16_t* __restrict__ q_lin, const bf16_t* __restrict__ k_lin, const bf16_t* __restrict__ v_lin,
     const bf16_t* __restrict__ q_norm_w, const bf16_t* __restrict__ k_norm_w, const float* __restrict__ rope_cos,
-    const float* __restrict__ rope_sin, bf16_t* __restrict__ q_out, bf16_t* __restrict__ kcache,
-    bf16_t* __restrict__ vcache, int T, int H, int Hkv, int cap, int offset, float eps) {
+    const float* __restrict__ rope_sin, bf16_t* __restrict__ q_out, const Rows rows, int T, int H, int Hkv, int cap, float eps) {
     typedef Act16<F16> A16;
     constexpr int LPR = D / 8;
     const int lane = threadIdx.x & 63;
@@ -26,7 +47,9 @@ __global__ __launch_bounds__(256) void qk_norm_rope_scatter_kernel(
     const int per_tok = H + 2 * Hkv;
     if (row >= (int64_t)T * per_tok) return;
     const int t = (int)(row / per_tok), hh = (int)(row % per_tok);
-    const int pos = offset + t;
+    int pos;
+    bf16_t *kcache, *vcache;
+    rows.at(t, cap, pos, kcache, vcache);
     if (hh >= H + Hkv) {   // v: plain copy into the slab
         const int kvh = hh - H - Hkv;
         *reinterpret_cast<u32x4*>(vcache + ((size_t)kvh * cap + pos) * D + c * 8) =
@@ -63,7 +86,7 @@ __global__ __launch_bounds__(256) void qk_norm_rope_scatter_kernel(
     u32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = A16::pack(y[2 * e], y[2 * e + 1]);
-    bf16_t* dst = is_q ? q_out + ((size_t)hh * T + t) * D : kcache + ((size_t)(hh - H) * cap + pos) * D;
+    bf16_t* dst = is_q ? q_out + Rows::q_row(t, hh, T, H) * D : kcache + ((size_t)(hh - H) * cap + pos) * D;
     *reinterpret_cast<u32x4*>(dst + c * 8) = o;
 }
 
@@ -100,17 +123,37 @@ int launch_qk_norm_rope_scatter(const bf16_t* q_lin, const bf16_t* k_lin, const 
     const int64_t rows = (int64_t)T * (H + 2 * Hkv);
     const int rpb = 256 / (D / 8);
     const unsigned blocks = (unsigned)((rows + rpb - 1) / rpb);
+    const PromptRows at = {kcache, vcache, offset};
     if (f16) {
         OMX_REQUIRE(D == 128, "qk_norm_rope: float16 models have head_dim 128");
-        qk_norm_rope_scatter_kernel<128, true><<<blocks, 256, 0, s>>>(q_lin, k_lin, v_lin, q_norm_w, k_norm_w, rope_cos, rope_sin,
-                                                                      q_out, kcache, vcache, T, H, Hkv, cap, offset, eps);
+        qk_norm_rope_scatter_kernel<128, PromptRows, true><<<blocks, 256, 0, s>>>(q_lin, k_lin, v_lin, q_norm_w, k_norm_w, rope_cos, rope_sin,
+                                                                                  q_out, at, T, H, Hkv, cap, eps);
     } else
     if (D == 128)
-        qk_norm_rope_scatter_kernel<128><<<blocks, 256, 0, s>>>(q_lin, k_lin, v_lin, q_norm_w, k_norm_w, rope_cos, rope_sin,
-                                                                q_out, kcache, vcache, T, H, Hkv, cap, offset, eps);
+        qk_norm_rope_scatter_kernel<128, PromptRows><<<blocks, 256, 0, s>>>(q_lin, k_lin, v_lin, q_norm_w, k_norm_w, rope_cos, rope_sin,
+                                                                            q_out, at, T, H, Hkv, cap, eps);
     else
-        qk_norm_rope_scatter_kernel<64><<<blocks, 256, 0, s>>>(q_lin, k_lin, v_lin, q_norm_w, k_norm_w, rope_cos, rope_sin,
-                                                               q_out, kcache, vcache, T, H, Hkv, cap, offset, eps);
+        qk_norm_rope_scatter_kernel<64, PromptRows><<<blocks, 256, 0, s>>>(q_lin, k_lin, v_lin, q_norm_w, k_norm_w, rope_cos, rope_sin,
+                                                                           q_out, at, T, H, Hkv, cap, eps);
+    OMX_LAUNCH_CHECK();
+    return 0;
+}
+
+// the same launch over the ragged rows of a batched decode step: q rows -> pf_qt[r][h][:], k / v rows -> the slabs of the row's slot
+int launch_batch_scatter(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s) {
+    const omx_qwen3_config& c = m->cfg;
+    const LayerW& L = m->layers[layer];
+    const int D = c.head_dim, H = m->H, Hkv = m->Hkv;
+    const int64_t rows = (int64_t)T * (H + 2 * Hkv);
+    const int rpb = 256 / (D / 8);
+    const unsigned blocks = (unsigned)((rows + rpb - 1) / rpb);
+    const SlotRows at = {rag.kbase[layer], rag.vbase[layer], rag.slot_stride, rag.slots, rag.row_slot};
+    if (D == 128)
+        qk_norm_rope_scatter_kernel<128, SlotRows><<<blocks, 256, 0, s>>>(m->pf_q, m->pf_k, m->pf_v, L.q_norm, L.k_norm, m->rope_cos, m->rope_sin,
+                                                                          m->pf_qt, at, T, H, Hkv, rag.cap, c.rms_norm_eps);
+    else
+        qk_norm_rope_scatter_kernel<64, SlotRows><<<blocks, 256, 0, s>>>(m->pf_q, m->pf_k, m->pf_v, L.q_norm, L.k_norm, m->rope_cos, m->rope_sin,
+                                                                         m->pf_qt, at, T, H, Hkv, rag.cap, c.rms_norm_eps);
     OMX_LAUNCH_CHECK();
     return 0;
 }

@@ -86,4 +86,21 @@ __device__ __forceinline__ uint32_t qfield(const uint32_t* w, int j) {
     return __builtin_amdgcn_alignbit(w[k + 1], w[k], o) & ((1u << B) - 1u);
 }
 
+// One row of QuantizedEmbedding::forward straight from the packed table, by one block: element j of row `id` as (float)q * scale + bias
+// with one rounding, the expression of dequantize_kernel / dequantize_chunk_kernel (quant.hip).  The text of qembed_rows_kernel
+// (engine_prefill.hip) and of the packed batch_embed_kernel (engine_batch.hip)
+template <int BITS>
+__device__ __forceinline__ void qembed_row(bf16_t* __restrict__ out, const uint32_t* __restrict__ table, const bf16_t* __restrict__ scales,
+                                           const bf16_t* __restrict__ biases, size_t id, int hidden, int group) {
+    const uint32_t* wrow = table + id * (size_t)(hidden / 32 * BITS);
+    const bf16_t* srow = scales + id * (size_t)(hidden / group);
+    const bf16_t* brow = biases ? biases + id * (size_t)(hidden / group) : nullptr;
+    for (int j = threadIdx.x; j < hidden; j += blockDim.x) {
+        const int p = j * BITS, k = p >> 5, o = p & 31;
+        const uint32_t q = (o + BITS <= 32 ? wrow[k] >> o : __builtin_amdgcn_alignbit(wrow[k + 1], wrow[k], o)) & ((1u << BITS) - 1u);
+        const float sc = bf16_to_f32(srow[j / group]), b = brow ? bf16_to_f32(brow[j / group]) : 0.f;
+        out[j] = f32_to_bf16((float)q * sc + b);
+    }
+}
+
 }  // namespace omx

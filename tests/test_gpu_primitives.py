@@ -329,6 +329,35 @@ def test_sdpa_decode_strided_kv_view_and_masks(omx):
     assert_bf16_close(got, ref, 1, atol=2e-3 * np.abs(ref).max())
 
 
+@pytest.mark.parametrize("mask_kind", ["none", "bool", "additive"])
+@pytest.mark.parametrize("Tk", [5, 63, 129, 300])   # waves of a split without a token / a clamped ragged tail / more than one split
+@pytest.mark.parametrize("D,H,Hkv", [
+    (128, 2, 2), (128, 4, 2), (128, 8, 2), (128, 8, 1),     # 1 / 2 / 4 / 8 query heads per KV head: every width the kernel is built at
+    (64, 2, 2), (64, 4, 2), (64, 8, 2), (64, 8, 1),
+    (64, 6, 2),                                              # 3 heads per KV head on the 4-wide build
+])
+def test_sdpa_decode_every_width_and_mask(omx, D, H, Hkv, Tk, mask_kind):
+    """The split-KV decode kernel at each of its eight (head_dim, heads per KV head) builds, plain and under a bool and an additive
+    [1, Tk] mask; batch 2, so the batch strides of q, K/V and the split workspace count."""
+    T = omx.ops.Tensor
+    B = 2
+    q = rc.bf16_round(rand((B, H, 1, D), 20) * 2)
+    k = rc.bf16_round(rand((B, Hkv, Tk, D), 21) * 2)
+    v = rc.bf16_round(rand((B, Hkv, Tk, D), 22))
+    scale = 1.0 / np.sqrt(D)
+    if mask_kind == "none":
+        mask, mask_t = None, None
+    elif mask_kind == "bool":   # token 0 stays, every third token after it goes: no row is fully masked (0 / 0 in kernel and oracle alike)
+        mask = (np.arange(Tk) % 3 != 1)[None, :]
+        mask_t = T.from_numpy(mask, "bool")
+    else:
+        mask = rc.bf16_round(rand((1, Tk), 26) * 3)
+        mask_t = T.from_numpy(mask, "bf16")
+    got = omx.ops.scaled_dot_product_attention(T.from_numpy(q), T.from_numpy(k), T.from_numpy(v), scale, mask_t).numpy()
+    ref = rc.scaled_dot_product_attention(q, k, v, scale, mask, "bf16")
+    assert_bf16_close(got, ref, 1, atol=2e-3 * np.abs(ref).max())
+
+
 def test_sdpa_softmax_spike_forces_rescale(omx):
     """One key far above the rest in a late tile: exercises the running-max rescale branch of the
     online softmax (cdna_hip_programming.md rule 26)."""
