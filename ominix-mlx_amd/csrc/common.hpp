@@ -107,6 +107,16 @@ __device__ __forceinline__ float wave_max(float v) {
     return fmaxf(fmaxf(readlane_f(v, 0), readlane_f(v, 16)), fmaxf(readlane_f(v, 32), readlane_f(v, 48)));
 }
 
+// greedy argmax as a plain u64 max, first index on ties (sampler.rs:9-12): key = (orderable(value) << 32) | ~index picks the larger
+// value, then the lower index.  The one text of the key of argmax_kernel (elementwise.hip) and of the EPI_ARGMAX partials of every GEMV
+// (gemv.hip, quant.hip, qgemv_mfma.hip), which sample_finalize_kernel compares across kernels
+__device__ __forceinline__ uint64_t argmax_key(float v, uint32_t idx) {
+    uint32_t u = __float_as_uint(v);
+    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    if (v != v) u = 0;   // NaN never wins
+    return ((uint64_t)u << 32) | (uint32_t)(~idx);
+}
+
 // block reductions over NW waves through a small LDS scratch (NW floats)
 template <int NW>
 __device__ __forceinline__ float block_sum(float v, float* scratch) {

@@ -106,15 +106,8 @@ __global__ __launch_bounds__(256) void take_rows_kernel(uint8_t* __restrict__ ou
 }
 
 // ---------------------------------------------------------------------------------
-// argmax over the last axis, first index on ties (sampler.rs:9-12)
-// key = (orderable(value) << 32) | ~index  -> a plain u64 max picks max value, min index
+// argmax over the last axis, first index on ties: a u64 max over argmax_key (common.hpp)
 // ---------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t argmax_key(float v, uint32_t idx) {
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    if (v != v) u = 0;   // NaN never wins
-    return ((uint64_t)u << 32) | (uint32_t)(~idx);
-}
 __device__ __forceinline__ uint64_t wave_max_u64(uint64_t k) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {

@@ -2,6 +2,7 @@
 #include "moe_route.hpp"
 #include "gemv.hpp"
 #include "act16.hpp"
+#include "gemv_parts.hpp"
 #include "peer.hpp"
 #include "launch_timing.hpp"
 
@@ -25,58 +26,63 @@ __device__ __forceinline__ const bf16_t* row_ptr(const GemvArgs& a, int row) {
     return a.w2 + (size_t)row * a.K;
 }
 
-// F16: float16 weights, widened to f32 (exact) for the same fma chain as bf16 -- not v_dot2_f32_f16, whose two products and the
-// accumulator meet in one unspecified rounding step: the chain keeps one rounding per product-add in a fixed order, the bound the
-// tests check, and the kernel is bound by HBM, not by these VALU ops
-template <bool F16 = false>
-__device__ __forceinline__ float dot8(const u32x4 w, const float (&xf)[8], float acc) {
-    typedef Act16<F16> A;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        acc = fmaf(A::lo(w[i]), xf[2 * i], acc);
-        acc = fmaf(A::hi(w[i]), xf[2 * i + 1], acc);
-    }
-    return acc;
-}
-
-__device__ __forceinline__ uint64_t argmax_key(float v, uint32_t idx) {
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    if (v != v) u = 0;
-    return ((uint64_t)u << 32) | (uint32_t)(~idx);
-}
-
-// F16: the same roundings in float16 (the packed float16 GEMV's epilogue, quant.hip)
+// the row's value (epi_bits, gemv_parts.hpp; F16: the same roundings in float16) and what only this family has: the bias under
+// EPI_STORE, the f32 / peer output
 template <int EPI, bool F16 = false>
 __device__ __forceinline__ void epilogue(const GemvArgs& a, int row, float v0, float v1, uint64_t& best) {
     typedef Act16<F16> A;
-    if (EPI == EPI_STORE) {
-        reinterpret_cast<bf16_t*>(a.out)[row] = A::bits(a.out_bias ? v0 + A::val(a.out_bias[row]) : v0);
-    } else if (EPI == EPI_F32) {
+    if constexpr (EPI == EPI_F32) {
         // (`best` carries the call's tag, read ONCE before the first weight load: a load here would wait behind -- drain -- the
         //  next batch's prefetch; the total is stored by peer_finish_rows)
         if (a.peer) peer_store_word(a.peer, (unsigned)best, row, __float_as_uint(v0));
         else reinterpret_cast<float*>(a.out)[row] = a.out_scale ? round_bf16(round_bf16(v0) * a.out_scale_f) : v0;
-    } else if (EPI == EPI_RESIDUAL) {
-        reinterpret_cast<bf16_t*>(a.out)[row] = A::bits(A::val(a.resid[row]) + A::rnd(v0));
-    } else if (EPI == EPI_SWIGLU) {
-        // nn::silu(gate) * up, every primitive's result held in bf16
-        // (qwen3-mlx/src/model.rs:264-265; mlx-rs/src/nn/activation.rs:876-880)
-        const float g = A::rnd(v0);
-        const float u = A::rnd(v1);
-        if (a.swiglu_single_round) {
-            // mlx_rs_core::fused_swiglu(up, gate) (metal_kernels.rs:11-18): one kernel, one rounding
-            reinterpret_cast<bf16_t*>(a.out)[row] = A::bits(g / (1.0f + expf(-g)) * u);
-        } else {
-            const float sg = A::rnd(1.0f / (1.0f + expf(-g)));
-            reinterpret_cast<bf16_t*>(a.out)[row] = A::bits(A::rnd(g * sg) * u);
-        }
-    } else if (EPI == EPI_ARGMAX) {
-        const bf16_t lb = A::bits(v0);
+    } else {
+        if (EPI == EPI_STORE) v0 = a.out_bias ? v0 + A::val(a.out_bias[row]) : v0;
+        const bf16_t lb = epi_bits<EPI, A>(v0, v1, EPI == EPI_RESIDUAL ? a.resid[row] : (bf16_t)0, a.swiglu_single_round);
         reinterpret_cast<bf16_t*>(a.out)[row] = lb;
-        const uint64_t key = argmax_key(A::val(lb), (uint32_t)(row + a.row_offset));
-        best = key > best ? key : best;
+        if (EPI == EPI_ARGMAX) {
+            const uint64_t key = argmax_key(A::val(lb), (uint32_t)(row + a.row_offset));
+            best = key > best ? key : best;
+        }
     }
+}
+
+// Which expert's matrices a block streams: expert e of w0 (and w1), or none of this rank's (false: block-uniform, the caller returns
+// before any barrier)
+__device__ __forceinline__ bool select_expert(const GemvArgs& a_in, GemvArgs& a, size_t e) {
+    if (!local_expert(e, a_in.w_sel_lo, a_in.w_sel_n)) return false;
+    a.w0 = a_in.w0 + e * a_in.w_estride;
+    if (a_in.w1) a.w1 = a_in.w1 + e * a_in.w_estride;
+    return true;
+}
+// batched / expert-selected form (MoE decode): blockIdx.y picks the activation row, the output row
+// block and, through a device index array, the expert whose weights are streamed
+__device__ __forceinline__ bool select_entry(const GemvArgs& a_in, GemvArgs& a) {
+    if (a_in.n_batch > 1 || a_in.w_sel) {
+        const int by = blockIdx.y;
+        a.x = a_in.x + (size_t)(by / a_in.x_div) * a_in.x_bstride;
+        a.out = reinterpret_cast<char*>(a_in.out) + (size_t)by * a_in.out_bstride_bytes;
+        if (a_in.w_sel) return select_expert(a_in, a, a_in.w_sel[by]);
+    }
+    return true;
+}
+
+// x := rnd16(x + rnd16(p)) on vector v of the row, p the slot-ordered f32 sum of the x_partial_n vectors at x_partial (the
+// tensor-parallel step's one all-reduced vector; MoE: the experts' weighted outputs); block 0 leaves the new row in x_out
+template <class A>
+__device__ __forceinline__ void fold_partial(u32x4& raw, const GemvArgs& a, int v) {
+    const f32x4 p0 = *(reinterpret_cast<const f32x4*>(a.x_partial) + 2 * v);
+    const f32x4 p1 = *(reinterpret_cast<const f32x4*>(a.x_partial) + 2 * v + 1);
+    float pp[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
+    for (int j = 1; j < a.x_partial_n; ++j) {
+        const f32x4* pj = reinterpret_cast<const f32x4*>(a.x_partial + (size_t)j * a.K) + 2 * v;
+        const f32x4 q0 = pj[0], q1 = pj[1];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { pp[e] += q0[e]; pp[4 + e] += q1[e]; }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) raw[q] = A::pack(A::lo(raw[q]) + A::rnd(pp[2 * q]), A::hi(raw[q]) + A::rnd(pp[2 * q + 1]));
+    if (a.x_out && blockIdx.x == 0) *(reinterpret_cast<u32x4*>(a.x_out) + v) = raw;
 }
 
 // EPI_F32 + peer, after a wave (or the block's reducing threads) issued the stores of rows [begin, end): lane / thread `idx` of
@@ -96,28 +102,13 @@ template <int NVW, int KSPLIT, int RB, int PRO, int EPI, bool TAIL = false, bool
 #define OMX_GEMV_MINWAVES 1   // (tuning builds: make VARIANT=w3 VARIANT_FLAGS=-DOMX_GEMV_MINWAVES=3 asks hipcc for <= 168 VGPRs)
 #endif
 __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const GemvArgs a_in) {
-    // batched / expert-selected form (MoE decode): blockIdx.y picks the activation row, the output row
-    // block and, through a device index array, the expert whose weights are streamed
     typedef Act16<F16> A;
     static_assert(!F16 || (PRO != PRO_ROUTE && EPI != EPI_F32), "float16: no routing prologue, no f32 output");
     GemvArgs a = a_in;
     if (EPI == EPI_F32) {
         if (a_in.out_scale) a.out_scale_f = bf16_to_f32(a_in.out_scale[blockIdx.y]);
     }
-    if (a_in.n_batch > 1 || a_in.w_sel) {
-        const int by = blockIdx.y;
-        a.x = a_in.x + (size_t)(by / a_in.x_div) * a_in.x_bstride;
-        a.out = reinterpret_cast<char*>(a_in.out) + (size_t)by * a_in.out_bstride_bytes;
-        if (a_in.w_sel) {
-            size_t e = a_in.w_sel[by];
-            if (a_in.w_sel_n > 0) {   // expert-parallel shard: block-uniform early exit for experts of other ranks
-                if (e < (size_t)a_in.w_sel_lo || e >= (size_t)(a_in.w_sel_lo + a_in.w_sel_n)) return;
-                e -= (size_t)a_in.w_sel_lo;
-            }
-            a.w0 = a_in.w0 + e * a_in.w_estride;
-            if (a_in.w1) a.w1 = a_in.w1 + e * a_in.w_estride;
-        }
-    }
+    if (!select_entry(a_in, a)) return;
     constexpr int LR = (EPI == EPI_SWIGLU) ? 2 : 1;
     constexpr int NV = NVW * KSPLIT;            // vectors per lane for the whole row
     constexpr int NR = RB * LR;
@@ -231,11 +222,7 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
             if (v < kvec) {
                 xv[i] = *(reinterpret_cast<const u32x4*>(xg) + v);
                 nwv[i] = *(reinterpret_cast<const u32x4*>(a.norm_w) + v);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    ss = fmaf(bf16lo(xv[i][q]), bf16lo(xv[i][q]), ss);
-                    ss = fmaf(bf16hi(xv[i][q]), bf16hi(xv[i][q]), ss);
-                }
+                ss = sumsq8<A>(xv[i], ss);
             }
             ss = wave_sum(ss);
             if (lane == 0) s_red8[wave + 4 * i] = ss;
@@ -249,13 +236,7 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
         for (int i = 0; i < PV; ++i) {
             const int v = threadIdx.x + i * kBlock;
             if (v < NV * 64) {
-                u32x4 o = {0u, 0u, 0u, 0u};
-                if (v < kvec) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        o[q] = pack_bf16(bf16lo(xv[i][q]) * rstd * bf16lo(nwv[i][q]), bf16hi(xv[i][q]) * rstd * bf16hi(nwv[i][q]));
-                }
-                xs[v] = o;
+                xs[v] = v < kvec ? norm8<A>(xv[i], nwv[i], rstd) : u32x4{0u, 0u, 0u, 0u};
             }
         }
         __syncthreads();
@@ -276,17 +257,11 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
         __syncthreads();
         if (wave == 0) route_from_logits(s_logit, 0, lane, a.route_E, a.route_k, a.route_mode, a.route_renorm, s_sel, s_score);
         __syncthreads();
-        size_t e = s_sel[blockIdx.y];
         if (blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x < a.route_k) {
             a.route_inds[threadIdx.x] = s_sel[threadIdx.x];
             a.route_scores[threadIdx.x] = s_score[threadIdx.x];
         }
-        if (a_in.w_sel_n > 0) {   // expert-parallel shard: block-uniform early exit for experts of other ranks
-            if (e < (size_t)a_in.w_sel_lo || e >= (size_t)(a_in.w_sel_lo + a_in.w_sel_n)) return;
-            e -= (size_t)a_in.w_sel_lo;
-        }
-        a.w0 = a_in.w0 + e * a_in.w_estride;
-        if (a_in.w1) a.w1 = a_in.w1 + e * a_in.w_estride;
+        if (!select_expert(a_in, a, s_sel[blockIdx.y])) return;   // (no barrier follows)
         if (active) OMX_ISSUE(wA, row_begin);
     } else
     // ---- prologue: stage x (bf16 / float16) in LDS; optionally x := bf16(x + bf16(partial)); RMS-normalise ----
@@ -301,31 +276,9 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
             if (v < NV * 64) {
                 u32x4 raw = (!TAIL || v < kvec) ? *(reinterpret_cast<const u32x4*>(xg) + v) : u32x4{0u, 0u, 0u, 0u};
                 if (PRO == PRO_RMSNORM) nwv[i] = *(reinterpret_cast<const u32x4*>(a.norm_w) + v);
-                if (a.x_partial) {
-                    const f32x4 p0 = *(reinterpret_cast<const f32x4*>(a.x_partial) + 2 * v);
-                    const f32x4 p1 = *(reinterpret_cast<const f32x4*>(a.x_partial) + 2 * v + 1);
-                    float pp[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
-                    for (int j = 1; j < a.x_partial_n; ++j) {   // MoE: the experts' weighted outputs, summed in slot order
-                        const f32x4* pj = reinterpret_cast<const f32x4*>(a.x_partial + (size_t)j * K) + 2 * v;
-                        const f32x4 q0 = pj[0], q1 = pj[1];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) { pp[e] += q0[e]; pp[4 + e] += q1[e]; }
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        raw[q] = A::pack(A::lo(raw[q]) + A::rnd(pp[2 * q]),
-                                         A::hi(raw[q]) + A::rnd(pp[2 * q + 1]));
-                    if (a.x_out && blockIdx.x == 0) *(reinterpret_cast<u32x4*>(a.x_out) + v) = raw;
-                }
+                if (a.x_partial) fold_partial<A>(raw, a, v);
                 xv[i] = raw;
-                if (PRO == PRO_RMSNORM) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const float lo = A::lo(raw[q]), hi = A::hi(raw[q]);
-                        ss = fmaf(lo, lo, ss);
-                        ss = fmaf(hi, hi, ss);
-                    }
-                }
+                if (PRO == PRO_RMSNORM) ss = sumsq8<A>(raw, ss);
             }
         }
         if (PRO == PRO_RMSNORM) {
@@ -334,15 +287,7 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
 #pragma unroll
             for (int i = 0; i < PV; ++i) {
                 const int v = threadIdx.x + i * kBlock;
-                if (v < NV * 64) {
-                    const u32x4 nw = nwv[i];
-                    u32x4 o;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        o[q] = A::pack(A::lo(xv[i][q]) * rstd * A::lo(nw[q]),
-                                       A::hi(xv[i][q]) * rstd * A::hi(nw[q]));
-                    xs[v] = o;
-                }
+                if (v < NV * 64) xs[v] = norm8<A>(xv[i], nwv[i], rstd);
             }
         } else {
 #pragma unroll
@@ -420,20 +365,7 @@ __global__ __launch_bounds__(kBlock) void gemv_generic_kernel(const GemvArgs a_i
     if (EPI == EPI_F32) {
         if (a_in.out_scale) a.out_scale_f = bf16_to_f32(a_in.out_scale[blockIdx.y]);
     }
-    if (a_in.n_batch > 1 || a_in.w_sel) {
-        const int by = blockIdx.y;
-        a.x = a_in.x + (size_t)(by / a_in.x_div) * a_in.x_bstride;
-        a.out = reinterpret_cast<char*>(a_in.out) + (size_t)by * a_in.out_bstride_bytes;
-        if (a_in.w_sel) {
-            size_t e = a_in.w_sel[by];
-            if (a_in.w_sel_n > 0) {
-                if (e < (size_t)a_in.w_sel_lo || e >= (size_t)(a_in.w_sel_lo + a_in.w_sel_n)) return;
-                e -= (size_t)a_in.w_sel_lo;
-            }
-            a.w0 = a_in.w0 + e * a_in.w_estride;
-            if (a_in.w1) a.w1 = a_in.w1 + e * a_in.w_estride;
-        }
-    }
+    if (!select_entry(a_in, a)) return;
     constexpr int LR = (EPI == EPI_SWIGLU) ? 2 : 1;
     constexpr int RB = (EPI == EPI_SWIGLU) ? 2 : 4;
     constexpr int NR = RB * LR;
@@ -447,43 +379,14 @@ __global__ __launch_bounds__(kBlock) void gemv_generic_kernel(const GemvArgs a_i
         float ss = 0.f;
         for (int v = threadIdx.x; v < kvec; v += kBlock) {
             u32x4 raw = *(reinterpret_cast<const u32x4*>(xg) + v);
-            if (a.x_partial) {
-                const f32x4 p0 = *(reinterpret_cast<const f32x4*>(a.x_partial) + 2 * v);
-                const f32x4 p1 = *(reinterpret_cast<const f32x4*>(a.x_partial) + 2 * v + 1);
-                float pp[8] = {p0[0], p0[1], p0[2], p0[3], p1[0], p1[1], p1[2], p1[3]};
-                for (int j = 1; j < a.x_partial_n; ++j) {
-                    const f32x4* pj = reinterpret_cast<const f32x4*>(a.x_partial + (size_t)j * K) + 2 * v;
-                    const f32x4 q0 = pj[0], q1 = pj[1];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) { pp[e] += q0[e]; pp[4 + e] += q1[e]; }
-                }
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    raw[q] = A::pack(A::lo(raw[q]) + A::rnd(pp[2 * q]), A::hi(raw[q]) + A::rnd(pp[2 * q + 1]));
-                if (a.x_out && blockIdx.x == 0) *(reinterpret_cast<u32x4*>(a.x_out) + v) = raw;
-            }
+            if (a.x_partial) fold_partial<A>(raw, a, v);
             xs[v] = raw;
-            if (PRO == PRO_RMSNORM) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float lo = A::lo(raw[q]), hi = A::hi(raw[q]);
-                    ss = fmaf(lo, lo, ss);
-                    ss = fmaf(hi, hi, ss);
-                }
-            }
+            if (PRO == PRO_RMSNORM) ss = sumsq8<A>(raw, ss);
         }
         if (PRO == PRO_RMSNORM) {
             ss = block_sum<kWaves>(ss, red);
             const float rstd = 1.0f / sqrtf(ss / (float)K + a.eps);
-            for (int v = threadIdx.x; v < kvec; v += kBlock) {
-                const u32x4 raw = xs[v];
-                const u32x4 nw = *(reinterpret_cast<const u32x4*>(a.norm_w) + v);
-                u32x4 o;
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    o[q] = A::pack(A::lo(raw[q]) * rstd * A::lo(nw[q]), A::hi(raw[q]) * rstd * A::hi(nw[q]));
-                xs[v] = o;
-            }
+            for (int v = threadIdx.x; v < kvec; v += kBlock) xs[v] = norm8<A>(xs[v], *(reinterpret_cast<const u32x4*>(a.norm_w) + v), rstd);
         }
         __syncthreads();
     }

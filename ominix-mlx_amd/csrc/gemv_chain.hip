@@ -18,6 +18,7 @@
 // bounded and a wait that gives up raises abort_flag (the engine then replays the steps with two launches) instead of hanging the GPU.
 #include "gemv.hpp"
 #include "act16.hpp"
+#include "gemv_parts.hpp"
 #include "granule.hpp"
 #include "launch_timing.hpp"
 
@@ -41,16 +42,6 @@ __device__ __forceinline__ const bf16_t* qkv_row_ptr(const GemvChainArgs& a, int
     if (row < a.n1) return a.w1 + (size_t)row * K;
     row -= a.n1;
     return a.w2 + (size_t)row * K;
-}
-
-// gemv.hip dot8: lo then hi of each dword, one fma chain
-__device__ __forceinline__ float dot8(const u32x4 w, const float (&xf)[8], float acc) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        acc = fmaf(bf16lo(w[i]), xf[2 * i], acc);
-        acc = fmaf(bf16hi(w[i]), xf[2 * i + 1], acc);
-    }
-    return acc;
 }
 
 // NVA = 16-byte vectors per lane per row per wave of phase A (K = NVA * 4 * 512); NVB = vectors per lane per row of phase B
@@ -134,8 +125,8 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
 #pragma unroll
             for (int w = 0; w < kSplit; ++w) v[e] += part[(2 * threadIdx.x + e) * kSplit + w];
         }
-        const uint32_t o2 = (uint32_t)A::bits(A::val((bf16_t)(res2 & 0xFFFFu)) + A::rnd(v[0])) |
-                            ((uint32_t)A::bits(A::val((bf16_t)(res2 >> 16)) + A::rnd(v[1])) << 16);
+        const uint32_t o2 = (uint32_t)epi_bits<EPI_RESIDUAL, A>(v[0], 0.f, (bf16_t)(res2 & 0xFFFFu), 0) |
+                            ((uint32_t)epi_bits<EPI_RESIDUAL, A>(v[1], 0.f, (bf16_t)(res2 >> 16), 0) << 16);
         reinterpret_cast<uint32_t*>(a.out)[row_begin / 2 + threadIdx.x] = o2;
         st_granule_u32(a.xg + row_begin / 2 + threadIdx.x, tag, o2);
     }
@@ -203,12 +194,7 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
 #pragma unroll
         for (int i = 0; i < PVB; ++i) {
             xv[i] = xs[threadIdx.x + i * kBlock];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float lo = A::lo(xv[i][q]), hi = A::hi(xv[i][q]);
-                ss = fmaf(lo, lo, ss);
-                ss = fmaf(hi, hi, ss);
-            }
+            ss = sumsq8<A>(xv[i], ss);
         }
         // block_sum<4> (common.hpp) with LDS-only barriers: wave sums, then the four of them added in wave order from 0.f
         ss = wave_sum(ss);
@@ -220,15 +206,7 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
         for (int i = 0; i < kWaves; ++i) ss += red[i];
         const float rstd = 1.0f / sqrtf(ss / (float)N + a.eps);
 #pragma unroll
-        for (int i = 0; i < PVB; ++i) {
-            const u32x4 nw = nwv[i];
-            u32x4 o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                o[q] = A::pack(A::lo(xv[i][q]) * rstd * A::lo(nw[q]),
-                               A::hi(xv[i][q]) * rstd * A::hi(nw[q]));
-            xs[threadIdx.x + i * kBlock] = o;
-        }
+        for (int i = 0; i < PVB; ++i) xs[threadIdx.x + i * kBlock] = norm8<A>(xv[i], nwv[i], rstd);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
     }
     float acc[RQ];

@@ -1,0 +1,81 @@
+// The arithmetic that the decode GEMV kernels share, each piece written ONCE: gemv.hip (bf16 / float16 weights), quant.hip (packed
+// weights, VALU), qgemv_mfma.hip (packed 4-bit, matrix cores), qgemv_rows.hip (packed, a handful of rows) and gemv_chain.hip (down +
+// q/k/v in one launch) must agree bit for bit -- the VALU-against-rows comparison is exact and token equality across the routes rests on
+// it -- so they call these instead of carrying a copy.  Everything here is inlined straight-line code on values: no pointer, no branch
+// enters a kernel's streaming loop through it.  A = Act16<F16> (act16.hpp): bfloat16, or float16 with the same rounding points.
+// (The packed kernels' unpack and activation staging are beside qfield in quant.hpp; argmax_key is in common.hpp.)
+#pragma once
+#include "act16.hpp"
+#include "gemv.hpp"
+
+namespace omx {
+
+// one 16-byte weight vector against its eight activations: lo then hi of each dword, one fma chain.
+// F16: float16 weights, widened to f32 (exact) for the same fma chain as bf16 -- not v_dot2_f32_f16, whose two products and the
+// accumulator meet in one unspecified rounding step: the chain keeps one rounding per product-add in a fixed order, the bound the
+// tests check, and the kernel is bound by HBM, not by these VALU ops
+template <bool F16 = false>
+__device__ __forceinline__ float dot8(const u32x4 w, const float (&xf)[8], float acc) {
+    typedef Act16<F16> A;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        acc = fmaf(A::lo(w[i]), xf[2 * i], acc);
+        acc = fmaf(A::hi(w[i]), xf[2 * i + 1], acc);
+    }
+    return acc;
+}
+
+// ---- RMSNorm prologue on one packed 16-byte vector (eight elements) ----
+// the squares of the eight elements join ss in one fma chain: lo then hi of dword q = 0..3
+template <class A>
+__device__ __forceinline__ float sumsq8(const u32x4 raw, float ss) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float lo = A::lo(raw[q]), hi = A::hi(raw[q]);
+        ss = fmaf(lo, lo, ss);
+        ss = fmaf(hi, hi, ss);
+    }
+    return ss;
+}
+// x * rstd * w, two products and one rounding per element
+template <class A>
+__device__ __forceinline__ u32x4 norm8(const u32x4 raw, const u32x4 nw, float rstd) {
+    u32x4 o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = A::pack(A::lo(raw[q]) * rstd * A::lo(nw[q]), A::hi(raw[q]) * rstd * A::hi(nw[q]));
+    return o;
+}
+
+// ---- the 16 bits a row leaves behind: v0 the row's f32 sum (v1: the `up` row's of a SwiGLU pair) ----
+// EPI_STORE / EPI_ARGMAX: the rounded sum (the caller stores it and, for EPI_ARGMAX, builds its argmax_key from A::val of it);
+// EPI_RESIDUAL: resid + the rounded sum, rounded again (resid_bits is read by the caller, under EPI_RESIDUAL only); EPI_SWIGLU below
+template <int EPI, class A>
+__device__ __forceinline__ uint16_t epi_bits(float v0, float v1, uint16_t resid_bits, int single_round) {
+    static_assert(EPI == EPI_STORE || EPI == EPI_RESIDUAL || EPI == EPI_SWIGLU || EPI == EPI_ARGMAX, "the 16-bit epilogues");
+    if (EPI == EPI_RESIDUAL) return A::bits(A::val(resid_bits) + A::rnd(v0));
+    if (EPI == EPI_SWIGLU) {
+        // nn::silu(gate) * up, every primitive's result held in 16 bits
+        // (qwen3-mlx/src/model.rs:264-265; mlx-rs/src/nn/activation.rs:876-880)
+        const float g = A::rnd(v0);
+        const float u = A::rnd(v1);
+        const float den = 1.0f + expf(-g);
+        // mlx_rs_core::fused_swiglu(up, gate) (metal_kernels.rs:11-18): one kernel, one rounding
+        if (single_round) return A::bits(g / den * u);
+        const float sg = A::rnd(1.0f / den);
+        return A::bits(A::rnd(g * sg) * u);
+    }
+    return A::bits(v0);
+}
+
+// ---- expert parallelism: only experts [lo, lo + n) live on this rank (n == 0: all of them) ----
+// false: expert e belongs to another rank and the block has no work (block-uniform: the caller returns BEFORE any barrier);
+// otherwise e becomes the index into this rank's stack
+__device__ __forceinline__ bool local_expert(size_t& e, int lo, int n) {
+    if (n > 0) {
+        if (e < (size_t)lo || e >= (size_t)(lo + n)) return false;
+        e -= (size_t)lo;
+    }
+    return true;
+}
+
+}  // namespace omx

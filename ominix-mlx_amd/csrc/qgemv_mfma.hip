@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "act16.hpp"
+#include "gemv_parts.hpp"
 #include "launch_timing.hpp"
 #include "quant.hpp"
 
@@ -26,13 +27,6 @@ namespace omx {
 namespace {
 
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-
-__device__ __forceinline__ uint64_t qm_argmax_key(float v, uint32_t idx) {   // the key of quant.hip / gemv.hip: larger value, then lower index
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    if (v != v) u = 0;
-    return ((uint64_t)u << 32) | (uint32_t)(~idx);
-}
 
 struct QmUnit {            // 16 rows x one superchunk: 8 KB of packed words + 1 KB of scale / bias pairs per wave
     u32x4 wd[8];
@@ -131,36 +125,15 @@ __global__ __launch_bounds__(KS * 64, (NU * NBUF <= 2 ? OMX_QM_MINW : 2)) void q
             for (int it = 0; it < 2; ++it) nwv[it] = *reinterpret_cast<const u32x4*>(a.norm_w + threadIdx.x * 8 + it * NT * 8);
             float ss = 0.f;
 #pragma unroll
-            for (int it = 0; it < 2; ++it)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    ss = fmaf(A16::lo(raw[it][c]), A16::lo(raw[it][c]), ss);
-                    ss = fmaf(A16::hi(raw[it][c]), A16::hi(raw[it][c]), ss);
-                }
+            for (int it = 0; it < 2; ++it) ss = sumsq8<A16>(raw[it], ss);
             ss = block_sum<KS>(ss, scr);
             const float rstd = 1.0f / sqrtf(ss / (float)K + a.eps);
 #pragma unroll
-            for (int it = 0; it < 2; ++it)
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-                    raw[it][c] = A16::pack(A16::lo(raw[it][c]) * rstd * A16::lo(nwv[it][c]), A16::hi(raw[it][c]) * rstd * A16::hi(nwv[it][c]));
+            for (int it = 0; it < 2; ++it) raw[it] = norm8<A16>(raw[it], nwv[it], rstd);
         }
+        // (a chunk = a quantisation group of 64: eight consecutive threads)
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int i = threadIdx.x * 8 + it * NT * 8;
-            const u32x4 o = raw[it];
-            u32x4 t;
-            t[0] = __builtin_amdgcn_perm(o[1], o[0], 0x05040100u); t[1] = __builtin_amdgcn_perm(o[3], o[2], 0x05040100u);
-            t[2] = __builtin_amdgcn_perm(o[1], o[0], 0x07060302u); t[3] = __builtin_amdgcn_perm(o[3], o[2], 0x07060302u);
-            *reinterpret_cast<u32x4*>(xs + i) = t;
-            float sv = 0.f;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) sv += A16::lo(o[c]) + A16::hi(o[c]);
-            sv += dpp_f<kDppXor1>(sv);
-            sv += dpp_f<kDppXor2>(sv);
-            sv += dpp_f<kDppHalfMirror>(sv);
-            if ((threadIdx.x & 7) == 0) xsum[i >> 6] = sv;
-        }
+        for (int it = 0; it < 2; ++it) stage_chunk<A16, 64, true>(xs, xsum, threadIdx.x * 8 + it * NT * 8, raw[it]);
     }
     __syncthreads();
 
@@ -182,17 +155,13 @@ __global__ __launch_bounds__(KS * 64, (NU * NBUF <= 2 ? OMX_QM_MINW : 2)) void q
         f32x4 D[8];
 #pragma unroll
         for (int t = 0; t < 8; ++t) D[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        const uint32_t c43 = A16::kMagicBytes;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
 #pragma unroll
             for (int t = 0; t < 8; ++t) {
-                const uint32_t wdw = U.wd[t][j];
-                const uint32_t lo = wdw & 0x0F0F0F0Fu, hi = (wdw >> 4) & 0x0F0F0F0Fu;
-                u32x4 f;
-                f[0] = __builtin_amdgcn_perm(c43, lo, 0x04010400u); f[1] = __builtin_amdgcn_perm(c43, lo, 0x04030402u);
-                f[2] = __builtin_amdgcn_perm(c43, hi, 0x04010400u); f[3] = __builtin_amdgcn_perm(c43, hi, 0x04030402u);
-                D[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[j], __builtin_bit_cast(bf16x8, f), D[t], 0, 0, 0);
+                uint32_t f[4];
+                nibble_pairs<A16>(U.wd[t][j], f);
+                D[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xa[j], __builtin_bit_cast(bf16x8, (u32x4{f[0], f[1], f[2], f[3]})), D[t], 0, 0, 0);
             }
         }
         // lane (n, q): groups 4 q + i of row n sit in D[2 q + (i >> 1)][i]
@@ -234,25 +203,15 @@ __global__ __launch_bounds__(KS * 64, (NU * NBUF <= 2 ? OMX_QM_MINW : 2)) void q
             }
             const int row = (SWIGLU ? tk : tk * NU + u) * 16 + nn;
             if (row < a.N) {
-                if (EPI == EPI_STORE) {
-                    a.out[row] = A16::bits(v0);
-                } else if (EPI == EPI_F32) {
+                if constexpr (EPI == EPI_F32) {
                     a.out_f32[row] = v0;
-                } else if (EPI == EPI_RESIDUAL) {
-                    a.out[row] = A16::bits(A16::val(a.resid[row]) + A16::rnd(v0));
-                } else if (EPI == EPI_SWIGLU) {
-                    const float g = A16::rnd(v0), uu = A16::rnd(v1);
-                    if (a.swiglu_single_round) {
-                        a.out[row] = A16::bits(g / (1.0f + expf(-g)) * uu);
-                    } else {
-                        const float sg = A16::rnd(1.0f / (1.0f + expf(-g)));
-                        a.out[row] = A16::bits(A16::rnd(g * sg) * uu);
-                    }
-                } else if (EPI == EPI_ARGMAX) {
-                    const bf16_t lb = A16::bits(v0);
+                } else {
+                    const bf16_t lb = epi_bits<EPI, A16>(v0, v1, EPI == EPI_RESIDUAL ? a.resid[row] : (bf16_t)0, a.swiglu_single_round);
                     a.out[row] = lb;
-                    const uint64_t key = qm_argmax_key(A16::val(lb), (uint32_t)(row + a.row_offset));
-                    best = key > best ? key : best;
+                    if (EPI == EPI_ARGMAX) {   // larger value, then lower index
+                        const uint64_t key = argmax_key(A16::val(lb), (uint32_t)(row + a.row_offset));
+                        best = key > best ? key : best;
+                    }
                 }
             }
         }

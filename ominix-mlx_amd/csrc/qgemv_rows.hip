@@ -14,6 +14,7 @@
 //   the unpacked operands against every staged row: VALU per 16 bytes of weights = unpack + M x the single-row dot products.
 #include "quant.hpp"
 #include "act16.hpp"
+#include "gemv_parts.hpp"
 #include "launch_timing.hpp"
 
 namespace omx {
@@ -146,22 +147,7 @@ __global__ __launch_bounds__(256) void qgemv_rows_kernel(const QRowsArgs ra) {
             const bf16_t* xg = a.x + (size_t)t * K + k0;
             bf16_t* xst = xs + (size_t)t * KC;
             float* xsm = xsum + t * (KC / EPL);
-            auto put = [&](int i, const u32x4 o) {                       // quant.hip qgemv_kernel's put(), on row t's chunk
-                if (BITS == 4) {
-                    u32x4 q;
-                    q[0] = __builtin_amdgcn_perm(o[1], o[0], 0x05040100u); q[1] = __builtin_amdgcn_perm(o[3], o[2], 0x05040100u);
-                    q[2] = __builtin_amdgcn_perm(o[1], o[0], 0x07060302u); q[3] = __builtin_amdgcn_perm(o[3], o[2], 0x07060302u);
-                    *reinterpret_cast<u32x4*>(xst + i) = q;
-                } else {
-                    *reinterpret_cast<u32x4*>(xst + i) = o;
-                }
-                float sv = 0.f;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) sv += A16::lo(o[q]) + A16::hi(o[q]);
-                if (EPL >= 16) sv += dpp_f<kDppXor1>(sv);
-                if (EPL >= 32) sv += dpp_f<kDppXor2>(sv);
-                if (((i >> 3) & (EPL / 8 - 1)) == 0) xsm[i / EPL] = sv;
-            };
+            auto put = [&](int i, const u32x4 o) { stage_chunk<A16, EPL, BITS == 4>(xst, xsm, i, o); };   // on row t's chunk
             constexpr int NV = KCM / 2048;                               // 16-byte vectors per thread and chunk (all in flight at once)
             u32x4 v[NV], nwv[NV];
 #pragma unroll
@@ -176,15 +162,7 @@ __global__ __launch_bounds__(256) void qgemv_rows_kernel(const QRowsArgs ra) {
             for (int it = 0; it < NV; ++it) {
                 const int i = threadIdx.x * 8 + it * 2048;
                 if (i < kc) {
-                    if (PRO == PRO_RMSNORM) {
-                        u32x4 o;
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            o[q] = A16::pack(A16::lo(v[it][q]) * rstd[t] * A16::lo(nwv[it][q]), A16::hi(v[it][q]) * rstd[t] * A16::hi(nwv[it][q]));
-                        put(i, o);
-                    } else {
-                        put(i, v[it]);
-                    }
+                    put(i, PRO == PRO_RMSNORM ? norm8<A16>(v[it], nwv[it], rstd[t]) : v[it]);
                 }
             }
         }
@@ -200,14 +178,7 @@ __global__ __launch_bounds__(256) void qgemv_rows_kernel(const QRowsArgs ra) {
             if (t >= M) break;
             const bf16_t* xg = a.x + (size_t)t * K;
             float ss = 0.f;
-            for (int i = threadIdx.x * 8; i < K; i += 256 * 8) {
-                const u32x4 raw = *reinterpret_cast<const u32x4*>(xg + i);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    ss = fmaf(A16::lo(raw[q]), A16::lo(raw[q]), ss);
-                    ss = fmaf(A16::hi(raw[q]), A16::hi(raw[q]), ss);
-                }
-            }
+            for (int i = threadIdx.x * 8; i < K; i += 256 * 8) ss = sumsq8<A16>(*reinterpret_cast<const u32x4*>(xg + i), ss);
             ss = block_sum<4>(ss, red);
             rstd[t] = 1.0f / sqrtf(ss / (float)K + a.eps);
         }
@@ -235,21 +206,10 @@ __global__ __launch_bounds__(256) void qgemv_rows_kernel(const QRowsArgs ra) {
                 bia[r] = SB ? bf16hi(u.sbv[r]) : bf16_to_f32(u.bi[r]);
                 if constexpr (CH) {
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const uint32_t q0 = qfield<BITS>(u.wd[r], 2 * i), q1 = qfield<BITS>(u.wd[r], 2 * i + 1);
-                        op[r][i] = ((q1 << 16) | q0) | (A16::kMagicBytes & 0xFF00FF00u);
-                    }
+                    for (int i = 0; i < 16; ++i) op[r][i] = field_pair<BITS, A16>(u.wd[r], i);
                 } else if constexpr (BITS == 4) {
 #pragma unroll
-                    for (int wi = 0; wi < W; ++wi) {
-                        const uint32_t wdw = u.wd[r][wi];
-                        const uint32_t lo = wdw & 0x0F0F0F0Fu, hi = (wdw >> 4) & 0x0F0F0F0Fu;
-                        const uint32_t c43 = A16::kMagicBytes;
-                        op[r][wi * 4 + 0] = __builtin_amdgcn_perm(c43, lo, 0x04010400u);
-                        op[r][wi * 4 + 1] = __builtin_amdgcn_perm(c43, lo, 0x04030402u);
-                        op[r][wi * 4 + 2] = __builtin_amdgcn_perm(c43, hi, 0x04010400u);
-                        op[r][wi * 4 + 3] = __builtin_amdgcn_perm(c43, hi, 0x04030402u);
-                    }
+                    for (int wi = 0; wi < W; ++wi) nibble_pairs<A16>(u.wd[r][wi], &op[r][wi * 4]);
                 } else {
 #pragma unroll
                     for (int wi = 0; wi < W; ++wi)
@@ -309,20 +269,7 @@ __global__ __launch_bounds__(256) void qgemv_rows_kernel(const QRowsArgs ra) {
                     for (int t = 0; t < MT; ++t) {
                         if (t >= M) break;
                         const float v0 = acc[LR * rr][t], v1 = acc[LR * rr + (LR - 1)][t];
-                        bf16_t* o = ob + (size_t)t * ld + col;
-                        if (EPI == EPI_STORE) {
-                            *o = A16::bits(v0);
-                        } else if (EPI == EPI_RESIDUAL) {
-                            *o = A16::bits(A16::val(a.resid[(size_t)t * N + row]) + A16::rnd(v0));
-                        } else if (EPI == EPI_SWIGLU) {
-                            const float g = A16::rnd(v0), uu = A16::rnd(v1);
-                            if (a.swiglu_single_round) {
-                                *o = A16::bits(g / (1.0f + expf(-g)) * uu);
-                            } else {
-                                const float sg = A16::rnd(1.0f / (1.0f + expf(-g)));
-                                *o = A16::bits(A16::rnd(g * sg) * uu);
-                            }
-                        }
+                        ob[(size_t)t * ld + col] = epi_bits<EPI, A16>(v0, v1, EPI == EPI_RESIDUAL ? a.resid[(size_t)t * N + row] : (bf16_t)0, a.swiglu_single_round);
                     }
                 }
             }

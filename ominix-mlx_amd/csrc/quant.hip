@@ -23,6 +23,7 @@
 
 #include "quant.hpp"
 #include "act16.hpp"
+#include "gemv_parts.hpp"
 #include "launch_timing.hpp"
 #include "vec.hpp"
 #include "workspace.hpp"
@@ -191,19 +192,12 @@ __global__ __launch_bounds__(256) void dequantize_any_chunk_kernel(typename Elem
     }
 }
 
-__device__ __forceinline__ uint64_t qargmax_key(float v, uint32_t idx) {
-    uint32_t u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    if (v != v) u = 0;
-    return ((uint64_t)u << 32) | (uint32_t)(~idx);
-}
-
 // W = u32 words per lane per step; a lane's W*EPW elements lie inside one group.
 // 2 / 3 / 5 / 6 bits (quant_chunked): W == BITS, a lane's chunk is 32 elements (one run of BITS words, streamed with dwordx2 / x3 / x4 + x1 /
 // x4 + x2 non-temporal loads), the activations stay in natural order, and a K that is not a multiple of 64 x 32 masks the tail lanes of the
-// last step.  Element pairs (q0, q1) become the bf16 pair (128 + q0, 128 + q1) by bit assembly -- each field one v_bfe_u32 (v_alignbit for
-// a straddling one) and the pair one v_lshl_or_b32 + one v_or_b32 of the 0x4300 magic -- into the same v_dot2 as the 4-bit branch.
-// PRO / EPI as in gemv.hip (same arithmetic and rounding points): RMSNorm prologue; store, residual add, SwiGLU
+// last step.  Element pairs (q0, q1) become the bf16 pair (128 + q0, 128 + q1) by bit assembly (field_pair, quant.hpp) for the same
+// v_dot2 as the 4-bit branch (nibble_pairs).
+// PRO / EPI as in gemv.hip, from the same text (gemv_parts.hpp): RMSNorm prologue; store, residual add, SwiGLU
 // over (gate, up) row pairs, logits + greedy-argmax partial.
 // SB: scales and biases come interleaved from QMat::sb (one load per row and step instead of two)
 template <int BITS, int W, int PRO, int EPI, int RB, bool SB = false, bool F16S = false>
@@ -222,10 +216,7 @@ __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
     const int by = blockIdx.y;
     const bf16_t* xg = a.x + (size_t)(by / a.x_div) * a.K;
     size_t e = a.w_sel ? a.w_sel[by] : 0;
-    if (a.w_sel_n > 0) {      // expert parallel: a slot routed to another rank's expert (block-uniform: before any barrier)
-        if (e < (size_t)a.w_sel_lo || e >= (size_t)(a.w_sel_lo + a.w_sel_n)) return;
-        e -= (size_t)a.w_sel_lo;
-    }
+    if (!local_expert(e, a.w_sel_lo, a.w_sel_n)) return;      // a slot routed to another rank's expert (block-uniform: before any barrier)
     bf16_t* out = a.out + (size_t)by * a.N;
 
     const int steps = CH ? (a.K + 64 * EPL - 1) / (64 * EPL) : a.K / (64 * EPL);
@@ -343,29 +334,16 @@ __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
                 float bia = SB ? (F16S ? scale_to_f32<true>((uint16_t)(u.sbv[r] >> 16)) : bf16hi(u.sbv[r])) : scale_to_f32<F16S>(u.bi[r]);
                 if constexpr (CH) {
 #pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const uint32_t q0 = qfield<BITS>(u.wd[r], 2 * i), q1 = qfield<BITS>(u.wd[r], 2 * i + 1);
-                        const uint32_t pr = ((q1 << 16) | q0) | (A16::kMagicBytes & 0xFF00FF00u);
-                        d = A16::dot2(xp[i], A16::unmagic(pr), d);
-                    }
+                    for (int i = 0; i < 16; ++i) d = A16::dot2(xp[i], A16::unmagic(field_pair<BITS, A16>(u.wd[r], i)), d);
                 }
 #pragma unroll
                 for (int wi = 0; wi < (CH ? 0 : W); ++wi) {
                     const uint32_t wdw = u.wd[r][wi];
                     if (BITS == 4) {
-                        // nibbles -> bf16 pairs by bit assembly: 0x4300 | q is the bf16 value 128 + q, so each v_dot2c
-                        // accumulates x . (128 + q); the 128 * sum(x) excess is folded into the bias term below
-                        // One v_perm per pair: the 0x43 exponent byte comes from the second source, the two nibble bytes from
-                        // the same masked word -- so a pair is (q0, q2), (q4, q6) of the even nibbles or (q1, q3), (q5, q7) of the
-                        // odd ones, and the activations were stored in LDS in that order (put() below).
-                        const uint32_t lo = wdw & 0x0F0F0F0Fu, hi = (wdw >> 4) & 0x0F0F0F0Fu;
-                        const uint32_t c43 = A16::kMagicBytes;   // bf16: 0x4300 | q = 128 + q; float16: 0x6400 | q = 1024 + q
-                        const uint32_t q0 = __builtin_amdgcn_perm(c43, lo, 0x04010400u), q1 = __builtin_amdgcn_perm(c43, lo, 0x04030402u);
-                        const uint32_t q2 = __builtin_amdgcn_perm(c43, hi, 0x04010400u), q3 = __builtin_amdgcn_perm(c43, hi, 0x04030402u);
-                        d = A16::dot2(xp[wi * 4 + 0], A16::unmagic(q0), d);
-                        d = A16::dot2(xp[wi * 4 + 1], A16::unmagic(q1), d);
-                        d = A16::dot2(xp[wi * 4 + 2], A16::unmagic(q2), d);
-                        d = A16::dot2(xp[wi * 4 + 3], A16::unmagic(q3), d);
+                        uint32_t qp[4];   // (the activations were stored in LDS in the order of these pairs: put() below)
+                        nibble_pairs<A16>(wdw, qp);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) d = A16::dot2(xp[wi * 4 + k], A16::unmagic(qp[k]), d);
                     } else {
 #pragma unroll
                         for (int b = 0; b < 4; ++b) {
@@ -388,26 +366,15 @@ __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
                     const int row = r0 + r;
                     if (row >= row_end) break;
                     const float v0 = acc[LR * r], v1 = acc[LR * r + (LR - 1)];
-                    if (EPI == EPI_STORE) {
-                        out[row] = A16::bits(v0);
-                    } else if (EPI == EPI_F32) {
+                    if constexpr (EPI == EPI_F32) {
                         a.out_f32[(size_t)by * a.N + row] = v0;
-                    } else if (EPI == EPI_RESIDUAL) {
-                        out[row] = A16::bits(A16::val(a.resid[row]) + A16::rnd(v0));
-                    } else if (EPI == EPI_SWIGLU) {
-                        // nn::silu(gate) * up, every primitive's result held in bf16 (qwen3-mlx/src/model.rs:264-265)
-                        const float g = A16::rnd(v0), uu = A16::rnd(v1);
-                        if (a.swiglu_single_round) {
-                            out[row] = A16::bits(g / (1.0f + expf(-g)) * uu);   // mlx_rs_core::fused_swiglu(up, gate)
-                        } else {
-                            const float sg = A16::rnd(1.0f / (1.0f + expf(-g)));
-                            out[row] = A16::bits(A16::rnd(g * sg) * uu);
-                        }
-                    } else if (EPI == EPI_ARGMAX) {
-                        const bf16_t lb = A16::bits(v0);
+                    } else {
+                        const bf16_t lb = epi_bits<EPI, A16>(v0, v1, EPI == EPI_RESIDUAL ? a.resid[row] : (bf16_t)0, a.swiglu_single_round);
                         out[row] = lb;
-                        const uint64_t key = qargmax_key(A16::val(lb), (uint32_t)(row + a.row_offset));
-                        best = key > best ? key : best;
+                        if (EPI == EPI_ARGMAX) {
+                            const uint64_t key = argmax_key(A16::val(lb), (uint32_t)(row + a.row_offset));
+                            best = key > best ? key : best;
+                        }
                     }
                 }
             }
@@ -423,23 +390,7 @@ __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
     // ---- prologue: x -> LDS as bf16 (RMS-normalised on the way in) and, in the same pass, the per-chunk sums
     //      sum(x_i) that every row's bias term shares (EPL elements = EPL/8 consecutive threads, reduced by DPP) ----
     static_assert(EPL >= 8, "a lane chunk must cover at least one 16-byte activation vector");
-    auto put = [&](int i, const u32x4 o) {
-        if (BITS == 4) {
-            // 8 consecutive activations are kept as (x0,x2) (x4,x6) (x1,x3) (x5,x7): the pairing of the one-perm nibble unpack
-            u32x4 t;
-            t[0] = __builtin_amdgcn_perm(o[1], o[0], 0x05040100u); t[1] = __builtin_amdgcn_perm(o[3], o[2], 0x05040100u);
-            t[2] = __builtin_amdgcn_perm(o[1], o[0], 0x07060302u); t[3] = __builtin_amdgcn_perm(o[3], o[2], 0x07060302u);
-            *reinterpret_cast<u32x4*>(xs + i) = t;
-        } else {
-            *reinterpret_cast<u32x4*>(xs + i) = o;
-        }
-        float sv = 0.f;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) sv += A16::lo(o[q]) + A16::hi(o[q]);
-        if (EPL >= 16) sv += dpp_f<kDppXor1>(sv);
-        if (EPL >= 32) sv += dpp_f<kDppXor2>(sv);
-        if (((i >> 3) & (EPL / 8 - 1)) == 0) xsum[i / EPL] = sv;
-    };
+    auto put = [&](int i, const u32x4 o) { stage_chunk<A16, EPL, BITS == 4>(xs, xsum, i, o); };
     if (PRO == PRO_RMSNORM && a.K <= 4096) {
         // the hidden-sized prologues (q/k/v, gate/up, lm_head: K <= 4096 = two vectors per thread): the row and the norm weights stay in
         // registers between the two passes -- one global round trip instead of two in a launch that is a chain of them.  Same sums.
@@ -455,47 +406,23 @@ __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
         }
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
-            if (threadIdx.x * 8 + it * 2048 < a.K) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    ss = fmaf(A16::lo(raw[it][q]), A16::lo(raw[it][q]), ss);
-                    ss = fmaf(A16::hi(raw[it][q]), A16::hi(raw[it][q]), ss);
-                }
-            }
+            if (threadIdx.x * 8 + it * 2048 < a.K) ss = sumsq8<A16>(raw[it], ss);
         }
         ss = block_sum<4>(ss, red);
         const float rstd = 1.0f / sqrtf(ss / (float)a.K + a.eps);
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
             const int i = threadIdx.x * 8 + it * 2048;
-            if (i < a.K) {
-                u32x4 o;
-#pragma unroll
-                for (int q = 0; q < 4; ++q)
-                    o[q] = A16::pack(A16::lo(raw[it][q]) * rstd * A16::lo(nwv[it][q]), A16::hi(raw[it][q]) * rstd * A16::hi(nwv[it][q]));
-                put(i, o);
-            }
+            if (i < a.K) put(i, norm8<A16>(raw[it], nwv[it], rstd));
         }
     } else if (PRO == PRO_RMSNORM) {
         float ss = 0.f;
-        for (int i = threadIdx.x * 8; i < a.K; i += 256 * 8) {
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(xg + i);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                ss = fmaf(A16::lo(raw[q]), A16::lo(raw[q]), ss);
-                ss = fmaf(A16::hi(raw[q]), A16::hi(raw[q]), ss);
-            }
-        }
+        for (int i = threadIdx.x * 8; i < a.K; i += 256 * 8) ss = sumsq8<A16>(*reinterpret_cast<const u32x4*>(xg + i), ss);
         ss = block_sum<4>(ss, red);
         const float rstd = 1.0f / sqrtf(ss / (float)a.K + a.eps);
         for (int i = threadIdx.x * 8; i < a.K; i += 256 * 8) {
             const u32x4 raw = *reinterpret_cast<const u32x4*>(xg + i);
-            const u32x4 nw = *reinterpret_cast<const u32x4*>(a.norm_w + i);
-            u32x4 o;
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                o[q] = A16::pack(A16::lo(raw[q]) * rstd * A16::lo(nw[q]), A16::hi(raw[q]) * rstd * A16::hi(nw[q]));
-            put(i, o);
+            put(i, norm8<A16>(raw, *reinterpret_cast<const u32x4*>(a.norm_w + i), rstd));
         }
     } else if (a.K <= 8 * 2048 && !a.rolled_stage) {
         // all of the row's vectors of this thread in flight at once (the rolled loop below waits for each 16-byte load before it

@@ -1,6 +1,7 @@
 // Packed-weight (MLX affine 2/3/4/5/6/8-bit) GEMV family: the decode-time Linear of a quantized checkpoint
 // (nn::QuantizedLinear::forward, mlx-rs/src/nn/quantized.rs:361-385; quant.hip for the format).
 #pragma once
+#include "act16.hpp"
 #include "common.hpp"
 #include "gemv.hpp"   // PRO_* / EPI_* codes shared with the bf16 GEMV family
 
@@ -84,6 +85,53 @@ __device__ __forceinline__ uint32_t qfield(const uint32_t* w, int j) {
     const int p = j * B, k = p >> 5, o = p & 31;
     if (o + B <= 32) return (w[k] >> o) & ((1u << B) - 1u);
     return __builtin_amdgcn_alignbit(w[k + 1], w[k], o) & ((1u << B) - 1u);
+}
+
+// ---- the unpack and the activation staging of the packed GEMVs (quant.hip, qgemv_rows.hip, qgemv_mfma.hip), written once ----
+// A = Act16<F16S>.  A field q becomes a 16-bit float by bit assembly: kMagicBytes' exponent byte over it, bf16 0x4300 | q = 128 + q,
+// float16 0x6400 | q = 1024 + q, so each dot product accumulates x . (magic + q); the bf16 form's 128 * sum(x) excess is folded into
+// the bias term (bias - 128 scale) * sum(x), the float16 form takes its 1024 off again before the product (A::unmagic).
+// 4 bits: the eight nibbles of a word as four magic-biased pairs.  One v_perm per pair: the exponent byte comes from the second source,
+// the two nibble bytes from the same masked word -- so the pairs are (q0, q2), (q4, q6) of the even nibbles and (q1, q3), (q5, q7) of
+// the odd ones, and the activations are staged in that order (stage_octet4)
+template <class A>
+__device__ __forceinline__ void nibble_pairs(uint32_t wdw, uint32_t* out) {
+    const uint32_t lo = wdw & 0x0F0F0F0Fu, hi = (wdw >> 4) & 0x0F0F0F0Fu;
+    const uint32_t c43 = A::kMagicBytes;
+    constexpr uint32_t kBytes02 = 0x04010400u, kBytes13 = 0x04030402u;   // (magic, byte 1, magic, byte 0), (magic, byte 3, magic, byte 2)
+    out[0] = __builtin_amdgcn_perm(c43, lo, kBytes02);
+    out[1] = __builtin_amdgcn_perm(c43, lo, kBytes13);
+    out[2] = __builtin_amdgcn_perm(c43, hi, kBytes02);
+    out[3] = __builtin_amdgcn_perm(c43, hi, kBytes13);
+}
+// eight consecutive activations (x0 .. x7, four packed pairs) as (x0,x2) (x4,x6) (x1,x3) (x5,x7): the pairing of nibble_pairs
+__device__ __forceinline__ u32x4 stage_octet4(const u32x4 o) {
+    u32x4 t;
+    t[0] = __builtin_amdgcn_perm(o[1], o[0], 0x05040100u); t[1] = __builtin_amdgcn_perm(o[3], o[2], 0x05040100u);
+    t[2] = __builtin_amdgcn_perm(o[1], o[0], 0x07060302u); t[3] = __builtin_amdgcn_perm(o[3], o[2], 0x07060302u);
+    return t;
+}
+// 2 / 3 / 5 / 6 bits: elements 2 i and 2 i + 1 of a run of 32 as one magic-biased pair, natural order -- each field one v_bfe_u32
+// (v_alignbit for a straddling one), the pair one v_lshl_or_b32 + one v_or_b32 of the magic
+template <int BITS, class A>
+__device__ __forceinline__ uint32_t field_pair(const uint32_t* wd, int i) {
+    const uint32_t q0 = qfield<BITS>(wd, 2 * i), q1 = qfield<BITS>(wd, 2 * i + 1);
+    return ((q1 << 16) | q0) | (A::kMagicBytes & 0xFF00FF00u);
+}
+// Stage the eight activations o = x[i, i + 8) of a row: into xs (OCTET4: in the 4-bit kernels' order) and into the sum over each lane
+// chunk of EPL elements that every row's bias term shares, xsum[i / EPL] -- EPL / 8 consecutive threads hold a chunk and reduce it
+// by DPP, so thread t of the block must stage vector t (+ a multiple of 64) of the row
+template <class A, int EPL, bool OCTET4>
+__device__ __forceinline__ void stage_chunk(bf16_t* xs, float* xsum, int i, const u32x4 o) {
+    static_assert(EPL == 8 || EPL == 16 || EPL == 32 || EPL == 64, "a lane chunk is 1, 2, 4 or 8 activation vectors");
+    *reinterpret_cast<u32x4*>(xs + i) = OCTET4 ? stage_octet4(o) : o;
+    float sv = 0.f;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) sv += A::lo(o[q]) + A::hi(o[q]);
+    if (EPL >= 16) sv += dpp_f<kDppXor1>(sv);
+    if (EPL >= 32) sv += dpp_f<kDppXor2>(sv);
+    if (EPL >= 64) sv += dpp_f<kDppHalfMirror>(sv);
+    if (((i >> 3) & (EPL / 8 - 1)) == 0) xsum[i / EPL] = sv;
 }
 
 // One row of QuantizedEmbedding::forward straight from the packed table, by one block: element j of row `id` as (float)q * scale + bias

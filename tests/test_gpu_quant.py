@@ -161,7 +161,8 @@ def test_mlx_c_quantized_entry_points(omx):
         mx.quantize(mx.Array.from_numpy(rand((4, 100), 1)))
 
 
-@pytest.mark.parametrize("M,bits,group,K", [(1, 4, 64, 1024), (5, 4, 32, 1024), (3, 8, 64, 1024), (40, 4, 64, 1024), (2, 4, 64, 14336)])
+@pytest.mark.parametrize("M,bits,group,K", [(1, 4, 64, 1024), (5, 4, 32, 1024), (3, 8, 64, 1024), (40, 4, 64, 1024), (2, 4, 64, 14336),
+                                            (1, 2, 32, 1024 + 32)])   # a chunked width in float16, the last step's lanes masked
 def test_quantized_matmul_in_float16(omx, M, bits, group, K):
     """A float16 MLX checkpoint (the reference's only Mixtral format is 4-bit, and MLX community 4-bit checkpoints are float16) runs
     in float16 END TO END in MLX (nn/quantized.rs:361-385): x, scales, biases and the result are float16, the accumulation float32.
@@ -245,6 +246,12 @@ def test_gemv_epilogue_codes_match_the_header():
     (768, 1024, PRO_RMSNORM, EPI_SWIGLU, 0, 0),         # one-wave blocks with the gate / up pair
     (640, 8192, PRO_NONE, EPI_STORE, 0, 0),
     (40000, 1024, PRO_RMSNORM, EPI_ARGMAX, 0, 0),       # a vocabulary matrix at hidden 1024: streaming one-wave blocks
+    # the epilogues other than the plain store behind the `row < N` guard: 40 rows = two 16-row blocks and half of a third
+    (40, 4096, PRO_NONE, EPI_RESIDUAL, 0, 0),
+    (40, 4096, PRO_RMSNORM, EPI_ARGMAX, 0, 0),
+    (40, 2048, PRO_RMSNORM, EPI_ARGMAX, 0, 0),          # ... at the VALU 4-bit kernel's 32-element lane chunks, one step per row
+    (48, 4096, PRO_RMSNORM, EPI_SWIGLU, 1, 0),          # RMSNorm + the single rounding (gate / up pairs take whole 16-row blocks)
+    (40, 2048, PRO_NONE, EPI_SWIGLU, 0, 0),             # ... ragged pairs: the VALU kernel on both settings
 ])
 def test_fused_packed_gemv_forms_match_oracle(omx, mfma, N, K, pro, epi, single, stack):
     lib = _bind_debug(omx)

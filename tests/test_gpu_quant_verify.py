@@ -95,15 +95,43 @@ def test_rows_kernel_bit_identical_across_groups(omx, bits, group, form):
     np.testing.assert_array_equal(got, want)
 
 
+def _hold_rows_to_numpy(omx, form, bits, group, M, K, seed):
+    """test_fused_packed_gemv_forms_match_numpy's tolerances against a float64 reference."""
+    pro, epi, single, _ = FORMS[form]
+    got, _, (x, nw, resid, mats) = _case(omx, bits, M, form, K, group, sb=False, seed=seed)
+    got = got.astype(np.float64)
+    xin = (rc.rms_norm(x, nw, 1e-6, "bf16") if pro == PRO_RMSNORM else x).astype(np.float64)
+    ws = [dequantize_any(m[0], m[1], m[2], group, "f32").astype(np.float64) for m in mats]
+    ys = [xin @ w.T for w in ws]
+    noise = [4 * 2.0 ** -9 * np.sqrt((xin ** 2) @ (w ** 2).T) for w in ws]
+    ulp = 2.0 ** -7
+    if epi == EPI_STORE:
+        assert (np.abs(got - ys[0]) <= np.abs(ys[0]) * ulp + noise[0] + 1e-6).all()
+    elif epi == EPI_RESIDUAL:
+        ref = resid.astype(np.float64) + ys[0]
+        assert (np.abs(got - ref) <= (np.abs(ref) + np.abs(ys[0])) * ulp + noise[0] + 1e-6).all()
+    else:
+        g, u = ys
+        sg = 1.0 / (1.0 + np.exp(-g))
+        ref = g * sg * u
+        tol = np.abs(ref) * 4 * ulp + 1.1 * (noise[0] + np.abs(g) * ulp) * np.abs(u) + (noise[1] + np.abs(u) * ulp) * np.abs(g * sg) + 1e-6
+        assert (np.abs(got - ref) <= tol).all()
+
+
 def test_rows_kernel_matches_numpy(omx):
-    """test_fused_packed_gemv_forms_match_numpy's tolerances, float64 reference, 5 rows of a 6-bit RMSNorm + store."""
-    bits, group, M, K = 6, 64, 5, 1536
-    got, _, (x, nw, _, mats) = _case(omx, bits, M, "norm_store", K, group, sb=False, seed=2300)
-    xin = rc.rms_norm(x, nw, 1e-6, "bf16").astype(np.float64)
-    w = dequantize_any(mats[0][0], mats[0][1], mats[0][2], group, "f32").astype(np.float64)
-    ys = xin @ w.T
-    noise = 4 * 2.0 ** -9 * np.sqrt((xin ** 2) @ (w ** 2).T)
-    assert (np.abs(got.astype(np.float64) - ys) <= np.abs(ys) * 2.0 ** -7 + noise + 1e-6).all()
+    """5 rows of a 6-bit RMSNorm + store."""
+    _hold_rows_to_numpy(omx, "norm_store", 6, 64, 5, 1536, seed=2300)
+
+
+@pytest.mark.parametrize("form,bits,group,K", [
+    ("residual", 4, 64, 2048),
+    ("residual", 3, 32, 1024 + 32),          # a chunked width whose last step masks lanes
+    ("norm_swiglu", 5, 32, 1024 + 32),
+    ("swiglu_single", 4, 64, 2048),
+])
+def test_rows_kernel_epilogues_match_numpy(omx, form, bits, group, K):
+    """The epilogues that only the bit comparison with the single-row kernel reached, 3 rows each."""
+    _hold_rows_to_numpy(omx, form, bits, group, 3, K, seed=2310 + bits)
 
 
 # ---- 2. the engine's verify pass on packed checkpoints ----
