@@ -396,6 +396,23 @@ typedef struct omx_attn_step_dbg_ {
     void* out; unsigned abort_flag;   /* out */
 } omx_attn_step_dbg;
 int omx_debug_attn_step(omx_attn_step_dbg* a, omx_stream stream);
+/* test hook of the few-row bf16 Linear (csrc/gemv_rows.hip): ONE launch over M <= 8 activation rows x [M, K] on caller-owned buffers,
+ * straight through launch_gemv_rows (segmented == 0) or launch_gemv_rows_segmented -- no N * K routing threshold in between.
+ * Plain: out [M, N] = x . w[N, K]^T (+ bias [N]) (relu) then + resid [M, N] (the product rounded first), or resid + product * gate [N].
+ * Segmented: n_plain <= 3 Linears {w [cols, K], bias [cols] or null, out [M, cols] with row stride ld}, then a SwiGLU pair w_gate /
+ * w_up [half, K] -> out_act [M, half] with row stride ld_act (act_mode 0: one rounding, 1: every primitive rounded); pre_norm_w [K]:
+ * RMSNorm of the rows inside the launch (M <= 4, K <= 4096).  Out: route_rpw, the output rows per wave (2 or 4) of the launch.  The
+ * launcher's refusals come back as its error text; nothing is launched then.  Synchronises the stream. */
+typedef struct omx_gemv_rows_seg_ { const void* w; const void* bias; void* out; int cols, ld; } omx_gemv_rows_seg;
+typedef struct omx_gemv_rows_dbg_ {
+    const void* x; int M, K, segmented;
+    const void* w; const void* bias; const void* resid; const void* gate; int relu, N; void* out;   /* plain */
+    omx_gemv_rows_seg seg[3]; int n_plain;                                                           /* segmented */
+    const void* w_gate; const void* w_up; void* out_act; int half, ld_act, act_mode;
+    const void* pre_norm_w; float pre_norm_eps;
+    int route_rpw;   /* out */
+} omx_gemv_rows_dbg;
+int omx_debug_gemv_rows(omx_gemv_rows_dbg* a, omx_stream stream);
 int omx_qwen3_stream(omx_qwen3 m, omx_stream* s);
 /* algorithmic HBM bytes of ONE decode step at context length ctx (SURVEY.md 8d formula)             */
 int omx_qwen3_step_bytes(omx_qwen3 m, int ctx, double* bytes);

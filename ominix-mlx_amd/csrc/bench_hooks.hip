@@ -508,6 +508,40 @@ extern "C" int omx_debug_attn_step(omx_attn_step_dbg* d, void* stream) {
     return rc;
 }
 
+extern "C" int omx_debug_gemv_rows(omx_gemv_rows_dbg* d, void* stream) {
+    using namespace omx;
+    OMX_REQUIRE(d && d->x, "omx_debug_gemv_rows: x is required");
+    hipStream_t s = (hipStream_t)stream;
+    int rc;
+    if (!d->segmented) {
+        OMX_REQUIRE(d->w && d->out, "omx_debug_gemv_rows: w and out are required");
+        OMX_REQUIRE(!d->gate || d->resid, "omx_debug_gemv_rows: the gated epilogue reads resid");
+        d->route_rpw = gemv_rows_rpw(d->N, 0);
+        rc = launch_gemv_rows((bf16_t*)d->out, (const bf16_t*)d->x, (const bf16_t*)d->w, (const bf16_t*)d->bias, (const bf16_t*)d->resid,
+                              (const bf16_t*)d->gate, d->M, d->N, d->K, d->relu, s);
+    } else {
+        OMX_REQUIRE(d->n_plain >= 0 && d->n_plain <= 3, "omx_debug_gemv_rows: %d plain segments (0..3)", d->n_plain);
+        GemmSegs g = {};
+        int rows = 0;
+        for (int i = 0; i < d->n_plain; ++i) {
+            const omx_gemv_rows_seg& p = d->seg[i];
+            OMX_REQUIRE(p.ld >= p.cols, "omx_debug_gemv_rows: segment %d has row stride %d < %d columns", i, p.ld, p.cols);
+            g.plain[i] = GemmSeg{(const bf16_t*)p.w, (const bf16_t*)p.bias, (bf16_t*)p.out, p.cols, p.ld, 0};
+            rows += p.cols;
+        }
+        g.n_plain = d->n_plain;
+        OMX_REQUIRE(d->half <= 0 || d->ld_act >= d->half, "omx_debug_gemv_rows: activation row stride %d < %d columns", d->ld_act, d->half);
+        g.w_gate = (const bf16_t*)d->w_gate; g.w_up = (const bf16_t*)d->w_up; g.out_act = (bf16_t*)d->out_act;
+        g.half = d->half; g.ld_act = d->ld_act; g.act_mode = d->act_mode;
+        g.pre_norm_w = (const bf16_t*)d->pre_norm_w; g.pre_norm_eps = d->pre_norm_eps;
+        d->route_rpw = gemv_rows_rpw(rows + 2 * d->half, d->half);
+        rc = launch_gemv_rows_segmented((const bf16_t*)d->x, d->M, d->K, g, s);
+    }
+    if (rc) return rc;
+    OMX_HIP_CHECK(hipStreamSynchronize(s));
+    return 0;
+}
+
 /* test hook of qgemv_rows.hip: M activation rows x [M, K] against n_members packed matrices (w / sc / bi / n: arrays of n_members; a
  * q | k | v stack, or gate and up for EPI_SWIGLU), out [M, N] (resid [M, N]).  use_sb: build the interleaved scale | bias words first.
  * reference != 0 runs what the rows kernel must reproduce bit for bit instead: launch_qgemv's VALU kernel (no matrix-core tiles) with

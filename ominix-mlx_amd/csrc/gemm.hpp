@@ -146,5 +146,7 @@ int launch_gemv_rows_segmented(const bf16_t* x, int M, int K, const GemmSegs& se
 bool gemv_rows_takes_norm(int M, int K, const GemmSegs& segs);
 int launch_gemv_rows(bf16_t* out, const bf16_t* x, const bf16_t* w, const bf16_t* bias, const bf16_t* resid, const bf16_t* gate, int M, int N,
                      int K, int relu, hipStream_t s);
+// output rows per wave (2 or 4) of a launch over N virtual rows (segmented: the plain columns + 2 * half; plain launches: half = 0)
+int gemv_rows_rpw(int N, int half);
 
 }  // namespace omx

@@ -227,14 +227,18 @@ int launch_rows_t(const RowsArgs& a, hipStream_t s) {
 #undef OMX_ROWS_CASE
 }
 int launch_rows(const RowsArgs& a, bool seg, hipStream_t s) {
-    // two rows per wave while four would give fewer than three blocks per CU (a SwiGLU pair needs its four: 2 gate + 2 up rows)
-    const bool narrow = a.N < 768 * 16 && !(seg && a.sg.half > 0);
+    const bool narrow = gemv_rows_rpw(a.N, seg ? a.sg.half : 0) == 2;
     // (one row per wave for N = 4096, 4 blocks per CU: -2 % at 5 rows, +11 % at 8 -- every wave re-reads all activation rows from LDS)
     if (seg) return narrow ? launch_rows_t<true, 2>(a, s) : launch_rows_t<true, 4>(a, s);
     return narrow ? launch_rows_t<false, 2>(a, s) : launch_rows_t<false, 4>(a, s);
 }
 
 }  // namespace
+
+int gemv_rows_rpw(int N, int half) {
+    // two rows per wave while four would give fewer than three blocks per CU (a SwiGLU pair needs its four: 2 gate + 2 up rows)
+    return N < 768 * 16 && half <= 0 ? 2 : 4;
+}
 
 bool gemv_rows_supported(int M, int N, int K, const void* x, const void* w) {
     return M >= 1 && M <= 8 && N >= 1 && K >= 8 && K % 8 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w)) & 15u) == 0;

@@ -50,6 +50,22 @@ class AttnStepDbg(ctypes.Structure):
                 ("chunk", c_int), ("nsplit", c_int), ("tk_max", c_int), ("out", c_void_p), ("abort_flag", c_uint32)]
 
 
+class GemvRowsSeg(ctypes.Structure):
+    """omx_gemv_rows_seg: one plain segment of a segmented few-row launch"""
+    _fields_ = [("w", c_void_p), ("bias", c_void_p), ("out", c_void_p), ("cols", c_int), ("ld", c_int)]
+
+
+class GemvRowsDbg(ctypes.Structure):
+    """omx_gemv_rows_dbg: one launch of the few-row bf16 Linear (omx_debug_gemv_rows), plain or segmented; route_rpw comes back
+    filled in."""
+    _fields_ = [("x", c_void_p), ("M", c_int), ("K", c_int), ("segmented", c_int),
+                ("w", c_void_p), ("bias", c_void_p), ("resid", c_void_p), ("gate", c_void_p), ("relu", c_int), ("N", c_int), ("out", c_void_p),
+                ("seg", GemvRowsSeg * 3), ("n_plain", c_int),
+                ("w_gate", c_void_p), ("w_up", c_void_p), ("out_act", c_void_p), ("half", c_int), ("ld_act", c_int), ("act_mode", c_int),
+                ("pre_norm_w", c_void_p), ("pre_norm_eps", c_float),
+                ("route_rpw", c_int)]
+
+
 ENGINE_SIGNATURES = {
     "omx_fill_uniform_2d": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64, c_uint32, c_float, c_float, c_int, c_void_p]),
@@ -105,6 +121,8 @@ ENGINE_SIGNATURES = {
     # entries) and the route it takes; the step attention (csrc/attn_step.hip) on caller-owned buffers
     "omx_debug_gemv_ex": (c_int, [ctypes.POINTER(GemvEx), c_void_p]),
     "omx_debug_attn_step": (c_int, [ctypes.POINTER(AttnStepDbg), c_void_p]),
+    # the few-row bf16 Linear (csrc/gemv_rows.hip), plain or segmented, without the GEMM entry's N * K routing threshold
+    "omx_debug_gemv_rows": (c_int, [ctypes.POINTER(GemvRowsDbg), c_void_p]),
     "omx_bench_qwen3_per_op": (c_int, [c_void_p, ctypes.POINTER(Qwen3Config), ctypes.POINTER(c_uint32), c_int, c_int, ctypes.POINTER(c_uint32),
                                        ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]),
 }

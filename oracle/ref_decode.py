@@ -83,6 +83,13 @@ def gemv_norm_depth(K):
     return 8 * ((K + 2047) // 2048) + 16
 
 
+def rows_norm_depth(K):
+    """longest f32 chain of the few-row kernel's in-launch RMSNorm (gemv_rows.hip, K <= 4096): one wave per activation row, lane l
+    runs `s += lo * lo; s += hi * hi` (the squares of bf16 values are exact in f32: one rounding per add) over the 8 elements of each of
+    its vectors l, l + 64, ... -- ceil(K / 512) vectors that are not staged zeros -- then the 6-level wave sum"""
+    return 8 * ((K + 511) // 512) + 6
+
+
 def norm_slack(W, x, nw, eps, dt):
     """(xn, slack per row): xn = dt(exact RMSNorm); the kernel's W . xn' differs from W . xn by at most sum_k |hi_k - lo_k| |W_rk| --
     only the elements whose rounding can flip (norm_candidates) contribute"""
@@ -96,7 +103,12 @@ def norm_slack(W, x, nw, eps, dt):
 def gemv_acc_depth(K):
     """longest chain of f32 roundings in a GEMV row's accumulation: a lane's fma chain over its 16-byte vectors (at most
     8 ceil(K / 512) products in every kernel: K / 64 per lane, a quarter of that per wave when the K is split), the 6-level wave sum
-    and the 4-part sum of a K split (+ 6 spare)"""
+    and the 4-part sum of a K split (+ 6 spare).
+    The few-row kernel (gemv_rows.hip) is covered too, read off its loop: per 4096-column chunk a lane owns vectors lane, lane + 64, ...
+    of the chunk's nv <= 512 -- 8 of a whole chunk, ceil(nv / 64) of the last; the others meet a staged zero row of x and add an exact
+    0 -- ceil(K / 512) vectors in all, chunk after chunk in ONE accumulator, 8 products each through four v_dot2c_f32_bf16 (two exact
+    products and the accumulator per instruction: at most one rounding per product), then the 6-level wave sum and the bias add:
+    8 ceil(K / 512) + 7"""
     return 8 * ((K + 511) // 512) + 16
 
 
@@ -122,16 +134,47 @@ def stored_candidates(exact, err, dt):
     return np.minimum(a, b), np.maximum(a, b)
 
 
-def check_residual(got, resid, exact, mag, n, dt, extra=0.0):
+def check_residual(got, resid, exact, mag, n, dt, extra=0.0, relu=False):
     """EPI_RESIDUAL: out = dt(r + dt(acc)).  dt(acc) lies in [lo, hi], the stored candidates of an accumulation within
     n u sum|x w| (+ extra) of the exact value, and y -> dt(r + y) (one f32 add of two dt values, one rounding) is monotone: got must
-    lie in [dt(r + lo), dt(r + hi)] -- a single value away from rounding midpoints"""
+    lie in [dt(r + lo), dt(r + hi)] -- a single value away from rounding midpoints.  relu: max(acc, 0) before the rounding (exact and
+    monotone, it commutes with the rounding: the candidates are clamped)"""
     lo, hi = stored_candidates(exact, n * U24 * mag + extra, dt)
+    if relu:
+        lo, hi = np.maximum(lo, 0.0), np.maximum(hi, 0.0)
     r32 = np.asarray(resid, np.float32)
     c_lo, c_hi = rnd(r32 + lo.astype(np.float32), dt), rnd(r32 + hi.astype(np.float32), dt)
     bad = np.nonzero((got < c_lo) | (got > c_hi))[0]
     assert bad.size == 0, f"{bad.size} residual rows off, e.g. {bad[0]}: got {got[bad[0]]} want {c_lo[bad[0]]} .. {c_hi[bad[0]]}"
     check_exact16(got, dt)
+
+
+def check_gate(got, resid, gate, exact, mag, n, dt, extra=0.0, relu=False):
+    """the gated residual of the GEMM epilogues: out = dt(r + acc * g), g per output column, no rounding in between.  acc lies within
+    E = n u sum|x w| (+ extra) of the exact value (clamped at 0 under relu: exact and monotone), so acc * g lies between the products
+    of the interval ends with g; the f32 product and the f32 add are one rounding each, relative u of |acc g| and of |r + acc g|: the
+    f32 sum lies in [r + p_lo - e, r + p_hi + e] with e = 4 u (|r| + max|p|) (2 u needed), and got must lie between the roundings of
+    the two ends (stored_candidates' argument, the rounding being monotone) -- a single value away from rounding midpoints"""
+    E = n * U24 * mag + extra
+    a, b = exact - E, exact + E
+    if relu:
+        a, b = np.maximum(a, 0.0), np.maximum(b, 0.0)
+    g, r = np.asarray(gate, np.float64), np.asarray(resid, np.float64)
+    p_lo, p_hi = np.minimum(a * g, b * g), np.maximum(a * g, b * g)
+    e = 4 * U24 * (np.abs(r) + np.maximum(np.abs(p_lo), np.abs(p_hi)))
+    c_lo, c_hi = rnd(r + p_lo - e, dt), rnd(r + p_hi + e, dt)
+    bad = np.nonzero((got < c_lo) | (got > c_hi))[0]
+    assert bad.size == 0, f"{bad.size} gated rows off, e.g. {bad[0]}: got {got[bad[0]]} want {c_lo[bad[0]]} .. {c_hi[bad[0]]}"
+    check_exact16(got, dt)
+
+
+def act_mode_single_round(act_mode):
+    """GemmSegs.act_mode (gemm.hpp) -> check_swiglu's single_round.  act_mode 0 (fused_swiglu): dt(g / (1 + expf(-g)) * u) on the
+    rounded g and u, one rounding -- single_round.  act_mode 1 (nn::silu(gate) * up, every primitive rounded): g = dt(acc_gate),
+    u = dt(acc_up), s = dt(1 / (1 + expf(-g))), dt(dt(g s) u) -- the four rounded values (gate, sigmoid, silu, up) are exactly
+    check_swiglu's "three roundings" form, whose g and u are already stored candidates: the sigmoid, the silu and the output."""
+    assert act_mode in (0, 1)
+    return 1 if act_mode == 0 else 0
 
 
 def check_swiglu(got, exact_g, mag_g, exact_u, mag_u, n, dt, single_round, extra_g=0.0, extra_u=0.0):

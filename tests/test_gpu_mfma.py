@@ -497,8 +497,9 @@ def test_linear_f32_on_the_f32_matrix_cores(omx, M, N, K, bias):
 ])
 def test_linear_rows_gemv(omx, monkeypatch, M, N, K):
     """csrc/gemv_rows.hip: a Linear over M <= 8 rows streams every weight row once against all rows (launch_gemm_impl routes there
-    when N * K >= 2^20).  Against the oracle, with bias / relu / residual epilogues as the GEMM kernels define them, and against the
-    matrix-core route (OMX_GEMV_ROWS=0) to one bf16 ulp."""
+    when N * K >= 2^20).  Through omx.ops.linear, so the plain mode at M = 5..8 only, with a bias and without: against the oracle and
+    against the matrix-core route (OMX_GEMV_ROWS=0) to one bf16 ulp, plus a one-hot transpose probe.  Every row count, the relu /
+    residual / gate epilogues, both row layouts and the segmented mode are held to float64 in tests/test_gpu_gemv_rows.py."""
     T = omx.ops.Tensor
     x = rc.bf16_round(rand((M, K), 61))
     w = rc.bf16_round(rand((N, K), 62) * 0.05)
