@@ -327,9 +327,28 @@ int omx_qwen3_trim(omx_qwen3 m, int n, uint32_t next_token);
  *            one at every size measured).  Every other call works on the slot's own copy; trim / reset / a prefill from position 0 of a slot lower the
  *            shared_len of that slot and of the slots that share with it to the chunk boundary they leave intact.  OMX_BATCH_SHARE=0
  *            (read by create): forks copy, shared_len stays 0, every row reads its own slab.
- *   shared:  owner and shared_len of a slot, from the device's table.                                                                  */
+ *   shared:  owner and shared_len of a slot, from the device's table.
+ *   create_kv: create with the K/V storage chosen (MLX's kv_bits).  kv_bits 0 = bf16 slabs, what create makes; 8 = every K row (after
+ *            q/k norm and RoPE) and V row stored as MLX affine codes, group 64 along the head dim, scales and biases bf16 -- mlx quantize's
+ *            arithmetic on the bf16 row, to the bit -- quantised as the row is appended, and every attention reads (float)code * scale +
+ *            bias: the decode step straight from the packed rows, a prompt pass from ONE bf16 staging pair the slot's rows are expanded
+ *            into layer by layer (its new rows included, replaced by their dequantised values before the attention).  136 instead of 256
+ *            bytes per cached token and KV head at head_dim 128.  Everything else as above; the grouped read of shared chunks is not
+ *            built for packed rows (OMX_BATCH_SHARE_MIN is ignored, `shared` reports as before).  Any other kv_bits is refused.
+ *   kv_bytes: bytes of K/V storage the batch allocated (the slabs only).
+ *   kv_read: HOST copies of rows [first, first + n) (cached rows only) of one slot and layer.  A bf16 batch: k_rows / v_rows bf16
+ *            [Hkv, n, D], the four scale / bias pointers null.  A kv_bits 8 batch: k_rows / v_rows MLX-layout uint32 [Hkv, n, D / 4]
+ *            (element j of a row = byte j, LSB first), scales and biases bf16 [Hkv, n, D / 64].
+ *   debug_attention: test hook, as omx_debug_attn_step -- the decode attention launch alone: row r = the caller's query q[r] ([n, H, D]
+ *            bf16, HOST) over ALL rows slot slots[r] holds of `layer`, out [n, H * D] bf16 (HOST).  Prefilled slots only; slot state is
+ *            untouched (the model's prompt scratch is used).                                                                           */
 typedef struct omx_qwen3_batch_* omx_qwen3_batch;
 int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int max_context);
+int omx_qwen3_batch_create_kv(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int max_context, int kv_bits);
+int omx_qwen3_batch_kv_bytes(omx_qwen3_batch b, size_t* bytes);
+int omx_qwen3_batch_kv_read(omx_qwen3_batch b, int slot, int layer, int first, int n, void* k_rows, void* v_rows, void* k_scales,
+                            void* k_biases, void* v_scales, void* v_biases);
+int omx_qwen3_batch_debug_attention(omx_qwen3_batch b, int layer, const int* slots, int n, const void* q, void* out);
 int omx_qwen3_batch_destroy(omx_qwen3_batch b);
 int omx_qwen3_batch_set_sampler(omx_qwen3_batch b, int slot, float temperature, uint64_t seed);
 int omx_qwen3_batch_set_sampling(omx_qwen3_batch b, int slot, const omx_sampling* p, uint64_t seed);

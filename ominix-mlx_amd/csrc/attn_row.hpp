@@ -1,7 +1,7 @@
 // The per-row arithmetic of a split of split-KV decode attention (Tq == 1), written once: what a (row, KV head, split) partial is, to
 // the bit.  attn_decode_kernel (attn_decode.hip: the per-op decode SDPA and the rows of a speculative verify pass) and
 // batch_attn_kernel / batch_attn_shared_kernel (engine_batch.hip) are built from it; they differ in where a row's query, K/V and token
-// range come from, and in the mask.
+// range come from (a source policy: bf16 rows, or the 8-bit affine rows of a kv_bits = 8 batch), and in the mask.
 //
 // Mapping (wave64, blocks of kBlock threads = kWaves waves): K/V rows are D bf16 = D/8 lanes x 16 B straight to registers, so a
 // wave-instruction covers 64/(D/8) consecutive tokens as one contiguous 1 KiB burst; the G = H/Hkv query heads of a KV head are
@@ -26,6 +26,42 @@ __device__ __forceinline__ void unpack8(const u32x4 r, float (&x)[8]) {
     }
 }
 
+// Where a split's K/V rows come from: how the 8 elements (chunk c) a lane owns of token row tc of a KV head are issued, what stays in
+// registers until they are used (Raw), and how they unpack to fp32.  bf16 rows [tokens, D]: one 16-byte load each
+struct KvBf16 {
+    typedef u32x4 Raw;
+    const bf16_t *K, *V;
+    template <int D>
+    __device__ __forceinline__ void issue(Raw& k, Raw& v, int tc, int c) const {
+        k = *reinterpret_cast<const u32x4*>(K + (size_t)tc * D + c * 8);
+        v = *reinterpret_cast<const u32x4*>(V + (size_t)tc * D + c * 8);
+    }
+    static __device__ __forceinline__ void unpack(const Raw& r, float (&x)[8]) { unpack8(r, x); }
+};
+// 8-bit MLX affine rows (group 64 along the head dim): codes [tokens, D] bytes, one word scale | bias (bf16 low | high) per group
+// [tokens, D / 64] -- an 8-byte load plus the word of the lane's group; element = (float)code * scale + bias, never rounded to bf16
+struct Kv8Raw {
+    u32x2 q;
+    uint32_t sb;
+};
+struct KvAffine8 {
+    typedef Kv8Raw Raw;
+    const uint8_t *K, *V;
+    const uint32_t *Ksb, *Vsb;
+    template <int D>
+    __device__ __forceinline__ void issue(Raw& k, Raw& v, int tc, int c) const {
+        k.q = *reinterpret_cast<const u32x2*>(K + (size_t)tc * D + c * 8);
+        v.q = *reinterpret_cast<const u32x2*>(V + (size_t)tc * D + c * 8);
+        k.sb = Ksb[(size_t)tc * (D / 64) + c / 8];
+        v.sb = Vsb[(size_t)tc * (D / 64) + c / 8];
+    }
+    static __device__ __forceinline__ void unpack(const Raw& r, float (&x)[8]) {
+        const float sc = bf16lo(r.sb), b = bf16hi(r.sb);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) x[e] = fmaf((float)((r.q[e >> 2] >> (8 * (e & 3))) & 0xFFu), sc, b);
+    }
+};
+
 // scores()'s mask hook: score d of token tok as it enters the softmax; live = the token lies inside the split's range (the others
 // score -inf whatever the hook returns, and a mask is not read for them).  No mask: as it is
 struct NoMask {
@@ -45,14 +81,18 @@ struct AttnRow {
 
     // the wave's STEP K and V rows from token tbase on, of a head whose rows start at Kb / Vb (row stride D); rows past the split's
     // end are clamped duplicates
-    static __device__ __forceinline__ void issue_kv(u32x4 (&kr)[kUnroll], u32x4 (&vr)[kUnroll], const bf16_t* Kb, const bf16_t* Vb,
-                                                    int tbase, int t_end, int sg, int c) {
+    template <class Src>
+    static __device__ __forceinline__ void issue_rows(typename Src::Raw (&kr)[kUnroll], typename Src::Raw (&vr)[kUnroll], const Src& src,
+                                                      int tbase, int t_end, int sg, int c) {
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
             const int tc = max(min(tbase + u * TPW + sg, t_end - 1), 0);
-            kr[u] = *reinterpret_cast<const u32x4*>(Kb + (size_t)tc * D + c * 8);
-            vr[u] = *reinterpret_cast<const u32x4*>(Vb + (size_t)tc * D + c * 8);
+            src.template issue<D>(kr[u], vr[u], tc, c);
         }
+    }
+    static __device__ __forceinline__ void issue_kv(u32x4 (&kr)[kUnroll], u32x4 (&vr)[kUnroll], const bf16_t* Kb, const bf16_t* Vb,
+                                                    int tbase, int t_end, int sg, int c) {
+        issue_rows(kr, vr, KvBf16{Kb, Vb}, tbase, t_end, sg, c);
     }
 
     // the G query heads of KV head kvh -> registers, pre-multiplied by scale in fp32; head h of the row at qrow + h * q_hs
@@ -75,15 +115,16 @@ struct AttnRow {
     }
 
     // scores of the wave's STEP tokens from t0 on against the K rows in kr, each through the mask hook; the V rows unpacked
-    template <class Mask>
-    __device__ __forceinline__ void scores(const u32x4 (&kr)[kUnroll], const u32x4 (&vr)[kUnroll], int t0, int t_end, int sg,
-                                           const Mask& mask, float (&s)[kUnroll][GT], float (&vf)[kUnroll][8]) const {
+    // (Src: the rows' source, KvBf16 / KvAffine8)
+    template <class Src, class Mask>
+    __device__ __forceinline__ void scores_of(const typename Src::Raw (&kr)[kUnroll], const typename Src::Raw (&vr)[kUnroll], int t0, int t_end,
+                                              int sg, const Mask& mask, float (&s)[kUnroll][GT], float (&vf)[kUnroll][8]) const {
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
             const int tok = t0 + u * TPW + sg;
             float kf[8];
-            unpack8(kr[u], kf);
-            unpack8(vr[u], vf[u]);
+            Src::unpack(kr[u], kf);
+            Src::unpack(vr[u], vf[u]);
             if (tok >= t_end) {   // clamped duplicate row: its p is 0, but 0 * garbage must stay 0
 #pragma unroll
                 for (int e = 0; e < 8; ++e) vf[u][e] = 0.f;
@@ -98,6 +139,12 @@ struct AttnRow {
                 s[u][g] = tok < t_end ? d : -INFINITY;
             }
         }
+    }
+
+    template <class Mask>
+    __device__ __forceinline__ void scores(const u32x4 (&kr)[kUnroll], const u32x4 (&vr)[kUnroll], int t0, int t_end, int sg,
+                                           const Mask& mask, float (&s)[kUnroll][GT], float (&vf)[kUnroll][8]) const {
+        scores_of<KvBf16>(kr, vr, t0, t_end, sg, mask, s, vf);
     }
 
     // running max / sum / output of the wave over those tokens

@@ -11,6 +11,10 @@
 // Attention splits are kChunk tokens wide whatever the batch holds: a sequence's partials, and the order its merge adds them in,
 // depend on its own length only, so a sequence's bits do not depend on its neighbours (attn_decode_kernel derives its chunk from the
 // launch's split count, which follows the longest sequence).
+//
+// kv_bits = 8 (omx_qwen3_batch_create_kv): the slots keep their K/V rows as 8-bit MLX affine codes (Kv8Layer, engine_model.hpp) --
+// quantised by the scatter as they are appended (SlotRows8, prefill.hip), read packed by batch_attn_kv8_kernel, the same block over
+// another row source (KvAffine8, attn_row.hpp); a prompt pass works on one bf16 staging pair (KvSlabs::packed).
 #include "attn_row.hpp"
 #include "engine_model.hpp"
 
@@ -59,10 +63,29 @@ struct BatchSharedArgs {
     int grp_owner[kMaxSlots], grp_shared[kMaxSlots];
 };
 
+// The slabs of a launch: rows(slot, kvh) = the source (attn_row.hpp) of that slot's KV head.  bf16 slabs [Hkv, cap, D] ...
+struct Bf16Slabs {
+    const BatchAttnArgs& a;
+    __device__ __forceinline__ KvBf16 rows(int slot, int kvh) const {
+        return {a.kbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride,
+                a.vbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride};
+    }
+};
+// ... and the 8-bit slabs of a kv_bits = 8 batch (Kv8Layer): codes slot_stride / head_stride bytes apart, scale | bias words sb_*
+struct Affine8Slabs {
+    Kv8Layer kv;
+    size_t slot_stride, head_stride, sb_slot_stride, sb_head_stride;
+    __device__ __forceinline__ KvAffine8 rows(int slot, int kvh) const {
+        const size_t at = (size_t)slot * slot_stride + (size_t)kvh * head_stride, sb = (size_t)slot * sb_slot_stride + (size_t)kvh * sb_head_stride;
+        return {kv.kq + at, kv.vq + at, kv.ksb + sb, kv.vsb + sb};
+    }
+};
+
 // block (r, kvh, split) on row r's own slab: K/V rows of the next step in flight while this step's are applied
-template <int D, int GT>
-__device__ __forceinline__ void attn_own_row(const BatchAttnArgs& a, unsigned char* smem, int r, int kvh, int split) {
+template <int D, int GT, class Slabs>
+__device__ __forceinline__ void attn_own_row(const BatchAttnArgs& a, const Slabs& slabs, unsigned char* smem, int r, int kvh, int split) {
     using Row = AttnRow<D, GT>;
+    typedef decltype(slabs.rows(0, 0)) Src;
     constexpr int LPR = Row::LPR, STEP = Row::STEP;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -75,20 +98,19 @@ __device__ __forceinline__ void attn_own_row(const BatchAttnArgs& a, unsigned ch
     if (t_begin >= Tk) return;          // (block-uniform: past this sequence's end)
     const int t_end = min(Tk, t_begin + a.chunk);
 
-    const bf16_t* Kb = a.kbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride;
-    const bf16_t* Vb = a.vbase + (size_t)slot * a.slot_stride + (size_t)kvh * a.head_stride;
+    const Src src = slabs.rows(slot, kvh);
 
-    u32x4 kr[kUnroll], vr[kUnroll];
+    typename Src::Raw kr[kUnroll], vr[kUnroll];
     int t0 = t_begin + wave * STEP;
-    if (t0 < t_end) Row::issue_kv(kr, vr, Kb, Vb, t0, t_end, sg, c);
+    if (t0 < t_end) Row::issue_rows(kr, vr, src, t0, t_end, sg, c);
 
     Row row;
     row.begin(a.q + (size_t)r * a.H * D, D, a.scale, kvh, G, c);
     for (; t0 < t_end; t0 += STEP * kWaves) {
         float s[kUnroll][GT];
         float vf[kUnroll][8];
-        row.scores(kr, vr, t0, t_end, sg, NoMask{}, s, vf);
-        if (t0 + STEP * kWaves < t_end) Row::issue_kv(kr, vr, Kb, Vb, t0 + STEP * kWaves, t_end, sg, c);
+        row.template scores_of<Src>(kr, vr, t0, t_end, sg, NoMask{}, s, vf);
+        if (t0 + STEP * kWaves < t_end) Row::issue_rows(kr, vr, src, t0 + STEP * kWaves, t_end, sg, c);
         row.update(s, vf);
     }
     row.finish(smem, a.ws_o, a.ws_ml, a.nsplit_cap, (size_t)r * a.H + kvh * G, G, split);
@@ -99,7 +121,15 @@ template <int D, int GT>
 __global__ __launch_bounds__(kBlock) void batch_attn_kernel(const BatchAttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int r = blockIdx.x / a.Hkv, kvh = blockIdx.x % a.Hkv;
-    attn_own_row<D, GT>(a, smem, r, kvh, blockIdx.y);
+    attn_own_row<D, GT>(a, Bf16Slabs{a}, smem, r, kvh, blockIdx.y);
+}
+
+// ... and every row on its own 8-bit slab (a kv_bits = 8 batch): the same block over packed rows, nothing expanded in memory
+template <int D, int GT>
+__global__ __launch_bounds__(kBlock) void batch_attn_kv8_kernel(const BatchAttnArgs a, const Affine8Slabs p) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const int r = blockIdx.x / a.Hkv, kvh = blockIdx.x % a.Hkv;
+    attn_own_row<D, GT>(a, p, smem, r, kvh, blockIdx.y);
 }
 
 // ---- the same launch when listed rows share a prefix (omx_qwen3_batch_fork).  The rows whose owner is row r's and whose shared span
@@ -129,7 +159,7 @@ __global__ __launch_bounds__(kBlock) void batch_attn_shared_kernel(const BatchSh
             }
     }
     if (__builtin_popcount(members) < sa.group_min) {
-        attn_own_row<D, GT>(a, smem, r, kvh, split);
+        attn_own_row<D, GT>(a, Bf16Slabs{a}, smem, r, kvh, split);
         return;
     }
     if (before % sa.group_rows) return;   // an earlier member's block takes this row
@@ -271,7 +301,7 @@ int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T,
     OMX_REQUIRE(rag.nsplit >= 1 && rag.nsplit <= rag.nsplit_cap, "batch attention: %d splits of %d", rag.nsplit, rag.nsplit_cap);
     BatchAttnArgs a = {};
     a.q = m->pf_qt;
-    a.kbase = rag.kbase[layer]; a.vbase = rag.vbase[layer];
+    if (!rag.kv8) { a.kbase = rag.kbase[layer]; a.vbase = rag.vbase[layer]; }
     a.slot_stride = rag.slot_stride; a.head_stride = (size_t)rag.cap * D;
     a.slots = rag.slots; a.row_slot = rag.row_slot;
     a.H = H; a.Hkv = Hkv; a.cap = rag.cap; a.chunk = rag.chunk; a.nsplit_cap = rag.nsplit_cap;
@@ -291,6 +321,25 @@ int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T,
                 "groups from %d members, %d rows per block", rag.chunk, rag.group_min, rag.group_rows);
     const dim3 grid(T * Hkv, rag.nsplit), block(kBlock);
     const int gt = G <= 1 ? 1 : G <= 2 ? 2 : G <= 4 ? 4 : 8;
+    if (rag.kv8) {   // the same grid and merge over the 8-bit slabs
+        OMX_REQUIRE(!rag.grouped, "batch attention: the grouped read is not built for 8-bit K/V slabs");
+        const Affine8Slabs p = {rag.kv8[layer], rag.slot_stride, (size_t)rag.cap * D, rag.sb_stride, (size_t)rag.cap * (D / 64)};
+#define OMX_BATCH_ATTN8_CASE(DD, GG)                                                                    \
+    if (D == DD && gt == GG) {                                                                          \
+        const size_t shmem = AttnRow<DD, GG>::SMEM_BYTES;                                               \
+        if (shmem > 48 * 1024)                                                                          \
+            OMX_HIP_CHECK(hipFuncSetAttribute((const void*)batch_attn_kv8_kernel<DD, GG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
+        batch_attn_kv8_kernel<DD, GG><<<grid, block, shmem, s>>>(a, p);                                 \
+        OMX_LAUNCH_CHECK();                                                                             \
+        batch_attn_merge_kernel<DD><<<T * H, DD, 0, s>>>(a);                                            \
+        OMX_LAUNCH_CHECK();                                                                             \
+        return 0;                                                                                       \
+    }
+        OMX_BATCH_ATTN8_CASE(128, 1) OMX_BATCH_ATTN8_CASE(128, 2) OMX_BATCH_ATTN8_CASE(128, 4) OMX_BATCH_ATTN8_CASE(128, 8)
+        OMX_BATCH_ATTN8_CASE(64, 1) OMX_BATCH_ATTN8_CASE(64, 2) OMX_BATCH_ATTN8_CASE(64, 4) OMX_BATCH_ATTN8_CASE(64, 8)
+#undef OMX_BATCH_ATTN8_CASE
+        return set_error("batch attention: head_dim %d unsupported (64 or 128)", D);
+    }
 #define OMX_BATCH_ATTN_CASE(DD, GG)                                                                     \
     if (D == DD && gt == GG) {                                                                          \
         const size_t shmem = AttnRow<DD, GG>::SMEM_BYTES;                                               \
@@ -320,7 +369,16 @@ struct omx_qwen3_batch_ {
     std::vector<bf16_t*> kbase, vbase;                 // per layer: [n_slots][Hkv, cap, D]
     std::vector<bf16_t*> slot_k[kMaxSlots], slot_v[kMaxSlots];   // the same slabs per slot, as the prompt pass takes them (KvSlabs)
     size_t slot_stride = 0;
+    // kv_bits = 8: no bf16 slabs; per layer the 8-bit slabs of all slots (layer8, Kv8Layer: slot s at + s * slot_stride codes and
+    // + s * sb_stride words) and the same per slot (slot8); ONE bf16 staging pair [Hkv, cap, D] every prompt pass attends over, named
+    // once per layer for KvSlabs (stage_k / stage_v); dbg_slots: the positions omx_qwen3_batch_debug_attention reads instead of `slots`
+    int kv_bits = 0;
+    std::vector<Kv8Layer> layer8, slot8[kMaxSlots];
+    size_t sb_stride = 0;
+    std::vector<bf16_t*> stage_k, stage_v;
+    size_t kv_bytes = 0;                               // bytes of K/V storage (slabs only)
     BatchSlot* slots = nullptr;                        // device [n_slots]
+    BatchSlot* dbg_slots = nullptr;
     int* row_slot = nullptr;                           // device [kMaxSlots]: the rows of the call in flight
     bf16_t *step_logits = nullptr, *slot_logits = nullptr;   // [kMaxSlots, V] rows of a step; [n_slots, V] kept per slot
     uint32_t* ring = nullptr;                          // [kRingSteps][kMaxSlots]
@@ -436,6 +494,20 @@ int lower_share(omx_qwen3_batch b, int slot, int pos) {
     return 0;
 }
 
+// the ragged launches' view of the batch, for sequences of up to `longest` tokens: slabs, slot table, workspace; no groups
+RaggedRows batch_rows(omx_qwen3_batch b, int longest) {
+    RaggedRows rag = {};
+    rag.slots = b->slots; rag.row_slot = b->row_slot;
+    rag.kbase = b->kbase.data(); rag.vbase = b->vbase.data();
+    rag.slot_stride = b->slot_stride; rag.cap = b->cap;
+    rag.chunk = kChunk; rag.nsplit_cap = b->nsplit_cap;
+    rag.nsplit = (longest + kChunk - 1) / kChunk;
+    rag.ws_o = b->ws_o; rag.ws_ml = b->ws_ml;
+    rag.kv8 = b->kv_bits ? b->layer8.data() : nullptr;
+    rag.sb_stride = b->sb_stride;
+    return rag;
+}
+
 int env_int(const char* name, int dflt, int lo, int hi) {
     const char* e = getenv(name);
     if (!e || !*e) return dflt;
@@ -451,7 +523,13 @@ int env_int(const char* name, int dflt, int lo, int hi) {
 extern "C" {
 
 int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int max_context) {
+    return omx_qwen3_batch_create_kv(out, m, n_slots, max_context, 0);
+}
+
+int omx_qwen3_batch_create_kv(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int max_context, int kv_bits) {
     OMX_REQUIRE(out && m, "omx_qwen3_batch_create: null argument");
+    OMX_REQUIRE(kv_bits == 0 || kv_bits == 8, "omx_qwen3_batch_create_kv: kv_bits %d unsupported (0 = bf16 K/V slabs, 8 = 8-bit MLX affine "
+                "rows of group 64)", kv_bits);
     OMX_REQUIRE(n_slots >= 1 && n_slots <= kMaxSlots, "omx_qwen3_batch_create: %d slots (1..%d)", n_slots, kMaxSlots);
     const omx_qwen3_config& c = m->cfg;
     OMX_REQUIRE(c.num_experts == 0, "omx_qwen3_batch_create: models with experts (MoE) are not supported; dense models only");
@@ -474,19 +552,40 @@ int omx_qwen3_batch_create(omx_qwen3_batch* out, omx_qwen3 m, int n_slots, int m
     b->cap = cap;
     for (int s = 0; s < kMaxSlots; ++s) b->sampling[s] = {0.f, 0, 1.f, 1.f, 0.f};
     const int D = c.head_dim, L = c.num_hidden_layers, V = m->V;
+    b->kv_bits = kv_bits;
     b->slot_stride = (size_t)m->Hkv * cap * D;
-    b->kbase.resize(L);
-    b->vbase.resize(L);
+    b->sb_stride = (size_t)m->Hkv * cap * (D / 64);
     int rc = 0;
-    for (int l = 0; l < L && !rc; ++l) {
+    if (kv_bits == 0) {
+        b->kbase.resize(L);
+        b->vbase.resize(L);
+    }
+    for (int l = 0; l < L && !rc && kv_bits == 0; ++l) {
         rc = batch_alloc(b, &b->kbase[l], b->slot_stride * n_slots) || batch_alloc(b, &b->vbase[l], b->slot_stride * n_slots);
+        b->kv_bytes += 2 * b->slot_stride * n_slots * sizeof(bf16_t);
         for (int s = 0; s < n_slots && !rc; ++s) {
             b->slot_k[s].push_back(b->kbase[l] + (size_t)s * b->slot_stride);
             b->slot_v[s].push_back(b->vbase[l] + (size_t)s * b->slot_stride);
         }
     }
+    for (int l = 0; l < L && !rc && kv_bits == 8; ++l) {
+        Kv8Layer q = {};
+        rc = batch_alloc(b, &q.kq, b->slot_stride * n_slots) || batch_alloc(b, &q.vq, b->slot_stride * n_slots) ||
+             batch_alloc(b, &q.ksb, b->sb_stride * n_slots) || batch_alloc(b, &q.vsb, b->sb_stride * n_slots);
+        b->kv_bytes += 2 * (b->slot_stride + b->sb_stride * sizeof(uint32_t)) * n_slots;
+        b->layer8.push_back(q);
+        for (int s = 0; s < n_slots && !rc; ++s)
+            b->slot8[s].push_back({q.kq + (size_t)s * b->slot_stride, q.vq + (size_t)s * b->slot_stride, q.ksb + (size_t)s * b->sb_stride,
+                                   q.vsb + (size_t)s * b->sb_stride});
+    }
+    if (kv_bits == 8 && !rc) {
+        bf16_t *sk = nullptr, *sv = nullptr;
+        rc = batch_alloc(b, &sk, b->slot_stride) || batch_alloc(b, &sv, b->slot_stride);
+        b->stage_k.assign(L, sk);
+        b->stage_v.assign(L, sv);
+    }
     b->nsplit_cap = cap / kChunk;
-    rc = rc || batch_alloc(b, &b->slots, (size_t)n_slots) || batch_alloc(b, &b->row_slot, (size_t)kMaxSlots) ||
+    rc = rc || batch_alloc(b, &b->slots, (size_t)n_slots) || batch_alloc(b, &b->dbg_slots, (size_t)n_slots) || batch_alloc(b, &b->row_slot, (size_t)kMaxSlots) ||
          batch_alloc(b, &b->step_logits, (size_t)kMaxSlots * V) || batch_alloc(b, &b->slot_logits, (size_t)n_slots * V) ||
          batch_alloc(b, &b->ring, (size_t)kRingSteps * kMaxSlots) ||
          batch_alloc(b, &b->ws_o, (size_t)kMaxSlots * m->H * b->nsplit_cap * D) || batch_alloc(b, &b->ws_ml, (size_t)kMaxSlots * m->H * b->nsplit_cap * 2);
@@ -564,7 +663,8 @@ int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt,
     if (m->cfg.quant_bits && !prow) dq_cache_prepare(m);
     if (prefill_reserve(m, n_prompt, !prow)) return 1;
     OMX_HIP_CHECK(hipMemcpyAsync(m->prompt_dev, prompt, (size_t)n_prompt * 4, hipMemcpyHostToDevice, s));
-    const KvSlabs kv = {b->slot_k[slot].data(), b->slot_v[slot].data(), b->cap};
+    const KvSlabs kv = b->kv_bits ? KvSlabs{b->stage_k.data(), b->stage_v.data(), b->cap, b->slot8[slot].data()}
+                                  : KvSlabs{b->slot_k[slot].data(), b->slot_v[slot].data(), b->cap};
     if (prefill_prefix_batched(m, n_prompt, off, nullptr, /*full_last=*/true, prow, &kv)) return 1;
     // the last row through the head and the slot's sampler: the sample launch turns pos = off + n - 1 into off + n
     BatchSlot v = {};
@@ -602,6 +702,15 @@ int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint
     for (size_t l = 0; l < b->kbase.size(); ++l) {
         OMX_HIP_CHECK(hipMemcpy2DAsync(b->slot_k[dst][l], pitch, b->slot_k[src][l], pitch, width, (size_t)m->Hkv, hipMemcpyDeviceToDevice, s));
         OMX_HIP_CHECK(hipMemcpy2DAsync(b->slot_v[dst][l], pitch, b->slot_v[src][l], pitch, width, (size_t)m->Hkv, hipMemcpyDeviceToDevice, s));
+    }
+    // (a kv_bits = 8 batch: the packed rows and their scale | bias words)
+    const size_t qpitch = (size_t)b->cap * D, qwidth = (size_t)pos * D, spitch = (size_t)b->cap * (D / 64) * 4, swidth = (size_t)pos * (D / 64) * 4;
+    for (size_t l = 0; l < b->layer8.size(); ++l) {
+        const Kv8Layer &from = b->slot8[src][l], &to = b->slot8[dst][l];
+        OMX_HIP_CHECK(hipMemcpy2DAsync(to.kq, qpitch, from.kq, qpitch, qwidth, (size_t)m->Hkv, hipMemcpyDeviceToDevice, s));
+        OMX_HIP_CHECK(hipMemcpy2DAsync(to.vq, qpitch, from.vq, qpitch, qwidth, (size_t)m->Hkv, hipMemcpyDeviceToDevice, s));
+        OMX_HIP_CHECK(hipMemcpy2DAsync(to.ksb, spitch, from.ksb, spitch, swidth, (size_t)m->Hkv, hipMemcpyDeviceToDevice, s));
+        OMX_HIP_CHECK(hipMemcpy2DAsync(to.vsb, spitch, from.vsb, spitch, swidth, (size_t)m->Hkv, hipMemcpyDeviceToDevice, s));
     }
     BatchSlot v = {};
     if (resample) {
@@ -671,13 +780,7 @@ int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int
     const bool packed = m->cfg.quant_bits != 0;
     if (prefill_reserve(m, n_slots, false)) return 1;
     OMX_HIP_CHECK(hipMemcpyAsync(b->row_slot, rows, (size_t)n_slots * 4, hipMemcpyHostToDevice, s));
-    RaggedRows rag = {};
-    rag.slots = b->slots; rag.row_slot = b->row_slot;
-    rag.kbase = b->kbase.data(); rag.vbase = b->vbase.data();
-    rag.slot_stride = b->slot_stride; rag.cap = b->cap;
-    rag.chunk = kChunk; rag.nsplit_cap = b->nsplit_cap;
-    rag.nsplit = (longest + kChunk - 1) / kChunk;   // the longest listed sequence at the end of the call
-    rag.ws_o = b->ws_o; rag.ws_ml = b->ws_ml;
+    RaggedRows rag = batch_rows(b, longest);        // the longest listed sequence at the end of the call
     // the groups of the call: positions only grow inside it, so a row that may read a split from its owner now may do so at every step
     rag.group_min = b->group_min; rag.group_rows = b->group_rows;
     for (int r = 0; r < n_slots; ++r) {
@@ -686,7 +789,7 @@ int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int
         rag.grp_shared[r] = sh;
         int same = 0;
         for (int q = 0; q <= r; ++q) same += sh > 0 && rag.grp_shared[q] > 0 && rag.grp_owner[q] == rag.grp_owner[r];
-        rag.grouped = rag.grouped || same >= b->group_min;
+        rag.grouped = rag.grouped || (same >= b->group_min && !b->kv_bits);   // (8-bit slabs: every row reads its own, always)
     }
     OMX_HIP_CHECK(hipEventRecord(m->ev0, s));
     for (int i = 0; i < n_steps; ++i) {
@@ -726,6 +829,76 @@ int omx_qwen3_batch_offset(omx_qwen3_batch b, int slot, int* offset) {
     OMX_HIP_CHECK(hipMemcpyAsync(&v, b->slots + slot, sizeof(v), hipMemcpyDeviceToHost, b->m->stream));
     OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
     *offset = v.pos;
+    return 0;
+}
+
+int omx_qwen3_batch_kv_bytes(omx_qwen3_batch b, size_t* bytes) {
+    OMX_REQUIRE(b && bytes, "omx_qwen3_batch_kv_bytes: null argument");
+    *bytes = b->kv_bytes;
+    return 0;
+}
+
+int omx_qwen3_batch_kv_read(omx_qwen3_batch b, int slot, int layer, int first, int n, void* k_rows, void* v_rows, void* k_scales,
+                            void* k_biases, void* v_scales, void* v_biases) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_kv_read");
+    omx_qwen3 m = b->m;
+    const int L = m->cfg.num_hidden_layers, D = m->cfg.head_dim, Hkv = m->Hkv, gpr = D / 64;
+    OMX_REQUIRE(layer >= 0 && layer < L, "omx_qwen3_batch_kv_read: layer %d out of range (0..%d)", layer, L - 1);
+    OMX_REQUIRE(k_rows && v_rows, "omx_qwen3_batch_kv_read: null argument");
+    OMX_REQUIRE(first >= 0 && n >= 1 && first + n <= b->pos[slot], "omx_qwen3_batch_kv_read: rows [%d, %d) of the %d slot %d holds", first,
+                first + n, b->pos[slot], slot);
+    hipStream_t s = m->stream;
+    if (!b->kv_bits) {
+        OMX_REQUIRE(!k_scales && !k_biases && !v_scales && !v_biases, "omx_qwen3_batch_kv_read: scales / biases asked of a bf16 batch "
+                    "(kv_bits 0 stores bf16 rows; pass null)");
+        const size_t pitch = (size_t)b->cap * D * 2, width = (size_t)n * D * 2;
+        OMX_HIP_CHECK(hipMemcpy2DAsync(k_rows, width, b->slot_k[slot][layer] + (size_t)first * D, pitch, width, (size_t)Hkv, hipMemcpyDeviceToHost, s));
+        OMX_HIP_CHECK(hipMemcpy2DAsync(v_rows, width, b->slot_v[slot][layer] + (size_t)first * D, pitch, width, (size_t)Hkv, hipMemcpyDeviceToHost, s));
+        OMX_HIP_CHECK(hipStreamSynchronize(s));
+        return 0;
+    }
+    OMX_REQUIRE(k_scales && k_biases && v_scales && v_biases, "omx_qwen3_batch_kv_read: a kv_bits 8 batch returns scales and biases; null argument");
+    // the codes of a row are MLX's words as they lie (element j = byte j, LSB first); the scale | bias words are split on the host
+    const Kv8Layer& q = b->slot8[slot][layer];
+    const size_t qpitch = (size_t)b->cap * D, qwidth = (size_t)n * D, spitch = (size_t)b->cap * gpr * 4, swidth = (size_t)n * gpr * 4;
+    std::vector<uint32_t> ksb((size_t)Hkv * n * gpr), vsb((size_t)Hkv * n * gpr);
+    OMX_HIP_CHECK(hipMemcpy2DAsync(k_rows, qwidth, q.kq + (size_t)first * D, qpitch, qwidth, (size_t)Hkv, hipMemcpyDeviceToHost, s));
+    OMX_HIP_CHECK(hipMemcpy2DAsync(v_rows, qwidth, q.vq + (size_t)first * D, qpitch, qwidth, (size_t)Hkv, hipMemcpyDeviceToHost, s));
+    OMX_HIP_CHECK(hipMemcpy2DAsync(ksb.data(), swidth, q.ksb + (size_t)first * gpr, spitch, swidth, (size_t)Hkv, hipMemcpyDeviceToHost, s));
+    OMX_HIP_CHECK(hipMemcpy2DAsync(vsb.data(), swidth, q.vsb + (size_t)first * gpr, spitch, swidth, (size_t)Hkv, hipMemcpyDeviceToHost, s));
+    OMX_HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t i = 0; i < ksb.size(); ++i) {
+        ((uint16_t*)k_scales)[i] = (uint16_t)(ksb[i] & 0xFFFFu); ((uint16_t*)k_biases)[i] = (uint16_t)(ksb[i] >> 16);
+        ((uint16_t*)v_scales)[i] = (uint16_t)(vsb[i] & 0xFFFFu); ((uint16_t*)v_biases)[i] = (uint16_t)(vsb[i] >> 16);
+    }
+    return 0;
+}
+
+int omx_qwen3_batch_debug_attention(omx_qwen3_batch b, int layer, const int* slots, int n, const void* q, void* out) {
+    OMX_REQUIRE(b && slots && q && out, "omx_qwen3_batch_debug_attention: null argument");
+    omx_qwen3 m = b->m;
+    const int L = m->cfg.num_hidden_layers, D = m->cfg.head_dim, H = m->H;
+    OMX_REQUIRE(layer >= 0 && layer < L, "omx_qwen3_batch_debug_attention: layer %d out of range (0..%d)", layer, L - 1);
+    OMX_REQUIRE(n >= 1 && n <= kMaxSlots, "omx_qwen3_batch_debug_attention: %d rows (1..%d)", n, kMaxSlots);
+    int longest = 0;
+    BatchSlot table[kMaxSlots] = {};
+    for (int r = 0; r < n; ++r) {
+        const int slot = slots[r];
+        OMX_REQUIRE(slot >= 0 && slot < b->n_slots, "omx_qwen3_batch_debug_attention: slot %d out of range (0..%d)", slot, b->n_slots - 1);
+        OMX_REQUIRE(b->prefilled[slot] && b->pos[slot] >= 1, "omx_qwen3_batch_debug_attention: slot %d has not been prefilled", slot);
+        table[slot].pos = b->pos[slot] - 1;   // the launch reads pos + 1 rows: the rows the slot holds, nothing appended
+        longest = std::max(longest, b->pos[slot]);
+    }
+    hipStream_t s = m->stream;
+    if (prefill_reserve(m, n, false)) return 1;
+    OMX_HIP_CHECK(hipMemcpyAsync(b->dbg_slots, table, (size_t)b->n_slots * sizeof(BatchSlot), hipMemcpyHostToDevice, s));
+    OMX_HIP_CHECK(hipMemcpyAsync(b->row_slot, slots, (size_t)n * 4, hipMemcpyHostToDevice, s));
+    OMX_HIP_CHECK(hipMemcpyAsync(m->pf_qt, q, (size_t)n * H * D * sizeof(bf16_t), hipMemcpyHostToDevice, s));
+    RaggedRows rag = batch_rows(b, longest);
+    rag.slots = b->dbg_slots;                 // the batch's own table stays as it is
+    if (launch_batch_attention(m, layer, rag, n, s)) return 1;
+    OMX_HIP_CHECK(hipMemcpyAsync(out, m->pf_attn, (size_t)n * H * D * sizeof(bf16_t), hipMemcpyDeviceToHost, s));
+    OMX_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
 }
 

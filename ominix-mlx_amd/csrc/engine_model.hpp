@@ -62,11 +62,23 @@ struct EncodeOpts {
 
 // (BatchSlot, one slot of a batch object in device memory: step_state.hpp)
 
-// KV slabs [Hkv, cap, D] per layer a batched pass appends to and attends over instead of the model's own (a batch slot's)
+// One layer of the 8-bit K/V slabs of a kv_bits = 8 batch (MLX affine codes, group 64 along the head dim; KvAffine8, attn_row.hpp):
+// codes [Hkv, cap, D] bytes and one word scale | bias (bf16 low | high) per group [Hkv, cap, D / 64] -- a slot's, or slot 0's of the
+// batch's allocation
+struct Kv8Layer {
+    uint8_t *kq, *vq;
+    uint32_t *ksb, *vsb;
+};
+
+// KV slabs [Hkv, cap, D] per layer a batched pass appends to and attends over instead of the model's own (a batch slot's).
+// packed (a slot of a kv_bits = 8 batch): k / v name the batch's ONE bf16 staging pair at every layer and packed[l] is the slot's
+// storage -- before layer l's scatter rows [0, off) are expanded into the pair, after it rows [off, off + T) are packed into packed[l]
+// and the pair's rows replaced by their dequantised values (launch_kv8_rows)
 struct KvSlabs {
     bf16_t* const* k;
     bf16_t* const* v;
     int cap;
+    const Kv8Layer* packed = nullptr;
 };
 
 // The ragged form of the batched pass: row r is the pending token of slot row_slot[r], at that slot's position, on that slot's slabs
@@ -86,6 +98,10 @@ struct RaggedRows {
     int grp_owner[8], grp_shared[8];
     bool grouped;
     int group_min, group_rows;
+    // a kv_bits = 8 batch: kv8[l] = layer l's 8-bit slabs, slot s at + s * slot_stride codes and + s * sb_stride words (kbase / vbase
+    // unused, never grouped)
+    const Kv8Layer* kv8;
+    size_t sb_stride;
 };
 
 }  // namespace omx
@@ -267,5 +283,6 @@ void launch_encoder_mask(bf16_t* mask, const uint8_t* am, int T, hipStream_t s);
 int launch_batch_embed(omx_qwen3 m, const RaggedRows& rag, int T, hipStream_t s);
 int launch_batch_scatter(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s);
 int launch_batch_attention(omx_qwen3 m, int layer, const RaggedRows& rag, int T, hipStream_t s);
+int launch_kv8_rows(const Kv8Layer& L, bf16_t* ks, bf16_t* vs, int Hkv, int D, int cap, int r0, int n, bool pack, hipStream_t s);
 
 }  // namespace omx

@@ -292,12 +292,16 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
         }
         bf16_t* const kc = kv ? kv->k[l] : m->kcache[l];
         bf16_t* const vc = kv ? kv->v[l] : m->vcache[l];
+        // (a slot of a kv_bits = 8 batch: what the slot holds of this layer into the staging pair the rows are appended to ...)
+        if (kv && kv->packed && launch_kv8_rows(kv->packed[l], kc, vc, Hkv, D, cap, 0, off, /*pack=*/false, s)) return 1;
         if (rag) {
             if (launch_batch_scatter(m, l, *rag, T, s)) return 1;
         } else
         if (launch_qk_norm_rope_scatter(m->pf_q, m->pf_k, m->pf_v, L.q_norm, L.k_norm, m->rope_cos, m->rope_sin, m->pf_qt,
                                         kc, vc, T, H, Hkv, D, cap, off, c.rms_norm_eps, s, f16))
             return 1;
+        // (... and the new rows packed into the slot's slabs, their staging copies replaced by what the codes dequantise to)
+        if (kv && kv->packed && launch_kv8_rows(kv->packed[l], kc, vc, Hkv, D, cap, off, T, /*pack=*/true, s)) return 1;
         if (!enc && !full_last && l == c.num_hidden_layers - 1) break;   // a prefix only has to leave its K/V rows behind
         const bool skv_off = env_off("OMX_PREFILL_SPLITKV");
         if (f16) {

@@ -56,14 +56,8 @@ __global__ __launch_bounds__(256) void quantize_kernel(uint32_t* __restrict__ pa
     }
     mx = wave_max(mx);
     mn = -wave_max(-mn);
-    float scale = fmaxf((mx - mn) / n_bins, 1e-7f);
-    const bool side = fabsf(mn) > fabsf(mx);
-    scale = side ? scale : -scale;
-    const float edge = side ? mn : mx;
-    const float q0 = rintf(edge / scale);
-    const bool at_zero = q0 == 0.f;
-    scale = at_zero ? scale : edge / q0;
-    const float bias = at_zero ? 0.f : edge;
+    float scale, bias;
+    affine_group(mx, mn, n_bins, scale, bias);
     if (lane == 0) {
         Elem<DT>::st(scales + g, scale);
         Elem<DT>::st(biases + g, bias);
@@ -74,7 +68,7 @@ __global__ __launch_bounds__(256) void quantize_kernel(uint32_t* __restrict__ pa
         uint32_t qv[2] = {0u, 0u};
         for (int i = 0; i < per_lane; ++i) {
             const int e = lane * per_lane + i;
-            if (e < group) qv[i] = (uint32_t)fminf(fmaxf(rintf((v[i] - bias) / scale), 0.f), n_bins);
+            if (e < group) qv[i] = (uint32_t)affine_code(v[i], scale, bias, n_bins);
         }
         const int n_words = group * BITS / 32;
         const int e_first = (32 * lane) / BITS;
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(256) void quantize_kernel(uint32_t* __restrict__ pa
     for (int i = 0; i < per_lane; ++i) {
         const int e = lane * per_lane + i;
         if (e < group) {
-            const float q = fminf(fmaxf(rintf((v[i] - bias) / scale), 0.f), n_bins);
+            const float q = affine_code(v[i], scale, bias, n_bins);
             word |= (uint32_t)q << ((e % EPW) * BITS);
         }
     }

@@ -134,6 +134,23 @@ __device__ __forceinline__ void stage_chunk(bf16_t* xs, float* xsum, int i, cons
     if (((i >> 3) & (EPL / 8 - 1)) == 0) xsum[i / EPL] = sv;
 }
 
+// MLX affine_quantize of one group, given its extremes: the f32 scale and bias the codes are computed with (the stored pair is their
+// rounding to the scales' dtype).  The text of quantize_kernel (quant.hip) and of the 8-bit K/V cache's append (prefill.hip)
+__device__ __forceinline__ void affine_group(float mx, float mn, float n_bins, float& scale, float& bias) {
+    scale = fmaxf((mx - mn) / n_bins, 1e-7f);
+    const bool side = fabsf(mn) > fabsf(mx);
+    scale = side ? scale : -scale;
+    const float edge = side ? mn : mx;
+    const float q0 = rintf(edge / scale);
+    const bool at_zero = q0 == 0.f;
+    scale = at_zero ? scale : edge / q0;
+    bias = at_zero ? 0.f : edge;
+}
+// ... and the code of element v under that pair
+__device__ __forceinline__ float affine_code(float v, float scale, float bias, float n_bins) {
+    return fminf(fmaxf(rintf((v - bias) / scale), 0.f), n_bins);
+}
+
 // One row of QuantizedEmbedding::forward straight from the packed table, by one block: element j of row `id` as (float)q * scale + bias
 // with one rounding, the expression of dequantize_kernel / dequantize_chunk_kernel (quant.hip).  The text of qembed_rows_kernel
 // (engine_prefill.hip) and of the packed batch_embed_kernel (engine_batch.hip)

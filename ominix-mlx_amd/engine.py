@@ -114,6 +114,11 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_batch_last_decode_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "omx_qwen3_batch_fork": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_batch_shared": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    # ... with its K/V storage chosen (kv_bits 8: MLX affine rows, quantised on append, read packed), and what reads the slabs back
+    "omx_qwen3_batch_create_kv": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int, c_int]),
+    "omx_qwen3_batch_kv_bytes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_size_t)]),
+    "omx_qwen3_batch_kv_read": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "omx_qwen3_batch_debug_attention": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p]),
     # test hook of the dense decode GEMV (csrc/gemv.hip): one launch of a prologue / epilogue form, bf16 or float16
     "omx_debug_gemv": (c_int, [c_void_p] * 9 + [c_int] * 7 + [c_float, c_int, c_void_p]),
     "omx_debug_gemv_grid": (c_int, [c_int, c_int]),
@@ -484,9 +489,10 @@ class Model:
         check(lib.omx_qwen3_step_bytes(self._h, ctx, ctypes.byref(v)))
         return v.value
 
-    def batch(self, n_slots: int, max_context: int = 0) -> "Batch":
-        """Up to 8 independent sequences decoded together on this model's weights (omx_qwen3_batch_*)."""
-        return Batch(self, n_slots, max_context)
+    def batch(self, n_slots: int, max_context: int = 0, kv_bits: int = 0) -> "Batch":
+        """Up to 8 independent sequences decoded together on this model's weights (omx_qwen3_batch_*).  kv_bits = 8: the K/V rows kept
+        as 8-bit MLX affine codes (group 64), quantised as they are appended and read packed by the decode attention; 0: bf16 slabs."""
+        return Batch(self, n_slots, max_context, kv_bits)
 
 
 class Batch:
@@ -494,10 +500,13 @@ class Batch:
     advances any subset of them with one weight stream per Linear.  The model's own prefill / decode / verify keep working beside it;
     calls on a model and its batches must not overlap (they share the model's stream and prompt scratch)."""
 
-    def __init__(self, model: Model, n_slots: int, max_context: int = 0):
-        self.model, self.n_slots = model, int(n_slots)
+    def __init__(self, model: Model, n_slots: int, max_context: int = 0, kv_bits: int = 0):
+        self.model, self.n_slots, self.kv_bits = model, int(n_slots), int(kv_bits)
         self._h = c_void_p()
-        check(lib.omx_qwen3_batch_create(ctypes.byref(self._h), model._h, int(n_slots), int(max_context)))
+        if self.kv_bits == 0:
+            check(lib.omx_qwen3_batch_create(ctypes.byref(self._h), model._h, int(n_slots), int(max_context)))
+        else:
+            check(lib.omx_qwen3_batch_create_kv(ctypes.byref(self._h), model._h, int(n_slots), int(max_context), self.kv_bits))
 
     def close(self) -> None:
         h = getattr(self, "_h", None)
@@ -572,6 +581,45 @@ class Batch:
 
     def reset(self, slot: int) -> None:
         check(lib.omx_qwen3_batch_reset(self._h, int(slot)))
+
+    def kv_bytes(self) -> int:
+        """Bytes of K/V storage the batch allocated (the slabs only)."""
+        v = ctypes.c_size_t()
+        check(lib.omx_qwen3_batch_kv_bytes(self._h, ctypes.byref(v)))
+        return v.value
+
+    def kv_rows(self, slot: int, layer: int, first: int = 0, n=None):
+        """Cached rows [first, first + n) (default: to the slot's offset) of one layer.  A bf16 batch: (k, v), each float32-widened
+        [Hkv, n, D].  A kv_bits = 8 batch: (k, v), each the MLX triplet (codes uint32 [Hkv, n, D / 4], scales, biases float32-widened
+        bf16 [Hkv, n, D / 64]) -- what ops.dequantize(..., 64, 8) takes."""
+        cfg = self.model.cfg
+        Hkv, D = int(cfg.num_key_value_heads), int(cfg.head_dim)
+        n = self.offset(slot) - int(first) if n is None else int(n)
+        widen = lambda raw: (raw.astype(np.uint32) << np.uint32(16)).view(np.float32)
+        if self.kv_bits == 0:
+            k, v = (np.empty((Hkv, max(n, 0), D), dtype=np.uint16) for _ in range(2))
+            check(lib.omx_qwen3_batch_kv_read(self._h, int(slot), int(layer), int(first), n, k.ctypes.data, v.ctypes.data, None, None, None, None))
+            return widen(k), widen(v)
+        k, v = (np.empty((Hkv, max(n, 0), D // 4), dtype=np.uint32) for _ in range(2))
+        ks, kb, vs, vb = (np.empty((Hkv, max(n, 0), D // 64), dtype=np.uint16) for _ in range(4))
+        check(lib.omx_qwen3_batch_kv_read(self._h, int(slot), int(layer), int(first), n, k.ctypes.data, v.ctypes.data, ks.ctypes.data,
+                                          kb.ctypes.data, vs.ctypes.data, vb.ctypes.data))
+        return (k, widen(ks), widen(kb)), (v, widen(vs), widen(vb))
+
+    def debug_attention(self, layer: int, slots, q) -> np.ndarray:
+        """Test hook: the decode attention launch alone.  q [n, H, D] (rounded to bf16) against ALL cached rows of slots[r] at `layer`
+        -> float32-widened bf16 [n, H * D].  Touches no slot state."""
+        ids = np.ascontiguousarray(slots, dtype=np.int32).ravel()
+        qf = np.ascontiguousarray(q, dtype=np.float32)
+        H, D = int(self.model.cfg.num_attention_heads), int(self.model.cfg.head_dim)
+        if qf.shape != (ids.size, H, D):
+            raise ValueError(f"debug_attention: q must be [{ids.size}, {H}, {D}], got {qf.shape}")
+        u = qf.view(np.uint32)
+        raw = ((u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) >> np.uint32(16)).astype(np.uint16)   # RNE to bf16
+        out = np.empty((ids.size, H * D), dtype=np.uint16)
+        check(lib.omx_qwen3_batch_debug_attention(self._h, int(layer), ids.ctypes.data_as(ctypes.POINTER(c_int)), ids.size,
+                                                  raw.ctypes.data, out.ctypes.data))
+        return (out.astype(np.uint32) << np.uint32(16)).view(np.float32)
 
     def last_decode_ms(self) -> float:
         """Device time of the steps of the last decode call (HIP events on the model's stream)."""

@@ -15,14 +15,23 @@
         bf16: eight slots forked from one prompt (Batch.fork) against eight slots prefilled independently with prompts of the same
         length, at every --fork-ctx, each with the grouped read of the shared span on and off (OMX_BATCH_SHARE=1 / 0) in a child
         process of its own; same windows, same device events.  One JSON line per row, then the table.  With --trace: one
-        configuration only (--fork-ctx C, OMX_BATCH_SHARE from the environment), eight forked slots, for a kernel trace."""
+        configuration only (--fork-ctx C, OMX_BATCH_SHARE from the environment), eight forked slots, for a kernel trace.
+    python tools/batch_decode.py --kv-bits 0 8 [--bits 0 4] [--ctx 2048 16384] [--steps 128] [--windows 3]
+        the K/V storage of the batch (Model.batch(kv_bits=...): 0 = bf16 slabs, 8 = 8-bit MLX affine rows read packed): per weight
+        format and context, B = 8 with every --kv-bits value in turn, each line in a child process of its own.  To reach a long
+        context quickly one slot is prefilled and forked seven times with OMX_BATCH_SHARE=0: the fork copies the rows and nothing is
+        shared, so every slot reads its own slab.  Same windows, same device events; the JSON lines carry the slab bytes
+        (Batch.kv_bytes) and the algorithmic K/V bytes a step's attention reads.  With --trace: the first --bits / --ctx / --kv-bits
+        only, filled the same way, for a kernel trace (--stats prints it)."""
 import argparse, csv, glob, json, os, subprocess, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
 ap.add_argument("--bits", type=int, nargs="+", default=[0, 4])
-ap.add_argument("--ctx", type=int, default=2048)
+ap.add_argument("--ctx", type=int, nargs="+", default=[2048], help="context per slot; the modes that take one use the first")
+ap.add_argument("--kv-bits", type=int, nargs="+", help="K/V storage of the batch (0 = bf16, 8 = 8-bit rows): the comparison described above")
+ap.add_argument("--kv-child", type=int, nargs=3, metavar=("BITS", "CTX", "KV_BITS"), help=argparse.SUPPRESS)
 ap.add_argument("--steps", type=int, default=128)
 ap.add_argument("--windows", type=int, default=3)
 ap.add_argument("--layers", type=int, default=36)
@@ -37,6 +46,27 @@ ap.add_argument("--top-k", type=int, default=0)
 ap.add_argument("--top-p", type=float, default=1.0)
 ap.add_argument("--presence-penalty", type=float, default=0.0)
 args = ap.parse_args()
+ctx_list, args.ctx = args.ctx, args.ctx[0]
+
+if args.kv_bits and not args.trace and not args.kv_child:
+    table = []
+    for bits in args.bits:
+        for ctx in ctx_list:
+            for kvb in args.kv_bits:
+                p = subprocess.run([sys.executable, os.path.abspath(__file__), "--kv-child", str(bits), str(ctx), str(kvb), "--steps", str(args.steps),
+                                    "--windows", str(args.windows), "--layers", str(args.layers)], env=dict(os.environ, OMX_BATCH_SHARE="0"),
+                                   stdout=subprocess.PIPE, text=True, stdin=subprocess.DEVNULL)
+                if p.returncode:
+                    sys.exit(f"--kv-child {bits} {ctx} {kvb} failed with status {p.returncode}")
+                for ln in p.stdout.splitlines():
+                    if ln.startswith("{"):
+                        print(ln, flush=True)
+                        table.append(json.loads(ln))
+    print(f"\n{'format':<12} {'context':>8} {'kv_bits':>8} {'ms/step':>9} {'tok/s':>9} {'slabs GB':>9} {'K/V read MB/layer':>18}")
+    for r in table:
+        print(f"{r['format']:<12} {r['ctx']:>8} {r['kv_bits']:>8} {r['ms_per_step']:>9.3f} {r['tok_s']:>9.1f} {r['kv_bytes'] / 1e9:>9.2f} "
+              f"{r['kv_read_bytes_per_layer'] / 1e6:>18.1f}")
+    sys.exit(0)
 
 if args.fork and not args.trace:
     # every (context, switch) in a process of its own: the switch is read when the batch is created, and no run inherits another's state
@@ -95,6 +125,32 @@ def median_ms(run, read_ms, steps, windows):
         ms.append(read_ms() / steps)
     return float(np.median(ms)), ms
 
+
+if args.kv_child or (args.kv_bits and args.trace):
+    bits, ctx, kvb = args.kv_child or (args.bits[0], args.ctx, args.kv_bits[0])
+    m = engine.Model(hidden_size=4096, num_hidden_layers=args.layers, intermediate_size=12288, num_attention_heads=32, num_key_value_heads=8,
+                     head_dim=128, vocab_size=V, max_context=ctx + 8 + args.steps * args.windows + 16,
+                     quantization={"bits": bits, "group_size": 64} if bits else None)
+    m.synth_weights()
+    fmt = f"{bits}-bit g64" if bits else "bf16"
+    b = m.batch(8, kv_bits=kvb)
+    b.prefill(0, prompt(ctx, 0))
+    for s in range(1, 8):
+        b.fork(0, s)
+    assert b.shared(1)[1] == 0, "run with OMX_BATCH_SHARE=0: the slots are meant to share nothing"
+    if args.trace:
+        b.decode(args.steps)
+        print(f"{fmt}, kv_bits {kvb}, 8 slots of {ctx} tokens: {b.last_decode_ms() / args.steps:.3f} ms per step", flush=True)
+    else:
+        b.decode(8)
+        ms, raw = median_ms(b.decode, b.last_decode_ms, args.steps, args.windows)
+        # a step's attention reads every cached row of every slot once per KV head: K and V, mid-run length
+        rows = 8 * 8 * (ctx + 8 + args.steps * args.windows // 2)
+        per_row = 2 * (128 * 2 if kvb == 0 else 128 + 4 * 128 // 64)
+        print(json.dumps({"format": fmt, "B": 8, "ctx": ctx, "kv_bits": kvb, "ms_per_step": ms, "tok_s": 8e3 / ms, "kv_bytes": b.kv_bytes(),
+                          "kv_read_bytes_per_layer": rows * per_row, "windows_ms": raw}), flush=True)
+    b.close(); m.close()
+    sys.exit(0)
 
 if args.fork_child or (args.fork and args.trace):
     import time

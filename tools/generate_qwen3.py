@@ -1,12 +1,13 @@
 """qwen3-mlx/examples/generate_qwen3.rs on the MI355X engine:
     python tools/generate_qwen3.py <model_dir> [prompt] [--temperature T] [--top-k K] [--top-p P] [--repetition-penalty R]
                                    [--presence-penalty Q] [--seed S] [--max-tokens N]
-    python tools/generate_qwen3.py <model_dir> --prompts-file FILE [--slots N] [--temperature T] [--seed S] [--max-tokens N]
-    python tools/generate_qwen3.py <model_dir> [prompt] --samples N [--temperature T] [--seed S] [--max-tokens N]
+    python tools/generate_qwen3.py <model_dir> --prompts-file FILE [--slots N] [--temperature T] [--seed S] [--max-tokens N] [--kv-bits 8]
+    python tools/generate_qwen3.py <model_dir> [prompt] --samples N [--temperature T] [--seed S] [--max-tokens N] [--kv-bits 8]
 (the filter flags --top-k / --top-p / --repetition-penalty / --presence-penalty apply to all three forms)
 --prompts-file: one prompt per line, decoded together over N slots of one loaded model (engine.Batch), every slot with these settings.
 --samples N: N completions (1..8) of the prompt -- or of every line of --prompts-file -- from ONE prefill: the prompt's slot is forked
 N - 1 times (Batch.fork); sibling i of every prompt draws with a fresh key sequence of seed S + i (Batch.set_sampler before its fork).
+--kv-bits 8 (the two batched forms): the batch keeps its K/V cache as 8-bit MLX affine rows (MLX's kv_bits; 0 = bf16, the default).
 Without flags: the example's plain temperature 0.7.  The Qwen3 model card's settings are --temperature 0.6 --top-k 20 --top-p 0.95."""
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,9 +28,12 @@ ap.add_argument("--max-tokens", type=int, default=100)
 ap.add_argument("--prompts-file", help="one prompt per line: all of them through generate_batch over --slots slots")
 ap.add_argument("--slots", type=int, default=8, help="sequences decoded together (1..8)")
 ap.add_argument("--samples", type=int, default=1, help="completions per prompt from one prefill (1..8)")
+ap.add_argument("--kv-bits", type=int, default=0, choices=[0, 8], help="K/V cache of the batched forms: 0 = bf16, 8 = 8-bit rows")
 args = ap.parse_args()
 if not 1 <= args.samples <= 8:
     ap.error("--samples must be 1..8")
+if args.kv_bits and not (args.prompts_file or args.samples > 1):
+    ap.error("--kv-bits applies to --prompts-file and --samples (the batched forms)")
 tokenizer = generate.load_tokenizer(args.model_dir)
 model = loader.load_model(args.model_dir)
 if args.prompts_file or args.samples > 1:
@@ -47,7 +51,7 @@ if args.prompts_file or args.samples > 1:
         eos = [int(t) for t in (e if isinstance(e, list) else [e])]
     n = args.samples
     filters = dict(top_k=args.top_k, top_p=args.top_p, repetition_penalty=args.repetition_penalty, presence_penalty=args.presence_penalty)
-    batch = model.batch(max(n, min(args.slots, len(prompts) * n)))
+    batch = model.batch(max(n, min(args.slots, len(prompts) * n)), kv_bits=args.kv_bits)
     if n == 1:
         for slot in range(batch.n_slots):
             batch.set_sampler(slot, args.temperature, args.seed + slot, **filters)
