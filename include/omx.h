@@ -234,6 +234,18 @@ int omx_qwen3_destroy(omx_qwen3 m);
  * engine reads raw pointers, so a tensor whose size disagrees with the config is refused here ("ShapeMismatch", the reference's
  * load-time shape error) instead of being read past its end                                         */
 int omx_qwen3_set_weight(omx_qwen3 m, const char* name, const void* ptr, size_t nbytes);
+/* Mixed-precision MLX checkpoints (mlx_lm.convert --quant-predicate mixed_*): config.json's "quantization" block carries, next to the
+ * global bits / group_size, an entry per module path ("model.layers.3.mlp.down_proj": {"group_size": 64, "bits": 6}).  The config's
+ * quant_bits / quant_group stay the BASE format; this call gives ONE packed matrix its own.  prefix: the module path as in the
+ * checkpoint -- model.embed_tokens, lm_head (untied models; a tied head has the embedding's format),
+ * model.layers.<i>.self_attn.{q,k,v,o}_proj, model.layers.<i>.mlp.{gate,up,down}_proj.  Legal after omx_qwen3_create and before any tensor
+ * of that prefix is set or synthesised.  Refused by name: an unknown prefix, bits outside {2,3,4,5,6,8}, a group outside {32,64,128} or
+ * one that does not divide the matrix's contraction width, a model without base quantization, and models with experts, tp_size /
+ * ep_size > 1, float16 triplets or attention_bias.  gate_proj and up_proj of a layer must end up in one format (checked when the
+ * weights are resolved).  A model without any such call launches exactly what it launched before. */
+int omx_qwen3_set_quant_format(omx_qwen3 m, const char* prefix, int bits, int group_size);
+/* the format of a packed matrix: its own, or the base format where nothing was set */
+int omx_qwen3_quant_format(omx_qwen3 m, const char* prefix, int* bits, int* group_size);
 /* device pointer (+ expected byte length; 0 = unknown) of a registered or synthesised tensor by checkpoint name */
 int omx_qwen3_get_weight(omx_qwen3 m, const char* name, const void** ptr, size_t* nbytes);
 /* allocate + fill every weight with the seeded synthetic generator (seed = base ^ crc32(name))      */

@@ -412,6 +412,39 @@ extern "C" int omx_debug_qgemv(void* out, float* out_f32, unsigned long long* ar
 }
 extern "C" int omx_debug_qgemv_grid(int N) { return omx::qgemv_grid(N); }
 
+/* test hook (tests/test_gpu_mixed_quant.py): a row-stacked packed GEMV whose members carry their OWN formats -- up to three members
+ * (w, scales, biases, n, bits, group; bf16 triplets), EPI_STORE, pro 0 none / 1 RMSNorm: the one launch of qgemv_stack_kernel.  The
+ * interleaved scale | bias words are built for K % 2048 == 0, as the engine builds them.  Synchronises the stream. */
+extern "C" int omx_debug_qgemv_mixed(void* out, const void* x, const void* norm_w, const void* const* w, const void* const* scales, const void* const* biases,
+                                     const int* n, const int* bits, const int* group, int n_members, int K, int pro, float eps, void* stream) {
+    using namespace omx;
+    OMX_REQUIRE(out && x && w && scales && biases && n && bits && group && n_members >= 1 && n_members <= 3, "omx_debug_qgemv_mixed: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    QGemvArgs a = {};
+    std::vector<void*> owned;
+    int rc = 0;
+    for (int i = 0; i < n_members && !rc; ++i) {
+        OMX_REQUIRE(w[i] && scales[i] && n[i] > 0, "omx_debug_qgemv_mixed: member %d is empty", i);
+        a.m[i] = QMat{(const uint32_t*)w[i], (const bf16_t*)scales[i], (const bf16_t*)biases[i], n[i]};
+        a.m[i].bits = bits[i]; a.m[i].group = group[i];
+        a.N += n[i];
+        if (group[i] > 0 && K % 2048 == 0 && K % group[i] == 0) {
+            uint32_t* sb = nullptr;
+            const size_t ng = (size_t)n[i] * (K / group[i]);
+            if (hipMalloc((void**)&sb, ng * 4) != hipSuccess) { rc = set_error("omx_debug_qgemv_mixed: out of memory"); break; }
+            owned.push_back(sb);
+            rc = launch_quant_interleave(sb, a.m[i].scales, a.m[i].biases, ng, s);
+            a.m[i].sb = sb;
+        }
+    }
+    a.K = K; a.group = group[0];
+    a.x = (const bf16_t*)x; a.norm_w = (const bf16_t*)norm_w; a.eps = eps; a.out = (bf16_t*)out;
+    if (!rc) rc = launch_qgemv(a, bits[0], pro, EPI_STORE, s);
+    (void)hipStreamSynchronize(s);
+    for (void* p : owned) (void)hipFree(p);
+    return rc;
+}
+
 /* test hook of the dense decode GEMV (gemv.hip): one launch_gemv of the given prologue / epilogue, bf16 (f16 = 0) or float16 (f16 = 1).
  * w0 [n0, K] | w1 | w2 row-stacked (q | k | v; N = n0 + n1 + rest), or gate (w0) / up (w1) [N, K] for EPI_SWIGLU.  EPI_ARGMAX writes
  * omx_debug_gemv_grid(N, K) partial keys to argmax_slot.  Synchronises the stream. */
@@ -686,7 +719,7 @@ extern "C" int omx_bench_gemv_warm(int N, int K, int pro, int epi, int n_copies,
 extern "C" int omx_qwen3_debug_step_forms(omx_qwen3 m, int* forms) {
     OMX_REQUIRE(m && forms, "omx_qwen3_debug_step_forms: null argument");
     forms[0] = omx::down_takes_qkv(m) ? 1 : 0;
-    forms[1] = omx::attention_takes_oproj(m) ? 1 : 0;
+    forms[1] = omx::any_layer_takes_oproj(m) ? 1 : 0;
     forms[2] = omx::step_engine_mode(m);
     forms[3] = m->chain_disabled ? 1 : 0;
     return 0;

@@ -418,9 +418,9 @@ int omx_qwen3_verify(omx_qwen3 m, const uint32_t* tokens, int n, uint32_t* greed
     // [final RMSNorm rows] -> [lm_head GEMM, n x V] -> [argmax per row]   (model.rs:423, 480-489; sampler.rs:9-18 at temperature 0)
     if (packed) {   // the packed head (or the tied q_embed table), the final RMSNorm as its prologue
         QGemvArgs a = {};
-        a.m[0] = m->q_head; a.m[0].n = V; a.N = V; a.K = hd; a.group = m->cfg.quant_group;
+        a.m[0] = m->q_head; a.m[0].n = V; a.N = V; a.K = hd; a.group = m->q_head.group;   // the head's own format
         a.x = m->pf_h; a.norm_w = m->final_norm; a.eps = m->cfg.rms_norm_eps; a.out = m->verify_logits;
-        if (packed_rows(a, n, nullptr, m->cfg.quant_bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
+        if (packed_rows(a, n, nullptr, m->q_head.bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
     } else {
         if (omx_rms_norm(m->pf_xn, m->pf_h, m->final_norm, n, hd, m->cfg.rms_norm_eps, OMX_BFLOAT16, s)) return 1;
         if (launch_gemm_bf16(m->verify_logits, m->pf_xn, m->lm_head, nullptr, n, V, hd, s)) return 1;
@@ -624,7 +624,7 @@ int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
         if (read_step_state(m, &st)) { rc = 1; break; }
         if (st.pos + 1 > m->cap) { set_error("omx_qwen3_time_step_kernels: context full"); rc = 1; break; }
         if (prepare_step(m, st.pos)) { rc = 1; break; }
-        fused_o = attention_takes_oproj(m);
+        fused_o = any_layer_takes_oproj(m);
         engine = step_engine_mode(m) == 1;
         hybrid = step_engine_mode(m) == 2;
         chain = !engine && !hybrid && down_takes_qkv(m);
@@ -700,7 +700,19 @@ int omx_qwen3_step_bytes(omx_qwen3 m, int ctx, double* bytes) {
     const double per_layer = hd * m->H * D + 2.0 * hd * m->Hkv * D + m->H * D * hd + ffn;
     // bytes per weight element: bf16 = 2; quantized = bits/8 packed + (scale + bias) bf16 per group
     const double bpe = c.quant_bits ? c.quant_bits / 8.0 + 4.0 / c.quant_group : 2.0;
-    const double w = bpe * (c.num_hidden_layers * per_layer + (double)m->V * hd);
+    double w = bpe * (c.num_hidden_layers * per_layer + (double)m->V * hd);
+    if (c.quant_bits && c.num_experts == 0 && !m->quant_formats.empty()) {   // per-matrix formats: every matrix at its own width
+        auto at = [&](const std::string& prefix, double n, double k) {
+            const std::pair<int, int> f = quant_format_of(m, prefix);
+            return n * k * (f.first / 8.0 + 4.0 / f.second);
+        };
+        w = at(c.tie_word_embeddings ? "model.embed_tokens" : "lm_head", m->V, hd);
+        for (int l = 0; l < c.num_hidden_layers; ++l) {
+            const std::string p = "model.layers." + std::to_string(l) + ".";
+            w += at(p + "self_attn.q_proj", m->H * D, hd) + at(p + "self_attn.k_proj", m->Hkv * D, hd) + at(p + "self_attn.v_proj", m->Hkv * D, hd) +
+                 at(p + "self_attn.o_proj", hd, m->H * D) + at(p + "mlp.gate_proj", m->I, hd) + at(p + "mlp.up_proj", m->I, hd) + at(p + "mlp.down_proj", hd, m->I);
+        }
+    }
     const double kv = (double)ctx * (2.0 * c.num_hidden_layers * m->Hkv * D * 2.0) + 2.0 * c.num_hidden_layers * m->Hkv * D * 2.0;
     *bytes = w + kv;
     return 0;

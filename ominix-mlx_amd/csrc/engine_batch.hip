@@ -284,11 +284,11 @@ int launch_batch_embed(omx_qwen3 m, const RaggedRows& rag, int T, hipStream_t s)
     const omx_qwen3_config& c = m->cfg;
     const int hd = c.hidden_size;
 #define OMX_BATCH_EMB(B) \
-    case B: batch_embed_kernel<B><<<T, 256, 0, s>>>(m->pf_h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, rag.slots, rag.row_slot, hd, c.quant_group); break;
-    switch (c.quant_bits) {
+    case B: batch_embed_kernel<B><<<T, 256, 0, s>>>(m->pf_h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, rag.slots, rag.row_slot, hd, m->q_embed.group); break;
+    switch (c.quant_bits ? m->q_embed.bits : 0) {      // (a packed table: the embedding's own format)
         case 0: batch_embed_kernel<0><<<T, 256, 0, s>>>(m->pf_h, m->embed, nullptr, nullptr, rag.slots, rag.row_slot, hd, 0); break;
         OMX_BATCH_EMB(2) OMX_BATCH_EMB(3) OMX_BATCH_EMB(4) OMX_BATCH_EMB(5) OMX_BATCH_EMB(6) OMX_BATCH_EMB(8)
-        default: return set_error("batch embed: quantization bits %d unsupported", c.quant_bits);
+        default: return set_error("batch embed: quantization bits %d unsupported", m->q_embed.bits);
     }
 #undef OMX_BATCH_EMB
     OMX_LAUNCH_CHECK();
@@ -457,9 +457,9 @@ int batch_head_and_sample(omx_qwen3_batch b, const bf16_t* x, const int* rows, i
     const int hd = m->cfg.hidden_size, V = m->V;
     if (m->cfg.quant_bits) {   // the packed head (or the tied q_embed table), the final RMSNorm as its prologue
         QGemvArgs a = {};
-        a.m[0] = m->q_head; a.m[0].n = V; a.N = V; a.K = hd; a.group = m->cfg.quant_group;
+        a.m[0] = m->q_head; a.m[0].n = V; a.N = V; a.K = hd; a.group = m->q_head.group;   // the head's own format
         a.x = x; a.norm_w = m->final_norm; a.eps = m->cfg.rms_norm_eps; a.out = b->step_logits;
-        if (packed_rows(a, M, nullptr, m->cfg.quant_bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
+        if (packed_rows(a, M, nullptr, m->q_head.bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
     } else {
         if (omx_rms_norm(m->pf_xn, x, m->final_norm, M, hd, m->cfg.rms_norm_eps, OMX_BFLOAT16, s)) return 1;
         if (launch_gemm_bf16(b->step_logits, m->pf_xn, m->lm_head, nullptr, M, V, hd, s)) return 1;

@@ -120,6 +120,9 @@ struct omx_qwen3_ {
     std::vector<LayerW> layers;
     std::vector<LayerQ> qlayers;             // quantized mode (cfg.quant_bits != 0)
     QMat q_embed = {}, q_head = {};
+    // per-matrix MLX formats (omx_qwen3_set_quant_format): module path -> (bits, group); a matrix without an entry has the base format
+    // cfg.quant_bits / quant_group.  resolve_weights writes each matrix's format into its QMat: the passes read it from there.
+    std::map<std::string, std::pair<int, int>> quant_formats;
     std::vector<const bf16_t*> sb_keys;   // scales pointers registered with quant_register_sb
     bf16_t* dq_buf = nullptr;                // dequantised weight of the GEMM in flight (batched prefill)
     size_t dq_cap = 0;
@@ -245,6 +248,8 @@ inline int dev_alloc(omx_qwen3 m, T** p, size_t n) {
 
 // engine_weights.hip
 int resolve_weights(omx_qwen3 m);
+// (bits, group) of the packed matrix at module path `prefix`: its own entry, else the base format
+std::pair<int, int> quant_format_of(omx_qwen3 m, const std::string& prefix);
 
 // engine_step.hip
 void drop_graphs(omx_qwen3 m);
@@ -255,7 +260,8 @@ int read_step_state(omx_qwen3 m, StepState* st);
 int write_step_state(omx_qwen3 m, const StepState& st);
 int reset_sampler_history(omx_qwen3 m);
 bool sampling_penalised(const omx_sampling& p);
-bool attention_takes_oproj(omx_qwen3 m);
+bool attention_takes_oproj(omx_qwen3 m, int layer);
+bool any_layer_takes_oproj(omx_qwen3 m);
 bool down_takes_qkv(omx_qwen3 m);
 int step_engine_mode(omx_qwen3 m);
 bool step_engine_takes(omx_qwen3 m);

@@ -121,11 +121,38 @@ static int reserve_ep_partial(omx_qwen3 m, int T) {
 }
 
 // one packed Linear of the verify pass over T rows: launch_qgemv_rows in blocks of <= 8 rows (x, resid, out and the member outputs
-// advance by the block's rows)
+// advance by the block's rows).  bits / g.group: the format of the members that carry none of their own; a stack whose members differ
+// (each into its own mout) runs as one launch per run of equal-format members -- row t of every member stays bit-identical to
+// launch_qgemv on row t alone, which is a function of the member's own format
 int packed_rows(const QGemvArgs& g, int T, bf16_t* const* mout, int bits, int pro, int epi, hipStream_t s) {
+    int fb[3] = {0, 0, 0}, fg[3] = {0, 0, 0}, first = -1;
+    bool mixed = false;
+    for (int i = 0; i < 3; ++i) {
+        if (!g.m[i].w) continue;
+        fb[i] = qmat_bits(g.m[i], bits); fg[i] = qmat_group(g.m[i], g.group);
+        if (first < 0) first = i;
+        else if (fb[i] != fb[first] || fg[i] != fg[first]) mixed = true;
+    }
+    if (mixed) {
+        OMX_REQUIRE(epi == EPI_STORE && mout, "packed rows: members of different formats need a plain store into per-member outputs (gate and up must share a format)");
+        for (int i = 0; i < 3;) {
+            if (!g.m[i].w) { ++i; continue; }
+            QGemvArgs r = g;
+            r.m[0] = r.m[1] = r.m[2] = QMat{};
+            r.N = 0; r.out = nullptr; r.group = fg[i];
+            bf16_t* outs[3] = {nullptr, nullptr, nullptr};
+            int j = i, k = 0;
+            for (; j < 3 && g.m[j].w && fb[j] == fb[i] && fg[j] == fg[i]; ++j, ++k) { r.m[k] = g.m[j]; outs[k] = mout[j]; r.N += g.m[j].n; }
+            if (packed_rows(r, T, outs, fb[i], pro, epi, s)) return 1;
+            i = j;
+        }
+        return 0;
+    }
+    QGemvArgs u = g;
+    if (first >= 0) { bits = fb[first]; u.group = fg[first]; }
     for (int t0 = 0; t0 < T; t0 += 8) {
         QRowsArgs ra = {};
-        ra.g = g;
+        ra.g = u;
         ra.M = std::min(8, T - t0);
         ra.g.x = g.x + (size_t)t0 * g.K;
         if (g.resid) ra.g.resid = g.resid + (size_t)t0 * g.N;
@@ -206,35 +233,35 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
             const size_t bytes = ((size_t)qm->n * K * 2 + 255) & ~(size_t)255;
             if (m->dq_cache_bytes + bytes <= m->dq_slab_bytes) {
                 bf16_t* keep = (bf16_t*)(m->dq_slab + m->dq_cache_bytes);
-                if (launch_dequantize_bf16(keep, qm->w, qm->scales, qm->biases, qm->n, K, c.quant_group, c.quant_bits, f16, s, f16)) return nullptr;
+                if (launch_dequantize_bf16(keep, qm->w, qm->scales, qm->biases, qm->n, K, qm->group, qm->bits, f16, s, f16)) return nullptr;
                 m->dq_cache[qm->w] = keep;
                 m->dq_cache_bytes += bytes;
                 return keep;
             }
             // (the slab is full -- matrices it was not sized for: those go through the scratch every time)
         }
-        if (launch_dequantize_bf16(m->dq_buf + at, qm->w, qm->scales, qm->biases, qm->n, K, c.quant_group, c.quant_bits, f16, s, f16)) return nullptr;
+        if (launch_dequantize_bf16(m->dq_buf + at, qm->w, qm->scales, qm->biases, qm->n, K, qm->group, qm->bits, f16, s, f16)) return nullptr;
         return m->dq_buf + at;
     };
     if (rag) {
         if (launch_batch_embed(m, *rag, T, s)) return 1;
     } else if (prow) {
-        const int bits = c.quant_bits;
+        const int bits = m->q_embed.bits;      // the embedding's own format
 #define OMX_QEMB_ROWS(B) \
-        case B: OMX_LAUNCH(qembed_rows_kernel<B>, T, 256, 0, s, m->pf_h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->prompt_dev, hd, c.quant_group); break;
+        case B: OMX_LAUNCH(qembed_rows_kernel<B>, T, 256, 0, s, m->pf_h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->prompt_dev, hd, m->q_embed.group); break;
         switch (bits) { OMX_QEMB_ROWS(2) OMX_QEMB_ROWS(3) OMX_QEMB_ROWS(4) OMX_QEMB_ROWS(5) OMX_QEMB_ROWS(6) OMX_QEMB_ROWS(8) }
 #undef OMX_QEMB_ROWS
         OMX_LAUNCH_CHECK();
     } else if (quant) {
         // QuantizedEmbedding::forward: gather the packed rows, dequantise (quantized.rs:192-203)
-        const int wpr = hd * c.quant_bits / 32, gpr = hd / c.quant_group;
+        const int wpr = hd * m->q_embed.bits / 32, gpr = hd / m->q_embed.group;
         uint32_t* rows_w = (uint32_t*)m->pf_xn;                       // scratch: [T, wpr] u32 fits in [T, hd] bf16
         bf16_t* rows_s = m->pf_h2;
         bf16_t* rows_b = m->pf_h2 + (size_t)T * gpr;
         if (omx_take_rows(rows_w, m->q_embed.w, m->prompt_dev, T, wpr, OMX_FLOAT32, s)) return 1;
         if (omx_take_rows(rows_s, m->q_embed.scales, m->prompt_dev, T, gpr, OMX_BFLOAT16, s)) return 1;
         if (omx_take_rows(rows_b, m->q_embed.biases, m->prompt_dev, T, gpr, OMX_BFLOAT16, s)) return 1;
-        if (launch_dequantize_bf16(m->pf_h, (const uint32_t*)rows_w, rows_s, rows_b, T, hd, c.quant_group, c.quant_bits, f16, s, f16)) return 1;
+        if (launch_dequantize_bf16(m->pf_h, (const uint32_t*)rows_w, rows_s, rows_b, T, hd, m->q_embed.group, m->q_embed.bits, f16, s, f16)) return 1;
     } else if (omx_take_rows(m->pf_h, m->embed, m->prompt_dev, T, hd, OMX_BFLOAT16, s)) {
         return 1;
     }
@@ -269,10 +296,10 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
         if (prow) {   // q | k | v with the RMSNorm prologue, each member into its own row buffer
             QGemvArgs a = {};
             a.m[0] = Q.q; a.m[1] = Q.k; a.m[2] = Q.v;
-            a.N = (H + 2 * Hkv) * D; a.K = hd; a.group = c.quant_group;
+            a.N = (H + 2 * Hkv) * D; a.K = hd; a.group = Q.q.group;
             a.x = h; a.norm_w = L.in_ln; a.eps = c.rms_norm_eps;
             bf16_t* const outs[3] = {m->pf_q, m->pf_k, m->pf_v};
-            if (packed_rows(a, T, outs, c.quant_bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
+            if (packed_rows(a, T, outs, Q.q.bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
         } else
         if (!qkv_norm && omx_rms_norm(m->pf_xn, h, L.in_ln, T, hd, c.rms_norm_eps, act_dt, s)) return 1;
         if (qkv_norm) { qkv.pre_norm_w = L.in_ln; qkv.pre_norm_eps = c.rms_norm_eps; }
@@ -344,18 +371,18 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
             return 1;
         if (prow) {   // o + residual
             QGemvArgs a = {};
-            a.m[0] = Q.o; a.N = hd; a.K = H * D; a.group = c.quant_group;
+            a.m[0] = Q.o; a.N = hd; a.K = H * D; a.group = Q.o.group;
             a.x = m->pf_attn; a.resid = h; a.out = h2;
-            if (packed_rows(a, T, nullptr, c.quant_bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
+            if (packed_rows(a, T, nullptr, Q.o.bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
             // gate / up + nn::silu(gate) * up with the RMSNorm prologue, then down + residual
             a = QGemvArgs{};
-            a.m[0] = Q.gate; a.m[1] = Q.up; a.N = I; a.K = hd; a.group = c.quant_group;
+            a.m[0] = Q.gate; a.m[1] = Q.up; a.N = I; a.K = hd; a.group = Q.gate.group;
             a.x = h2; a.norm_w = L.post_ln; a.eps = c.rms_norm_eps; a.out = m->pf_g;
-            if (packed_rows(a, T, nullptr, c.quant_bits, PRO_RMSNORM, EPI_SWIGLU, s)) return 1;
+            if (packed_rows(a, T, nullptr, Q.gate.bits, PRO_RMSNORM, EPI_SWIGLU, s)) return 1;
             a = QGemvArgs{};
-            a.m[0] = Q.down; a.N = hd; a.K = I; a.group = c.quant_group;
+            a.m[0] = Q.down; a.N = hd; a.K = I; a.group = Q.down.group;
             a.x = m->pf_g; a.resid = h2; a.out = h;
-            if (packed_rows(a, T, nullptr, c.quant_bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
+            if (packed_rows(a, T, nullptr, Q.down.bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
             continue;
         }
         if (!(w = W(L.o, &Q.o, H * D)) || row_split(h2, m->pf_attn, w, h, H * D)) return 1;

@@ -219,19 +219,29 @@ static int add_sampling_noise(omx_qwen3 m, hipStream_t s) {
                                m->V * tp, 1.0f / m->temperature, m->f16, s);
 }
 
-// O projection inside the attention launch (csrc/attn_step.hip): bf16 weights, single rank, a shape the kernel has a register layout
-// for; OMX_ATTN_OPROJ=0 keeps the two launches
-bool attention_takes_oproj(omx_qwen3 m) {
+// O projection inside the attention launch of layer `layer` (csrc/attn_step.hip): bf16 weights -- or a packed checkpoint's layer whose OWN
+// O matrix is 4-bit --, single rank, a shape the kernel has a register layout for; OMX_ATTN_OPROJ=0 keeps the two launches
+bool attention_takes_oproj(omx_qwen3 m, int layer) {
     const bool off = env_off("OMX_ATTN_OPROJ");        // (read per call: tests flip it between engines of one process)
     const omx_qwen3_config& c = m->cfg;
     // (tensor parallel: the rank's heads and columns -- the launch then leaves the f32 partial for the all-reduce)
     // every block of that launch waits on others: all Hkv * nsplit of them must be resident, one per CU
     if (off || m->oproj_disabled || m->Hkv * m->attn_nsplit > m->cus) return false;
-    if (c.quant_bits == 4)   // 4-bit checkpoint: the packed O matrix with its interleaved scale | bias words (built at load for K % 2048 == 0)
-        return c.ep_size <= 1 && c.tp_size <= 1 && !c.quant_scales_f16 && !m->qlayers.empty() && m->qlayers[0].o.sb != nullptr &&
-               attn_step_oproj_q4_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size, c.quant_group);
-    // (a dense float16 model: the O projection stays its own launch -- the attention launch's O phase is bf16-only)
-    return c.quant_bits == 0 && !m->f16 && attn_step_oproj_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size);
+    if (c.quant_bits) {
+        // the packed O matrix in ITS format, with its interleaved scale | bias words (built at load for K % 2048 == 0)
+        if (c.ep_size > 1 || c.tp_size > 1 || c.quant_scales_f16 || layer < 0 || layer >= (int)m->qlayers.size()) return false;
+        const QMat& o = m->qlayers[layer].o;
+        return o.bits == 4 && o.sb != nullptr && attn_step_oproj_q4_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size, o.group);
+    }
+    // (a dense float16 model: the O projection stays its own launch -- the attention launch's O phase is bf16-only; every layer alike)
+    return !m->f16 && attn_step_oproj_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size);
+}
+
+// ... of ANY layer: what the fallback ladder and the step-forms hook ask (a mixed-precision checkpoint's layers may differ)
+bool any_layer_takes_oproj(omx_qwen3 m) {
+    for (int l = 0; l < m->cfg.num_hidden_layers; ++l)
+        if (attention_takes_oproj(m, l)) return true;
+    return false;
 }
 
 // down + residual of a layer and [RMSNorm + q/k/v] of the next one as ONE launch (csrc/gemv_chain.hip): the dense bf16 step of a single rank
@@ -282,7 +292,7 @@ static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* re
         a.o_resid = resid; a.o_out = out; a.o_out_f32 = out_f32; a.o_rows = c.hidden_size; a.xg = m->attn_xg;
         if (c.quant_bits) {
             const QMat& o = m->qlayers[l].o;
-            a.o_wq = o.w; a.o_sb = o.sb; a.o_group = c.quant_group;
+            a.o_wq = o.w; a.o_sb = o.sb; a.o_group = o.group;
         } else {
             a.o_w = L.o;
         }
@@ -306,11 +316,11 @@ int enqueue_step_tail(omx_qwen3 m, bool with_head, const bf16_t* h, const float*
     }
     if (c.quant_bits) {
         QGemvArgs a = {};
-        a.m[0] = m->q_head; a.m[0].n = m->V; a.N = m->V; a.K = c.hidden_size; a.group = c.quant_group;
+        a.m[0] = m->q_head; a.m[0].n = m->V; a.N = m->V; a.K = c.hidden_size; a.group = m->q_head.group;   // the head's own format
         a.x = h; a.norm_w = m->final_norm; a.eps = c.rms_norm_eps; a.out = m->logits; a.scales_f16 = c.quant_scales_f16 != 0;
         a.argmax_slot = m->argmax_partials;
         a.row_offset = c.tp_rank * m->V;                 // this rank's vocabulary shard
-        if (launch_qgemv(a, c.quant_bits, PRO_RMSNORM, EPI_ARGMAX, s)) return 1;
+        if (launch_qgemv(a, m->q_head.bits, PRO_RMSNORM, EPI_ARGMAX, s)) return 1;
     } else {
         GemvArgs a = {};
         a.w0 = m->lm_head; a.n0 = m->V; a.N = m->V; a.K = c.hidden_size;
@@ -337,13 +347,14 @@ int enqueue_step_tail(omx_qwen3 m, bool with_head, const bf16_t* h, const float*
 static int enqueue_step_quant(omx_qwen3 m, bool with_head) {
     const omx_qwen3_config& c = m->cfg;
     hipStream_t s = m->stream;
-    const int hd = c.hidden_size, D = c.head_dim, bits = c.quant_bits, group = c.quant_group;
+    const int hd = c.hidden_size, D = c.head_dim;
     const bool sf16 = c.quant_scales_f16 != 0;
+    // every launch takes its format from its members (QMat::bits / group, written by resolve_weights): a checkpoint's matrices may differ
     // 4 / 8 bits: whole fields per word; 2 / 3 / 5 / 6: runs of 32 elements (quant_chunked)
 #define OMX_QEMBED(KERNEL, B)                                                                                                      \
-    case B: OMX_LAUNCH(KERNEL<B>, 4, 256, 0, s, m->h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->st, hd, group, m->step_seq, \
+    case B: OMX_LAUNCH(KERNEL<B>, 4, 256, 0, s, m->h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->st, hd, m->q_embed.group, m->step_seq, \
                        m->rope_cur, m->rope_cos, m->rope_sin, D / 2, sf16); break;
-    switch (bits) {
+    switch (m->q_embed.bits) {
         OMX_QEMBED(qembed_chunk_kernel, 2) OMX_QEMBED(qembed_chunk_kernel, 3) OMX_QEMBED(qembed_kernel, 4)
         OMX_QEMBED(qembed_chunk_kernel, 5) OMX_QEMBED(qembed_chunk_kernel, 6) OMX_QEMBED(qembed_kernel, 8)
     }
@@ -368,32 +379,32 @@ static int enqueue_step_quant(omx_qwen3 m, bool with_head) {
         {   // [RMSNorm + QKV]
             QGemvArgs a = {};
             a.m[0] = Q.q; a.m[1] = Q.k; a.m[2] = Q.v;
-            a.N = (m->H + 2 * m->Hkv) * D; a.K = hd; a.group = group;
+            a.N = (m->H + 2 * m->Hkv) * D; a.K = hd; a.group = Q.q.group;
             a.x = h; a.norm_w = L.in_ln; a.eps = c.rms_norm_eps; a.out = m->qkv; a.scales_f16 = sf16;
-            if (launch_qgemv(a, bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
+            if (launch_qgemv(a, Q.q.bits, PRO_RMSNORM, EPI_STORE, s)) return 1;
         }
-        const bool fused_o = !tp && attention_takes_oproj(m);
+        const bool fused_o = !tp && attention_takes_oproj(m, l);
         // [q/k RMSNorm + RoPE + cache append + split-KV SDPA + merge]: the bf16 kernel (+ [O + residual] on the packed matrix)
         if (enqueue_attention(m, l, s, fused_o ? h : nullptr, fused_o ? hn : nullptr)) return 1;
         if (fused_o) {
             std::swap(h, hn);
         } else if (tp) {   // [O partial] [all-reduce] [+ residual]
             QGemvArgs a = {};
-            a.m[0] = Q.o; a.N = hd; a.K = m->H * D; a.group = group;
+            a.m[0] = Q.o; a.N = hd; a.K = m->H * D; a.group = Q.o.group;
             a.x = m->attn_out; a.out_f32 = m->partial_a; a.scales_f16 = sf16;
-            if (launch_qgemv(a, bits, PRO_NONE, EPI_F32, s) || reduce_fold(m->partial_a)) return 1;
+            if (launch_qgemv(a, Q.o.bits, PRO_NONE, EPI_F32, s) || reduce_fold(m->partial_a)) return 1;
         } else {   // [O + residual]
             QGemvArgs a = {};
-            a.m[0] = Q.o; a.N = hd; a.K = m->H * D; a.group = group;
+            a.m[0] = Q.o; a.N = hd; a.K = m->H * D; a.group = Q.o.group;
             a.x = m->attn_out; a.resid = h; a.out = hn; a.scales_f16 = sf16;
-            if (launch_qgemv(a, bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
+            if (launch_qgemv(a, Q.o.bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
             std::swap(h, hn);
         }
         if (c.num_experts > 0 && c.tp_size > 1) {
             // expert tensor parallel on packed stacks (round 5): [replicated packed router + this rank's columns of the routed experts]
             // [all-reduce of the slots' f32 partials] [weighted sum + residual with the single-device roundings]
             if (omx_moe_block_partial_tp_q(m->moe_y, m->moe_inds, m->moe_scores, h, L.post_ln, c.rms_norm_eps, OMX_QMOE_ARGS(Q), 1, hd, m->moe_I, c.num_experts, c.num_experts_per_tok, c.moe_mode,
-                                           c.norm_topk_prob, group, bits, sf16 ? 1 : 0, s))
+                                           c.norm_topk_prob, c.quant_group, c.quant_bits, sf16 ? 1 : 0, s))
                 return 1;
             if (allreduce_sum(m, m->moe_y, (size_t)c.num_experts_per_tok * hd)) return 1;
             if (omx_moe_combine_slots_ex(hn, m->moe_y, m->moe_scores, h, 1, hd, c.num_experts_per_tok, sf16 ? 1 : 0, s)) return 1;
@@ -404,34 +415,34 @@ static int enqueue_step_quant(omx_qwen3 m, bool with_head) {
             // expert parallel on packed stacks (round 5): this rank's experts only, the f32 partial all-reduced and folded into the residual
             const int el = c.num_experts / c.ep_size;
             if (omx_moe_block_partial_ep_q(m->partial_b, h, L.post_ln, c.rms_norm_eps, m->moe_xn, OMX_QMOE_ARGS(Q), 1, hd, c.moe_intermediate_size, c.num_experts,
-                                           c.num_experts_per_tok, c.moe_mode, c.norm_topk_prob, c.ep_rank * el, el, group, bits, sf16 ? 1 : 0, s))
+                                           c.num_experts_per_tok, c.moe_mode, c.norm_topk_prob, c.ep_rank * el, el, c.quant_group, c.quant_bits, sf16 ? 1 : 0, s))
                 return 1;
             if (reduce_fold(m->partial_b)) return 1;
             continue;
         }
         if (c.num_experts > 0) {   // [RMSNorm + router] [selection] [RMSNorm + expert gate/up + SwiGLU] [expert down] [sum + residual]
             if (omx_moe_block_forward_q_ex(hn, h, h, L.post_ln, c.rms_norm_eps, m->moe_xn, OMX_QMOE_ARGS(Q), 1, hd, c.moe_intermediate_size,
-                                           c.num_experts, c.num_experts_per_tok, c.moe_mode, c.norm_topk_prob, group, bits, sf16 ? 1 : 0, s))
+                                           c.num_experts, c.num_experts_per_tok, c.moe_mode, c.norm_topk_prob, c.quant_group, c.quant_bits, sf16 ? 1 : 0, s))
                 return 1;
             std::swap(h, hn);
             continue;
         }
         {   // [RMSNorm + gate/up + SwiGLU]
             QGemvArgs a = {};
-            a.m[0] = Q.gate; a.m[1] = Q.up; a.N = m->I; a.K = hd; a.group = group;
+            a.m[0] = Q.gate; a.m[1] = Q.up; a.N = m->I; a.K = hd; a.group = Q.gate.group;
             a.x = h; a.norm_w = L.post_ln; a.eps = c.rms_norm_eps; a.out = m->act; a.scales_f16 = sf16;
-            if (launch_qgemv(a, bits, PRO_RMSNORM, EPI_SWIGLU, s)) return 1;
+            if (launch_qgemv(a, Q.gate.bits, PRO_RMSNORM, EPI_SWIGLU, s)) return 1;
         }
         if (tp) {   // [down partial] [all-reduce] [+ residual]
             QGemvArgs a = {};
-            a.m[0] = Q.down; a.N = hd; a.K = m->I; a.group = group;
+            a.m[0] = Q.down; a.N = hd; a.K = m->I; a.group = Q.down.group;
             a.x = m->act; a.out_f32 = m->partial_b; a.scales_f16 = sf16;
-            if (launch_qgemv(a, bits, PRO_NONE, EPI_F32, s) || reduce_fold(m->partial_b)) return 1;
+            if (launch_qgemv(a, Q.down.bits, PRO_NONE, EPI_F32, s) || reduce_fold(m->partial_b)) return 1;
         } else {   // [down + residual]
             QGemvArgs a = {};
-            a.m[0] = Q.down; a.N = hd; a.K = m->I; a.group = group;
+            a.m[0] = Q.down; a.N = hd; a.K = m->I; a.group = Q.down.group;
             a.x = m->act; a.resid = h; a.out = hn; a.scales_f16 = sf16;
-            if (launch_qgemv(a, bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
+            if (launch_qgemv(a, Q.down.bits, PRO_NONE, EPI_RESIDUAL, s)) return 1;
             std::swap(h, hn);
         }
     }
@@ -506,7 +517,7 @@ static int enqueue_step_hybrid(omx_qwen3 m, bool with_head) {
     for (int l = 0; l < L; ++l) {
         time_next_launch(m, l, KC_QKV);                      // (the segment's time is booked on the q/k/v class of the layer it ends in)
         if (enqueue_step_engine(m, s, l)) return 1;
-        const bool fused_o = attention_takes_oproj(m);
+        const bool fused_o = attention_takes_oproj(m, l);
         time_next_launch(m, l, KC_ATTN);
         if (enqueue_attention(m, l, s, fused_o ? m->h : nullptr, fused_o ? m->h2 : nullptr, nullptr)) return 1;
         if (!fused_o) {
@@ -570,7 +581,7 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             if (launch_gemv(a, PRO_RMSNORM, EPI_STORE, s)) return 1;
             if (pending) { std::swap(h, hn); pending = nullptr; pending_n = 1; }
         }
-        const bool fused_o = attention_takes_oproj(m);
+        const bool fused_o = attention_takes_oproj(m, l);
         time_next_launch(m, l, KC_ATTN);
         // [q/k RMSNorm + RoPE + cache append + split-KV SDPA + merge]  model.rs:172-210
         if (enqueue_attention(m, l, s, fused_o ? h : nullptr, fused_o && !tp ? hn : nullptr, fused_o && tp ? m->partial_a : nullptr)) return 1;
@@ -817,7 +828,7 @@ int step_fallback(omx_qwen3 m, const StepState& st) {
     if (m->allreduce != nullptr || m->cfg.tp_size > 1 || m->cfg.ep_size > 1) return 1;
     if (!m->chain_disabled && down_takes_qkv(m)) m->chain_disabled = true;
     else if (!m->se_disabled && step_engine_takes(m)) m->se_disabled = true;
-    else if (!m->oproj_disabled && attention_takes_oproj(m)) m->oproj_disabled = true;
+    else if (!m->oproj_disabled && any_layer_takes_oproj(m)) m->oproj_disabled = true;
     else return 1;
     drop_graphs(m);
     OMX_HIP_CHECK(hipMemsetAsync(m->wait_abort, 0, 4, m->stream));

@@ -13,6 +13,29 @@ static uint32_t crc32_str(const char* s) {
 
 namespace omx {
 
+std::pair<int, int> quant_format_of(omx_qwen3 m, const std::string& prefix) {
+    auto it = m->quant_formats.find(prefix);
+    return it != m->quant_formats.end() ? it->second : std::make_pair(m->cfg.quant_bits, m->cfg.quant_group);
+}
+
+// The packed Linear / embedding the forward reads at module path `prefix` of a dense model: its contraction width K, or 0 for a path
+// that names none (layer index out of range, a norm, an lm_head the tied model does not have)
+static int packed_module_k(omx_qwen3 m, const std::string& prefix) {
+    const omx_qwen3_config& c = m->cfg;
+    if (prefix == "model.embed_tokens") return c.hidden_size;
+    if (prefix == "lm_head") return c.tie_word_embeddings ? 0 : c.hidden_size;
+    if (prefix.compare(0, 13, "model.layers.") != 0) return 0;
+    const size_t dot = prefix.find('.', 13);
+    if (dot == std::string::npos || dot == 13) return 0;
+    const std::string idx = prefix.substr(13, dot - 13);
+    if (idx.find_first_not_of("0123456789") != std::string::npos || idx.size() > 6 || atoi(idx.c_str()) >= c.num_hidden_layers) return 0;
+    const std::string sub = prefix.substr(dot + 1);
+    if (sub == "self_attn.q_proj" || sub == "self_attn.k_proj" || sub == "self_attn.v_proj" || sub == "mlp.gate_proj" || sub == "mlp.up_proj") return c.hidden_size;
+    if (sub == "self_attn.o_proj") return m->H * c.head_dim;
+    if (sub == "mlp.down_proj") return m->I;
+    return 0;
+}
+
 int resolve_weights(omx_qwen3 m) {
     if (m->weights_resolved) return 0;
     if (!m->dq_cache.empty()) {   // the weights changed under the dequantised copies of the prompt pass
@@ -35,8 +58,10 @@ int resolve_weights(omx_qwen3 m) {
         const bf16_t *w = nullptr, *sc = nullptr, *bi = nullptr;
         if (get(prefix + ".weight", &w) || get(prefix + ".scales", &sc) || get(prefix + ".biases", &bi)) return 1;
         *out = QMat{(const uint32_t*)w, sc, bi, n};
+        const std::pair<int, int> fmt = quant_format_of(m, prefix);   // the matrix's own format travels with it
+        out->bits = fmt.first; out->group = fmt.second;
         if (interleave && K > 0 && K % 2048 == 0) {   // (scale, bias) words for the packed-weight GEMV (quant.hpp)
-            const size_t ng = (size_t)stack * n * (K / c.quant_group);
+            const size_t ng = (size_t)stack * n * (K / fmt.second);
             uint32_t* sb = nullptr;
             if (dev_alloc(m, &sb, ng) || launch_quant_interleave(sb, sc, bi, ng, m->stream)) return 1;
             out->sb = sb;
@@ -45,7 +70,7 @@ int resolve_weights(omx_qwen3 m) {
         }
         // the dense decode step's matrices once more as matrix-core tiles (qgemv_mfma.hip; OMX_QGEMV_MFMA=0: the VALU kernel only)
         const bool tiles_off = env_off("OMX_QGEMV_MFMA");        // (read per model: tests compare the two kernels in one process)
-        if (!tiles_off && stack == 1 && K > 0 && !c.quant_scales_f16 && qgemv4m_shape_ok(K, c.quant_group, c.quant_bits)) {
+        if (!tiles_off && stack == 1 && K > 0 && !c.quant_scales_f16 && qgemv4m_shape_ok(K, fmt.second, fmt.first)) {
             uint32_t* tiles = nullptr;
             if (dev_alloc(m, &tiles, qgemv4m_tile_words(n, K)) || launch_qgemv4m_repack(tiles, (const uint32_t*)w, sc, bi, n, K, m->stream)) return 1;
             out->tiles = tiles;
@@ -91,6 +116,10 @@ int resolve_weights(omx_qwen3 m) {
                    lin(p + "mlp.down_proj", hd, &L.down, &Q.down, m->I)) {
             return 1;
         }
+        // the SwiGLU launch computes a (gate, up) row pair in one wave: one format for the two
+        OMX_REQUIRE(!quant || c.num_experts > 0 || (Q.gate.bits == Q.up.bits && Q.gate.group == Q.up.group),
+                    "InvalidConfig: layer %d: mlp.gate_proj (%d-bit group %d) and mlp.up_proj (%d-bit group %d) must share a quantization format",
+                    i, Q.gate.bits, Q.gate.group, Q.up.bits, Q.up.group);
     }
     if (lin("model.embed_tokens", c.vocab_size, &m->embed, &m->q_embed, 0) || get("model.norm.weight", &m->final_norm)) return 1;
     if (quant) {
@@ -140,11 +169,12 @@ static size_t expected_weight_bytes(omx_qwen3 m, const std::string& name) {
     if (kind < 0) return 0;
     const bool quant = c.quant_bits != 0;
     // [n, k] Linear (x stack): dense bf16, or the packed triplet of a quantized checkpoint; bias [n]
+    const std::pair<int, int> fmt = quant_format_of(m, stem);   // the matrix's own format
     auto lin = [&](size_t n, size_t k, size_t stack = 1) -> size_t {
         if (kind == 3) return n * 2;
         if (!quant) return kind == 0 ? stack * n * k * 2 : 0;
-        if (kind == 0) return stack * n * (k * c.quant_bits / 32) * 4;
-        return stack * n * (k / c.quant_group) * 2;
+        if (kind == 0) return stack * n * (k * fmt.first / 32) * 4;
+        return stack * n * (k / fmt.second) * 2;
     };
     auto vec = [&](size_t n) -> size_t { return kind == 0 ? n * 2 : 0; };
     if (stem == "model.embed_tokens") return lin(c.vocab_size, hd);
@@ -183,6 +213,43 @@ int omx_qwen3_set_weight(omx_qwen3 m, const char* name, const void* ptr, size_t 
     OMX_REQUIRE(m->g_full == nullptr, "omx_qwen3_set_weight: weights are frozen once the decode step is built");
     m->named[name] = ptr;
     m->weights_resolved = false;
+    return 0;
+}
+
+// The MLX format of ONE packed matrix (a mixed-precision checkpoint: config.json "quantization" carries an entry per module path next to
+// the global bits / group_size).  Legal until a tensor of that prefix is registered or synthesised: its byte counts, repacks and tiles
+// follow the format.
+int omx_qwen3_set_quant_format(omx_qwen3 m, const char* prefix, int bits, int group_size) {
+    OMX_REQUIRE(m && prefix, "omx_qwen3_set_quant_format: null argument");
+    const omx_qwen3_config& c = m->cfg;
+    OMX_REQUIRE(c.quant_bits != 0, "omx_qwen3_set_quant_format: %s: the model has no base quantization (a bf16 / float16 checkpoint)", prefix);
+    OMX_REQUIRE(c.num_experts == 0, "omx_qwen3_set_quant_format: %s: per-matrix formats with experts (num_experts %d) are not supported", prefix, c.num_experts);
+    OMX_REQUIRE(c.tp_size <= 1 && c.ep_size <= 1, "omx_qwen3_set_quant_format: %s: per-matrix formats under tensor / expert parallelism (tp_size %d, ep_size %d) are not supported",
+                prefix, c.tp_size, c.ep_size);
+    OMX_REQUIRE(!c.quant_scales_f16, "omx_qwen3_set_quant_format: %s: per-matrix formats with float16 triplets (scales_dtype float16) are not supported", prefix);
+    OMX_REQUIRE(!c.attention_bias, "omx_qwen3_set_quant_format: %s: per-matrix formats with attention_bias are not supported", prefix);
+    const int K = packed_module_k(m, prefix);
+    OMX_REQUIRE(K > 0, "omx_qwen3_set_quant_format: unknown prefix %s (a packed module of this model: model.embed_tokens, lm_head of an untied model, "
+                "model.layers.<i>.self_attn.{q,k,v,o}_proj, model.layers.<i>.mlp.{gate,up,down}_proj)", prefix);
+    OMX_REQUIRE(quant_bits_ok(bits), "omx_qwen3_set_quant_format: %s: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", prefix, bits);
+    OMX_REQUIRE(group_size == 32 || group_size == 64 || group_size == 128, "omx_qwen3_set_quant_format: %s: group_size must be 32, 64 or 128 (got %d)", prefix, group_size);
+    OMX_REQUIRE(K % group_size == 0, "omx_qwen3_set_quant_format: %s: the contraction width (%d) must be divisible by the group size (%d)", prefix, K, group_size);
+    const std::string p = prefix;
+    for (const char* leaf : {".weight", ".scales", ".biases"})
+        OMX_REQUIRE(m->named.find(p + leaf) == m->named.end(), "omx_qwen3_set_quant_format: %s%s is already set: a matrix's format is fixed before its tensors arrive", prefix, leaf);
+    OMX_REQUIRE(m->g_full == nullptr, "omx_qwen3_set_quant_format: weights are frozen once the decode step is built");
+    m->quant_formats[p] = std::make_pair(bits, group_size);
+    m->weights_resolved = false;
+    return 0;
+}
+
+// ... and the format a matrix has: its own, or the base format where nothing was set
+int omx_qwen3_quant_format(omx_qwen3 m, const char* prefix, int* bits, int* group_size) {
+    OMX_REQUIRE(m && prefix && bits && group_size, "omx_qwen3_quant_format: null argument");
+    OMX_REQUIRE(m->cfg.quant_bits != 0, "omx_qwen3_quant_format: %s: the model has no base quantization", prefix);
+    OMX_REQUIRE(m->cfg.num_experts > 0 || packed_module_k(m, prefix) > 0, "omx_qwen3_quant_format: unknown prefix %s", prefix);
+    const std::pair<int, int> fmt = quant_format_of(m, prefix);
+    *bits = fmt.first; *group_size = fmt.second;
     return 0;
 }
 
@@ -239,10 +306,11 @@ static int synth_weights_impl(omx_qwen3 m, uint32_t base_seed, bool peaked) {
             if (omx_fill_uniform_2d(scratch, rows, cols, ld_full ? ld_full : cols, row0, col0, seed, amp_w, 0.0f, OMX_BFLOAT16, m->stream)) return 1;
             uint32_t* pk = nullptr;
             bf16_t *sc = nullptr, *bi = nullptr;
-            if (dev_alloc(m, &pk, (size_t)(rows * cols * c.quant_bits / 32)) || dev_alloc(m, &sc, (size_t)(rows * cols / c.quant_group)) ||
-                dev_alloc(m, &bi, (size_t)(rows * cols / c.quant_group)))
+            const std::pair<int, int> fmt = quant_format_of(m, prefix);   // quantised in the matrix's own format
+            if (dev_alloc(m, &pk, (size_t)(rows * cols * fmt.first / 32)) || dev_alloc(m, &sc, (size_t)(rows * cols / fmt.second)) ||
+                dev_alloc(m, &bi, (size_t)(rows * cols / fmt.second)))
                 return 1;
-            if (omx_quantize(pk, sc, bi, scratch, rows, (int)cols, c.quant_group, c.quant_bits, OMX_BFLOAT16, m->stream)) return 1;
+            if (omx_quantize(pk, sc, bi, scratch, rows, (int)cols, fmt.second, fmt.first, OMX_BFLOAT16, m->stream)) return 1;
             m->named[prefix + ".weight"] = pk;
             m->named[prefix + ".scales"] = sc;
             m->named[prefix + ".biases"] = bi;
@@ -270,10 +338,11 @@ static int synth_weights_impl(omx_qwen3 m, uint32_t base_seed, bool peaked) {
                         uint32_t* pk = nullptr;
                         bf16_t *sc = nullptr, *bi = nullptr;
                         const int64_t rows = E * Il;
-                        if (dev_alloc(m, &pk, (size_t)(rows * hd * c.quant_bits / 32)) || dev_alloc(m, &sc, (size_t)(rows * hd / c.quant_group)) ||
-                            dev_alloc(m, &bi, (size_t)(rows * hd / c.quant_group)))
+                        const std::pair<int, int> fmt = quant_format_of(m, prefix);
+                        if (dev_alloc(m, &pk, (size_t)(rows * hd * fmt.first / 32)) || dev_alloc(m, &sc, (size_t)(rows * hd / fmt.second)) ||
+                            dev_alloc(m, &bi, (size_t)(rows * hd / fmt.second)))
                             return 1;
-                        if (omx_quantize(pk, sc, bi, scratch, rows, hd, c.quant_group, c.quant_bits, OMX_BFLOAT16, m->stream)) return 1;
+                        if (omx_quantize(pk, sc, bi, scratch, rows, hd, fmt.second, fmt.first, OMX_BFLOAT16, m->stream)) return 1;
                         m->named[prefix + ".weight"] = pk; m->named[prefix + ".scales"] = sc; m->named[prefix + ".biases"] = bi;
                         return 0;
                     };

@@ -37,11 +37,11 @@ struct PerOp {
     mlx_array matmul(mlx_array a, mlx_array b) { OP(mlx_matmul(&r, a, b, s)); }
     mlx_array linear(mlx_array x, mlx_array w) { return matmul(x, t(w)); }      // nn::Linear::forward (linear.rs:87-92), no bias
     // nn::QuantizedLinear::forward (quantized.rs:366-375): quantized_matmul(x, w, scales, biases, transpose = true, group_size, bits)
-    int q_group = 64, q_bits = 4;
-    mlx_array qmm(mlx_array x, mlx_array w, mlx_array sc, mlx_array bi) {
+    // (group_size, bits: the QuantizedLinear's own -- a mixed-precision checkpoint's modules differ)
+    mlx_array qmm(mlx_array x, mlx_array w, mlx_array sc, mlx_array bi, int q_group, int q_bits) {
         OP(mlx_quantized_matmul(&r, x, w, sc, bi, true, mlx_optional_int{q_group, true}, mlx_optional_int{q_bits, true}, "affine", s));
     }
-    mlx_array dequantize(mlx_array w, mlx_array sc, mlx_array bi) {
+    mlx_array dequantize(mlx_array w, mlx_array sc, mlx_array bi, int q_group, int q_bits) {
         OP(mlx_dequantize(&r, w, sc, bi, mlx_optional_int{q_group, true}, mlx_optional_int{q_bits, true}, "affine", mlx_optional_dtype{MLX_BFLOAT16, false}, s));
     }
     mlx_array reshape(mlx_array a, std::vector<int> sh) { OP(mlx_reshape(&r, a, sh.data(), sh.size(), s)); }
@@ -123,6 +123,7 @@ struct KvCache {
 // a Linear's tensors: the bf16 matrix, or the (packed weight, scales, biases) triplet of an MLX-quantized checkpoint (model.rs:621-727)
 struct Lin {
     mlx_array w{nullptr}, sc{nullptr}, bi{nullptr};
+    int bits = 0, group = 0;      // a packed Linear's own format (omx_qwen3_quant_format)
     void release() { for (mlx_array* a : {&w, &sc, &bi}) if (a->ctx) { mlx_array_free(*a); a->ctx = nullptr; } }
 };
 struct LayerW { Lin q, k, v, o, gate, up, down; mlx_array in_ln, post_ln, q_norm, k_norm; };
@@ -162,8 +163,9 @@ extern "C" int omx_bench_qwen3_per_op_ex(omx_qwen3 model, const omx_qwen3_config
     // a Linear [n, k] by its key prefix: `.weight` alone, or the quantized triplet
     auto borrow_lin = [&](const std::string& prefix, int n, int k, Lin* out) -> int {
         if (!quant) return borrow(prefix + ".weight", {n, k}, &out->w);
-        return borrow(prefix + ".weight", {n, k * cfg->quant_bits / 32}, &out->w, MLX_UINT32) ||
-               borrow(prefix + ".scales", {n, k / cfg->quant_group}, &out->sc) || borrow(prefix + ".biases", {n, k / cfg->quant_group}, &out->bi);
+        if (omx_qwen3_quant_format(model, prefix.c_str(), &out->bits, &out->group)) return 1;
+        return borrow(prefix + ".weight", {n, k * out->bits / 32}, &out->w, MLX_UINT32) ||
+               borrow(prefix + ".scales", {n, k / out->group}, &out->sc) || borrow(prefix + ".biases", {n, k / out->group}, &out->bi);
     };
     std::vector<LayerW> W(L);
     Lin embed, head;
@@ -182,8 +184,7 @@ extern "C" int omx_bench_qwen3_per_op_ex(omx_qwen3 model, const omx_qwen3_config
     if (rc) return 1;
     PerOp P;
     P.s = mlx_default_gpu_stream_new();
-    if (quant) { P.q_group = cfg->quant_group; P.q_bits = cfg->quant_bits; }
-    auto lin = [&](mlx_array x, const Lin& w) { return quant ? P.qmm(x, w.w, w.sc, w.bi) : P.linear(x, w.w); };
+    auto lin = [&](mlx_array x, const Lin& w) { return quant ? P.qmm(x, w.w, w.sc, w.bi, w.group, w.bits) : P.linear(x, w.w); };
     std::vector<KvCache> cache(L);
     const float scale = 1.0f / sqrtf((float)D);
 
@@ -192,7 +193,7 @@ extern "C" int omx_bench_qwen3_per_op_ex(omx_qwen3 model, const omx_qwen3_config
     // the end of their scopes -- i.e. BEFORE the caller's async_eval: an intermediate nobody holds may then be fused away (mlxc_lazy.hpp).
     auto forward_sample = [&](mlx_array idx, int n, mlx_array* y, mlx_array* keep_logits = nullptr) -> int {
         // Embedding::forward -> [1, n, hidden]; QuantizedEmbedding (quantized.rs:120-164): the picked rows of the triplet, dequantised
-        mlx_array h = quant ? P.dequantize(P.take_axis(embed.w, idx, 0), P.take_axis(embed.sc, idx, 0), P.take_axis(embed.bi, idx, 0))
+        mlx_array h = quant ? P.dequantize(P.take_axis(embed.w, idx, 0), P.take_axis(embed.sc, idx, 0), P.take_axis(embed.bi, idx, 0), embed.group, embed.bits)
                             : P.take_axis(embed.w, idx, 0);
         const char* mode = n > 1 ? "causal" : "";                                    // create_attention_mask (utils.rs:156-188)
         for (int l = 0; l < L; ++l) {

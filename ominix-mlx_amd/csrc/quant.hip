@@ -18,6 +18,7 @@
 #include <hip/hip_fp16.h>
 #include "common.hpp"
 #include "gemm.hpp"
+#include <climits>
 #include <mutex>
 #include <unordered_map>
 
@@ -194,268 +195,86 @@ __global__ __launch_bounds__(256) void dequantize_any_chunk_kernel(typename Elem
 // PRO / EPI as in gemv.hip, from the same text (gemv_parts.hpp): RMSNorm prologue; store, residual add, SwiGLU
 // over (gate, up) row pairs, logits + greedy-argmax partial.
 // SB: scales and biases come interleaved from QMat::sb (one load per row and step instead of two)
+// The kernel's text is qgemv_body.inc, which one member of a mixed-format stack (qgemv_member below) includes too.
+// What each macro must expand to at an include site (a wrong expansion compiles and addresses the wrong rows):
+//   QGB_BX          int expression: this block's index among the blocks that cover the QGB_N rows (4 waves x a.rows_per_wave rows each)
+//   QGB_N           int expression: rows of the matrix / stack this block works on; every row index is clamped to QGB_N - 1 for loads
+//                   and stores are guarded by row < QGB_N
+//   QGB_GROUP       int expression: elements per scale / bias of those rows (divides a.K)
+//   QGB_COL0        EMPTY, or `+ <int expression>`: spliced behind `(size_t)by * a.N` in the address of output element 0 of the rows
+//                   -- the first output column of the matrix inside the launch's output row
+//   QGB_FIND_MEMBER EMPTY, or one statement that turns the stack row `row` into (member index `mi`, row inside that member)
+//   QGB_MEMBER      an lvalue of type const QMat: the matrix row `row` belongs to (it may use `mi`)
 template <int BITS, int W, int PRO, int EPI, int RB, bool SB = false, bool F16S = false>
 __global__ __launch_bounds__(256) void qgemv_kernel(const QGemvArgs a) {
-    typedef Act16<F16S> A16;                                // activations / outputs: bfloat16, or float16 for a float16 checkpoint (F16S)
-    constexpr bool CH = quant_chunked(BITS);
-    static_assert(!CH || W == BITS, "a chunked width streams one run of BITS words per lane and step");
-    constexpr int EPW = 32 / BITS, EPL = CH ? 32 : W * EPW;          // elements per lane per step
-    constexpr int LR = (EPI == EPI_SWIGLU) ? 2 : 1;         // physical rows per logical row
-    constexpr int NR = RB * LR;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    bf16_t* xs = reinterpret_cast<bf16_t*>(smem);                       // [K]
-    float* xsum = reinterpret_cast<float*>(smem + (size_t)a.K * 2);     // [K / EPL]
-    float* red = xsum + a.K / EPL;                                      // [8]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int by = blockIdx.y;
-    const bf16_t* xg = a.x + (size_t)(by / a.x_div) * a.K;
-    size_t e = a.w_sel ? a.w_sel[by] : 0;
-    if (!local_expert(e, a.w_sel_lo, a.w_sel_n)) return;      // a slot routed to another rank's expert (block-uniform: before any barrier)
-    bf16_t* out = a.out + (size_t)by * a.N;
+    // the rows of the stack a.m[0 .. 2], written from column 0: block blockIdx.x of a.N rows in groups of a.group
+#define QGB_BX blockIdx.x
+#define QGB_N a.N
+#define QGB_GROUP a.group
+#define QGB_COL0
+#define QGB_FIND_MEMBER if (row >= a.m[0].n) { row -= a.m[0].n; mi = 1; if (row >= a.m[1].n) { row -= a.m[1].n; mi = 2; } }
+#define QGB_MEMBER a.m[mi]
+#include "qgemv_body.inc"
+#undef QGB_BX
+#undef QGB_N
+#undef QGB_GROUP
+#undef QGB_COL0
+#undef QGB_FIND_MEMBER
+#undef QGB_MEMBER
+}
 
-    const int steps = CH ? (a.K + 64 * EPL - 1) / (64 * EPL) : a.K / (64 * EPL);
-    const int nchunks = a.K / EPL;     // (CH: lanes of the last step at chunk >= nchunks load and add nothing)
-    const int words_per_row = CH ? a.K / 32 * BITS : a.K / EPW, groups_per_row = a.K / a.group;
-    const int row_begin = (blockIdx.x * 4 + wave) * a.rows_per_wave;
-    const int row_end = min(row_begin + a.rows_per_wave, a.N);
-    uint64_t best = 0;
-    // physical row pr of the batch: which member matrix, which row inside it
-    auto locate = [&](int pr, const uint32_t*& wq, const bf16_t*& sc, const bf16_t*& bi, const uint32_t*& sbp) {
-        int mi, row;
-        if (EPI == EPI_SWIGLU) {
-            mi = pr & 1;
-            row = min(pr >> 1, a.N - 1);
-        } else {
-            row = min(pr, a.N - 1);
-            mi = 0;
-            if (row >= a.m[0].n) { row -= a.m[0].n; mi = 1; if (row >= a.m[1].n) { row -= a.m[1].n; mi = 2; } }
-        }
-        const QMat& M = a.m[mi];
-        wq = M.w + e * a.w_estride + (size_t)row * words_per_row;
-        sc = M.scales + e * a.s_estride + (size_t)row * groups_per_row;
-        bi = M.biases ? M.biases + e * a.s_estride + (size_t)row * groups_per_row : nullptr;
-        sbp = SB ? M.sb + e * a.s_estride + (size_t)row * groups_per_row : nullptr;
-    };
-    // A "unit" = one K step of one batch of RB logical rows (NR physical rows): NR x W words + NR scales + NR biases per
-    // lane.  Units of consecutive steps / batches are streamed through TWO register sets: the loads of unit f+1 are in
-    // flight while unit f is multiplied (the weights are read once, straight to registers, non-temporal).
-    struct Unit {
-        uint32_t wd[NR][W];
-        bf16_t sc[NR], bi[NR];
-        uint32_t sbv[NR];
-    };
-    const int nbatch = (row_end - row_begin + RB - 1) / RB;
-    const int nunits = nbatch > 0 ? nbatch * steps : 0;
-    const uint32_t* rw[NR];      // row pointers of the batch being ISSUED (issue order is monotonic in f)
-    const bf16_t* rs[NR];
-    const bf16_t* rb[NR];
-    const uint32_t* rsb[NR];
-    auto issue = [&](Unit& u, int f) {
-        const int st = f % steps;
-        if (st == 0) {
-            const int r0 = row_begin + (f / steps) * RB;
-#pragma unroll
-            for (int r = 0; r < NR; ++r) locate(EPI == EPI_SWIGLU ? 2 * (r0 + r / 2) + (r & 1) : r0 + r, rw[r], rs[r], rb[r], rsb[r]);
-        }
-        const int chunk = st * 64 + lane;
-        const int g = chunk * EPL / a.group;
-        if constexpr (CH) {
-            if (chunk >= nchunks) return;    // (never consumed: see consume)
-        }
-#pragma unroll
-        for (int r = 0; r < NR; ++r) {
-            const uint32_t* p = rw[r] + (size_t)chunk * W;
-            if constexpr (CH) {
-                // BITS words at a 4-byte aligned address (the x3 / x4 forms need only dword alignment on gfx950)
-                typedef uint32_t v4a __attribute__((ext_vector_type(4), aligned(4)));
-                typedef uint32_t v3a __attribute__((ext_vector_type(3), aligned(4)));
-                typedef uint32_t v2a __attribute__((ext_vector_type(2), aligned(4)));
-                if (W == 2) {
-                    const v2a v = __builtin_nontemporal_load(reinterpret_cast<const v2a*>(p));
-                    u.wd[r][0] = v[0]; u.wd[r][W > 1 ? 1 : 0] = v[1];
-                } else if (W == 3) {
-                    const v3a v = __builtin_nontemporal_load(reinterpret_cast<const v3a*>(p));
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) u.wd[r][k < W ? k : 0] = v[k];
-                } else {
-                    const v4a v = __builtin_nontemporal_load(reinterpret_cast<const v4a*>(p));
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) u.wd[r][k < W ? k : 0] = v[k];
-                    if (W == 5) {
-                        u.wd[r][W > 4 ? 4 : 0] = __builtin_nontemporal_load(p + 4);
-                    } else {
-                        const v2a t = __builtin_nontemporal_load(reinterpret_cast<const v2a*>(p + 4));
-                        u.wd[r][W > 4 ? 4 : 0] = t[0]; u.wd[r][W > 5 ? 5 : 0] = t[1];
-                    }
-                }
-            } else if (W == 4) {
-                const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-                u.wd[r][0] = v[0]; u.wd[r][W > 1 ? 1 : 0] = v[1]; u.wd[r][W > 2 ? 2 : 0] = v[2]; u.wd[r][W > 3 ? 3 : 0] = v[3];
-            } else if (W == 2) {
-                const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
-                u.wd[r][0] = v[0]; u.wd[r][W > 1 ? 1 : 0] = v[1];
-            } else {
-                u.wd[r][0] = __builtin_nontemporal_load(p);
-            }
-            if (SB) {
-                u.sbv[r] = rsb[r][g];
-            } else {
-                u.sc[r] = rs[r][g];
-                u.bi[r] = rb[r] ? rb[r][g] : (bf16_t)0;
-            }
-        }
-    };
-    float acc[NR];
-#pragma unroll
-    for (int r = 0; r < NR; ++r) acc[r] = 0.f;
-    auto consume = [&](const Unit& u, int f) {
-        const int r0 = row_begin + (f / steps) * RB, st = f % steps;
-        const int chunk = st * 64 + lane;
-        const bool live = !CH || chunk < nchunks;
-        uint32_t xp[EPL / 2];   // the lane's activations, still packed bf16 pairs
-        if (live) {
-#pragma unroll
-            for (int j = 0; j < EPL / 8; ++j) {
-                const u32x4 xv = *reinterpret_cast<const u32x4*>(xs + (size_t)chunk * EPL + j * 8);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) xp[j * 4 + q] = xv[q];
-            }
-            const float xsm = xsum[chunk];
-#pragma unroll
-            for (int r = 0; r < NR; ++r) {
-                float d = 0.f;
-                const float scl = SB ? (F16S ? scale_to_f32<true>((uint16_t)u.sbv[r]) : bf16lo(u.sbv[r])) : scale_to_f32<F16S>(u.sc[r]);
-                float bia = SB ? (F16S ? scale_to_f32<true>((uint16_t)(u.sbv[r] >> 16)) : bf16hi(u.sbv[r])) : scale_to_f32<F16S>(u.bi[r]);
-                if constexpr (CH) {
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) d = A16::dot2(xp[i], A16::unmagic(field_pair<BITS, A16>(u.wd[r], i)), d);
-                }
-#pragma unroll
-                for (int wi = 0; wi < (CH ? 0 : W); ++wi) {
-                    const uint32_t wdw = u.wd[r][wi];
-                    if (BITS == 4) {
-                        uint32_t qp[4];   // (the activations were stored in LDS in the order of these pairs: put() below)
-                        nibble_pairs<A16>(wdw, qp);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) d = A16::dot2(xp[wi * 4 + k], A16::unmagic(qp[k]), d);
-                    } else {
-#pragma unroll
-                        for (int b = 0; b < 4; ++b) {
-                            const uint32_t xw = xp[wi * 2 + (b >> 1)];
-                            d = fmaf((b & 1) ? A16::hi(xw) : A16::lo(xw), (float)((wdw >> (8 * b)) & 0xFFu), d);
-                        }
-                    }
-                }
-                if (BITS == 4 || CH) bia = fmaf(-A16::kMagic, scl, bia);
-                acc[r] = fmaf(scl, d, acc[r]);
-                acc[r] = fmaf(bia, xsm, acc[r]);
-            }
-        }
-        if (st == steps - 1) {   // the batch's rows are complete: reduce, epilogue, restart the accumulators
-#pragma unroll
-            for (int r = 0; r < NR; ++r) acc[r] = wave_sum(acc[r]);
-            if (lane == 0) {
-#pragma unroll
-                for (int r = 0; r < RB; ++r) {
-                    const int row = r0 + r;
-                    if (row >= row_end) break;
-                    const float v0 = acc[LR * r], v1 = acc[LR * r + (LR - 1)];
-                    if constexpr (EPI == EPI_F32) {
-                        a.out_f32[(size_t)by * a.N + row] = v0;
-                    } else {
-                        const bf16_t lb = epi_bits<EPI, A16>(v0, v1, EPI == EPI_RESIDUAL ? a.resid[row] : (bf16_t)0, a.swiglu_single_round);
-                        out[row] = lb;
-                        if (EPI == EPI_ARGMAX) {
-                            const uint64_t key = argmax_key(A16::val(lb), (uint32_t)(row + a.row_offset));
-                            best = key > best ? key : best;
-                        }
-                    }
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < NR; ++r) acc[r] = 0.f;
-        }
-    };
-    // the first two units go out before the activation is even loaded: they depend on the weights only
-    Unit uA, uB;
-    if (nunits > 0) issue(uA, 0);
-    if (nunits > 1) issue(uB, 1);
+// ... for block bx of ONE matrix M1 (n_rows rows in ITS <BITS, W> and group) whose rows start at column col0 of the launch's output row
+template <int BITS, int W, int PRO, int RB, bool SB>
+__device__ __forceinline__ void qgemv_member(const QGemvArgs& a, const int bx, const int n_rows, const int group, const QMat& M1, const int col0) {
+    constexpr int EPI = EPI_STORE;
+    constexpr bool F16S = false;
+    // (macros as listed above qgemv_kernel) the n_rows rows of M1 alone, written from column col0: no member walk, `mi` unused
+#define QGB_BX bx
+#define QGB_N n_rows
+#define QGB_GROUP group
+#define QGB_COL0 +col0
+#define QGB_FIND_MEMBER
+#define QGB_MEMBER ((void)mi, M1)
+#include "qgemv_body.inc"
+#undef QGB_BX
+#undef QGB_N
+#undef QGB_GROUP
+#undef QGB_COL0
+#undef QGB_FIND_MEMBER
+#undef QGB_MEMBER
+}
 
-    // ---- prologue: x -> LDS as bf16 (RMS-normalised on the way in) and, in the same pass, the per-chunk sums
-    //      sum(x_i) that every row's bias term shares (EPL elements = EPL/8 consecutive threads, reduced by DPP) ----
-    static_assert(EPL >= 8, "a lane chunk must cover at least one 16-byte activation vector");
-    auto put = [&](int i, const u32x4 o) { stage_chunk<A16, EPL, BITS == 4>(xs, xsum, i, o); };
-    if (PRO == PRO_RMSNORM && a.K <= 4096) {
-        // the hidden-sized prologues (q/k/v, gate/up, lm_head: K <= 4096 = two vectors per thread): the row and the norm weights stay in
-        // registers between the two passes -- one global round trip instead of two in a launch that is a chain of them.  Same sums.
-        u32x4 raw[2], nwv[2];
-        float ss = 0.f;
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int i = threadIdx.x * 8 + it * 2048;
-            if (i < a.K) {
-                raw[it] = *reinterpret_cast<const u32x4*>(xg + i);
-                nwv[it] = *reinterpret_cast<const u32x4*>(a.norm_w + i);
-            }
-        }
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            if (threadIdx.x * 8 + it * 2048 < a.K) ss = sumsq8<A16>(raw[it], ss);
-        }
-        ss = block_sum<4>(ss, red);
-        const float rstd = 1.0f / sqrtf(ss / (float)a.K + a.eps);
-#pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int i = threadIdx.x * 8 + it * 2048;
-            if (i < a.K) put(i, norm8<A16>(raw[it], nwv[it], rstd));
-        }
-    } else if (PRO == PRO_RMSNORM) {
-        float ss = 0.f;
-        for (int i = threadIdx.x * 8; i < a.K; i += 256 * 8) ss = sumsq8<A16>(*reinterpret_cast<const u32x4*>(xg + i), ss);
-        ss = block_sum<4>(ss, red);
-        const float rstd = 1.0f / sqrtf(ss / (float)a.K + a.eps);
-        for (int i = threadIdx.x * 8; i < a.K; i += 256 * 8) {
-            const u32x4 raw = *reinterpret_cast<const u32x4*>(xg + i);
-            put(i, norm8<A16>(raw, *reinterpret_cast<const u32x4*>(a.norm_w + i), rstd));
-        }
-    } else if (a.K <= 8 * 2048 && !a.rolled_stage) {
-        // all of the row's vectors of this thread in flight at once (the rolled loop below waits for each 16-byte load before it
-        // issues the next: six dependent L2 round trips in the down projection's prologue, K = 12288)
-        u32x4 v[8];
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int i = threadIdx.x * 8 + it * 2048;
-            if (i < a.K) v[it] = *reinterpret_cast<const u32x4*>(xg + i);
-        }
-#pragma unroll
-        for (int it = 0; it < 8; ++it) {
-            const int i = threadIdx.x * 8 + it * 2048;
-            if (i < a.K) put(i, v[it]);
-        }
-    } else {
-        for (int i = threadIdx.x * 8; i < a.K; i += 256 * 8) put(i, *reinterpret_cast<const u32x4*>(xg + i));
+// A q | k | v stack whose members differ in format, as ONE launch: the members' grids laid end to end, every member starting on a block
+// boundary.  A block finds its member from blockIdx.x (block-uniform compares on the plan) and runs that member's <BITS, W> text on the
+// member's rows in the member's group: the activation is staged per block for ONE width (stage_octet4 order at 4 bits, EPL by width),
+// which is why a block serves one format.  EPI_STORE on bf16 triplets, one activation row.
+struct QStackPlan {
+    int first[3];     // first block of member i (INT_MAX: absent)
+    int fmt[3];       // bits | W << 8
+    int group[3];
+    int col0[3];      // first output column of member i
+};
+template <int PRO, int RB, bool SB>
+__global__ __launch_bounds__(256) void qgemv_stack_kernel(const QGemvArgs a, const QStackPlan p) {
+    const int b = blockIdx.x;
+    const int mi = b >= p.first[2] ? 2 : b >= p.first[1] ? 1 : 0;
+    QMat M;
+    M.w = mi == 2 ? a.m[2].w : mi == 1 ? a.m[1].w : a.m[0].w;
+    M.scales = mi == 2 ? a.m[2].scales : mi == 1 ? a.m[1].scales : a.m[0].scales;
+    M.biases = mi == 2 ? a.m[2].biases : mi == 1 ? a.m[1].biases : a.m[0].biases;
+    M.sb = mi == 2 ? a.m[2].sb : mi == 1 ? a.m[1].sb : a.m[0].sb;
+    M.n = mi == 2 ? a.m[2].n : mi == 1 ? a.m[1].n : a.m[0].n;
+    const int bx = b - (mi == 2 ? p.first[2] : mi == 1 ? p.first[1] : 0);
+    const int fmt = mi == 2 ? p.fmt[2] : mi == 1 ? p.fmt[1] : p.fmt[0];
+    const int group = mi == 2 ? p.group[2] : mi == 1 ? p.group[1] : p.group[0];
+    const int col0 = mi == 2 ? p.col0[2] : mi == 1 ? p.col0[1] : 0;
+#define OMX_QSTACK_CASE(B, WW) \
+    case (B | (WW << 8)): qgemv_member<B, WW, PRO, RB, SB>(a, bx, M.n, group, M, col0); break;
+    switch (fmt) {
+        OMX_QSTACK_CASE(2, 2) OMX_QSTACK_CASE(3, 3) OMX_QSTACK_CASE(5, 5) OMX_QSTACK_CASE(6, 6)
+        OMX_QSTACK_CASE(4, 4) OMX_QSTACK_CASE(4, 2) OMX_QSTACK_CASE(4, 1) OMX_QSTACK_CASE(8, 4) OMX_QSTACK_CASE(8, 2)
     }
-    __syncthreads();
-
-    for (int f = 0; f < nunits; f += 2) {
-        if (f > 0 && f + 1 < nunits) issue(uB, f + 1);
-        consume(uA, f);
-        if (f + 1 >= nunits) break;
-        if (f + 2 < nunits) issue(uA, f + 2);
-        consume(uB, f + 1);
-    }
-    if (EPI == EPI_ARGMAX) {
-        uint64_t* bred = reinterpret_cast<uint64_t*>(red);
-        __syncthreads();
-        if (lane == 0) bred[wave] = best;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint64_t b = bred[0];
-#pragma unroll
-            for (int w = 1; w < 4; ++w) b = bred[w] > b ? bred[w] : b;
-            a.argmax_slot[blockIdx.x] = b;
-        }
-    }
+#undef OMX_QSTACK_CASE
 }
 
 template <int BITS, int W>
@@ -501,30 +320,45 @@ int launch_qgemv_w(const QGemvArgs& a, int pro, int epi, hipStream_t s) {
     return set_error("quantized gemv: unsupported prologue/epilogue combination %d/%d", pro, epi);
 }
 
+// words per lane and step of the non-chunked widths (4 / 8 bits) for a row of K elements in groups of `group`: the widest of 4, 2, 1 whose
+// lane chunk divides K / 64 and lies inside one group; 0: none (a chunked width streams BITS words).  With it the lane's chunk -- and so
+// the order of every row's sums -- is a function of the matrix's own (bits, group, K) alone.
+int qgemv_words(int bits, int K, int group) {
+    if (quant_chunked(bits)) return (K > 0 && K % 32 == 0 && group >= 32) ? bits : 0;
+    const int EPW = 32 / bits;
+    int W = 4;
+    while (W * EPW > 8 && (K % (64 * W * EPW) != 0 || W * EPW > group)) W >>= 1;
+    return (K % (64 * W * EPW) == 0 && W * EPW <= group && W * EPW >= 8) ? W : 0;
+}
+
+// rows per wave of a launch over N logical rows: long streams for the vocabulary matrix, one batch per wave otherwise; small matrices:
+// two rows per wave -- and the tuning knobs that override it
+int qgemv_rows_per_wave(int N, int K, int epi) {
+    int rpw = N >= 65536 ? 16 : (N <= 8192 && epi != EPI_SWIGLU) ? 2 : 4;
+    if (const char* e = getenv("OMX_QGEMV_RPW_SMALL"))   // tuning knob: rows per wave of the small matrices (2 or 4)
+        if (N <= 8192 && epi != EPI_SWIGLU && (atoi(e) == 2 || atoi(e) == 4)) rpw = atoi(e);
+    if (const char* e = getenv("OMX_QGEMV_RPW_LONGK"))   // ... of the small matrices with a long row (K > 8192: the down projection)
+        if (N <= 8192 && K > 8192 && epi != EPI_SWIGLU && (atoi(e) == 2 || atoi(e) == 4 || atoi(e) == 8)) rpw = atoi(e);
+    if (const char* e = getenv("OMX_QGEMV_RPW_GU"))      // ... of the gate/up pair launch (logical rows: 2, 4, 8)
+        if (epi == EPI_SWIGLU && N < 65536 && (atoi(e) == 2 || atoi(e) == 4 || atoi(e) == 8)) rpw = atoi(e);
+    return rpw;
+}
+
 template <int BITS>
 int launch_qgemv_bits(const QGemvArgs& a_in, int pro, int epi, hipStream_t s) {
     QGemvArgs a = a_in;
     constexpr int EPW = 32 / BITS;
+    const int W = qgemv_words(BITS, a.K, a.group);
     if constexpr (quant_chunked(BITS)) {
-        OMX_REQUIRE(a.K > 0 && a.K % 32 == 0 && a.group >= 32, "quantized_matmul: K=%d unsupported for %d-bit group %d", a.K, BITS, a.group);
-    }
-    int W = 4;
-    if constexpr (!quant_chunked(BITS)) {
-        while (W * EPW > 8 && (a.K % (64 * W * EPW) != 0 || W * EPW > a.group)) W >>= 1;
-        OMX_REQUIRE(a.K % (64 * W * EPW) == 0 && W * EPW <= a.group && W * EPW >= 8, "quantized_matmul: K=%d unsupported for %d-bit group %d (K must be a multiple of %d)",
+        OMX_REQUIRE(W != 0, "quantized_matmul: K=%d unsupported for %d-bit group %d", a.K, BITS, a.group);
+    } else {
+        OMX_REQUIRE(W != 0, "quantized_matmul: K=%d unsupported for %d-bit group %d (K must be a multiple of %d)",
                     a.K, BITS, a.group, 64 * EPW);
     }
     if (a.n_batch < 1) a.n_batch = 1;
     if (a.x_div < 1) a.x_div = 1;
-    // long streams for the vocabulary matrix, one batch per wave otherwise; small matrices: two rows per wave
-    a.rows_per_wave = a.N >= 65536 ? 16 : (a.N <= 8192 && epi != EPI_SWIGLU) ? 2 : 4;
-    if (const char* e = getenv("OMX_QGEMV_RPW_SMALL"))   // tuning knob: rows per wave of the small matrices (2 or 4)
-        if (a.N <= 8192 && epi != EPI_SWIGLU && (atoi(e) == 2 || atoi(e) == 4)) a.rows_per_wave = atoi(e);
+    a.rows_per_wave = qgemv_rows_per_wave(a.N, a.K, epi);
     if (const char* e = getenv("OMX_QGEMV_ROLLED_STAGE")) a.rolled_stage = e[0] == '1';
-    if (const char* e = getenv("OMX_QGEMV_RPW_LONGK"))   // ... of the small matrices with a long row (K > 8192: the down projection)
-        if (a.N <= 8192 && a.K > 8192 && epi != EPI_SWIGLU && (atoi(e) == 2 || atoi(e) == 4 || atoi(e) == 8)) a.rows_per_wave = atoi(e);
-    if (const char* e = getenv("OMX_QGEMV_RPW_GU"))      // ... of the gate/up pair launch (logical rows: 2, 4, 8)
-        if (epi == EPI_SWIGLU && a.N < 65536 && (atoi(e) == 2 || atoi(e) == 4 || atoi(e) == 8)) a.rows_per_wave = atoi(e);
     if constexpr (quant_chunked(BITS)) {
         return launch_qgemv_w<BITS, BITS>(a, pro, epi, s);
     } else {
@@ -537,7 +371,6 @@ int launch_qgemv_bits(const QGemvArgs& a_in, int pro, int epi, hipStream_t s) {
 
 // quantize / dequantize alone take what mlx_rs::ops::quantize takes: MLX's affine widths 2, 3, 4, 5, 6 and 8 on bfloat16 / float16 /
 // float32 (the reference's own value test loops [2, 4, 8] on float32: ops/quantization.rs:289-305)
-bool quant_bits_ok(int bits) { return bits == 2 || bits == 3 || bits == 4 || bits == 5 || bits == 6 || bits == 8; }
 int check_format_qdq(const char* who, int K, int group, int bits, int dtype) {
     OMX_REQUIRE(dtype == OMX_BFLOAT16 || dtype == OMX_FLOAT16 || dtype == OMX_FLOAT32, "%s: bf16 / f16 / f32 only (got dtype %d)", who, dtype);
     OMX_REQUIRE(quant_bits_ok(bits), "%s: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", who, bits);
@@ -596,7 +429,72 @@ int qgemv_grid(int N) {
     return ((N + rpw - 1) / rpw + 3) / 4;
 }
 
-int launch_qgemv(const QGemvArgs& a, int bits, int pro, int epi, hipStream_t s) {
+// the q | k | v stack with members of different formats as ONE launch (qgemv_stack_kernel); fb / fg: the members' bits / groups
+static int launch_qgemv_stack(const QGemvArgs& a_in, const int* fb, const int* fg, int pro, hipStream_t s) {
+    QGemvArgs a = a_in;
+    a.rows_per_wave = qgemv_rows_per_wave(a.N, a.K, EPI_STORE);
+    if (const char* e = getenv("OMX_QGEMV_ROLLED_STAGE")) a.rolled_stage = e[0] == '1';
+    a.n_batch = 1; a.x_div = 1;
+    QStackPlan p = {};
+    int blocks = 0, col = 0, min_epl = 64;
+    bool sb = true;
+    for (int i = 0; i < 3; ++i) {
+        p.first[i] = INT_MAX;
+        if (!a.m[i].w) continue;
+        OMX_REQUIRE(i == 0 || a.m[i - 1].w, "quantized gemv: the members of a stack are m[0], m[1], m[2] in order");
+        const int W = qgemv_words(fb[i], a.K, fg[i]);
+        OMX_REQUIRE(W != 0, "quantized gemv: K=%d unsupported for %d-bit group %d (member %d of a mixed stack)", a.K, fb[i], fg[i], i);
+        p.first[i] = blocks; p.fmt[i] = fb[i] | (W << 8); p.group[i] = fg[i]; p.col0[i] = col;
+        blocks += ((a.m[i].n + a.rows_per_wave - 1) / a.rows_per_wave + 3) / 4;
+        col += a.m[i].n;
+        min_epl = std::min(min_epl, quant_chunked(fb[i]) ? 32 : W * (32 / fb[i]));
+        if (!a.m[i].sb) sb = false;
+    }
+    OMX_REQUIRE(col == a.N && blocks > 0, "quantized gemv: the stack's members hold %d rows, N = %d", col, a.N);
+    const size_t shmem = (size_t)a.K * 2 + (size_t)(a.K / min_epl) * 4 + 64;
+    const dim3 grid(blocks), block(256);
+#define OMX_QSTACK_LAUNCH(P)                                                                                        \
+    if (pro == P) {                                                                                                 \
+        if (a.rows_per_wave == 2) {                                                                                 \
+            if (sb) OMX_LAUNCH((qgemv_stack_kernel<P, 2, true>), grid, block, shmem, s, a, p);                      \
+            else OMX_LAUNCH((qgemv_stack_kernel<P, 2, false>), grid, block, shmem, s, a, p);                        \
+        } else {                                                                                                    \
+            if (sb) OMX_LAUNCH((qgemv_stack_kernel<P, 4, true>), grid, block, shmem, s, a, p);                      \
+            else OMX_LAUNCH((qgemv_stack_kernel<P, 4, false>), grid, block, shmem, s, a, p);                        \
+        }                                                                                                           \
+        OMX_LAUNCH_CHECK();                                                                                         \
+        return 0;                                                                                                   \
+    }
+    OMX_QSTACK_LAUNCH(PRO_NONE)
+    OMX_QSTACK_LAUNCH(PRO_RMSNORM)
+#undef OMX_QSTACK_LAUNCH
+    return set_error("quantized gemv: unsupported prologue %d for a stack of mixed formats", pro);
+}
+
+int launch_qgemv(const QGemvArgs& a_in, int bits, int pro, int epi, hipStream_t s) {
+    // the format each member runs in: its own where it carries one, else the launch's
+    int fb[3] = {0, 0, 0}, fg[3] = {0, 0, 0}, first = -1;
+    bool mixed = false;
+    for (int i = 0; i < 3; ++i) {
+        if (!a_in.m[i].w) continue;
+        fb[i] = qmat_bits(a_in.m[i], bits); fg[i] = qmat_group(a_in.m[i], a_in.group);
+        if (first < 0) first = i;
+        else if (fb[i] != fb[first] || fg[i] != fg[first]) mixed = true;
+    }
+    if (mixed) {
+        OMX_REQUIRE(epi != EPI_SWIGLU, "quantized gemv: gate (%d-bit group %d) and up (%d-bit group %d) must share a format", fb[0], fg[0], fb[1], fg[1]);
+        OMX_REQUIRE(epi == EPI_STORE && !a_in.scales_f16 && a_in.n_batch <= 1 && !a_in.w_sel && a_in.w_sel_n == 0,
+                    "quantized gemv: a stack of mixed formats is a plain store of one activation row on bf16 triplets");
+        for (int i = 0; i < 3; ++i)
+            if (a_in.m[i].w) {
+                OMX_REQUIRE(quant_bits_ok(fb[i]), "quantized gemv: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", fb[i]);
+                OMX_REQUIRE(fg[i] == 32 || fg[i] == 64 || fg[i] == 128, "quantized gemv: group_size must be 32, 64 or 128 (got %d)", fg[i]);
+                OMX_REQUIRE(a_in.K > 0 && a_in.K % fg[i] == 0, "quantized gemv: the row width (%d) must be divisible by the group size (%d)", a_in.K, fg[i]);
+            }
+        return launch_qgemv_stack(a_in, fb, fg, pro, s);
+    }
+    QGemvArgs a = a_in;
+    if (first >= 0) { bits = fb[first]; a.group = fg[first]; }
     OMX_REQUIRE(quant_bits_ok(bits), "quantized gemv: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", bits);
     if (bits == 4) {
         const int r = launch_qgemv4m(a, pro, epi, s);

@@ -18,6 +18,9 @@ struct QMat {               // one member of a row-stacked weight (q | k | v) --
     // optional second repack (round 6, qgemv_mfma.hip): the matrix in 9 KB tiles of 16 rows x 1 024 columns (words in the order the
     // matrix-core kernel's lanes consume them, the tile's scale | bias words behind them) -- 4-bit, group 64, K = 4096 / 12288
     const uint32_t* tiles = nullptr;
+    // the matrix's own MLX format where it travels with the matrix (a checkpoint whose matrices differ: the engine fills both in for
+    // every matrix); 0 = the launch's (launch_qgemv's `bits`, QGemvArgs::group)
+    int bits = 0, group = 0;
 };
 int launch_quant_interleave(uint32_t* sb, const bf16_t* scales, const bf16_t* biases, size_t n_groups, hipStream_t s);
 // The raw-pointer C entry points (omx_moe_block_forward_q ...) receive the checkpoint's scales pointer; an engine that built the
@@ -55,7 +58,13 @@ struct QGemvArgs {
 int launch_dequantize_bf16(bf16_t* out, const uint32_t* packed, const void* scales, const void* biases, int64_t rows, int cols, int group_size,
                            int bits, bool scales_f16, hipStream_t s, bool out_f16 = false);   // out_f16: the result in float16 (a float16 model's prompt pass)
 
+// bits / a.group: the format of every member that carries none of its own (QMat::bits / group == 0).  Members of one format: today's
+// launches.  Members that differ (EPI_STORE stacks of bf16 triplets, one activation row): ONE launch of qgemv_stack_kernel.  Either way a
+// member's rows are bit for bit what the VALU kernel gives for that member launched alone.
 int launch_qgemv(const QGemvArgs& a, int bits, int pro, int epi, hipStream_t s);
+// the format member i of a launch runs in
+inline int qmat_bits(const QMat& m, int dflt) { return m.bits ? m.bits : dflt; }
+inline int qmat_group(const QMat& m, int dflt) { return m.group ? m.group : dflt; }
 // qgemv_mfma.hip (round 6): the dense 4-bit group-64 single-row forms on the matrix cores.  0 launched, -1 not its shape (take the VALU kernel), 1 error
 int launch_qgemv4m(const QGemvArgs& a, int pro, int epi, hipStream_t s);
 bool qgemv4m_shape_ok(int K, int group, int bits);
@@ -79,6 +88,7 @@ int launch_qgemv_rows(const QRowsArgs& a, int bits, int pro, int epi, hipStream_
 // The widths whose fields do not divide a word (3, 5, 6) and 2: a run of 32 elements is exactly BITS consecutive words, element j the
 // BITS-wide field at bit j * BITS of that little-endian bit string (a field may straddle two words).  j must be a compile-time constant
 // after unrolling: one v_bfe_u32, or v_alignbit + mask for a straddling field.
+inline bool quant_bits_ok(int bits) { return bits == 2 || bits == 3 || bits == 4 || bits == 5 || bits == 6 || bits == 8; }   // MLX's affine widths
 constexpr bool quant_chunked(int bits) { return bits == 2 || bits == 3 || bits == 5 || bits == 6; }
 template <int B>
 __device__ __forceinline__ uint32_t qfield(const uint32_t* w, int j) {

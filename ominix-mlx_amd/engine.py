@@ -100,6 +100,9 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_verify_logits": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "omx_qwen3_trim": (c_int, [c_void_p, c_int, c_uint32]),
     "omx_qwen3_get_weight": (c_int, [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t)]),
+    # mixed-precision MLX checkpoints: one packed matrix's own (bits, group_size), and the query
+    "omx_qwen3_set_quant_format": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_int]),
+    "omx_qwen3_quant_format": (c_int, [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     # batched decode: up to 8 independent sequences per step on one loaded model (csrc/engine_batch.hip)
     "omx_qwen3_batch_create": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int]),
     "omx_qwen3_batch_destroy": (c_int, [c_void_p]),
@@ -163,9 +166,78 @@ def dense_dtype_is_f16(dtype) -> bool:
     raise OmxError(f"Model: dtype {dtype!r} (bfloat16 or float16)")
 
 
-def expected_shape(c: Qwen3Config, name: str):
+QUANT_BITS, QUANT_GROUPS = (2, 3, 4, 5, 6, 8), (32, 64, 128)
+_QUANT_SCALARS = ("bits", "group_size", "mode", "scales_dtype")
+
+
+def quant_formats(quantization):
+    """config.json's "quantization" block -> (base, table): base = (bits, group_size) or None for an unquantised checkpoint, table =
+    {module path: (bits, group_size)} for the nested per-module entries a mixed-precision MLX checkpoint carries next to the global
+    pair ("model.layers.3.mlp.down_proj": {"group_size": 64, "bits": 6}).  An entry's missing field is the base's.  "mode" is accepted
+    only as "affine"; an entry that is False / True (an unquantised or default member inside a packed model) or names another mode is
+    refused with the module path.  Pure: no device, no model."""
+    if not quantization:
+        return None, {}
+    q = dict(quantization)
+    if str(q.get("mode", "affine")) != "affine":
+        raise OmxError(f"InvalidConfig: quantization mode {q['mode']!r} (only MLX's affine mode is supported)")
+    base = (int(q.get("bits", 0)), int(q.get("group_size", 64)))
+    if base[0] == 0:          # (bits 0 is the config field's "not quantised")
+        return None, {}
+    if base[0] not in QUANT_BITS:
+        raise OmxError(f"InvalidConfig: quantization bits {base[0]} (2, 3, 4, 5, 6, 8)")
+    if base[1] not in QUANT_GROUPS:
+        raise OmxError(f"InvalidConfig: quantization group_size {base[1]} (32, 64, 128)")
+    table = {}
+    for prefix, entry in q.items():
+        if prefix in _QUANT_SCALARS:
+            continue
+        if isinstance(entry, bool):
+            raise OmxError(f"InvalidConfig: quantization entry {prefix}: {entry} -- a member that is not an affine (bits, group_size) "
+                           "format of its own inside a packed model is not supported")
+        if not isinstance(entry, dict):
+            continue      # (other scalar keys of the block say nothing about a matrix)
+        if str(entry.get("mode", "affine")) != "affine":
+            raise OmxError(f"InvalidConfig: quantization entry {prefix}: mode {entry['mode']!r} (only MLX's affine mode is supported)")
+        bits, group = int(entry.get("bits", base[0])), int(entry.get("group_size", base[1]))
+        if bits not in QUANT_BITS:
+            raise OmxError(f"InvalidConfig: quantization entry {prefix}: bits {bits} (2, 3, 4, 5, 6, 8)")
+        if group not in QUANT_GROUPS:
+            raise OmxError(f"InvalidConfig: quantization entry {prefix}: group_size {group} (32, 64, 128)")
+        table[prefix] = (bits, group)
+    return base, table
+
+
+def mixed_recipe(recipe: str, num_layers: int):
+    """The layers whose v_proj and down_proj an `mlx_lm.convert --quant-predicate mixed_<low>_<high>` checkpoint keeps at the wide
+    format, as (low_bits, high_bits, [layer indices]).  The rule is written down FROM MEMORY of mlx_lm (its source is not at hand) and
+    nothing in the engine depends on it being mlx_lm's: layer i is wide when i < L // 8 or i >= 7 * L // 8 or (i - L // 8) % 3 == 2;
+    lm_head is wide, everything else narrow, group 64."""
+    known = {"mixed_2_6": (2, 6), "mixed_3_4": (3, 4), "mixed_3_6": (3, 6), "mixed_4_6": (4, 6)}
+    if recipe not in known:
+        raise OmxError(f"mixed_recipe: {recipe!r} (one of {', '.join(sorted(known))})")
+    low, high = known[recipe]
+    L = int(num_layers)
+    wide = [i for i in range(L) if i < L // 8 or i >= 7 * L // 8 or (i - L // 8) % 3 == 2]
+    return low, high, wide
+
+
+def mixed_recipe_quantization(recipe: str, num_layers: int, tie_word_embeddings: bool = False, group_size: int = 64) -> dict:
+    """mixed_recipe as the config.json "quantization" block such a checkpoint would carry."""
+    low, high, wide = mixed_recipe(recipe, num_layers)
+    q = {"group_size": group_size, "bits": low}
+    for i in wide:
+        for sub in ("self_attn.v_proj", "mlp.down_proj"):
+            q[f"model.layers.{i}.{sub}"] = {"group_size": group_size, "bits": high}
+    if not tie_word_embeddings:
+        q["lm_head"] = {"group_size": group_size, "bits": high}
+    return q
+
+
+def expected_shape(c: Qwen3Config, name: str, formats=None):
     """Shape the engine will read for checkpoint tensor `name` on THIS rank (after the TP / EP slicing), or None for a
-    name the forward does not use.  Mirrors resolve_weights in csrc/engine_weights.hip."""
+    name the forward does not use.  Mirrors resolve_weights in csrc/engine_weights.hip.  formats: {module path: (bits, group_size)} of
+    the matrices that have a format of their own (quant_formats); every other packed matrix has the config's base format."""
     tp, ep = max(c.tp_size, 1), max(c.ep_size, 1)
     hd, D = c.hidden_size, c.head_dim
     H, Hkv, I, V = c.num_attention_heads // tp, max(1, c.num_key_value_heads // tp), c.intermediate_size // tp, c.vocab_size
@@ -187,9 +259,10 @@ def expected_shape(c: Qwen3Config, name: str):
             return (n,)
         if not quant:
             return tuple(stack) + (n, k) if leaf_kind == "weight" else None
+        bits, group = (formats or {}).get(stem, (c.quant_bits, c.quant_group))      # the matrix's own format
         if leaf_kind == "weight":
-            return tuple(stack) + (n, k * c.quant_bits // 32)
-        return tuple(stack) + (n, k // c.quant_group)
+            return tuple(stack) + (n, k * bits // 32)
+        return tuple(stack) + (n, k // group)
 
     if stem == "model.embed_tokens":
         return lin(V, hd)
@@ -230,7 +303,8 @@ class Model:
                  num_experts=0, num_experts_per_tok=0, moe_intermediate_size=0, moe_mode="qwen3_moe", norm_topk_prob=False,
                  qk_norm=True, ep_rank=0, ep_size=1, attention_bias=False, dtype="bfloat16", **_ignored):
         """quantization: config.json's {"bits": 2|3|4|5|6|8, "group_size": 64} (model.rs:63) or None for a bf16 checkpoint (2, 3,
-        5 and 6 bits: dense single-rank models only); + "scales_dtype":
+        5 and 6 bits: dense single-rank models only); nested entries {module path: {"bits", "group_size"}} give single matrices a
+        format of their own (a mixed-precision MLX checkpoint; quant_formats; dense single-rank bf16-triplet models); + "scales_dtype":
         "float16" when the checkpoint's scales / biases are float16 (loader.load_model reads it off the tensors' dtype).
         num_experts > 0: sparse-MoE feed-forward in every layer -- moe_mode "qwen3_moe" (qwen3_moe.rs ModelArgs :60-87) or
         "mixtral" (mixtral-mlx ModelArgs :54-80, with qk_norm=False and moe_intermediate_size = intermediate_size).
@@ -238,6 +312,7 @@ class Model:
         float16 end to end, like MLX runs a checkpoint saved in float16 (single rank, dense MLP, head_dim 128)."""
         require_device()
         q = quantization or {}
+        _, table = quant_formats(quantization)
         f16_weights = dense_dtype_is_f16(dtype)
         self.cfg = Qwen3Config(hidden_size, num_hidden_layers, intermediate_size, num_attention_heads,
                                num_key_value_heads, head_dim, vocab_size, rms_norm_eps, rope_theta,
@@ -251,6 +326,12 @@ class Model:
         self._h = c_void_p()
         check(lib.omx_qwen3_create(ctypes.byref(self._h), ctypes.byref(self.cfg)))
         self._keep = []
+        # per-matrix formats: what differs from the base goes to the engine (an entry that repeats the base changes nothing; a tied head
+        # has the embedding's format, so a stray lm_head entry of a tied model names no matrix)
+        base = (self.cfg.quant_bits, self.cfg.quant_group)
+        self.quant_table = {p: f for p, f in table.items() if f != base and not (p == "lm_head" and self.cfg.tie_word_embeddings)}
+        for prefix, (bits, group) in self.quant_table.items():
+            check(lib.omx_qwen3_set_quant_format(self._h, prefix.encode(), bits, group))
 
     def close(self) -> None:
         h = getattr(self, "_h", None)
@@ -315,7 +396,13 @@ class Model:
             check(lib.omx_qwen3_set_weight(self._h, name.encode(), t.ptr, t.nbytes))
 
     def expected_shape(self, name: str):
-        return expected_shape(self.cfg, name)
+        return expected_shape(self.cfg, name, self.quant_table)
+
+    def quant_format(self, prefix: str) -> tuple:
+        """(bits, group_size) of the packed matrix at module path `prefix`: its own, or the base format (omx_qwen3_quant_format)."""
+        bits, group = c_int(), c_int()
+        check(lib.omx_qwen3_quant_format(self._h, prefix.encode(), ctypes.byref(bits), ctypes.byref(group)))
+        return bits.value, group.value
 
     def synth_weights(self, base_seed: int = 0x0C0FFEE5, peaked: bool = False) -> None:
         """peaked: embedding std 64 and lm_head[v] = table[(v + 1) mod V] -- greedy tokens count down with top-1 margins far above the
