@@ -125,6 +125,33 @@ int omx_set_workspace(void* ws, size_t bytes);   /* caller-provided scratch used
  *      out[r] = first index of the maximum of logits[r, :]  (u32).                              */
 int omx_argmax(uint32_t* out, const void* logits, int64_t rows, int n, omx_dtype dtype, omx_stream stream);
 
+/* ---- per-row log-probability of a target column (csrc/logprob.hip): what a text's log-likelihood is made of.  The reference gets it
+ *      from the [B, L, V] logits of qwen3-mlx/src/model.rs:480-490 by log_softmax + take; here no softmax row is ever written.
+ *      logits: bf16 [rows, ld] (ld >= V, the row stride in elements), targets: DEVICE u32 [rows].
+ *        lse[r]      = log sum_v exp(logits[r, v])                       (f32; nullable)
+ *        logprobs[r] = f32(logits[r, targets[r]]) - lse[r]               (0 where targets[r] == OMX_NO_TARGET)
+ *        greedy[r]   = first index of the row's maximum, omx_argmax's rule  (nullable)
+ *      A target >= V that is not OMX_NO_TARGET gives logprobs[r] = NaN (no chunk holds it); nothing is read out of bounds.
+ *      The rule: a row is cut into 1024-column chunks counted from column 0; one wave reduces one (row, chunk) to
+ *      (m = max, l = sum exp(x - m) in f32: 16 terms per lane in index order, then a fixed lane tree, arg = first index of m);
+ *      a second launch merges a row's ceil(V/1024) partials in ascending chunk order: M = max m_j, L = sum l_j * exp(m_j - M),
+ *      lse = M + log L.  Chunk grid and every summation order are functions of V alone, so a row's bits depend on neither the
+ *      number of rows, the rows it shares a launch with, nor the panel widths of the two-phase form.
+ *      Refused: V % 8 != 0, ld % 8 != 0 (16-byte loads), a dtype other than OMX_BFLOAT16, V > 2^20.
+ *      omx_logprob_rows: the whole row as one panel, the partials in the library workspace.
+ *      The two-phase form the engine uses: omx_logprob_partial reduces the chunks of columns [c0, c0 + P) of the row, read from a
+ *      panel [rows, ld] whose column 0 is the row's column c0 (c0 % 1024 == 0; P % 1024 == 0 unless c0 + P == V), into
+ *      partials [rows, ceil(V/1024), 2] f32 (m, l) + part_arg [rows, ceil(V/1024)] u32 and tgt [rows] f32 (written by the one chunk
+ *      that holds the target); omx_logprob_merge, once every chunk has been written, produces the three outputs.              */
+#define OMX_NO_TARGET 0xFFFFFFFFu
+#define OMX_LOGPROB_CHUNK 1024
+int omx_logprob_rows(float* logprobs, uint32_t* greedy /*nullable*/, float* lse /*nullable*/, const void* logits, int64_t ld,
+                     const uint32_t* targets, int64_t rows, int V, omx_dtype dtype /*OMX_BFLOAT16*/, omx_stream stream);
+int omx_logprob_partial(float* partials, uint32_t* part_arg, float* tgt, const void* panel, int64_t ld, int c0, int P,
+                        const uint32_t* targets, int64_t rows, int V, omx_dtype dtype, omx_stream stream);
+int omx_logprob_merge(float* logprobs, uint32_t* greedy /*nullable*/, float* lse /*nullable*/, const float* partials,
+                      const uint32_t* part_arg, const float* tgt, const uint32_t* targets, int64_t rows, int V, omx_stream stream);
+
 /* ---- a10, temperature branch: MLX's keyed generator + categorical sampler.
  *      mlx/c/random.h:37-72,129-139,149-157 (mlx_random_bits / _categorical* / _gumbel / _key / _split* / _uniform),
  *      called by mlx-rs/src/random.rs:98-115 (key, split), :397-414 (gumbel), :456-497 (categorical) and through
@@ -293,6 +320,18 @@ int omx_qwen3_verify(omx_qwen3 m, const uint32_t* tokens, int n, uint32_t* greed
 int omx_qwen3_sampler_state(omx_qwen3 m, uint32_t* state2, int set);
 int omx_qwen3_verify_logits(omx_qwen3 m, int row, void* host_bf16, int n);
 int omx_qwen3_trim(omx_qwen3 m, int n, uint32_t next_token);
+/* Score a text (csrc/engine_score.hip): logprobs[i] = log p(targets[i] | cache, tokens[0..i]) for every one of the n tokens, from ONE
+ * batched prompt pass -- the log-likelihood the reference would take from the [B, L, V] logits of model.rs:480-490.  The head runs over
+ * all n rows in vocabulary panels (OMX_SCORE_PANEL columns, a multiple of 1024, default 16384, read per call): [panel GEMM] [chunk
+ * partials, omx_logprob_partial] per panel and one merge; no [n, V] tensor exists.  A packed head (or tied packed embedding) is
+ * dequantised a panel at a time in its own format.  targets[i] == OMX_NO_TARGET: logprobs[i] = 0.  greedy[i] (nullable) = argmax of
+ * row i.  Bookkeeping is omx_qwen3_verify's: the n tokens run on top of the cache, their K/V rows are appended, the pending input token
+ * becomes the last row's argmax (omx_qwen3_trim(m, 0, tok) sets another).  1 <= n <= the prompt buffer, cached + n + 1 <= max_context.
+ * The sampler is not consulted.  Refused by name: tensor / expert parallel models (a sharded vocabulary), float16 models, ids and
+ * targets out of range.  last_score_ms: device time of the last call's prompt pass and of its head (norm, panels, merge).          */
+int omx_qwen3_score(omx_qwen3 m, const uint32_t* tokens, int n, const uint32_t* targets /*[n], OMX_NO_TARGET = none*/,
+                    float* logprobs /*[n]*/, uint32_t* greedy /*[n], nullable*/);
+int omx_qwen3_last_score_ms(omx_qwen3 m, float* pass_ms, float* head_ms);
 /* Batched decode (csrc/engine_batch.hip): up to 8 independent sequences on ONE loaded model.  The reference's Model::forward and KVCache
  * carry a batch dimension ([B, L] ids, [B, Hkv, T, D] cache, mlx-rs-core/src/cache.rs); a batch object is its ragged form: every slot is a
  * sequence with its own K/V slabs, position, pending token and sampler, and one decode step advances any chosen subset of the slots with

@@ -90,6 +90,9 @@ SIGNATURES = {
     "omx_sdpa_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "omx_set_workspace": (c_int, [c_void_p, c_size_t]),
     "omx_argmax": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "omx_logprob_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "omx_logprob_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
+    "omx_logprob_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "omx_random_key": (c_int, [c_void_p, ctypes.c_uint64, c_void_p]),
     "omx_random_split": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "omx_random_bits": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -178,6 +178,7 @@ int omx_qwen3_destroy(omx_qwen3 m) {
     if (m->dq_slab) (void)hipFree(m->dq_slab);
     if (m->verify_logits) (void)hipFree(m->verify_logits);
     if (m->verify_tokens) (void)hipFree(m->verify_tokens);
+    score_release(m);
     if (m->pf_ep_partial) (void)hipFree(m->pf_ep_partial);
     for (bf16_t* p : {m->pf_h, m->pf_h2, m->pf_xn, m->pf_q, m->pf_k, m->pf_v, m->pf_qt, m->pf_attn, m->pf_g, m->pf_u})
         if (p) (void)hipFree(p);

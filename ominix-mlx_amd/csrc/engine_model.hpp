@@ -1,5 +1,6 @@
 // The Qwen3 engine's model object and what its translation units share: engine.hip (the C API), engine_weights.hip (checkpoint
-// tensors), engine_step.hip (the decode step and its captured forms), engine_prefill.hip (the batched prompt / verify / encoder pass).
+// tensors), engine_step.hip (the decode step and its captured forms), engine_prefill.hip (the batched prompt / verify / encoder pass),
+// engine_score.hip (omx_qwen3_score: that pass + the head over every row in vocabulary panels).
 // The library is built without relocatable device code: a kernel lives in the unit that launches it, another unit reaches it through
 // a host launcher declared here.
 #pragma once
@@ -164,6 +165,15 @@ struct omx_qwen3_ {
     bf16_t* verify_logits = nullptr;            // [verify_cap, V]: every row's logits of the last omx_qwen3_verify
     uint32_t* verify_tokens = nullptr;
     int verify_cap = 0, verify_rows = 0;
+    // omx_qwen3_score (engine_score.hip): one vocabulary panel of logits [score_rows, score_panel], the chunk partials of every row,
+    // and (packed head) the panel's dequantised head rows [score_panel, hidden]; allocated on first use and on growth
+    bf16_t *score_panel_buf = nullptr, *score_dq = nullptr;
+    float *score_part = nullptr, *score_tgt = nullptr, *score_lp = nullptr;
+    uint32_t *score_arg = nullptr, *score_targets = nullptr, *score_greedy = nullptr;
+    int score_rows = 0, score_panel = 0;
+    bool score_dq_on = false;
+    hipEvent_t score_ev[3] = {nullptr, nullptr, nullptr};
+    float last_score_pass_ms = 0.f, last_score_head_ms = 0.f;
     std::vector<hipEvent_t>* kernel_events = nullptr;   // set for eager steps by omx_qwen3_time_step_kernels: [layer][class][begin, end]
 
     void* comm = nullptr;
@@ -283,6 +293,9 @@ int packed_rows(const QGemvArgs& g, int T, bf16_t* const* mout, int bits, int pr
 int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = nullptr, bool full_last = false, bool packed_rows_pass = false,
                            const KvSlabs* kv = nullptr, const RaggedRows* rag = nullptr);
 void launch_encoder_mask(bf16_t* mask, const uint8_t* am, int T, hipStream_t s);
+
+// engine_score.hip
+void score_release(omx_qwen3 m);   // the buffers and events of omx_qwen3_score (destroy)
 
 // the ragged launches of a batched decode step over T <= 8 rows (RaggedRows; engine_batch.hip, the scatter beside its prompt form in
 // prefill.hip); q rows go to pf_qt as [T, H, D], the attention output to pf_attn as [T, H * D]

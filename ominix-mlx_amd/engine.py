@@ -99,6 +99,8 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_verify": (c_int, [c_void_p, ctypes.POINTER(c_uint32), c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_verify_logits": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "omx_qwen3_trim": (c_int, [c_void_p, c_int, c_uint32]),
+    "omx_qwen3_score": (c_int, [c_void_p, ctypes.POINTER(c_uint32), c_int, ctypes.POINTER(c_uint32), ctypes.POINTER(c_float), ctypes.POINTER(c_uint32)]),
+    "omx_qwen3_last_score_ms": (c_int, [c_void_p, ctypes.POINTER(c_float), ctypes.POINTER(c_float)]),
     "omx_qwen3_get_weight": (c_int, [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_size_t)]),
     # mixed-precision MLX checkpoints: one packed matrix's own (bits, group_size), and the query
     "omx_qwen3_set_quant_format": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_int]),
@@ -488,6 +490,29 @@ class Model:
     def trim(self, n: int, next_token: int) -> None:
         """KeyValueCache::trim(n) (missing in the reference, speculative.rs:165-169) + the next step's input token."""
         check(lib.omx_qwen3_trim(self._h, n, int(next_token)))
+
+    def score(self, tokens, next_token=None, return_greedy=False):
+        """Per-token log-probabilities of a text from ONE batched pass on top of the cache (omx_qwen3_score): entry i is
+        log p(tokens[i + 1] | cache, tokens[:i + 1]), float32 [n - 1] -- or [n] with next_token, the target of the last position.  The n
+        tokens are appended to the cache (offset() advances by n); the pending input token becomes the last row's argmax, trim(0, tok)
+        sets another.  return_greedy: also the argmax of every one of the n rows, uint32 [n]."""
+        ids = np.ascontiguousarray(np.asarray(tokens, dtype=np.uint32).ravel())
+        last = 0xFFFFFFFF if next_token is None else int(next_token)
+        targets = np.ascontiguousarray(np.concatenate([ids[1:], np.array([last], dtype=np.uint32)]), dtype=np.uint32)
+        lp = np.zeros(ids.size, dtype=np.float32)
+        greedy = np.zeros(ids.size, dtype=np.uint32)
+        u32p = ctypes.POINTER(c_uint32)
+        check(lib.omx_qwen3_score(self._h, ids.ctypes.data_as(u32p), ids.size, targets.ctypes.data_as(u32p),
+                                  lp.ctypes.data_as(ctypes.POINTER(c_float)), greedy.ctypes.data_as(u32p)))
+        if next_token is None:
+            lp = lp[:-1]
+        return (lp, greedy) if return_greedy else lp
+
+    def last_score_ms(self) -> tuple:
+        """Device ms of the last score() call: (the prompt pass, the head: final norm + panel GEMMs + statistics + merge)."""
+        a, b = c_float(), c_float()
+        check(lib.omx_qwen3_last_score_ms(self._h, ctypes.byref(a), ctypes.byref(b)))
+        return a.value, b.value
 
     def last_decode_ms(self) -> float:
         v = c_float()

@@ -9,6 +9,8 @@
 
     generate_batch                       many prompts over the slots of an `engine.Batch` (the reference batches through the [B, L]
                                          ids of Model::forward; here the sequences are ragged and retire one by one)
+    perplexity                           the strided log-likelihood evaluation of a token sequence over `engine.Model.score` (the
+                                         reference's Model::forward returns the [B, L, V] logits it would be taken from)
 
 The model side is `engine.Model` / `engine.Generate` / `engine.Batch` (the HIP decode engine); nothing here touches the GPU."""
 from __future__ import annotations
@@ -201,3 +203,32 @@ def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int,
             if finished(i):
                 retire(slot, i)
     return outputs
+
+
+def perplexity(model, ids: Sequence[int], ctx: int = 2048, stride: Optional[int] = None) -> dict:
+    """Perplexity of a token sequence, the standard strided evaluation: windows ids[b : b + ctx] at b = 0, stride, 2 stride, ... each
+    scored from an empty cache (model.reset(), then ONE model.score pass; the token behind the window, where the text has one, is the
+    target of the window's last position), and of every window only the targets no earlier window counted enter the sum -- so each of
+    the len(ids) - 1 targets is counted exactly once, conditioned on at least ctx - stride + 1 tokens where the text has them.  stride
+    defaults to ctx (windows side by side).  Returns {"tokens": targets counted, "nll": their summed negative log-likelihood in nats,
+    "ppl": exp(nll / tokens)}.  Pure host logic over model.reset / model.score."""
+    import math
+    ids = [int(t) for t in ids]
+    stride = ctx if stride is None else int(stride)
+    if len(ids) < 2:
+        raise ValueError("perplexity: a text of at least 2 tokens is needed (the first token has no context to be predicted from)")
+    if ctx < 1 or stride < 1 or stride > ctx:
+        raise ValueError(f"perplexity: ctx = {ctx} must be positive and stride = {stride} in 1..ctx")
+    n = len(ids)
+    nll, done, begin = 0.0, 0, 0            # done: the targets ids[1 .. done] are counted (ids[0] is nobody's target)
+    while done < n - 1:
+        end = min(begin + ctx, n)
+        model.reset()
+        # lp[i] = log p(ids[begin + i + 1] | ids[begin : begin + i + 1]); with a token behind the window, also the last position's
+        lp = model.score(ids[begin:end], next_token=ids[end] if end < n else None)
+        last = min(end, n - 1)
+        for t in range(done + 1, last + 1):
+            nll -= float(lp[t - begin - 1])
+        done = last
+        begin += stride
+    return {"tokens": n - 1, "nll": nll, "ppl": math.exp(nll / (n - 1))}

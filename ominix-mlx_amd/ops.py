@@ -268,6 +268,32 @@ def argmax(logits: Tensor) -> Tensor:
     return out
 
 
+NO_TARGET = 0xFFFFFFFF   # OMX_NO_TARGET: a row without a target column (its logprob is 0)
+
+
+def logprob_rows(logits: Tensor, targets: Tensor, V: Optional[int] = None, panels: Optional[Sequence[int]] = None):
+    """Per-row log-probability of a target column (csrc/logprob.hip): logits bf16 [rows, ld] of which the first V columns are the row
+    (default V = ld), targets u32 [rows].  Returns (logprobs f32 [rows], lse f32 [rows], greedy u32 [rows]).  panels: widths of the
+    column panels of the two-phase form (omx_logprob_partial per panel, read in place at the row stride ld, then one omx_logprob_merge);
+    None: omx_logprob_rows, the whole row as one panel.  The results carry the same bits either way."""
+    rows, ld = logits.size // logits.shape[-1], logits.shape[-1]
+    V = ld if V is None else int(V)
+    lp, lse, greedy = Tensor((rows,), FLOAT32), Tensor((rows,), FLOAT32), Tensor((rows,), UINT32)
+    if panels is None:
+        check(lib.omx_logprob_rows(lp.ptr, greedy.ptr, lse.ptr, logits.ptr, ld, targets.ptr, rows, V, logits.dtype, None))
+        return lp, lse, greedy
+    if sum(int(p) for p in panels) != V:
+        raise OmxError(f"logprob_rows: panels {list(panels)} do not add up to V = {V}")
+    nch = (V + 1023) // 1024
+    part, arg, tgt = Tensor((rows, nch, 2), FLOAT32), Tensor((rows, nch), UINT32), Tensor((rows,), FLOAT32)
+    c0 = 0
+    for p in panels:
+        check(lib.omx_logprob_partial(part.ptr, arg.ptr, tgt.ptr, logits.ptr + 2 * c0, ld, c0, int(p), targets.ptr, rows, V, logits.dtype, None))
+        c0 += int(p)
+    check(lib.omx_logprob_merge(lp.ptr, greedy.ptr, lse.ptr, part.ptr, arg.ptr, tgt.ptr, targets.ptr, rows, V, None))
+    return lp, lse, greedy
+
+
 def cast(x: Tensor, dtype) -> Tensor:
     """mlx_rs as_dtype between bf16 / f16 / f32 (one rounding)."""
     out = Tensor(x.shape, dtype)
