@@ -451,6 +451,31 @@ typedef struct omx_gemv_ex_ {
     int route_nv, route_ksplit, route_tail, route_rows_per_wave, route_blocks;   /* out */
 } omx_gemv_ex;
 int omx_debug_gemv_ex(omx_gemv_ex* a, omx_stream stream);
+/* test hook of the packed decode GEMV (csrc/quant.hip, qgemv_mfma.hip): ONE launch_qgemv with every field the engines set.
+ * In: up to three members m[0 .. 2] (n == 0 ends the list; bits / group 0: the launch's) -- a row stack (N = sum of n), or gate m[0] /
+ * up m[1] of N rows each for epi 2; N, K, group, bits, pro (0 none, 1 RMSNorm), epi (0 store, 1 residual, 2 SwiGLU, 3 logits + argmax
+ * partials, 4 f32 row sums), eps, single_round; scales_f16 (float16 triplets: x, norm_w, resid and out are float16 too); use_sb: build
+ * the interleaved scale | bias words first, for any K; use_tiles: build the matrix-core tiles where the shape has them; mfma: the
+ * matrix-core mode of this call (0 never), restored afterwards; row_offset, rolled_stage; the batch fields n_batch, x_div, w_sel
+ * [n_batch] expert ids, w_estride words / s_estride groups between experts, w_sel_lo / w_sel_n, n_experts (matrices per member's stack,
+ * for use_sb; 0 = 1); x, norm_w, resid; out [n_batch, N], out_f32 (epi 4), argmax_slot with its capacity argmax_slot_n (a launch that
+ * needs more is refused on the host).  Out, the route the launchers report: route_kernel (1 the VALU kernel on one format, 2 the
+ * mixed-format stack kernel, 3 the matrix-core kernel), its BITS / W / RB (stack: 0 / 0 / RB), the resolved rows_per_wave, SB, F16S,
+ * blocks along x, dynamic LDS bytes and, on the matrix cores, KS / NU / NBUF.  dry_run != 0: only the route (no device needed, no
+ * pointer read).  Synchronises the stream. */
+typedef struct omx_qgemv_member_ { const void* w; const void* scales; const void* biases; int n, bits, group; } omx_qgemv_member;
+typedef struct omx_qgemv_ex_ {
+    omx_qgemv_member m[3];
+    int N, K, group, bits, pro, epi; float eps; int single_round;
+    int scales_f16, use_sb, use_tiles, mfma, row_offset, rolled_stage;
+    int n_batch, x_div; const unsigned* w_sel; long long w_estride, s_estride; int w_sel_lo, w_sel_n, n_experts;
+    const void* x; const void* norm_w; const void* resid;
+    void* out; float* out_f32; unsigned long long* argmax_slot; int argmax_slot_n;
+    int dry_run;
+    int route_kernel, route_bits, route_w, route_rb, route_rows_per_wave, route_sb, route_f16s, route_blocks, route_lds_bytes,
+        route_ks, route_nu, route_nbuf;   /* out */
+} omx_qgemv_ex;
+int omx_debug_qgemv_ex(omx_qgemv_ex* a, omx_stream stream);
 /* test hook of the step attention (csrc/attn_step.hip): ONE launch_attn_step on caller-owned buffers, without the O projection.
  * qkv [H*D | Hkv*D | Hkv*D] raw, K / V slabs [Hkv, cap, D], q/k norm weights [D] (both null: no q/k norm), rope_cur [D] f32
  * cos | sin of `pos`, granules [granules_n] (kept by the caller: leftovers of earlier calls stay, as in the engine), tag

@@ -1,6 +1,7 @@
 // Measurement hooks (not part of the drop-in surface): time one kernel family with HIP events on
 // the stream it is launched on.  Weight buffers are rotated through `n_copies` distinct
 // allocations so that the 256 MiB Infinity Cache cannot serve re-reads (MI355X_MICROARCH.md).
+#include <algorithm>
 #include <vector>
 
 #include "gemm.hpp"
@@ -573,6 +574,101 @@ extern "C" int omx_debug_gemv_rows(omx_gemv_rows_dbg* d, void* stream) {
     if (rc) return rc;
     OMX_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
+}
+
+namespace omx { extern int g_qgemv_mfma_mode; }   // qgemv_mfma.hip
+
+/* test hook of the packed decode GEMV: ONE launch_qgemv with every field of the launch, as the engines fill them in (include/omx.h
+ * lists the fields), and the route the launchers report.  The route is taken first, on the host; what the launch needs (argmax slots)
+ * is checked against it before anything runs.  Synchronises the stream. */
+extern "C" int omx_debug_qgemv_ex(omx_qgemv_ex* d, void* stream) {
+    using namespace omx;
+    OMX_REQUIRE(d && d->N > 0 && d->K > 0, "omx_debug_qgemv_ex: bad arguments");
+    OMX_REQUIRE(d->pro == PRO_NONE || d->pro == PRO_RMSNORM, "omx_debug_qgemv_ex: prologue %d", d->pro);
+    hipStream_t s = (hipStream_t)stream;
+    const uint32_t* const kDummy = reinterpret_cast<const uint32_t*>(uintptr_t(64));   // "present" in a launch that never runs
+    const int n_experts = d->n_experts > 1 ? d->n_experts : 1;
+    QGemvArgs a = {};
+    int rows = 0, n_members = 0;
+    for (int i = 0; i < 3; ++i) {
+        const omx_qgemv_member& m = d->m[i];
+        if (m.n <= 0) break;
+        OMX_REQUIRE(d->dry_run || (m.w && m.scales), "omx_debug_qgemv_ex: member %d has no weights / scales", i);
+        a.m[i] = QMat{d->dry_run ? kDummy : (const uint32_t*)m.w, (const bf16_t*)m.scales, (const bf16_t*)m.biases, m.n};
+        a.m[i].bits = m.bits; a.m[i].group = m.group;
+        rows += m.n; n_members = i + 1;
+    }
+    OMX_REQUIRE(n_members >= 1, "omx_debug_qgemv_ex: no member");
+    if (d->epi == EPI_SWIGLU) OMX_REQUIRE(n_members == 2 && d->m[0].n == d->N && d->m[1].n == d->N, "omx_debug_qgemv_ex: SwiGLU takes gate and up of N rows each");
+    else OMX_REQUIRE(rows == d->N, "omx_debug_qgemv_ex: the members hold %d rows, N = %d", rows, d->N);
+    a.N = d->N; a.K = d->K; a.group = d->group;
+    a.x = (const bf16_t*)d->x; a.norm_w = (const bf16_t*)d->norm_w; a.eps = d->eps; a.resid = (const bf16_t*)d->resid;
+    a.out = (bf16_t*)d->out; a.out_f32 = d->out_f32; a.argmax_slot = d->argmax_slot; a.swiglu_single_round = d->single_round;
+    a.scales_f16 = d->scales_f16; a.row_offset = d->row_offset; a.rolled_stage = d->rolled_stage;
+    a.n_batch = d->n_batch; a.x_div = d->x_div; a.w_sel = d->w_sel; a.w_estride = (size_t)d->w_estride; a.s_estride = (size_t)d->s_estride;
+    a.w_sel_lo = d->w_sel_lo; a.w_sel_n = d->w_sel_n;
+    // the route first, with placeholders where the repacks will be
+    bool tiles_ok[3] = {false, false, false};
+    for (int i = 0; i < n_members; ++i) {
+        const int b = qmat_bits(a.m[i], d->bits), g = qmat_group(a.m[i], d->group);
+        OMX_REQUIRE(g > 0 && d->K % g == 0, "omx_debug_qgemv_ex: the row width (%d) must be divisible by the group size (%d)", d->K, g);
+        if (d->use_sb) a.m[i].sb = kDummy;
+        tiles_ok[i] = d->use_tiles && n_experts == 1 && qgemv4m_shape_ok(d->K, g, b);
+        if (tiles_ok[i]) a.m[i].tiles = kDummy;
+    }
+    QGemvRoute r = {};
+    r.dry_run = 1;
+    const int saved_mode = g_qgemv_mfma_mode;
+    g_qgemv_mfma_mode = d->mfma;
+    int rc = launch_qgemv(a, d->bits, d->pro, d->epi, s, &r);
+    g_qgemv_mfma_mode = saved_mode;
+    if (rc) return rc;
+    OMX_REQUIRE(r.kernel != 0, "omx_debug_qgemv_ex: the launchers reported no route");
+    d->route_kernel = r.kernel; d->route_bits = r.bits; d->route_w = r.W; d->route_rb = r.RB; d->route_rows_per_wave = r.rows_per_wave;
+    d->route_sb = r.SB; d->route_f16s = r.F16S; d->route_blocks = r.blocks; d->route_lds_bytes = r.lds_bytes;
+    d->route_ks = r.KS; d->route_nu = r.NU; d->route_nbuf = r.NBUF;
+    if (d->dry_run) return 0;
+    OMX_REQUIRE(d->x && (d->epi == EPI_F32 ? (void*)d->out_f32 : d->out), "omx_debug_qgemv_ex: x and the output are required");
+    OMX_REQUIRE(d->pro != PRO_RMSNORM || d->norm_w, "omx_debug_qgemv_ex: the RMSNorm prologue reads norm_w");
+    OMX_REQUIRE(d->epi != EPI_RESIDUAL || d->resid, "omx_debug_qgemv_ex: the residual epilogue reads resid");
+    if (d->epi == EPI_ARGMAX) {
+        // the matrix-core kernel also clears the slots up to qgemv_grid(N), which the engines reduce
+        const int need = r.kernel == 3 ? std::max(r.blocks, qgemv_grid(d->N)) : r.blocks;
+        OMX_REQUIRE(d->argmax_slot && need <= d->argmax_slot_n, "omx_debug_qgemv_ex: the launch writes %d argmax partials, the slot holds %d",
+                    need, d->argmax_slot_n);
+    }
+    OMX_REQUIRE(!d->w_sel || (d->n_batch >= 1 && d->x_div >= 1), "omx_debug_qgemv_ex: an expert-selected launch needs n_batch and x_div");
+    std::vector<void*> owned;
+    for (int i = 0; i < n_members && !rc; ++i) {
+        const int g = qmat_group(a.m[i], d->group);
+        a.m[i].sb = nullptr; a.m[i].tiles = nullptr;
+        if (d->use_sb) {
+            const size_t per = (size_t)a.m[i].n * (d->K / g), ng = n_experts > 1 ? (size_t)(n_experts - 1) * a.s_estride + per : per;
+            uint32_t* sb = nullptr;
+            if (hipMalloc((void**)&sb, ng * 4) != hipSuccess) { rc = set_error("omx_debug_qgemv_ex: out of memory"); break; }
+            owned.push_back(sb);
+            rc = launch_quant_interleave(sb, a.m[i].scales, a.m[i].biases, ng, s);
+            a.m[i].sb = sb;
+        }
+        if (tiles_ok[i] && !rc) {
+            uint32_t* t = nullptr;
+            if (hipMalloc((void**)&t, qgemv4m_tile_words(a.m[i].n, d->K) * 4) != hipSuccess) { rc = set_error("omx_debug_qgemv_ex: out of memory"); break; }
+            owned.push_back(t);
+            rc = launch_qgemv4m_repack(t, a.m[i].w, a.m[i].scales, a.m[i].biases, a.m[i].n, d->K, s);
+            a.m[i].tiles = t;
+        }
+    }
+    if (!rc) {
+        QGemvRoute r2 = {};
+        g_qgemv_mfma_mode = d->mfma;
+        rc = launch_qgemv(a, d->bits, d->pro, d->epi, s, &r2);
+        g_qgemv_mfma_mode = saved_mode;
+        if (!rc && (r2.kernel != r.kernel || r2.blocks != r.blocks || r2.lds_bytes != r.lds_bytes))
+            rc = set_error("omx_debug_qgemv_ex: the launch took kernel %d with %d blocks, the dry pass reported kernel %d with %d", r2.kernel, r2.blocks, r.kernel, r.blocks);
+    }
+    (void)hipStreamSynchronize(s);
+    for (void* p : owned) (void)hipFree(p);
+    return rc;
 }
 
 /* test hook of qgemv_rows.hip: M activation rows x [M, K] against n_members packed matrices (w / sc / bi / n: arrays of n_members; a

@@ -269,8 +269,13 @@ __global__ __launch_bounds__(KS * 64, (NU * NBUF <= 2 ? OMX_QM_MINW : 2)) void q
 }
 
 template <int KS, int NU, int PRO, int EPI, int NBUF>
-int launch_one(const QGemvArgs& a, int grid, hipStream_t s) {
+int launch_one(const QGemvArgs& a, int grid, hipStream_t s, QGemvRoute* route) {
     const size_t shmem = (size_t)KS * 1024 * 2 + (size_t)KS * 16 * 4 + (size_t)2 * NU * KS * 16 * 4 + 32 * 8 + 64;
+    if (route) {
+        route->kernel = 3; route->bits = 4; route->W = 4; route->RB = 0; route->rows_per_wave = 0; route->SB = 1; route->F16S = 0;
+        route->blocks = grid; route->lds_bytes = (int)shmem; route->KS = KS; route->NU = NU; route->NBUF = NBUF;
+        if (route->dry_run) return 0;
+    }
     OMX_LAUNCH_TIMED((qgemv4m_kernel<KS, NU, PRO, EPI, NBUF>), dim3(grid), dim3(KS * 64), shmem, s, a);
     OMX_LAUNCH_CHECK();
     return 0;
@@ -287,23 +292,23 @@ int stream_grid() {   // blocks of a streaming launch (the vocabulary matrix): t
 }
 
 template <int KS>
-int launch_ks(const QGemvArgs& a_in, int pro, int epi, hipStream_t s) {
+int launch_ks(const QGemvArgs& a_in, int pro, int epi, hipStream_t s, QGemvRoute* route) {
     QGemvArgs a = a_in;
     const int n_rb = (a.N + 15) / 16;
     if (epi == EPI_SWIGLU) {
-        if (pro == PRO_RMSNORM) return launch_one<KS, 2, PRO_RMSNORM, EPI_SWIGLU, 1>(a, n_rb, s);
-        return launch_one<KS, 2, PRO_NONE, EPI_SWIGLU, 1>(a, n_rb, s);
+        if (pro == PRO_RMSNORM) return launch_one<KS, 2, PRO_RMSNORM, EPI_SWIGLU, 1>(a, n_rb, s, route);
+        return launch_one<KS, 2, PRO_NONE, EPI_SWIGLU, 1>(a, n_rb, s, route);
     }
     if (epi == EPI_ARGMAX && pro == PRO_RMSNORM) {
         const int slots = qgemv_grid(a.N), grid = std::min(std::min(n_rb, slots), stream_grid());
         a.rolled_stage = slots;      // (a field the VALU kernel's A/B switch owns: here the number of argmax slots to leave defined)
-        if (grid * 3 <= n_rb) return launch_one<KS, 1, PRO_RMSNORM, EPI_ARGMAX, 3>(a, grid, s);
-        return launch_one<KS, 1, PRO_RMSNORM, EPI_ARGMAX, 1>(a, std::min(n_rb, slots), s);
+        if (grid * 3 <= n_rb) return launch_one<KS, 1, PRO_RMSNORM, EPI_ARGMAX, 3>(a, grid, s, route);
+        return launch_one<KS, 1, PRO_RMSNORM, EPI_ARGMAX, 1>(a, std::min(n_rb, slots), s, route);
     }
-    if (epi == EPI_STORE && pro == PRO_RMSNORM) return launch_one<KS, 1, PRO_RMSNORM, EPI_STORE, 1>(a, n_rb, s);
-    if (epi == EPI_STORE && pro == PRO_NONE) return launch_one<KS, 1, PRO_NONE, EPI_STORE, 1>(a, n_rb, s);
-    if (epi == EPI_RESIDUAL && pro == PRO_NONE) return launch_one<KS, 1, PRO_NONE, EPI_RESIDUAL, 1>(a, n_rb, s);
-    if (epi == EPI_F32 && pro == PRO_NONE) return launch_one<KS, 1, PRO_NONE, EPI_F32, 1>(a, n_rb, s);
+    if (epi == EPI_STORE && pro == PRO_RMSNORM) return launch_one<KS, 1, PRO_RMSNORM, EPI_STORE, 1>(a, n_rb, s, route);
+    if (epi == EPI_STORE && pro == PRO_NONE) return launch_one<KS, 1, PRO_NONE, EPI_STORE, 1>(a, n_rb, s, route);
+    if (epi == EPI_RESIDUAL && pro == PRO_NONE) return launch_one<KS, 1, PRO_NONE, EPI_RESIDUAL, 1>(a, n_rb, s, route);
+    if (epi == EPI_F32 && pro == PRO_NONE) return launch_one<KS, 1, PRO_NONE, EPI_F32, 1>(a, n_rb, s, route);
     return -1;
 }
 
@@ -324,7 +329,7 @@ int g_qgemv_mfma_mode = 1;    // 0: never (tests flip it through omx_debug_qgemv
                               // OMX_QGEMV_MFMA=0 makes the engine (and the bench hook) build no tiles
 
 // 0: launched; -1: not a shape / form of this kernel (the caller takes quant.hip's VALU kernel); 1: error
-int launch_qgemv4m(const QGemvArgs& a, int pro, int epi, hipStream_t s) {
+int launch_qgemv4m(const QGemvArgs& a, int pro, int epi, hipStream_t s, QGemvRoute* route) {
     if (g_qgemv_mfma_mode == 0 || a.group != 64 || a.scales_f16 || a.n_batch > 1 || a.w_sel || a.w_sel_n > 0 || a.N < 16) return -1;
     if (!qgemv4m_shape_ok(a.K, a.group, 4)) return -1;
     for (int i = 0; i < 3; ++i)
@@ -337,13 +342,13 @@ int launch_qgemv4m(const QGemvArgs& a, int pro, int epi, hipStream_t s) {
         if (a.m[2].w && a.m[1].n % 16 != 0) return -1;
     }
     switch (a.K / 1024) {
-        case 1: return launch_ks<1>(a, pro, epi, s);
-        case 2: return launch_ks<2>(a, pro, epi, s);
-        case 3: return launch_ks<3>(a, pro, epi, s);
-        case 4: return launch_ks<4>(a, pro, epi, s);
-        case 6: return launch_ks<6>(a, pro, epi, s);
-        case 8: return launch_ks<8>(a, pro, epi, s);
-        default: return launch_ks<12>(a, pro, epi, s);
+        case 1: return launch_ks<1>(a, pro, epi, s, route);
+        case 2: return launch_ks<2>(a, pro, epi, s, route);
+        case 3: return launch_ks<3>(a, pro, epi, s, route);
+        case 4: return launch_ks<4>(a, pro, epi, s, route);
+        case 6: return launch_ks<6>(a, pro, epi, s, route);
+        case 8: return launch_ks<8>(a, pro, epi, s, route);
+        default: return launch_ks<12>(a, pro, epi, s, route);
     }
 }
 

@@ -277,8 +277,14 @@ __global__ __launch_bounds__(256) void qgemv_stack_kernel(const QGemvArgs a, con
 #undef OMX_QSTACK_CASE
 }
 
+// the (prologue, epilogue) pairs qgemv_kernel is instantiated for
+static bool qgemv_form_built(int pro, int epi) {
+    return (pro == PRO_NONE && (epi == EPI_STORE || epi == EPI_RESIDUAL || epi == EPI_SWIGLU || epi == EPI_F32)) ||
+           (pro == PRO_RMSNORM && (epi == EPI_STORE || epi == EPI_SWIGLU || epi == EPI_ARGMAX));
+}
+
 template <int BITS, int W>
-int launch_qgemv_w(const QGemvArgs& a, int pro, int epi, hipStream_t s) {
+int launch_qgemv_w(const QGemvArgs& a, int pro, int epi, hipStream_t s, QGemvRoute* route) {
     constexpr int EPW = 32 / BITS;
     const int groups = (a.N + a.rows_per_wave - 1) / a.rows_per_wave;
     const dim3 grid((groups + 3) / 4, a.n_batch > 1 ? a.n_batch : 1), block(256);
@@ -290,6 +296,12 @@ int launch_qgemv_w(const QGemvArgs& a, int pro, int epi, hipStream_t s) {
     bool sb = W == 4 || quant_chunked(BITS);
     for (int i = 0; i < 3 && sb; ++i)
         if (a.m[i].w && !a.m[i].sb) sb = false;
+    if (route && qgemv_form_built(pro, epi)) {
+        route->kernel = 1; route->bits = BITS; route->W = W; route->RB = (epi == EPI_SWIGLU || a.rows_per_wave == 2) ? 2 : 4;
+        route->rows_per_wave = a.rows_per_wave; route->SB = sb; route->F16S = a.scales_f16 != 0;
+        route->blocks = (int)grid.x; route->lds_bytes = (int)shmem; route->KS = route->NU = route->NBUF = 0;
+        if (route->dry_run) return 0;
+    }
 #define OMX_QGEMV_LAUNCH(P, E, SBF, F16)                                                       \
     {                                                                                         \
         if (E == EPI_SWIGLU || a.rows_per_wave == 2) OMX_LAUNCH((qgemv_kernel<BITS, W, P, E, 2, SBF, F16>), grid, block, shmem, s, a); \
@@ -332,9 +344,13 @@ int qgemv_words(int bits, int K, int group) {
 }
 
 // rows per wave of a launch over N logical rows: long streams for the vocabulary matrix, one batch per wave otherwise; small matrices:
-// two rows per wave -- and the tuning knobs that override it
+// two rows per wave -- and the tuning knobs that override it.  An EPI_ARGMAX launch takes no knob: its block count is the number of
+// partial keys the engines sized their slots for and reduce (qgemv_grid, which sees neither K nor the environment) -- with
+// OMX_QGEMV_RPW_SMALL=4 a vocabulary of N <= 8192 wrote half of them and the reduction read the rest as they were left
+int qgemv_default_rpw(int N, int epi) { return N >= 65536 ? 16 : (N <= 8192 && epi != EPI_SWIGLU) ? 2 : 4; }
 int qgemv_rows_per_wave(int N, int K, int epi) {
-    int rpw = N >= 65536 ? 16 : (N <= 8192 && epi != EPI_SWIGLU) ? 2 : 4;
+    int rpw = qgemv_default_rpw(N, epi);
+    if (epi == EPI_ARGMAX) return rpw;
     if (const char* e = getenv("OMX_QGEMV_RPW_SMALL"))   // tuning knob: rows per wave of the small matrices (2 or 4)
         if (N <= 8192 && epi != EPI_SWIGLU && (atoi(e) == 2 || atoi(e) == 4)) rpw = atoi(e);
     if (const char* e = getenv("OMX_QGEMV_RPW_LONGK"))   // ... of the small matrices with a long row (K > 8192: the down projection)
@@ -345,26 +361,26 @@ int qgemv_rows_per_wave(int N, int K, int epi) {
 }
 
 template <int BITS>
-int launch_qgemv_bits(const QGemvArgs& a_in, int pro, int epi, hipStream_t s) {
+int launch_qgemv_bits(const QGemvArgs& a_in, int pro, int epi, hipStream_t s, QGemvRoute* route) {
     QGemvArgs a = a_in;
-    constexpr int EPW = 32 / BITS;
     const int W = qgemv_words(BITS, a.K, a.group);
     if constexpr (quant_chunked(BITS)) {
         OMX_REQUIRE(W != 0, "quantized_matmul: K=%d unsupported for %d-bit group %d", a.K, BITS, a.group);
     } else {
+        // (the narrowest lane chunk is 8 elements -- one 16-byte activation vector -- at either width: 64 lanes x 8)
         OMX_REQUIRE(W != 0, "quantized_matmul: K=%d unsupported for %d-bit group %d (K must be a multiple of %d)",
-                    a.K, BITS, a.group, 64 * EPW);
+                    a.K, BITS, a.group, 64 * 8);
     }
     if (a.n_batch < 1) a.n_batch = 1;
     if (a.x_div < 1) a.x_div = 1;
     a.rows_per_wave = qgemv_rows_per_wave(a.N, a.K, epi);
     if (const char* e = getenv("OMX_QGEMV_ROLLED_STAGE")) a.rolled_stage = e[0] == '1';
     if constexpr (quant_chunked(BITS)) {
-        return launch_qgemv_w<BITS, BITS>(a, pro, epi, s);
+        return launch_qgemv_w<BITS, BITS>(a, pro, epi, s, route);
     } else {
-        if (W == 4) return launch_qgemv_w<BITS, 4>(a, pro, epi, s);
-        if (W == 2) return launch_qgemv_w<BITS, 2>(a, pro, epi, s);
-        if constexpr (BITS == 4) return launch_qgemv_w<BITS, 1>(a, pro, epi, s);
+        if (W == 4) return launch_qgemv_w<BITS, 4>(a, pro, epi, s, route);
+        if (W == 2) return launch_qgemv_w<BITS, 2>(a, pro, epi, s, route);
+        if constexpr (BITS == 4) return launch_qgemv_w<BITS, 1>(a, pro, epi, s, route);
         return set_error("quantized gemv: K=%d too small for %d-bit weights", a.K, BITS);
     }
 }
@@ -425,12 +441,12 @@ const uint32_t* quant_find_sb(const bf16_t* scales) {
 }
 
 int qgemv_grid(int N) {
-    const int rpw = N >= 65536 ? 16 : N <= 8192 ? 2 : 4;
+    const int rpw = qgemv_default_rpw(N, EPI_ARGMAX);
     return ((N + rpw - 1) / rpw + 3) / 4;
 }
 
 // the q | k | v stack with members of different formats as ONE launch (qgemv_stack_kernel); fb / fg: the members' bits / groups
-static int launch_qgemv_stack(const QGemvArgs& a_in, const int* fb, const int* fg, int pro, hipStream_t s) {
+static int launch_qgemv_stack(const QGemvArgs& a_in, const int* fb, const int* fg, int pro, hipStream_t s, QGemvRoute* route) {
     QGemvArgs a = a_in;
     a.rows_per_wave = qgemv_rows_per_wave(a.N, a.K, EPI_STORE);
     if (const char* e = getenv("OMX_QGEMV_ROLLED_STAGE")) a.rolled_stage = e[0] == '1';
@@ -453,6 +469,11 @@ static int launch_qgemv_stack(const QGemvArgs& a_in, const int* fb, const int* f
     OMX_REQUIRE(col == a.N && blocks > 0, "quantized gemv: the stack's members hold %d rows, N = %d", col, a.N);
     const size_t shmem = (size_t)a.K * 2 + (size_t)(a.K / min_epl) * 4 + 64;
     const dim3 grid(blocks), block(256);
+    if (route && (pro == PRO_NONE || pro == PRO_RMSNORM)) {
+        route->kernel = 2; route->bits = 0; route->W = 0; route->RB = a.rows_per_wave == 2 ? 2 : 4; route->rows_per_wave = a.rows_per_wave;
+        route->SB = sb; route->F16S = 0; route->blocks = blocks; route->lds_bytes = (int)shmem; route->KS = route->NU = route->NBUF = 0;
+        if (route->dry_run) return 0;
+    }
 #define OMX_QSTACK_LAUNCH(P)                                                                                        \
     if (pro == P) {                                                                                                 \
         if (a.rows_per_wave == 2) {                                                                                 \
@@ -471,7 +492,7 @@ static int launch_qgemv_stack(const QGemvArgs& a_in, const int* fb, const int* f
     return set_error("quantized gemv: unsupported prologue %d for a stack of mixed formats", pro);
 }
 
-int launch_qgemv(const QGemvArgs& a_in, int bits, int pro, int epi, hipStream_t s) {
+int launch_qgemv(const QGemvArgs& a_in, int bits, int pro, int epi, hipStream_t s, QGemvRoute* route) {
     // the format each member runs in: its own where it carries one, else the launch's
     int fb[3] = {0, 0, 0}, fg[3] = {0, 0, 0}, first = -1;
     bool mixed = false;
@@ -491,21 +512,21 @@ int launch_qgemv(const QGemvArgs& a_in, int bits, int pro, int epi, hipStream_t 
                 OMX_REQUIRE(fg[i] == 32 || fg[i] == 64 || fg[i] == 128, "quantized gemv: group_size must be 32, 64 or 128 (got %d)", fg[i]);
                 OMX_REQUIRE(a_in.K > 0 && a_in.K % fg[i] == 0, "quantized gemv: the row width (%d) must be divisible by the group size (%d)", a_in.K, fg[i]);
             }
-        return launch_qgemv_stack(a_in, fb, fg, pro, s);
+        return launch_qgemv_stack(a_in, fb, fg, pro, s, route);
     }
     QGemvArgs a = a_in;
     if (first >= 0) { bits = fb[first]; a.group = fg[first]; }
     OMX_REQUIRE(quant_bits_ok(bits), "quantized gemv: bits must be 2, 3, 4, 5, 6 or 8 (got %d)", bits);
     if (bits == 4) {
-        const int r = launch_qgemv4m(a, pro, epi, s);
+        const int r = launch_qgemv4m(a, pro, epi, s, route);
         if (r >= 0) return r;
     }
     switch (bits) {
-    case 2: return launch_qgemv_bits<2>(a, pro, epi, s);
-    case 3: return launch_qgemv_bits<3>(a, pro, epi, s);
-    case 5: return launch_qgemv_bits<5>(a, pro, epi, s);
-    case 6: return launch_qgemv_bits<6>(a, pro, epi, s);
-    default: return bits == 4 ? launch_qgemv_bits<4>(a, pro, epi, s) : launch_qgemv_bits<8>(a, pro, epi, s);
+    case 2: return launch_qgemv_bits<2>(a, pro, epi, s, route);
+    case 3: return launch_qgemv_bits<3>(a, pro, epi, s, route);
+    case 5: return launch_qgemv_bits<5>(a, pro, epi, s, route);
+    case 6: return launch_qgemv_bits<6>(a, pro, epi, s, route);
+    default: return bits == 4 ? launch_qgemv_bits<4>(a, pro, epi, s, route) : launch_qgemv_bits<8>(a, pro, epi, s, route);
     }
 }
 

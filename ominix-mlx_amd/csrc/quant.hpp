@@ -45,7 +45,9 @@ struct QGemvArgs {
     int swiglu_single_round;    // EPI_SWIGLU: fused_swiglu(up, gate) (one rounding, metal_kernels.rs:11-18) instead of nn::silu(g)*u
     int rolled_stage;           // A/B: stage the activation with the rolled loop (OMX_QGEMV_ROLLED_STAGE=1)
     int scales_f16;             // scales / biases (and QMat::sb's halves) hold float16 bit patterns: a float16 MLX checkpoint.  The
-                                // activations stay bf16; every group's scale / bias enters the arithmetic as its exact float32 value
+                                // activations, norm weights, residual and outputs are float16 too then (Act16<true>: x, norm_w, resid
+                                // and out hold float16 bit patterns); every group's scale / bias enters the arithmetic as its exact
+                                // float32 value
     // tensor parallel (round 4): EPI_F32 leaves the unrounded f32 row sums of this rank's K slice in out_f32 [N] (the all-reduce and the
     // fold into the residual follow as their own launches); EPI_ARGMAX numbers its rows from row_offset (this rank's vocabulary shard)
     float* out_f32;             // (batched: [n_batch, N])
@@ -61,16 +63,26 @@ int launch_dequantize_bf16(bf16_t* out, const uint32_t* packed, const void* scal
 // bits / a.group: the format of every member that carries none of its own (QMat::bits / group == 0).  Members of one format: today's
 // launches.  Members that differ (EPI_STORE stacks of bf16 triplets, one activation row): ONE launch of qgemv_stack_kernel.  Either way a
 // member's rows are bit for bit what the VALU kernel gives for that member launched alone.
-int launch_qgemv(const QGemvArgs& a, int bits, int pro, int epi, hipStream_t s);
+// route (optional): what the launch resolved to, filled in by the launcher that takes it -- untouched where the launch is refused
+struct QGemvRoute {
+    int dry_run;              // in: fill in the route and launch nothing (no device needed)
+    int kernel;               // 1 qgemv_kernel (VALU, one format), 2 qgemv_stack_kernel (mixed formats), 3 qgemv4m_kernel (matrix cores)
+    int bits, W, RB;          // the instantiation (stack: 0, 0 -- each member runs its own <BITS, W>; matrix cores: 4, 4, 0)
+    int rows_per_wave;        // resolved (matrix cores: 0, a wave owns a 16-row tile)
+    int SB, F16S;
+    int blocks, lds_bytes;    // blocks along x, dynamic LDS bytes
+    int KS, NU, NBUF;         // matrix cores only
+};
+int launch_qgemv(const QGemvArgs& a, int bits, int pro, int epi, hipStream_t s, QGemvRoute* route = nullptr);
 // the format member i of a launch runs in
 inline int qmat_bits(const QMat& m, int dflt) { return m.bits ? m.bits : dflt; }
 inline int qmat_group(const QMat& m, int dflt) { return m.group ? m.group : dflt; }
 // qgemv_mfma.hip (round 6): the dense 4-bit group-64 single-row forms on the matrix cores.  0 launched, -1 not its shape (take the VALU kernel), 1 error
-int launch_qgemv4m(const QGemvArgs& a, int pro, int epi, hipStream_t s);
+int launch_qgemv4m(const QGemvArgs& a, int pro, int epi, hipStream_t s, QGemvRoute* route = nullptr);
 bool qgemv4m_shape_ok(int K, int group, int bits);
 size_t qgemv4m_tile_words(int n, int K);            // u32 words of the tile form of an [n, K] matrix
 int launch_qgemv4m_repack(uint32_t* tiles, const uint32_t* wq, const bf16_t* scales, const bf16_t* biases, int n, int K, hipStream_t s);
-int qgemv_grid(int N);          // blocks launch_qgemv uses == argmax partials written
+int qgemv_grid(int N);          // blocks launch_qgemv's VALU kernel uses for an EPI_ARGMAX launch == argmax partials the engines reduce
 
 // qgemv_rows.hip: M <= 8 activation rows against one packed matrix (or a q | k | v stack, a gate / up pair) with every packed word read
 // once per launch -- the speculative verify pass of a quantized checkpoint.  g carries launch_qgemv's fields with their meaning for ONE

@@ -40,6 +40,27 @@ class GemvEx(ctypes.Structure):
                 ("route_nv", c_int), ("route_ksplit", c_int), ("route_tail", c_int), ("route_rows_per_wave", c_int), ("route_blocks", c_int)]
 
 
+class QGemvMember(ctypes.Structure):
+    """omx_qgemv_member: one packed matrix of a launch, with its own format (0: the launch's)"""
+    _fields_ = [("w", c_void_p), ("scales", c_void_p), ("biases", c_void_p), ("n", c_int), ("bits", c_int), ("group", c_int)]
+
+
+class QGemvEx(ctypes.Structure):
+    """omx_qgemv_ex: every field of one packed decode GEMV launch (omx_debug_qgemv_ex); route_* are filled in by the call."""
+    _fields_ = [("m", QGemvMember * 3),
+                ("N", c_int), ("K", c_int), ("group", c_int), ("bits", c_int), ("pro", c_int), ("epi", c_int), ("eps", c_float),
+                ("single_round", c_int),
+                ("scales_f16", c_int), ("use_sb", c_int), ("use_tiles", c_int), ("mfma", c_int), ("row_offset", c_int), ("rolled_stage", c_int),
+                ("n_batch", c_int), ("x_div", c_int), ("w_sel", c_void_p), ("w_estride", ctypes.c_longlong), ("s_estride", ctypes.c_longlong),
+                ("w_sel_lo", c_int), ("w_sel_n", c_int), ("n_experts", c_int),
+                ("x", c_void_p), ("norm_w", c_void_p), ("resid", c_void_p),
+                ("out", c_void_p), ("out_f32", c_void_p), ("argmax_slot", c_void_p), ("argmax_slot_n", c_int),
+                ("dry_run", c_int),
+                ("route_kernel", c_int), ("route_bits", c_int), ("route_w", c_int), ("route_rb", c_int), ("route_rows_per_wave", c_int),
+                ("route_sb", c_int), ("route_f16s", c_int), ("route_blocks", c_int), ("route_lds_bytes", c_int),
+                ("route_ks", c_int), ("route_nu", c_int), ("route_nbuf", c_int)]
+
+
 class AttnStepDbg(ctypes.Structure):
     """omx_attn_step_dbg: one step-attention launch on caller-owned buffers (omx_debug_attn_step); chunk / nsplit / abort_flag
     come back filled in."""
@@ -131,6 +152,8 @@ ENGINE_SIGNATURES = {
     # entries) and the route it takes; the step attention (csrc/attn_step.hip) on caller-owned buffers
     "omx_debug_gemv_ex": (c_int, [ctypes.POINTER(GemvEx), c_void_p]),
     "omx_debug_attn_step": (c_int, [ctypes.POINTER(AttnStepDbg), c_void_p]),
+    # the packed decode GEMV (csrc/quant.hip, qgemv_mfma.hip): every field of the launch, and the kernel it resolved to
+    "omx_debug_qgemv_ex": (c_int, [ctypes.POINTER(QGemvEx), c_void_p]),
     # the few-row bf16 Linear (csrc/gemv_rows.hip), plain or segmented, without the GEMM entry's N * K routing threshold
     "omx_debug_gemv_rows": (c_int, [ctypes.POINTER(GemvRowsDbg), c_void_p]),
     "omx_bench_qwen3_per_op": (c_int, [c_void_p, ctypes.POINTER(Qwen3Config), ctypes.POINTER(c_uint32), c_int, c_int, ctypes.POINTER(c_uint32),
