@@ -512,7 +512,9 @@ int omx_qwen3_stream(omx_qwen3 m, omx_stream* s);
 /* algorithmic HBM bytes of ONE decode step at context length ctx (SURVEY.md 8d formula)             */
 int omx_qwen3_step_bytes(omx_qwen3 m, int ctx, double* bytes);
 /* how the decode step is executed once built: 0 = not built yet, 1 = step graph (one launch per phase,
- * replayed as a hipGraph; one graph per 1024-token context bucket), 2 = the same launches issued eagerly */
+ * replayed as a hipGraph; one graph per 1024-token context bucket), 2 = the same launches issued eagerly, 3 = AQL replay on the
+ * engine's own queue; bits 8..11: the rungs of the give-up ladder this engine has gone down (gate/up out of the attention launch,
+ * down + q/k/v as two launches, persistent step off, O projection out of the attention launch) */
 int omx_qwen3_decode_path(omx_qwen3 m, int* path);
 /* debug hook (tools/attn_step_trace.py): run ONE decode step eagerly with the attention launches stamping the
  * 100 MHz wall clock; host receives [layers][attention splits][kv heads][8], *blocks = splits * kv heads     */
@@ -521,14 +523,16 @@ int omx_qwen3_debug_trace_step(omx_qwen3 m, unsigned long long* host, size_t n_w
  * (the dispatch's begin / end timestamps on the step's stream); us[7] = average microseconds of {QKV GEMV, attention, O GEMV,
  * gate/up + SwiGLU GEMV, down GEMV, lm_head, persistent step launch (all layers; the five per-layer figures are 0 then)}.  bench.py's roofline.achieved is the gate/up figure.  Dense bf16 single-rank models.
  * Where down and the next layer's q/k/v are one launch (csrc/gemv_chain.hip), its duration is split between the down and the QKV figure in
- * proportion to their algorithmic bytes. */
+ * proportion to their algorithmic bytes; where gate/up + SwiGLU rides in the attention launch (csrc/attn_step.hip), that launch's duration
+ * is split the same way between the attention and the gate/up figure. */
 int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us);
 /* debug hook (tools/step_engine_trace.py): ONE eager decode step on the persistent engine (csrc/step_engine.hip, OMX_STEP_ENGINE=1)
  * with per-CU wall-clock stamps; host receives [CUs][64] words, *cus = CUs of the device */
 int omx_qwen3_debug_trace_engine(omx_qwen3 m, unsigned long long* host, size_t n_words, int* cus);
 /* test hooks of the decode step's forms.  step_forms: what the NEXT step would take -- forms[0] = down + the next layer's q/k/v in one
  * launch (csrc/gemv_chain.hip, OMX_DOWN_QKV=0 turns it off), forms[1] = the O projection inside the attention launch, forms[2] = the
- * persistent-step mode, forms[3] = 1 once a give-up switched the first off for this engine.  raise_give_up: sets, from the host, the word
+ * persistent-step mode, forms[3] = 1 once a give-up switched the first off for this engine, forms[4] = gate/up + SwiGLU inside the
+ * attention launch (OMX_ATTN_GATEUP=0 turns it off), forms[5] = 1 once a give-up switched that off (forms holds six ints).  raise_give_up: sets, from the host, the word
  * a wait inside a launch raises when it gives up; the next omx_qwen3_decode then replays its steps on the next form of the ladder */
 int omx_qwen3_debug_step_forms(omx_qwen3 m, int* forms);
 int omx_qwen3_debug_raise_give_up(omx_qwen3 m);

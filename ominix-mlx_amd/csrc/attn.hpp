@@ -58,8 +58,16 @@ struct AttnStepArgs {
     const uint32_t* o_sb;       // [o_rows, H*D/group] scale | bias << 16 (QMat::sb)
     int o_group;
     int f16;                    // the model runs in float16 (a float16 MLX checkpoint): qkv, norm weights, K / V slabs and `out` hold float16
+    // ---- optional [RMSNorm + gate/up + SwiGLU] of the same layer behind the bf16 O projection (gu_gate != null; attn_step_gateup_ok) ----
+    const bf16_t* gu_gate;      // [gu_rows, o_rows] row-major (model.rs:263-265)
+    const bf16_t* gu_up;
+    const bf16_t* gu_norm_w;    // [o_rows] post-attention RMSNorm weight
+    bf16_t* gu_out;             // [gu_rows] = silu(gate . xn) * up . xn with the roundings of gemv_kernel<8, 1, 1, PRO_RMSNORM, EPI_SWIGLU>
+    int gu_rows;
+    uint64_t* hg;               // granules [o_rows / 2]: {two packed bf16 of the hidden row the O projection leaves, tag}
 };
 bool attn_step_oproj_ok(int H, int Hkv, int D, int nsplit, int o_rows);
+bool attn_step_gateup_ok(int H, int Hkv, int D, int nsplit, int o_rows, int gu_rows);
 bool attn_step_oproj_q4_ok(int H, int Hkv, int D, int nsplit, int o_rows, int group);
 int attn_step_block_tokens(int D);
 void attn_step_plan(int tk_max, int Hkv, int G, int D, int* chunk, int* nsplit);

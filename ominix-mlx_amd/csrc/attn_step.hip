@@ -32,6 +32,7 @@
 
 #include "attn.hpp"
 #include "act16.hpp"
+#include "gemv_parts.hpp"
 #include "granule.hpp"
 #include "launch_timing.hpp"
 
@@ -209,6 +210,107 @@ __device__ __forceinline__ void oproj_await_vector(const AttnStepArgs& a, u32x4*
     }
 }
 
+// ---- [RMSNorm + gate/up + SwiGLU] of the layer behind the O projection (attn_step_kernel, GU > 0) ----
+// The launch's 256 blocks x 8 waves share the 12 288 (gate, up) row pairs, kGuPairs each.  The hidden row the O projection leaves crosses
+// the launch a third time as granules {two packed bf16, tag}: the scheme of gemv_chain.hip's phase B, whose texts (gemv_parts.hpp) this
+// phase calls -- the arithmetic is gemv_kernel<8, 1, 1, PRO_RMSNORM, EPI_SWIGLU>'s, bit for bit.
+constexpr int kGuPairs = 6, kGuHidden = 4096, kGuNV = kGuHidden / 512;
+
+// one (gate, up) pair into a register set: w[0] the gate row, w[1] the up row
+__device__ __forceinline__ void gateup_issue(const AttnStepArgs& a, u32x4 (*w)[kGuNV], int pair, int lane) {
+    const u32x4* g = reinterpret_cast<const u32x4*>(a.gu_gate + (size_t)pair * kGuHidden);
+    const u32x4* u = reinterpret_cast<const u32x4*>(a.gu_up + (size_t)pair * kGuHidden);
+#pragma unroll
+    for (int j = 0; j < kGuNV; ++j) {
+        w[0][j] = ld_nt(g + j * 64 + lane);
+        w[1][j] = ld_nt(u + j * 64 + lane);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep the loads HERE: the scheduler would sink them to their use
+}
+
+// ... reduced against the normalised row in LDS: gemv.hip's OMX_COMPUTE with NR = 2, then its SwiGLU epilogue
+__device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4 (*w)[kGuNV], const u32x4* xs, int pair, int lane) {
+    typedef Act16<false> A;
+    float acc[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < kGuNV; ++j) {
+        const u32x4 xp = xs[j * 64 + lane];
+        float xf[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            xf[2 * q] = A::lo(xp[q]);
+            xf[2 * q + 1] = A::hi(xp[q]);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) acc[r] = dot8(w[r][j], xf, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) acc[r] = wave_sum(acc[r]);
+    if (lane == 0) a.gu_out[pair] = epi_bits<EPI_SWIGLU, A>(acc[0], acc[1], (bf16_t)0, 0);
+}
+
+// Every wave of every block ends here.  `pub_rows` > 0: the block's O rows [pub_row0, + pub_rows) are parked in sm_pub (a block of O
+// waves holds an even number of rows from an even row on: whole granules).  Wave 0 -- no weight load in flight: a granule asked for
+// behind 32 KB of weights would only arrive after them -- publishes them, watches, sweeps the row into LDS and only then asks for ITS
+// first pair (form 2 of the down -> q/k/v edge); the other waves' pairs are in flight through the hop.
+// Measured at Qwen3-8B shapes, ctx 2 k (EXPERIMENTS C-2): waves 1..7 asking for their first pair HERE, once their O rows are consumed,
+// 343.4 tok/s against the parent's 337.7; asking right behind the O rows' own loads instead -- 57 MB more parked in front of the split
+// merge and the attention vector's sweep -- 338.1: no gain left.
+template <bool TRACE>
+__device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, float* red, const uint16_t* sm_pub, unsigned tag, int lane,
+                                             int wave, int pub_row0, int pub_rows, unsigned long long* tr) {
+    typedef Act16<false> A;
+    const int pair0 = (((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * kWaves + wave) * kGuPairs;
+    u32x4 wA[2][kGuNV];
+    constexpr int PV = kGuNV * 64 / 256;              // vectors of the row per thread of the first four waves
+    u32x4 nwv[PV];
+#pragma unroll
+    for (int i = 0; i < PV; ++i) nwv[i] = *(reinterpret_cast<const u32x4*>(a.gu_norm_w) + (threadIdx.x & 255) + i * 256);
+    u32x4 wB[2][kGuNV];
+    if (wave != 0) gateup_issue(a, wA, pair0, lane);
+    lds_barrier();   // every wave is done with the attention vector in `xs` and has parked its O rows
+    if (wave == 0) {
+        if (lane < pub_rows / 2) st_granule_u32(a.hg + pub_row0 / 2 + lane, tag, reinterpret_cast<const unsigned*>(sm_pub)[lane]);
+        constexpr int GPL = kGuHidden / 2 / 64;       // granules per lane
+        for (unsigned spins = 0; spins < kSpinLimit; ++spins) {   // politely: one granule of every eighth producer, a sleep between looks
+            const unsigned long long g = ld_granule(a.hg + (size_t)lane * GPL + (GPL - 1));
+            if (__all((unsigned)(g >> 32) == tag)) break;
+            __builtin_amdgcn_s_sleep(4);
+        }
+        unsigned long long g[GPL];
+        for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+            for (int i = 0; i < GPL; ++i) g[i] = ld_granule(a.hg + (size_t)i * 64 + lane);
+            bool ok = true;
+#pragma unroll
+            for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
+            if (__all(ok)) break;
+            if (spins >= kSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
+                if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                break;
+            }
+            __builtin_amdgcn_s_sleep(4);
+        }
+        unsigned* sx = reinterpret_cast<unsigned*>(xs);   // the raw row, natural element order
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) sx[i * 64 + lane] = (unsigned)g[i];
+        if (TRACE && lane == 0 && pub_rows > 0) tr[4] = wall_clock64();
+        gateup_issue(a, wA, pair0, lane);
+    }
+    lds_barrier();
+    rmsnorm_in_lds<A, PV>(xs, red, nwv, kGuHidden, a.eps, threadIdx.x < 256);
+    // pair p is reduced from one register set while pair p + 1 is in flight
+    static_assert(kGuPairs % 2 == 0, "whole double-buffer rounds");
+#pragma unroll
+    for (int p = 0; p < kGuPairs; p += 2) {
+        gateup_issue(a, wB, pair0 + p + 1, lane);
+        gateup_reduce(a, wA, xs, pair0 + p, lane);
+        if (TRACE && p == 0 && threadIdx.x == 0) tr[7] = wall_clock64();
+        if (p + 2 < kGuPairs) gateup_issue(a, wA, pair0 + p + 2, lane);
+        gateup_reduce(a, wB, xs, pair0 + p + 1, lane);
+    }
+}
+
 // The O-projection phase of a non-consumer block (attn_step_kernel, NVW > 0): R weight rows per wave go out NOW -- the block's
 // latency-critical work is over and its attention registers are free -- then the merged attention vector is awaited and swept into
 // LDS, then the separate O GEMV's arithmetic (gemv.hip gemv_kernel<NVW, 1, 2, PRO_NONE, EPI_RESIDUAL>) runs on the held rows.
@@ -216,9 +318,10 @@ __device__ __forceinline__ void oproj_await_vector(const AttnStepArgs& a, u32x4*
 // queues ahead of the q / K / V rows (they land at 6.7 us instead of 2.1); issued after that round landed, in every block -> a wave's
 // memory instructions queue in order behind its own prefetch, the partial stores left 1.5 us and the gather 0.5 us later (kernel
 // 13.8 us, still 2.4 us/layer better than two launches).
-template <int NVW, int R>
+// GU (the gate/up rows follow in this launch, gateup_phase): the rounded rows are parked in `sm_pub` for the block's publishing wave
+template <int NVW, int R, bool GU = false>
 __device__ __forceinline__ void oproj_phase(const AttnStepArgs& a, u32x4* sm_x, unsigned tag, int lane, int wave, int o_row0,
-                                            unsigned long long* tr) {
+                                            unsigned long long* tr, uint16_t* sm_pub = nullptr, int pub_row0 = 0) {
     u32x4 ow[R][NVW];
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -249,7 +352,11 @@ __device__ __forceinline__ void oproj_phase(const AttnStepArgs& a, u32x4* sm_x, 
         for (int r = 0; r < R; ++r)
             if (o_row0 + r < a.o_rows) {
                 if (a.o_out_f32) a.o_out_f32[o_row0 + r] = acc[r];   // the O GEMV's EPI_F32: this rank's partial, un-rounded
-                else a.o_out[o_row0 + r] = f32_to_bf16(bf16_to_f32(o_res[r]) + round_bf16(acc[r]));
+                else {
+                    const bf16_t hb = f32_to_bf16(bf16_to_f32(o_res[r]) + round_bf16(acc[r]));
+                    a.o_out[o_row0 + r] = hb;
+                    if (GU) sm_pub[o_row0 + r - pub_row0] = hb;
+                }
             }
     }
     if (tr && threadIdx.x == 0) tr[6] = wall_clock64();
@@ -349,9 +456,10 @@ __device__ __forceinline__ void oproj_phase_q4(const AttnStepArgs& a, u32x4* sm_
 }
 
 
-template <int D, int GT, bool TRACE, int NVW, bool F16 = false>
+template <int D, int GT, bool TRACE, int NVW, bool F16 = false, bool GU = false>
 __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs a) {
     static_assert(!F16 || NVW == 0, "the O projection rides in the launch for bfloat16 models only");
+    static_assert(!GU || (NVW == kGuNV && D == 128), "gate/up follows the bf16 O projection of hidden 4096 only");
     typedef Act16<F16> A16;
     constexpr int LPR = D / 8;            // lanes per K/V row
     constexpr int TPW = 64 / LPR;         // token rows per wave-instruction == one unit
@@ -538,7 +646,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
             }
         }
         __syncthreads();
-        if (TRACE && threadIdx.x == 0) tr[7] = wall_clock64();
+        if (TRACE && !GU && threadIdx.x == 0) tr[7] = wall_clock64();   // (GU: the stamp marks the first reduced pair instead)
         // ---- merge the 8 waves x TPW rows; the split's partial leaves as tagged granules ----
         for (int idx = threadIdx.x; idx < G * D; idx += kBlock) {
             const int g = idx / D, d = idx % D;
@@ -576,6 +684,16 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
         const int rows = hi ? a.o_rpw : a.o_rpw - 1;
         const int o_row0 = hi ? g * a.o_rpw : a.o_nhi * a.o_rpw + (g - a.o_nhi) * (a.o_rpw - 1);
         unsigned long long* otr = TRACE ? tr : nullptr;
+        if constexpr (GU) {
+            // the block's eight waves hold consecutive rows: from where, and how many (wave 0 publishes them)
+            auto row0_of = [&](int w) { return w < a.o_nhi ? w * a.o_rpw : a.o_nhi * a.o_rpw + (w - a.o_nhi) * (a.o_rpw - 1); };
+            const int pub_row0 = row0_of(g - wave), pub_rows = row0_of(g - wave + kWaves) - pub_row0;
+            uint16_t* sm_pub = reinterpret_cast<uint16_t*>(sm_l);   // (the split merge is done with sm_m / sm_l: a block barrier ago)
+            if (rows == 2) oproj_phase<NV, 2, true>(a, sm_x, tag, lane, wave, o_row0, otr, sm_pub, pub_row0);
+            else oproj_phase<NV, 3, true>(a, sm_x, tag, lane, wave, o_row0, otr, sm_pub, pub_row0);
+            gateup_phase<TRACE>(a, sm_x, sm_m, sm_pub, tag, lane, wave, pub_row0, pub_rows, otr);
+            return;
+        } else
         if constexpr (QO) {
             if (rows <= 1) oproj_phase_q4<NV, 1>(a, sm_x, sm_xsum, tag, lane, wave, o_row0, otr);
             else if (rows == 2) oproj_phase_q4<NV, 2>(a, sm_x, sm_xsum, tag, lane, wave, o_row0, otr);
@@ -603,7 +721,11 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
         else gather_head<D, 3, F16>(a, base, n_active, tag, lane, dim, out, xg_head);
         if (TRACE && threadIdx.x == 0) tr[4] = wall_clock64();
     }
-
+    if constexpr (GU) {
+        // the consumer blocks take their share of the pairs once their heads are merged and published (block-uniform: split < G here)
+        lds_barrier();
+        gateup_phase<TRACE>(a, sm_x, sm_m, nullptr, tag, lane, wave, 0, 0, TRACE ? tr : nullptr);
+    }
 }
 
 }  // namespace
@@ -647,6 +769,15 @@ bool attn_step_oproj_q4_ok(int H, int Hkv, int D, int nsplit, int o_rows, int gr
     return (K == 2048 || K == 4096) && (group == 32 || group == 64 || group == 128) && attn_step_oproj_ok(H, Hkv, D, nsplit, o_rows);
 }
 
+// ... and [RMSNorm + gate/up + SwiGLU] behind it: the one shape whose 256 blocks x 8 waves take kGuPairs (gate, up) pairs each, every
+// O block holding whole granules (two or three rows per wave, the three-row waves filling whole blocks)
+bool attn_step_gateup_ok(int H, int Hkv, int D, int nsplit, int o_rows, int gu_rows) {
+    const int blocks = Hkv * nsplit, waves = (blocks - H) * kWaves;
+    if (D != 128 || H * D != kGuHidden || o_rows != kGuHidden || H / std::max(Hkv, 1) != 4 || blocks != 256) return false;
+    if (gu_rows != blocks * kWaves * kGuPairs || !attn_step_oproj_ok(H, Hkv, D, nsplit, o_rows)) return false;
+    return oproj_rows_per_wave(H, Hkv, nsplit, o_rows) == 3 && (o_rows - waves * 2) % kWaves == 0;
+}
+
 int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
     AttnStepArgs a = a_in;
     const int G = a.H / a.Hkv;
@@ -670,6 +801,10 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
         // its (possibly clamped) row: a wave of the phase always holds at least one
         a.o_nhi = a.o_rpw > 1 ? a.o_rows - waves * (a.o_rpw - 1) : waves;
     }
+    if (a.gu_gate)
+        OMX_REQUIRE(a.o_w && a.o_out && !a.o_out_f32 && !a.f16 && a.gu_up && a.gu_norm_w && a.gu_out && a.hg &&
+                        attn_step_gateup_ok(a.H, a.Hkv, D, a.nsplit, a.o_rows, a.gu_rows),
+                    "decode attention + gate/up: shape does not qualify (%d blocks, %d O rows, %d pairs)", a.Hkv * a.nsplit, a.o_rows, a.gu_rows);
     const dim3 grid(a.Hkv, a.nsplit), block(kBlock);
     const int gt = G <= 1 ? 1 : G <= 2 ? 2 : G <= 4 ? 4 : 8;
 #define OMX_ATTN_LAUNCH(DD, GG, TT, NN)                                                                                  \
@@ -681,10 +816,25 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
         OMX_LAUNCH_CHECK();                                                                                              \
         return 0;                                                                                                        \
     }
+#define OMX_ATTN_LAUNCH_GU(TT)                                                                                           \
+    {                                                                                                                    \
+        OMX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_step_kernel<128, 4, TT, kGuNV, false, true>,                 \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                      \
+        OMX_LAUNCH_TIMED((attn_step_kernel<128, 4, TT, kGuNV, false, true>), grid, block, shmem, s, a);                  \
+        OMX_LAUNCH_CHECK();                                                                                              \
+        return 0;                                                                                                        \
+    }
 #define OMX_ATTN_STEP_CASE(DD, GG)                                                                                       \
     if (D == DD && gt == GG) {                                                                                           \
         const size_t shmem = ((size_t)kWaves * (64 / (DD / 8)) * GG * DD + 2 * kWaves * GG) * sizeof(float) +            \
                              (size_t)(GG + 1) * (DD / 8) * 16 + (size_t)nvw * 64 * 16 + (qo ? (size_t)nvw * 64 : 0);     \
+        if (a.gu_gate) {   /* gate/up behind the O projection: one shape (attn_step_gateup_ok) */                         \
+            if constexpr (DD == 128 && GG == 4) {                                                                        \
+                if (a.trace) OMX_ATTN_LAUNCH_GU(true)                                                                    \
+                OMX_ATTN_LAUNCH_GU(false)                                                                                \
+            }                                                                                                            \
+            return set_error("decode attention + gate/up: no instantiation for head_dim %d, group %d", DD, GG);         \
+        }                                                                                                                \
         if (a.trace && !qo) {   /* timeline builds: the plain kernel and the widest fused one */                        \
             if (nvw == 0) OMX_ATTN_LAUNCH(DD, GG, true, 0)                                                               \
             if (nvw == 8) OMX_ATTN_LAUNCH(DD, GG, true, 8)                                                               \
@@ -717,6 +867,7 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
     OMX_ATTN_STEP_CASE(128, 1) OMX_ATTN_STEP_CASE(128, 2) OMX_ATTN_STEP_CASE(128, 4) OMX_ATTN_STEP_CASE(128, 8)
     OMX_ATTN_STEP_CASE(64, 1) OMX_ATTN_STEP_CASE(64, 2) OMX_ATTN_STEP_CASE(64, 4) OMX_ATTN_STEP_CASE(64, 8)
 #undef OMX_ATTN_STEP_CASE
+#undef OMX_ATTN_LAUNCH_GU
 #undef OMX_ATTN_LAUNCH
     return set_error("decode attention: head_dim %d unsupported (64 or 128)", D);
 }

@@ -140,7 +140,8 @@ int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) {
             return 1;
     }
     if (dev_alloc(m, &m->rope_cur, (size_t)D) || dev_alloc(m, &m->attn_gran, attn_step_ws_granules(m->H, D)) ||
-        dev_alloc(m, &m->attn_xg, (size_t)m->H * D / 2 + 8) || dev_alloc(m, &m->chain_gran, (size_t)c.hidden_size / 2 + 8))
+        dev_alloc(m, &m->attn_xg, (size_t)m->H * D / 2 + 8) || dev_alloc(m, &m->chain_gran, (size_t)c.hidden_size / 2 + 8) ||
+        dev_alloc(m, &m->gateup_gran, (size_t)c.hidden_size / 2 + 8))
         return 1;
     if (dev_alloc(m, &m->step_seq, 16) || dev_alloc(m, &m->wait_abort, 16)) return 1;
     {
@@ -608,7 +609,9 @@ int omx_qwen3_debug_trace_step(omx_qwen3 m, unsigned long long* host, size_t n_w
  * gate/up + SwiGLU GEMV, down GEMV, lm_head} over layers and steps.  Dense bf16 single-rank models only.
  * Where down and the next layer's q/k/v are one launch (gemv_chain.hip, layers 0 .. L-2), that launch is booked on the down class of its
  * layer and its duration is split between `down` and `qkv` in proportion to their algorithmic bytes: the q/k/v pairs of layers 1 .. L-1
- * are never armed and never read, no class comes back as 0 and the classes still sum to the step. */
+ * are never armed and never read, no class comes back as 0 and the classes still sum to the step.
+ * Where gate/up + SwiGLU rides in the attention launch (attention_takes_gateup), that launch is booked on the attention class and its
+ * duration is split the same way between `attention` (the K/V rows read at this position + the O matrix) and `gate_up`. */
 int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
     OMX_REQUIRE(m && us && steps > 0, "omx_qwen3_time_step_kernels: bad arguments");
     OMX_REQUIRE(!m->cfg.quant_bits && m->cfg.num_experts == 0 && m->allreduce == nullptr, "omx_qwen3_time_step_kernels: dense bf16 single-rank models only");
@@ -618,6 +621,7 @@ int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
     double sum[KC_COUNT] = {};
     int rc = 0;
     bool fused_o = false, engine = false, hybrid = false, chain = false;
+    const double o_bytes = (double)m->H * m->cfg.head_dim * m->cfg.hidden_size, gu_bytes = 2.0 * m->cfg.hidden_size * m->I;
     const double qkv_bytes = (double)(m->H + 2 * m->Hkv) * m->cfg.head_dim * m->cfg.hidden_size, down_bytes = (double)m->cfg.hidden_size * m->I;
     arm_launch_events(nullptr, nullptr);
     for (int it = 0; it < steps && !rc; ++it) {
@@ -641,7 +645,14 @@ int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
                 if (l < L && k == KC_O && fused_o) continue;     // that pair was never armed
                 if (hybrid && l < L && (k == KC_GATE_UP || (k == KC_DOWN && l != L - 1))) continue;   // one segment launch covers them
                 if (chain && l > 0 && l < L && k == KC_QKV) continue;   // done inside the previous layer's down launch
+                const bool gateup = l < L && !engine && !hybrid && attention_takes_gateup(m, l);
+                if (gateup && k == KC_GATE_UP) continue;         // done inside the layer's attention launch
                 OMX_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+                if (gateup && k == KC_ATTN) {   // one launch for two classes: shared by bytes
+                    const double attn_bytes = 2.0 * m->Hkv * m->cfg.head_dim * (st.pos + 1) + o_bytes;
+                    sum[KC_GATE_UP] += ms * 1e3 * (gu_bytes / (gu_bytes + attn_bytes));
+                    ms *= (float)(attn_bytes / (gu_bytes + attn_bytes));
+                }
                 if (chain && l < L - 1 && k == KC_DOWN) {   // one launch for two classes: shared by bytes
                     sum[KC_QKV] += ms * 1e3 * (qkv_bytes / (qkv_bytes + down_bytes));
                     ms *= (float)(down_bytes / (qkv_bytes + down_bytes));
@@ -687,6 +698,8 @@ int omx_qwen3_debug_trace_engine(omx_qwen3 m, unsigned long long* host, size_t n
 int omx_qwen3_decode_path(omx_qwen3 m, int* path) {
     OMX_REQUIRE(m && path, "omx_qwen3_decode_path: null argument");
     *path = m->eager ? 2 : (m->aql_full && step_aql_mode(m)) ? 3 : m->g_full ? 1 : 0;   // 3: AQL replay on the engine's own queue
+    // bits 8..11: the rungs of step_fallback's ladder this engine has gone down, in the ladder's order
+    *path |= (m->gateup_disabled ? 1 : 0) << 8 | (m->chain_disabled ? 1 : 0) << 9 | (m->se_disabled ? 1 : 0) << 10 | (m->oproj_disabled ? 1 : 0) << 11;
     return 0;
 }
 

@@ -256,6 +256,19 @@ bool down_takes_qkv(omx_qwen3 m) {
     return gemv_chain_grid(c.hidden_size) <= kGemvChainBlocksPerCU * m->cus;
 }
 
+// [RMSNorm + gate/up + SwiGLU] of layer `layer` inside its attention + O launch (csrc/attn_step.hip, gateup_phase): the dense bf16 step of a
+// single rank on its launch-per-op form with the O projection in the attention launch, no rows-per-wave override of the two GEMVs the
+// phase stands for, the one shape the kernel shares out evenly (hidden 4096, intermediate 12288, 32 / 8 heads of 128: every split
+// plan of these heads has 256 blocks) and that grid resident as a whole.  A q/k/v bias (Qwen2 wiring) does not touch gate/up and is allowed; OMX_ATTN_GATEUP=0 keeps the two launches
+bool attention_takes_gateup(omx_qwen3 m, int layer) {
+    const bool off = env_off("OMX_ATTN_GATEUP");       // (read per call: tests flip it between engines of one process)
+    const omx_qwen3_config& c = m->cfg;
+    if (off || m->gateup_disabled || c.quant_bits != 0 || m->f16 || c.num_experts > 0 || c.tp_size > 1 || c.ep_size > 1 || m->allreduce != nullptr) return false;
+    if (step_engine_mode(m) != 0 || env_int("OMX_GEMV_RPW_O", 0) != 0 || env_int("OMX_GEMV_RPW_GU", 0) != 0) return false;
+    if (!m->gateup_gran || m->cus < 256 || !attention_takes_oproj(m, layer)) return false;
+    return attn_step_gateup_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size, m->I);
+}
+
 // OMX_PEER_FUSED: a GEMV whose blocks poll their peers' stores must be resident as a whole -- a block waiting for a peer's row while
 // that peer's matching block waits for a free CU behind OUR unscheduled blocks never finishes (it gives up after 2^23 polls and voids
 // the step).  The streaming kernels hold at least two 4-wave blocks per CU (<= 256 VGPRs, a few KB of LDS); beyond that the standalone
@@ -265,8 +278,10 @@ static bool peer_fused_fits(omx_qwen3 m, int N, int K) {
 }
 
 // the attention launch of layer l of a decode step (both the bf16 and the packed-weight step use the bf16 KV kernels);
-// resid / out != null: the layer's O projection + residual rides in the same launch (attention_takes_oproj)
-static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* resid = nullptr, bf16_t* out = nullptr, float* out_f32 = nullptr) {
+// resid / out != null: the layer's O projection + residual rides in the same launch (attention_takes_oproj); gateup: and its
+// [RMSNorm + gate/up + SwiGLU] behind that (attention_takes_gateup)
+static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* resid = nullptr, bf16_t* out = nullptr, float* out_f32 = nullptr,
+                             bool gateup = false) {
     const omx_qwen3_config& c = m->cfg;
     const int D = c.head_dim;
     const LayerW& L = m->layers[l];
@@ -296,6 +311,10 @@ static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* re
         } else {
             a.o_w = L.o;
         }
+    }
+    if (gateup) {
+        a.gu_gate = L.gate; a.gu_up = L.up; a.gu_norm_w = L.post_ln; a.gu_out = m->act; a.gu_rows = m->I;
+        a.hg = m->gateup_gran;
     }
     return launch_attn_step(a, D, s);
 }
@@ -584,7 +603,8 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
         const bool fused_o = attention_takes_oproj(m, l);
         time_next_launch(m, l, KC_ATTN);
         // [q/k RMSNorm + RoPE + cache append + split-KV SDPA + merge]  model.rs:172-210
-        if (enqueue_attention(m, l, s, fused_o ? h : nullptr, fused_o && !tp ? hn : nullptr, fused_o && tp ? m->partial_a : nullptr)) return 1;
+        const bool gateup = fused_o && !tp && !pending && attention_takes_gateup(m, l);
+        if (enqueue_attention(m, l, s, fused_o ? h : nullptr, fused_o && !tp ? hn : nullptr, fused_o && tp ? m->partial_a : nullptr, gateup)) return 1;
         if (fused_o && tp) {   // the rank's f32 partial of the O projection came out of the attention launch
             if (allreduce_sum(m, m->partial_a, hd)) return 1;
             pending = m->partial_a;
@@ -650,7 +670,7 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             std::swap(h, hn);
             continue;
         }
-        {   // [RMSNorm + gate/up GEMV + SwiGLU]  model.rs:263-265,326
+        if (!gateup) {   // [RMSNorm + gate/up GEMV + SwiGLU]  model.rs:263-265,326 (gateup: happened in the attention launch)
             GemvArgs a = {};
             a.w0 = L.gate; a.w1 = L.up; a.n0 = m->I; a.N = m->I; a.K = hd;
             a.x = h; a.x_partial = pending; a.x_partial_n = pending_n; a.x_out = pending ? hn : nullptr;
@@ -817,16 +837,24 @@ int step_health(omx_qwen3 m) {
     return 0;
 }
 
-// A launch whose workgroups wait on each other (down + q/k/v in one launch, the persistent step, the O projection inside the attention launch) gave up: some
+// A launch whose workgroups wait on each other (gate/up inside the attention launch, down + q/k/v in one launch, the persistent step, the O projection inside the attention launch) gave up: some
 // workgroup was not resident -- another process or stream holds CUs.  Drop to the next form that needs less co-residency, restore the
 // step state the call started from and let the caller run the steps again (the KV rows they wrote are rewritten).  Returns 0 when a
-// retry is possible.
+// retry is possible.  The first rung switches off BOTH launches in which a GEMV's weight rows stream across a granule hop (gate/up inside
+// the attention launch, down + q/k/v): the flag does not say which launch gave up, both want every CU's register file for themselves, and
+// what they save together (3 %) is nothing against a second voided call.
 int step_fallback(omx_qwen3 m, const StepState& st) {
     if (m->temperature != 0.f || m->filter_on) return 1;       // the sampler's key sequence / token history advanced: no silent replay
     // more than one rank: a local replay would re-enqueue every all-reduce of the n steps (and the argmax one) on THIS rank only -- its
     // peers never issue them, so the collectives would pair with the peers' next call (wrong sums or a hang).  Report the abort instead.
     if (m->allreduce != nullptr || m->cfg.tp_size > 1 || m->cfg.ep_size > 1) return 1;
-    if (!m->chain_disabled && down_takes_qkv(m)) m->chain_disabled = true;
+    bool gateup = false;
+    for (int l = 0; l < m->cfg.num_hidden_layers && !m->gateup_disabled; ++l) gateup = gateup || attention_takes_gateup(m, l);
+    const bool chain = !m->chain_disabled && down_takes_qkv(m);
+    if (gateup || chain) {
+        m->gateup_disabled = m->gateup_disabled || gateup;
+        m->chain_disabled = m->chain_disabled || chain;
+    }
     else if (!m->se_disabled && step_engine_takes(m)) m->se_disabled = true;
     else if (!m->oproj_disabled && any_layer_takes_oproj(m)) m->oproj_disabled = true;
     else return 1;

@@ -15,8 +15,6 @@ namespace {
 constexpr int kBlock = 256;   // 4 waves
 constexpr int kWaves = 4;
 
-__device__ __forceinline__ u32x4 ld_nt(const u32x4* p) { return __builtin_nontemporal_load(p); }
-
 __device__ __forceinline__ const bf16_t* row_ptr(const GemvArgs& a, int row) {
     // wave-uniform: which of the stacked matrices owns this row
     if (row < a.n0) return a.w0 + (size_t)row * a.K;

@@ -33,8 +33,6 @@ constexpr int kRowsA = 8;     // phase A: rows per workgroup (resolve_rpw of a K
 constexpr int kRB = 2;        // phase A: rows per register batch
 constexpr unsigned kSpinLimit = 1u << 15;   // passes (~1 us each) before a wait gives up
 
-__device__ __forceinline__ u32x4 ld_nt(const u32x4* p) { return __builtin_nontemporal_load(p); }
-
 __device__ __forceinline__ const bf16_t* qkv_row_ptr(const GemvChainArgs& a, int row, int K) {
     // wave-uniform: which of the stacked matrices owns this row
     if (row < a.n0) return a.w0 + (size_t)row * K;
@@ -187,7 +185,9 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
 #undef OMX_ISSUE_QKV
     // (barriers of this phase wait for LDS only: the q/k/v rows stay in flight across them)
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    // RMS-normalise into LDS (gemv.hip, PRO_RMSNORM): thread t owns vectors t, t + 256 (in place: nobody else touches them)
+    // RMS-normalise into LDS (gemv.hip, PRO_RMSNORM): thread t owns vectors t, t + 256 (in place: nobody else touches them).
+    // (The same sequence is rmsnorm_in_lds of gemv_parts.hpp, which attn_step.hip calls; it stays written out here because calling the
+    //  helper reorders this kernel's instruction stream -- EXPERIMENTS C-2 -- and the kernel's measured form is kept.)
     {
         float ss = 0.f;
         u32x4 xv[PVB];

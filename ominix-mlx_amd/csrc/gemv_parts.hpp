@@ -46,6 +46,37 @@ __device__ __forceinline__ u32x4 norm8(const u32x4 raw, const u32x4 nw, float rs
     return o;
 }
 
+// ---- the PRO_RMSNORM prologue on a row that already sits in LDS (a kernel that received it as granules in mid-launch), in place ----
+// Thread t of the first 256 (`member`) owns vectors t, t + 256, ...: the same sumsq8 chain, block_sum<4> (common.hpp: wave sums, then the
+// four of them added in wave order from 0.f) and norm8 as gemv_kernel's prologue.  Every barrier waits for LDS only, so weight rows the
+// caller has asked for stay in flight across it; ALL waves of the workgroup call this (the waves past the fourth only join the barriers).
+__device__ __forceinline__ u32x4 ld_nt(const u32x4* p) { return __builtin_nontemporal_load(p); }   // a weight vector: streamed once
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+template <class A, int PV>
+__device__ __forceinline__ void rmsnorm_in_lds(u32x4* xs, float* red, const u32x4 (&nwv)[PV], int n, float eps, bool member) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float ss = 0.f;
+    u32x4 xv[PV];
+#pragma unroll
+    for (int i = 0; i < PV; ++i) {
+        xv[i] = xs[(threadIdx.x & 255) + i * 256];
+        ss = sumsq8<A>(xv[i], ss);
+    }
+    ss = wave_sum(ss);
+    lds_barrier();
+    if (member && lane == 0) red[wave] = ss;
+    lds_barrier();
+    ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) ss += red[i];
+    const float rstd = 1.0f / sqrtf(ss / (float)n + eps);
+    if (member) {
+#pragma unroll
+        for (int i = 0; i < PV; ++i) xs[threadIdx.x + i * 256] = norm8<A>(xv[i], nwv[i], rstd);
+    }
+    lds_barrier();
+}
+
 // ---- the 16 bits a row leaves behind: v0 the row's f32 sum (v1: the `up` row's of a SwiGLU pair) ----
 // EPI_STORE / EPI_ARGMAX: the rounded sum (the caller stores it and, for EPI_ARGMAX, builds its argmax_key from A::val of it);
 // EPI_RESIDUAL: resid + the rounded sum, rounded again (resid_bits is read by the caller, under EPI_RESIDUAL only); EPI_SWIGLU below

@@ -595,10 +595,13 @@ class Model:
         return s.value or 0
 
     def decode_path(self) -> str:
-        """'graph' | 'eager' | 'aql' (packets on the engine's own HSA queue, OMX_STEP_AQL) once the first step ran ('unbuilt' before)."""
+        """'graph' | 'eager' | 'aql' (packets on the engine's own HSA queue, OMX_STEP_AQL) once the first step ran ('unbuilt' before);
+        followed by the rungs of the fallback ladder a give-up has taken on this engine, e.g. 'graph gateup_disabled'."""
         v = c_int()
         check(lib.omx_qwen3_decode_path(self._h, ctypes.byref(v)))
-        return ("unbuilt", "graph", "eager", "aql")[v.value]
+        path = ("unbuilt", "graph", "eager", "aql")[v.value & 0xFF]
+        return path + "".join(" " + name for bit, name in enumerate(("gateup_disabled", "chain_disabled", "engine_disabled", "oproj_disabled"))
+                              if v.value >> (8 + bit) & 1)
 
     KERNEL_CLASSES = ("qkv", "attention", "o", "gate_up", "down", "lm_head", "step_engine")
 
@@ -611,9 +614,10 @@ class Model:
 
     def step_forms(self) -> dict:
         """Which in-launch folds the next decode step would take (test hook, omx_qwen3_debug_step_forms)."""
-        f = (c_int * 4)()
+        f = (c_int * 6)()
         check(lib.omx_qwen3_debug_step_forms(self._h, f))
-        return {"down_qkv": bool(f[0]), "attn_oproj": bool(f[1]), "step_engine": int(f[2]), "down_qkv_gave_up": bool(f[3])}
+        return {"down_qkv": bool(f[0]), "attn_oproj": bool(f[1]), "step_engine": int(f[2]), "down_qkv_gave_up": bool(f[3]),
+                "attn_gateup": bool(f[4]), "attn_gateup_gave_up": bool(f[5])}
 
     def raise_give_up(self) -> None:
         """Set, from the host, the word a wait inside a launch raises when it gives up (test hook of the fallback ladder)."""

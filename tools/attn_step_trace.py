@@ -10,7 +10,8 @@ from ominix_mlx_amd import engine
 lib = omx.lib
 ctx = int(sys.argv[1]) if len(sys.argv) > 1 else 2048
 L = int(sys.argv[2]) if len(sys.argv) > 2 else 12
-m = engine.Model(hidden_size=4096, num_hidden_layers=L, intermediate_size=12288, num_attention_heads=32,
+H = 32
+m = engine.Model(hidden_size=4096, num_hidden_layers=L, intermediate_size=12288, num_attention_heads=H,
                  num_key_value_heads=8, head_dim=128, vocab_size=151936, max_context=ctx + 256)
 m.synth_weights()
 m.prefill((np.arange(ctx, dtype=np.uint32) * 7919) % 151936)
@@ -22,17 +23,27 @@ nb = nb.value
 t = buf[:L * nb * 8].reshape(L, nb, 8).astype(np.int64)
 names = ["block start", "loads landed, q/k normed+roped", "own chunk done", "granules stored", "gather + merge done (consumers)",
          "attention vector swept into LDS (O projection)", "O rows stored", "all waves' partials parked in LDS (block barrier)"]
-print(f"{nb} blocks per launch, {L} layers, ctx {ctx}")
-for ev, nm in enumerate(names):
+# gate/up inside the launch (OMX_ATTN_GATEUP): stamp 7 marks the first reduced (gate, up) pair of wave 0 -- the sweeping wave, whose pair
+# is asked for last -- and stamp 4 of an O block (blocks past the first H: the consumers come first) the hidden row swept into LDS.
+# Hop three is hidden when "first pair reduced" follows "hidden row swept" by less than a weight round trip.
+gateup = m.step_forms()["attn_gateup"]
+n_cons = H   # consumer blocks: one per query head, the launch's first blocks
+events = [(ev, nm, slice(None)) for ev, nm in enumerate(names)]
+if gateup:
+    events[4] = (4, names[4], slice(0, n_cons))
+    events[7] = (7, "gate/up: first pair reduced (wave 0)", slice(None))
+    events.insert(7, (4, "gate/up: hidden row swept into LDS (O blocks)", slice(n_cons, None)))
+print(f"{nb} blocks per launch, {L} layers, ctx {ctx}, gate/up in the launch: {gateup}")
+for ev, nm, blocks in events:
     rows = []
     for l in range(1, L):
         t0 = t[l, :, 0][t[l, :, 0] > 0].min()
-        v = t[l, :, ev]
+        v = t[l, blocks, ev]
         v = v[v > 0]
         if v.size:
             rows.append(((v - t0) / 100.0))
     if rows:
         allv = np.concatenate(rows)
-        print(f"  {nm:34s} median {np.median(allv):6.2f} us   p90 {np.percentile(allv, 90):6.2f}   max(median over layers) "
+        print(f"  {nm:48s} median {np.median(allv):6.2f} us   p90 {np.percentile(allv, 90):6.2f}   max(median over layers) "
               f"{np.median([r.max() for r in rows]):6.2f}   n/layer {allv.size // (L - 1)}")
 m.close()
