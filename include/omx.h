@@ -426,6 +426,8 @@ int omx_qwen3_last_prefill_ms(omx_qwen3 m, float* ms);   /* same for the last om
 int omx_qwen3_dequant_bytes(omx_qwen3 m, size_t* bytes);
 /* test hook: copy an internal bf16 buffer ("h","h2","qkv","attn_out","act","k<l>","v<l>") to the host */
 int omx_qwen3_debug_read(omx_qwen3 m, const char* name, void* host, size_t n_elems);
+/* test hook: the other way, n_elems 16-bit patterns from the host into the same buffers (the caller keeps n_elems inside the buffer) */
+int omx_qwen3_debug_write(omx_qwen3 m, const char* name, const void* host, size_t n_elems);
 /* test hook of the dense decode GEMV (csrc/gemv.hip): ONE launch with prologue `pro` (0 none, 1 RMSNorm) and epilogue `epi` (0 store
  * [+ bias], 1 residual, 2 SwiGLU over gate w0 / up w1, 3 logits + argmax partials), bf16 (f16 = 0) or float16 (f16 = 1) operands.
  * w0 | w1 | w2 are row-stacked ([n0 | n1 | rest] rows of K) for the other epilogues.  argmax_slot: omx_debug_gemv_grid(N, K) keys. */
@@ -517,7 +519,8 @@ int omx_qwen3_step_bytes(omx_qwen3 m, int ctx, double* bytes);
  * down + q/k/v as two launches, persistent step off, O projection out of the attention launch) */
 int omx_qwen3_decode_path(omx_qwen3 m, int* path);
 /* debug hook (tools/attn_step_trace.py): run ONE decode step eagerly with the attention launches stamping the
- * 100 MHz wall clock; host receives [layers][attention splits][kv heads][8], *blocks = splits * kv heads     */
+ * 100 MHz wall clock; host receives [layers][attention splits][kv heads][16] (word 10 of a block whose launch carries gate/up is
+ * a count, the (gate, up) pairs its waves reduced: 48), *blocks = splits * kv heads     */
 int omx_qwen3_debug_trace_step(omx_qwen3 m, unsigned long long* host, size_t n_words, int* blocks);
 /* measurement hook: `steps` real decode steps run eagerly, every launch of the per-layer kernels carrying its own HIP event pair
  * (the dispatch's begin / end timestamps on the step's stream); us[7] = average microseconds of {QKV GEMV, attention, O GEMV,

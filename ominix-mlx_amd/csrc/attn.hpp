@@ -25,6 +25,7 @@ struct AttnDecodeArgs {
 };
 
 // ---- the decode engine's attention launch (attn_step.hip): q/k norm + RoPE + cache append + split-KV SDPA + split merge ----
+constexpr int kAttnTraceWords = 16;   // trace words per block of the launch (AttnStepArgs::trace)
 struct AttnStepArgs {
     const bf16_t* qkv;          // raw projections of the current token [H*D | Hkv*D | Hkv*D] (QKV GEMV output)
     bf16_t* k;                  // KV slabs [Hkv, cap, D]
@@ -43,7 +44,8 @@ struct AttnStepArgs {
     uint64_t* ws;               // granules [H][nsplit][D + 2]  ({f32, tag} each: o[D], m, l)
     bf16_t* out;                // [H*D]
     unsigned* abort_flag;       // raised when a gather gave up (results void)
-    unsigned long long* trace;  // optional: 8 wall-clock stamps per block [nsplit][Hkv][8] (tools/attn_step_trace.py)
+    unsigned long long* trace;  // optional: kAttnTraceWords words per block [nsplit][Hkv][kAttnTraceWords], wall-clock stamps and, from
+                                // the gate/up phase, the block's count of reduced pairs (tools/attn_step_trace.py)
     // ---- optional O projection in the same launch (o_w != null; attn_step_oproj_ok says whether the shape qualifies) ----
     const bf16_t* o_w;          // [o_rows, H*D] row-major (nn::Linear weight, model.rs:214)
     const bf16_t* o_resid;      // [o_rows] residual stream entering the layer

@@ -166,7 +166,39 @@ __device__ __forceinline__ float dot8_chain(const u32x4 w, const u32x4 xp, float
 
 constexpr int kORows = 4;   // most O-projection rows a wave holds (attn_step_oproj_ok)
 
-// the merged attention vector: awaited, then swept from its granules into LDS (natural element order); a block-wide step
+// ---- [RMSNorm + gate/up + SwiGLU] of the layer behind the O projection (attn_step_kernel, GU > 0) ----
+// The launch's 256 blocks share the 12 288 (gate, up) row pairs: block b owns pairs [b * kGuBlockPairs, + kGuBlockPairs) and its eight waves
+// draw them from a ticket counter in LDS (gateup_claim), one ticket per gateup_issue, drawn one reduce ahead -- a wave that starts late (wave 0, which brings the
+// hidden row in) simply draws fewer.  The hidden row the O projection leaves crosses the launch a third time as granules {two packed bf16,
+// tag}: the scheme of gemv_chain.hip's phase B, whose texts (gemv_parts.hpp) this phase calls -- the arithmetic is
+// gemv_kernel<8, 1, 1, PRO_RMSNORM, EPI_SWIGLU>'s, bit for bit (a pair's value depends on its rows and the row in LDS, not on who reduces it).
+constexpr int kGuBlockPairs = 48, kGuHidden = 4096, kGuNV = kGuHidden / 512;
+// the phase's words in LDS (behind the attention vector; zeroed ahead of the launch's first barrier, so nothing outlives a
+// launch): the ticket counter, the pairs reduced (TRACE)
+enum { kGuTicket = 0, kGuReduced = 1, kGuWords = 4 };
+
+// the next ticket of the block, wave-uniform.  Tickets >= kGuBlockPairs: nothing left (every wave draws exactly one of those)
+__device__ __forceinline__ int gateup_claim(int* sm_gu, int lane) {
+    int t = 0;
+    if (lane == 0) t = __hip_atomic_fetch_add(sm_gu + kGuTicket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_amdgcn_readfirstlane(t);
+}
+
+// one (gate, up) pair into a register set: w[0] the gate row, w[1] the up row
+__device__ __forceinline__ void gateup_issue(const AttnStepArgs& a, u32x4 (*w)[kGuNV], int pair, int lane) {
+    const u32x4* g = reinterpret_cast<const u32x4*>(a.gu_gate + (size_t)pair * kGuHidden);
+    const u32x4* u = reinterpret_cast<const u32x4*>(a.gu_up + (size_t)pair * kGuHidden);
+#pragma unroll
+    for (int j = 0; j < kGuNV; ++j) {
+        w[0][j] = ld_nt(g + j * 64 + lane);
+        w[1][j] = ld_nt(u + j * 64 + lane);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep the loads HERE: the scheduler would sink them to their use
+}
+
+// the merged attention vector: awaited, then swept from its granules into LDS (natural element order); a block-wide step.
+// (With gate/up in the launch, the first pair of waves 1..7 asked for right behind a peeled first pass of this sweep, tags read behind a
+//  counted wait: measured SLOWER than asking once the O rows are consumed -- EXPERIMENTS C-3 -- and not in the tree.)
 template <int NVW>
 __device__ __forceinline__ void oproj_await_vector(const AttnStepArgs& a, u32x4* sm_x, unsigned tag, int lane, int wave) {
     // wait politely: ONE wave watches one granule per consumer wave (the last of its 32) with a sleep between looks; only then does
@@ -210,25 +242,7 @@ __device__ __forceinline__ void oproj_await_vector(const AttnStepArgs& a, u32x4*
     }
 }
 
-// ---- [RMSNorm + gate/up + SwiGLU] of the layer behind the O projection (attn_step_kernel, GU > 0) ----
-// The launch's 256 blocks x 8 waves share the 12 288 (gate, up) row pairs, kGuPairs each.  The hidden row the O projection leaves crosses
-// the launch a third time as granules {two packed bf16, tag}: the scheme of gemv_chain.hip's phase B, whose texts (gemv_parts.hpp) this
-// phase calls -- the arithmetic is gemv_kernel<8, 1, 1, PRO_RMSNORM, EPI_SWIGLU>'s, bit for bit.
-constexpr int kGuPairs = 6, kGuHidden = 4096, kGuNV = kGuHidden / 512;
-
-// one (gate, up) pair into a register set: w[0] the gate row, w[1] the up row
-__device__ __forceinline__ void gateup_issue(const AttnStepArgs& a, u32x4 (*w)[kGuNV], int pair, int lane) {
-    const u32x4* g = reinterpret_cast<const u32x4*>(a.gu_gate + (size_t)pair * kGuHidden);
-    const u32x4* u = reinterpret_cast<const u32x4*>(a.gu_up + (size_t)pair * kGuHidden);
-#pragma unroll
-    for (int j = 0; j < kGuNV; ++j) {
-        w[0][j] = ld_nt(g + j * 64 + lane);
-        w[1][j] = ld_nt(u + j * 64 + lane);
-    }
-    __builtin_amdgcn_sched_barrier(0);   // keep the loads HERE: the scheduler would sink them to their use
-}
-
-// ... reduced against the normalised row in LDS: gemv.hip's OMX_COMPUTE with NR = 2, then its SwiGLU epilogue
+// a pair in a register set reduced against the normalised row in LDS: gemv.hip's OMX_COMPUTE with NR = 2, then its SwiGLU epilogue
 __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4 (*w)[kGuNV], const u32x4* xs, int pair, int lane) {
     typedef Act16<false> A;
     float acc[2] = {0.f, 0.f};
@@ -250,24 +264,37 @@ __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4
 }
 
 // Every wave of every block ends here.  `pub_rows` > 0: the block's O rows [pub_row0, + pub_rows) are parked in sm_pub (a block of O
-// waves holds an even number of rows from an even row on: whole granules).  Wave 0 -- no weight load in flight: a granule asked for
-// behind 32 KB of weights would only arrive after them -- publishes them, watches, sweeps the row into LDS and only then asks for ITS
-// first pair (form 2 of the down -> q/k/v edge); the other waves' pairs are in flight through the hop.
-// Measured at Qwen3-8B shapes, ctx 2 k (EXPERIMENTS C-2): waves 1..7 asking for their first pair HERE, once their O rows are consumed,
-// 343.4 tok/s against the parent's 337.7; asking right behind the O rows' own loads instead -- 57 MB more parked in front of the split
-// merge and the attention vector's sweep -- 338.1: no gain left.
+// waves holds an even number of rows from an even row on: whole granules).  Waves 1..7 ask for their first pair at once.  Wave 0 -- no
+// weight load in flight: a granule asked for behind 32 KB of weights would only arrive after them -- publishes the rows, watches, and
+// asks for the whole hidden row ONCE in straight-line code; right behind those 32 granule loads the block meets at an LDS-only barrier,
+// wave 0 asks for its first pair and the others for their SECOND: all of it is queued behind the sweep -- it cannot delay it -- and
+// streams while the row makes its round trip and is normalised.  Wave 0 reads the tags behind a counted wait (hipcc counts loads exactly
+// in straight-line code only; the pair stays in flight); a tag that is not there yet (rare) sends it into the draining retry loop.
+// Every wave passes the same three barriers on every path, the give-up included.
+// Issue points measured at Qwen3-8B shapes, ctx 2 k:
+//   * (EXPERIMENTS C-2) first pair of waves 1..7 HERE, once their O rows are consumed: 343.4 tok/s against the parent's 337.7; right
+//     behind the O rows' own loads -- 57 MB more parked in front of the split merge and the attention vector's sweep -- 338.1: no gain;
+//   * (EXPERIMENTS C-3) pairs drawn from the block's ticket counter instead of six per wave: 346.4 against the parent's 344.4; with wave
+//     0's first and the others' second pair behind the hidden row's sweep as well: 347.5; the first pair of waves 1..7 moved up behind
+//     the ATTENTION VECTOR's sweep on top of that: 343.9, slower than the parent -- that sweep feeds the O rows every block waits for;
+//   * wave 0's second pair asked for as soon as the row is in LDS instead of behind the norm: 342.7 against 346.4.
 template <bool TRACE>
-__device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, float* red, const uint16_t* sm_pub, unsigned tag, int lane,
-                                             int wave, int pub_row0, int pub_rows, unsigned long long* tr) {
+__device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, float* red, int* sm_gu, const uint16_t* sm_pub, unsigned tag,
+                                             int lane, int wave, int pub_row0, int pub_rows, unsigned long long* tr) {
     typedef Act16<false> A;
-    const int pair0 = (((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * kWaves + wave) * kGuPairs;
-    u32x4 wA[2][kGuNV];
+    const int pair0 = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * kGuBlockPairs;
     constexpr int PV = kGuNV * 64 / 256;              // vectors of the row per thread of the first four waves
     u32x4 nwv[PV];
 #pragma unroll
     for (int i = 0; i < PV; ++i) nwv[i] = *(reinterpret_cast<const u32x4*>(a.gu_norm_w) + (threadIdx.x & 255) + i * 256);
-    u32x4 wB[2][kGuNV];
-    if (wave != 0) gateup_issue(a, wA, pair0, lane);
+    u32x4 wA[2][kGuNV], wB[2][kGuNV];
+    int tA = 0, tB;
+    // (the two tickets a wave draws ahead of the norm are below kGuBlockPairs, no check: all sixteen are drawn before the barrier in front
+    //  of it, and the tickets that are compared with kGuBlockPairs are drawn behind it)
+    if (wave != 0) {
+        tA = gateup_claim(sm_gu, lane);
+        gateup_issue(a, wA, pair0 + tA, lane);
+    }
     lds_barrier();   // every wave is done with the attention vector in `xs` and has parked its O rows
     if (wave == 0) {
         if (lane < pub_rows / 2) st_granule_u32(a.hg + pub_row0 / 2 + lane, tag, reinterpret_cast<const unsigned*>(sm_pub)[lane]);
@@ -278,36 +305,91 @@ __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, f
             __builtin_amdgcn_s_sleep(4);
         }
         unsigned long long g[GPL];
-        for (unsigned spins = 0;; ++spins) {
 #pragma unroll
-            for (int i = 0; i < GPL; ++i) g[i] = ld_granule(a.hg + (size_t)i * 64 + lane);
-            bool ok = true;
+        for (int i = 0; i < GPL; ++i) g[i] = ld_granule(a.hg + (size_t)i * 64 + lane);
+        __builtin_amdgcn_sched_barrier(0);
+        lds_barrier();   // the sweep is in the CU's queue: what the block asks for now is behind it
+        tA = gateup_claim(sm_gu, lane);
+        gateup_issue(a, wA, pair0 + tA, lane);
+        unsigned bad = 0;
 #pragma unroll
-            for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
-            if (__all(ok)) break;
-            if (spins >= kSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
-                if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
+        for (int i = 0; i < GPL; ++i) bad |= (unsigned)(g[i] >> 32) ^ tag;
+        asm volatile("; hidden row: tags read behind the first (gate, up) pair" : "+v"(bad));
+        if (!__all(bad == 0)) {
+            for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+                for (int i = 0; i < GPL; ++i) g[i] = ld_granule(a.hg + (size_t)i * 64 + lane);
+                bool ok = true;
+#pragma unroll
+                for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
+                if (__all(ok)) break;
+                if (spins >= kSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
+                    if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(4);
             }
-            __builtin_amdgcn_s_sleep(4);
         }
         unsigned* sx = reinterpret_cast<unsigned*>(xs);   // the raw row, natural element order
 #pragma unroll
         for (int i = 0; i < GPL; ++i) sx[i * 64 + lane] = (unsigned)g[i];
         if (TRACE && lane == 0 && pub_rows > 0) tr[4] = wall_clock64();
-        gateup_issue(a, wA, pair0, lane);
+        tB = gateup_claim(sm_gu, lane);   // drawn on this side of the barrier (see above), asked for behind the norm
+    } else {
+        lds_barrier();
+        tB = gateup_claim(sm_gu, lane);
+        gateup_issue(a, wB, pair0 + tB, lane);
     }
     lds_barrier();
     rmsnorm_in_lds<A, PV>(xs, red, nwv, kGuHidden, a.eps, threadIdx.x < 256);
-    // pair p is reduced from one register set while pair p + 1 is in flight
-    static_assert(kGuPairs % 2 == 0, "whole double-buffer rounds");
-#pragma unroll
-    for (int p = 0; p < kGuPairs; p += 2) {
-        gateup_issue(a, wB, pair0 + p + 1, lane);
-        gateup_reduce(a, wA, xs, pair0 + p, lane);
-        if (TRACE && p == 0 && threadIdx.x == 0) tr[7] = wall_clock64();
-        if (p + 2 < kGuPairs) gateup_issue(a, wA, pair0 + p + 2, lane);
-        gateup_reduce(a, wB, xs, pair0 + p + 1, lane);
+    // Wave 0 asks for its second pair only now: the norm's last barrier waits for every load of the first four waves (hipcc drains in
+    // front of it), and a pair asked for when the row was in LDS would hold the whole block for its round trip.  (Two arms with an asm
+    // text of their own: merged, the wait in front of the first reduce would drain wave 0's second pair.)
+    if (wave == 0) {
+        gateup_issue(a, wB, pair0 + tB, lane);
+        gateup_reduce(a, wA, xs, pair0 + tA, lane);
+        if (TRACE && threadIdx.x == 0) tr[7] = wall_clock64();
+        asm volatile("; first pair reduced: wave 0, its second pair just asked for" ::: "memory");
+    } else {
+        gateup_reduce(a, wA, xs, pair0 + tA, lane);
+        asm volatile("; first pair reduced: the second pair came in through the hop" ::: "memory");
+    }
+    // Both sets are in flight.  A set is reduced and refilled with the pair of the wave's next ticket -- or, with no pair left, the other
+    // set is reduced and the wave is done.  Wave-uniform branches over two named sets, each arm with a load count of its own: hipcc's waits
+    // stay counted (a refill skipped under a condition makes the wait that follows drain the set in flight).  The ticket of a refill is
+    // drawn one reduce AHEAD (nA, nB): the LDS round trip hides behind the reduce, and with the draw at the loop's head hipcc drained the
+    // set in flight there (s_waitcnt vmcnt(0) in front of the draw's first VALU write): 346.4 against 347.5 tok/s, EXPERIMENTS C-3
+    int n_reduced = 1;
+    int nA = gateup_claim(sm_gu, lane), nB;
+    for (;;) {
+        if (nA >= kGuBlockPairs) {
+            gateup_reduce(a, wB, xs, pair0 + tB, lane);
+            ++n_reduced;
+            break;
+        }
+        tA = nA;
+        gateup_issue(a, wA, pair0 + tA, lane);
+        nB = gateup_claim(sm_gu, lane);
+        gateup_reduce(a, wB, xs, pair0 + tB, lane);
+        if (nB >= kGuBlockPairs) {
+            gateup_reduce(a, wA, xs, pair0 + tA, lane);
+            n_reduced += 2;
+            break;
+        }
+        tB = nB;
+        gateup_issue(a, wB, pair0 + tB, lane);
+        nA = gateup_claim(sm_gu, lane);
+        gateup_reduce(a, wA, xs, pair0 + tA, lane);
+        n_reduced += 2;
+    }
+    if constexpr (TRACE) {   // when wave 0 and wave 7 reduced their last pair, and how many pairs the block reduced
+        if (lane == 0) {
+            __hip_atomic_fetch_add(sm_gu + kGuReduced, n_reduced, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            if (wave == 0) tr[8] = wall_clock64();
+            if (wave == kWaves - 1) tr[9] = wall_clock64();
+        }
+        lds_barrier();
+        if (threadIdx.x == 0) tr[10] = (unsigned long long)sm_gu[kGuReduced];
     }
 }
 
@@ -473,6 +555,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
     u32x4* sm_q = reinterpret_cast<u32x4*>(sm_l + kWaves * GT);   // [GT + 1][LPR]: roped q heads and the new k row, packed bf16
     u32x4* sm_x = sm_q + (GT + 1) * LPR;                          // OPROJ: [NV * 64] the attention vector, packed bf16
     float* sm_xsum = reinterpret_cast<float*>(sm_x + NV * 64);    // QO: [NV * 16] sums of 32 consecutive elements
+    int* sm_gu = reinterpret_cast<int*>(sm_x + NV * 64);          // GU: [kGuWords] the gate/up phase's ticket counter and TRACE count
 
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
@@ -480,8 +563,11 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
     const int sg = lane / LPR;            // token row inside the unit
     const int kvh = blockIdx.x, split = blockIdx.y;
     const int G = a.H / a.Hkv;
-    unsigned long long* tr = TRACE ? a.trace + ((size_t)split * a.Hkv + kvh) * 8 : nullptr;
+    unsigned long long* tr = TRACE ? a.trace + ((size_t)split * a.Hkv + kvh) * kAttnTraceWords : nullptr;
     if (TRACE && threadIdx.x == 0) tr[0] = wall_clock64();
+    if constexpr (GU) {   // (every wave passes the barrier below before it draws a ticket)
+        if (threadIdx.x < kGuWords) sm_gu[threadIdx.x] = 0;
+    }
 
     bf16_t* Kb = a.k + (size_t)kvh * a.kv_head_stride;
     bf16_t* Vb = a.v + (size_t)kvh * a.kv_head_stride;
@@ -691,7 +777,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
             uint16_t* sm_pub = reinterpret_cast<uint16_t*>(sm_l);   // (the split merge is done with sm_m / sm_l: a block barrier ago)
             if (rows == 2) oproj_phase<NV, 2, true>(a, sm_x, tag, lane, wave, o_row0, otr, sm_pub, pub_row0);
             else oproj_phase<NV, 3, true>(a, sm_x, tag, lane, wave, o_row0, otr, sm_pub, pub_row0);
-            gateup_phase<TRACE>(a, sm_x, sm_m, sm_pub, tag, lane, wave, pub_row0, pub_rows, otr);
+            gateup_phase<TRACE>(a, sm_x, sm_m, sm_gu, sm_pub, tag, lane, wave, pub_row0, pub_rows, otr);
             return;
         } else
         if constexpr (QO) {
@@ -724,7 +810,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
     if constexpr (GU) {
         // the consumer blocks take their share of the pairs once their heads are merged and published (block-uniform: split < G here)
         lds_barrier();
-        gateup_phase<TRACE>(a, sm_x, sm_m, nullptr, tag, lane, wave, 0, 0, TRACE ? tr : nullptr);
+        gateup_phase<TRACE>(a, sm_x, sm_m, sm_gu, nullptr, tag, lane, wave, 0, 0, TRACE ? tr : nullptr);
     }
 }
 
@@ -769,12 +855,12 @@ bool attn_step_oproj_q4_ok(int H, int Hkv, int D, int nsplit, int o_rows, int gr
     return (K == 2048 || K == 4096) && (group == 32 || group == 64 || group == 128) && attn_step_oproj_ok(H, Hkv, D, nsplit, o_rows);
 }
 
-// ... and [RMSNorm + gate/up + SwiGLU] behind it: the one shape whose 256 blocks x 8 waves take kGuPairs (gate, up) pairs each, every
+// ... and [RMSNorm + gate/up + SwiGLU] behind it: the one shape whose 256 blocks take kGuBlockPairs (gate, up) pairs each, every
 // O block holding whole granules (two or three rows per wave, the three-row waves filling whole blocks)
 bool attn_step_gateup_ok(int H, int Hkv, int D, int nsplit, int o_rows, int gu_rows) {
     const int blocks = Hkv * nsplit, waves = (blocks - H) * kWaves;
     if (D != 128 || H * D != kGuHidden || o_rows != kGuHidden || H / std::max(Hkv, 1) != 4 || blocks != 256) return false;
-    if (gu_rows != blocks * kWaves * kGuPairs || !attn_step_oproj_ok(H, Hkv, D, nsplit, o_rows)) return false;
+    if (gu_rows != blocks * kGuBlockPairs || !attn_step_oproj_ok(H, Hkv, D, nsplit, o_rows)) return false;
     return oproj_rows_per_wave(H, Hkv, nsplit, o_rows) == 3 && (o_rows - waves * 2) % kWaves == 0;
 }
 
@@ -827,7 +913,8 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
 #define OMX_ATTN_STEP_CASE(DD, GG)                                                                                       \
     if (D == DD && gt == GG) {                                                                                           \
         const size_t shmem = ((size_t)kWaves * (64 / (DD / 8)) * GG * DD + 2 * kWaves * GG) * sizeof(float) +            \
-                             (size_t)(GG + 1) * (DD / 8) * 16 + (size_t)nvw * 64 * 16 + (qo ? (size_t)nvw * 64 : 0);     \
+                             (size_t)(GG + 1) * (DD / 8) * 16 + (size_t)nvw * 64 * 16 + (qo ? (size_t)nvw * 64 : 0) +    \
+                             (a.gu_gate ? kGuWords * sizeof(int) : 0);                                                   \
         if (a.gu_gate) {   /* gate/up behind the O projection: one shape (attn_step_gateup_ok) */                         \
             if constexpr (DD == 128 && GG == 4) {                                                                        \
                 if (a.trace) OMX_ATTN_LAUNCH_GU(true)                                                                    \

@@ -536,10 +536,9 @@ int omx_qwen3_last_logits(omx_qwen3 m, void* host_bf16, int n) {
     return 0;
 }
 
-/* test/debug hook: copy an internal bf16 buffer to the host ("h","h2","qkv","attn_out","act","k<l>","v<l>") */
-int omx_qwen3_debug_read(omx_qwen3 m, const char* name, void* host, size_t n_elems) {
-    OMX_REQUIRE(m && name && host, "omx_qwen3_debug_read: null argument");
-    const void* src = nullptr;
+// the device buffer a debug name stands for (omx_qwen3_debug_read / _write); null: unknown name or layer
+static void* debug_buffer(omx_qwen3 m, const char* name) {
+    void* src = nullptr;
     const std::string s(name);
     if (s == "h") src = m->h;
     else if (s == "h2") src = m->h2;
@@ -548,7 +547,7 @@ int omx_qwen3_debug_read(omx_qwen3 m, const char* name, void* host, size_t n_ele
     else if (s == "act") src = m->act;
     else if (s.rfind("g_", 0) == 0 && m->se_gran) {   // granule buffers of the persistent step (8 bytes each: n_elems = 4 x granules)
         const size_t hd = m->cfg.hidden_size, D = m->cfg.head_dim;
-        const uint64_t* g = m->se_gran;
+        uint64_t* g = m->se_gran;
         if (s == "g_x") src = g;
         else if (s == "g_x1") src = g + hd / 2;
         else if (s == "g_qkv") src = g + hd;
@@ -557,11 +556,27 @@ int omx_qwen3_debug_read(omx_qwen3 m, const char* name, void* host, size_t n_ele
     }
     else if (s.size() > 1 && (s[0] == 'k' || s[0] == 'v')) {
         const int l = atoi(s.c_str() + 1);
-        OMX_REQUIRE(l >= 0 && l < (int)m->kcache.size(), "omx_qwen3_debug_read: bad layer in %s", name);
-        src = s[0] == 'k' ? m->kcache[l] : m->vcache[l];
+        if (l >= 0 && l < (int)m->kcache.size()) src = s[0] == 'k' ? m->kcache[l] : m->vcache[l];
     }
-    OMX_REQUIRE(src != nullptr, "omx_qwen3_debug_read: unknown buffer %s", name);
+    return src;
+}
+
+/* test/debug hook: copy an internal bf16 buffer to the host ("h","h2","qkv","attn_out","act","k<l>","v<l>") */
+int omx_qwen3_debug_read(omx_qwen3 m, const char* name, void* host, size_t n_elems) {
+    OMX_REQUIRE(m && name && host, "omx_qwen3_debug_read: null argument");
+    const void* src = debug_buffer(m, name);
+    OMX_REQUIRE(src != nullptr, "omx_qwen3_debug_read: unknown buffer or layer %s", name);
     OMX_HIP_CHECK(hipMemcpyAsync(host, src, n_elems * 2, hipMemcpyDeviceToHost, m->stream));
+    OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return 0;
+}
+
+/* ... and the other way: n_elems 16-bit patterns from the host into the buffer (a test poisons `act` to see every element rewritten) */
+int omx_qwen3_debug_write(omx_qwen3 m, const char* name, const void* host, size_t n_elems) {
+    OMX_REQUIRE(m && name && host, "omx_qwen3_debug_write: null argument");
+    void* dst = debug_buffer(m, name);
+    OMX_REQUIRE(dst != nullptr, "omx_qwen3_debug_write: unknown buffer %s", name);
+    OMX_HIP_CHECK(hipMemcpyAsync(dst, host, n_elems * 2, hipMemcpyHostToDevice, m->stream));
     OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
     return 0;
 }
@@ -579,14 +594,16 @@ int omx_qwen3_stream(omx_qwen3 m, omx_stream* s) {
 }
 
 /* debug hook (tools/attn_step_trace.py): run ONE decode step eagerly with the attention launches stamping the 100 MHz wall clock:
- * host receives [layers][attn splits][kv heads][8] = {block start, loads landed + q/k normed and roped, own chunk done, granules
- * stored, gathered and merged (consumer blocks), -, -, -}; *blocks = splits * kv heads */
+ * host receives [layers][attn splits][kv heads][16] = {block start, loads landed + q/k normed and roped, own chunk done, granules
+ * stored, gathered and merged (consumer blocks), attention vector swept, O rows stored, partials parked; with gate/up in the launch
+ * (csrc/attn_step.hip gateup_phase): [4] of an O block the hidden row swept, [7] first pair reduced, [8] / [9] last pair of wave 0 / of
+ * wave 7 reduced, [10] NOT a stamp: the pairs the block's waves reduced (48 each); the rest 0}; *blocks = splits * kv heads */
 int omx_qwen3_debug_trace_step(omx_qwen3 m, unsigned long long* host, size_t n_words, int* blocks) {
     OMX_REQUIRE(m && host && blocks, "omx_qwen3_debug_trace_step: null argument");
     StepState st;
     if (read_step_state(m, &st)) return 1;
     if (prepare_step(m, st.pos)) return 1;
-    const size_t per_layer = (size_t)m->attn_nsplit * m->Hkv * 8, need = per_layer * m->cfg.num_hidden_layers;
+    const size_t per_layer = (size_t)m->attn_nsplit * m->Hkv * kAttnTraceWords, need = per_layer * m->cfg.num_hidden_layers;
     OMX_REQUIRE(n_words >= need, "omx_qwen3_debug_trace_step: buffer of %zu words, need %zu", n_words, need);
     unsigned long long* dev = nullptr;
     OMX_HIP_CHECK(hipMalloc(&dev, need * 8));

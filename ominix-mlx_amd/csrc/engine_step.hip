@@ -301,7 +301,7 @@ static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* re
     a.ws = m->attn_gran;
     a.out = m->attn_out;
     a.abort_flag = m->wait_abort;
-    a.trace = m->attn_trace ? m->attn_trace + (size_t)l * m->attn_nsplit * m->Hkv * 8 : nullptr;
+    a.trace = m->attn_trace ? m->attn_trace + (size_t)l * m->attn_nsplit * m->Hkv * kAttnTraceWords : nullptr;
     a.f16 = m->f16;   // a float16 checkpoint runs in float16 end to end
     if (resid && (out || out_f32)) {
         a.o_resid = resid; a.o_out = out; a.o_out_f32 = out_f32; a.o_rows = c.hidden_size; a.xg = m->attn_xg;

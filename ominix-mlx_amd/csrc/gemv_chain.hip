@@ -151,7 +151,9 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
     // ---- waves 1..3 ask for their q/k/v rows NOW: HBM keeps streaming through the hop.  Wave 0 -- whose loads return in order, so that
     //      a granule asked for behind 24 KB of weights would only arrive after them -- first brings the row in: it watches one granule of
     //      every eighth producer politely (a sleep between looks), sweeps all N / 2 granules into LDS, and only then asks for ITS rows,
-    //      which queue behind the other waves' 3/4 of the matrix: the hop costs the launch nothing while it is shorter than that stream ----
+    //      which queue behind the other waves' 3/4 of the matrix: the hop costs the launch nothing while it is shorter than that stream.
+    //      (Measured, EXPERIMENTS C-3: wave 0 asking for its rows right BEHIND a peeled first pass of the sweep, tags read behind
+    //      s_waitcnt vmcnt(24) -- 344.26 / 344.44 tok/s against 344.29 / 344.44, 230 VGPRs instead of 138: nothing, not in the tree.) ----
     unsigned* sx = reinterpret_cast<unsigned*>(xs);   // the raw row, natural element order
     if (wave != 0) {
         OMX_ISSUE_QKV();

@@ -109,6 +109,7 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_last_prefill_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "omx_qwen3_dequant_bytes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_size_t)]),
     "omx_qwen3_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
+    "omx_qwen3_debug_write": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
     "omx_qwen3_stream": (c_int, [c_void_p, ctypes.POINTER(c_void_p)]),
     "omx_qwen3_step_bytes": (c_int, [c_void_p, c_int, ctypes.POINTER(ctypes.c_double)]),
     "omx_qwen3_decode_path": (c_int, [c_void_p, ctypes.POINTER(c_int)]),

@@ -16,16 +16,19 @@ m = engine.Model(hidden_size=4096, num_hidden_layers=L, intermediate_size=12288,
 m.synth_weights()
 m.prefill((np.arange(ctx, dtype=np.uint32) * 7919) % 151936)
 m.decode(8)
-buf = np.zeros(L * 64 * 8 * 8, np.uint64)
+W = 16   # trace words per block (csrc/attn.hpp kAttnTraceWords)
+buf = np.zeros(L * 64 * 8 * W, np.uint64)
 nb = ctypes.c_int()
 omx.check(lib.omx_qwen3_debug_trace_step(m._h, buf.ctypes.data, buf.size, ctypes.byref(nb)))
 nb = nb.value
-t = buf[:L * nb * 8].reshape(L, nb, 8).astype(np.int64)
+t = buf[:L * nb * W].reshape(L, nb, W).astype(np.int64)
 names = ["block start", "loads landed, q/k normed+roped", "own chunk done", "granules stored", "gather + merge done (consumers)",
          "attention vector swept into LDS (O projection)", "O rows stored", "all waves' partials parked in LDS (block barrier)"]
 # gate/up inside the launch (OMX_ATTN_GATEUP): stamp 7 marks the first reduced (gate, up) pair of wave 0 -- the sweeping wave, whose pair
 # is asked for last -- and stamp 4 of an O block (blocks past the first H: the consumers come first) the hidden row swept into LDS.
 # Hop three is hidden when "first pair reduced" follows "hidden row swept" by less than a weight round trip.
+# Stamps 8 and 9: wave 0 and wave 7 done with their last pair (the pairs are drawn from a ticket counter in the block: the two end
+# together); word 10 is a count, not a stamp: the pairs the block's waves reduced (48).
 gateup = m.step_forms()["attn_gateup"]
 n_cons = H   # consumer blocks: one per query head, the launch's first blocks
 events = [(ev, nm, slice(None)) for ev, nm in enumerate(names)]
@@ -33,6 +36,8 @@ if gateup:
     events[4] = (4, names[4], slice(0, n_cons))
     events[7] = (7, "gate/up: first pair reduced (wave 0)", slice(None))
     events.insert(7, (4, "gate/up: hidden row swept into LDS (O blocks)", slice(n_cons, None)))
+    events.append((8, "gate/up: last pair of wave 0 reduced", slice(None)))
+    events.append((9, "gate/up: last pair of wave 7 reduced", slice(None)))
 print(f"{nb} blocks per launch, {L} layers, ctx {ctx}, gate/up in the launch: {gateup}")
 for ev, nm, blocks in events:
     rows = []
@@ -46,4 +51,9 @@ for ev, nm, blocks in events:
         allv = np.concatenate(rows)
         print(f"  {nm:48s} median {np.median(allv):6.2f} us   p90 {np.percentile(allv, 90):6.2f}   max(median over layers) "
               f"{np.median([r.max() for r in rows]):6.2f}   n/layer {allv.size // (L - 1)}")
+if gateup:
+    tail = (t[1:, :, 8] - t[1:, :, 9]) / 100.0
+    print(f"  wave 0 behind wave 7 at the end of a block: median {np.median(tail):6.2f} us   p90 {np.percentile(tail, 90):6.2f}   "
+          f"max {tail.max():6.2f}")
+    print(f"  pairs reduced per block: min {t[:, :, 10].min()}   max {t[:, :, 10].max()}")
 m.close()
