@@ -151,6 +151,28 @@ int omx_logprob_partial(float* partials, uint32_t* part_arg, float* tgt, const v
                         const uint32_t* targets, int64_t rows, int V, omx_dtype dtype, omx_stream stream);
 int omx_logprob_merge(float* logprobs, uint32_t* greedy /*nullable*/, float* lse /*nullable*/, const float* partials,
                       const uint32_t* part_arg, const float* tgt, const uint32_t* targets, int64_t rows, int V, omx_stream stream);
+/* ---- ... with the row's top_n alternatives beside it: what a decode step reports about the token it drew (omx_qwen3_set_logprobs).
+ *      logprobs, greedy and lse are BIT FOR BIT what omx_logprob_rows writes for the same inputs: the chunk grid, the summation orders
+ *      and the arithmetic above are the same text.  Besides them
+ *        top_ids[r, j]      = the j-th column of row r in the order (logit descending, column index ascending) -- the order of the 64-bit
+ *                             key the samplers draw with (+0 above -0, NaN below everything), so top_ids[r, 0] == greedy[r] always
+ *        top_logprobs[r, j] = f32(logits[r, top_ids[r, j]]) - lse[r]      (one f32 subtraction from the row's own lse)
+ *      Only columns < V take part; the padding up to ld is never read as a logit.  1 <= top_n <= min(OMX_LOGPROBS_MAX_TOP, V); anything
+ *      else is refused, as are the dtypes and shapes omx_logprob_rows refuses.  Two launches for all rows whatever top_n is: the chunk
+ *      wave also leaves the chunk's own best top_n (top_n rounds of a wave-wide maximum over its 1024 keys, in registers), the merge
+ *      block picks the row's top_n from the heads of the ceil(V/1024) descending lists.  A row's outputs depend on neither the number
+ *      of rows, the rows beside it, nor the panel widths of the two-phase form.
+ *      Two-phase form: omx_logprob_top_partial = omx_logprob_partial + cand [rows, ceil(V/1024), top_n] u32 (a chunk's candidates, an
+ *      internal encoding); omx_logprob_top_merge, once every chunk has been written.                                              */
+#define OMX_LOGPROBS_MAX_TOP 20
+int omx_logprob_rows_top(float* logprobs, uint32_t* greedy /*nullable*/, float* lse /*nullable*/, uint32_t* top_ids /*[rows, top_n]*/,
+                         float* top_logprobs /*[rows, top_n]*/, const void* logits, int64_t ld, const uint32_t* targets, int64_t rows,
+                         int V, int top_n, omx_dtype dtype /*OMX_BFLOAT16*/, omx_stream stream);
+int omx_logprob_top_partial(float* partials, uint32_t* part_arg, float* tgt, uint32_t* cand, const void* panel, int64_t ld, int c0, int P,
+                            const uint32_t* targets, int64_t rows, int V, int top_n, omx_dtype dtype, omx_stream stream);
+int omx_logprob_top_merge(float* logprobs, uint32_t* greedy /*nullable*/, float* lse /*nullable*/, uint32_t* top_ids, float* top_logprobs,
+                          const float* partials, const uint32_t* part_arg, const float* tgt, const uint32_t* cand,
+                          const uint32_t* targets, int64_t rows, int V, int top_n, omx_stream stream);
 
 /* ---- a10, temperature branch: MLX's keyed generator + categorical sampler.
  *      mlx/c/random.h:37-72,129-139,149-157 (mlx_random_bits / _categorical* / _gumbel / _key / _split* / _uniform),
@@ -306,6 +328,22 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
 int omx_qwen3_decode(omx_qwen3 m, int n, uint32_t* tokens_out);
 /* copy the logits of the last executed step ([vocab_local] bf16) to a host buffer                  */
 int omx_qwen3_last_logits(omx_qwen3 m, void* host_bf16, int n);
+/* Per-token log-probabilities of the tokens being generated, inside the step (opt-in; off, nothing the engine launches or allocates
+ * changes).  set_logprobs: top_n = -1 off (default), 0 = the drawn token's log-probability only, 1..min(OMX_LOGPROBS_MAX_TOP, V) = with that
+ * many alternatives.  While on, every sampled token -- the prefill's first and each decode step, which stays ONE hipGraph per context
+ * bucket -- is followed by the two launches of omx_logprob_rows_top over the step's logits row; the target is the token the finalize
+ * just wrote, on the device, and the results go into rings beside the token ring at the entry the device derives from its own count.
+ * What is reported is the log-softmax of the row omx_qwen3_last_logits returns, the model's RAW logits: before temperature, top-k /
+ * top-p and penalties -- what omx_qwen3_score reports for the same position.  Under a sampler the drawn token need not be top_ids[0].
+ * The OMX_STEP_AQL / OMX_STEP_ENGINE forms of the step are not taken while it is on (as with a sampler).
+ *   decode_logprobs: omx_qwen3_decode + logprobs [n] and, top_n > 0, top_ids / top_logprobs [n, top_n] (both nullable), HOST buffers.
+ *   last_logprobs:   the same for the most recently sampled token (after a prefill: its first token); top_ids / top_logprobs nullable.
+ * Refused by name: tensor / expert parallel models (a sharded vocabulary), float16 models, top_n outside -1..min(20, V), and
+ * decode_logprobs / last_logprobs while off (last_logprobs also before any token was sampled since set_logprobs).               */
+int omx_qwen3_set_logprobs(omx_qwen3 m, int top_n);
+int omx_qwen3_decode_logprobs(omx_qwen3 m, int n, uint32_t* tokens_out, float* logprobs /*[n]*/, uint32_t* top_ids /*[n, top_n], nullable*/,
+                              float* top_logprobs /*[n, top_n], nullable*/);
+int omx_qwen3_last_logprobs(omx_qwen3 m, float* logprob, uint32_t* top_ids /*[top_n], nullable*/, float* top_logprobs /*nullable*/);
 /* Speculative decoding support (mlx-rs-core/src/speculative.rs).
  *   verify: verify_draft_tokens :132-161 -- the n tokens [last accepted, draft 1 .. draft n-1] in ONE batched pass on top of the cache
  *           (their K/V rows are appended), greedy_out[i] = argmax of the logits after token i; afterwards the pending input token is
@@ -411,6 +449,20 @@ int omx_qwen3_batch_trim(omx_qwen3_batch b, int slot, int n, uint32_t next_token
 int omx_qwen3_batch_reset(omx_qwen3_batch b, int slot);
 int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint32_t* first_token);
 int omx_qwen3_batch_shared(omx_qwen3_batch b, int slot, int* owner, int* shared_len);
+/* Per-token log-probabilities in the batched step: omx_qwen3_set_logprobs' rule, ONE setting for the batch (top_n -1 = off, the
+ * default; 0; 1..min(OMX_LOGPROBS_MAX_TOP, V)).  While on, the step's sampler -- plain or filtered -- is followed by the same two launches
+ * over the T rows of the step's logits, the targets being the tokens the sampler just wrote to the token ring; the results are laid out
+ * as the token ring is and the host still waits once per call.  The values are those of the raw rows omx_qwen3_batch_logits returns.
+ * A row's values do not depend on what runs beside it: a slot's bits are the same alone, among eight and in any order.
+ *   decode_logprobs: omx_qwen3_batch_decode + logprobs [n_steps, n_slots] and (nullable) top_ids / top_logprobs [n_steps, n_slots, top_n].
+ *   last_logprobs:   of the slot's most recently sampled token: a prefill's or fork's first token, or its last step's.  A
+ *                    fork(resample) sibling has its OWN drawn token's value over the source's kept row; fork(resample = 0) copies the
+ *                    source's.  Refused while off, and on a slot that has sampled nothing since set_logprobs.                   */
+int omx_qwen3_batch_set_logprobs(omx_qwen3_batch b, int top_n);
+int omx_qwen3_batch_decode_logprobs(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out,
+                                    float* logprobs /*[n_steps, n_slots]*/, uint32_t* top_ids /*[n_steps, n_slots, top_n], nullable*/,
+                                    float* top_logprobs /*nullable*/);
+int omx_qwen3_batch_last_logprobs(omx_qwen3_batch b, int slot, float* logprob, uint32_t* top_ids /*nullable*/, float* top_logprobs /*nullable*/);
 /* device time of the steps of the last omx_qwen3_batch_decode call (HIP events on the model's stream), ms */
 int omx_qwen3_batch_last_decode_ms(omx_qwen3_batch b, float* ms);
 /* measurement hook (csrc/per_op_route.hip): qwen3-mlx's Model::forward + Generate::next replayed call for call through the mlx-c handle ABI

@@ -93,6 +93,12 @@ SIGNATURES = {
     "omx_logprob_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "omx_logprob_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "omx_logprob_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "omx_logprob_rows_top": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
+                                     c_void_p]),
+    "omx_logprob_top_partial": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_int, c_int,
+                                        c_int, c_void_p]),
+    "omx_logprob_top_merge": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_int, c_int, c_void_p]),
     "omx_random_key": (c_int, [c_void_p, ctypes.c_uint64, c_void_p]),
     "omx_random_split": (c_int, [c_void_p, c_void_p, c_int, c_void_p]),
     "omx_random_bits": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -257,6 +257,38 @@ int omx_qwen3_set_sampling(omx_qwen3 m, const omx_sampling* p, uint64_t seed) {
     return 0;
 }
 
+/* Per-token log-probabilities inside the step: the two launches of logprob.hip's top-n form behind the finalize of every sampled
+ * token (enqueue_step_tail), over the raw logits row.  They are launch sites of the captured step: the graphs are dropped. */
+int omx_qwen3_set_logprobs(omx_qwen3 m, int top_n) {
+    OMX_REQUIRE(m, "omx_qwen3_set_logprobs: null model");
+    const omx_qwen3_config& c = m->cfg;
+    OMX_REQUIRE(top_n < 0 || (c.tp_size <= 1 && c.ep_size <= 1 && m->allreduce == nullptr),
+                "omx_qwen3_set_logprobs: tensor / expert parallel models are not supported (tp_size %d, ep_size %d: a rank holds a "
+                "vocabulary shard, the row's log-sum-exp would need an all-reduce)", c.tp_size, c.ep_size);
+    OMX_REQUIRE(top_n < 0 || !m->f16, "omx_qwen3_set_logprobs: float16 models (float16 weights or float16 triplets) are not supported: the row reduction "
+                "reads bfloat16 logits");
+    OMX_REQUIRE(top_n >= -1 && top_n <= OMX_LOGPROBS_MAX_TOP && top_n <= m->V,
+                "omx_qwen3_set_logprobs: top_n = %d is outside -1..min(%d, V = %d) (-1 = off, 0 = the drawn token only)", top_n,
+                OMX_LOGPROBS_MAX_TOP, m->V);
+    OMX_REQUIRE(top_n < 0 || (m->V % 8 == 0 && m->V <= (1 << 20)),
+                "omx_qwen3_set_logprobs: vocabulary %d must be a multiple of 8 and at most 2^20 (omx_logprob_rows' shapes)", m->V);
+    if (top_n >= 0 && !m->lp_ring) {
+        uint8_t* scratch = nullptr;
+        if (dev_alloc(m, &m->lp_ring, (size_t)m->ring_cap) || dev_alloc(m, &m->top_lp_ring, (size_t)m->ring_cap * OMX_LOGPROBS_MAX_TOP) ||
+            dev_alloc(m, &m->top_id_ring, (size_t)m->ring_cap * OMX_LOGPROBS_MAX_TOP) ||
+            dev_alloc(m, &scratch, logprob_top_scratch_bytes(1, m->V, OMX_LOGPROBS_MAX_TOP)))
+            return 1;
+        m->lp_scratch = scratch;
+        OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
+    }
+    if (top_n != m->lp_top) {
+        recapture_step(m);
+        m->lp_top = top_n;
+        m->lp_valid = false;
+    }
+    return 0;
+}
+
 /* The sampler's key-sequence state (mlx-rs RandomState: two words).  The reference's speculative loop draws the draft's and the
  * target's tokens from ONE global sequence (speculative.rs:104-109: `categorical!` without a key); two engine models reproduce that by
  * handing this state back and forth.  set != 0 writes `state2` into the model, otherwise the model's state is read out. */
@@ -303,6 +335,7 @@ int omx_qwen3_encode(omx_qwen3 m, const uint32_t* ids, int n, const uint8_t* att
 int omx_qwen3_reset(omx_qwen3 m) {
     OMX_REQUIRE(m, "omx_qwen3_reset: null model");
     OMX_HIP_CHECK(hipMemsetAsync(m->st, 0, sizeof(StepState), m->stream));
+    m->lp_valid = false;   // the count the rings are indexed by starts again
     if (reset_sampler_history(m)) return 1;
     OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
     return 0;
@@ -374,6 +407,7 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
     OMX_HIP_CHECK(hipMemcpyAsync(first_token, m->out_ring + (count_before % m->ring_cap), 4, hipMemcpyDeviceToHost, m->stream));
     OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
     OMX_HIP_CHECK(hipEventElapsedTime(&m->last_prefill_ms, m->ev0, m->ev1));
+    m->lp_valid = m->lp_top >= 0;
     return step_health(m);
 }
 
@@ -490,8 +524,8 @@ int omx_qwen3_last_prefill_ms(omx_qwen3 m, float* ms) {
     return 0;
 }
 
-int omx_qwen3_decode(omx_qwen3 m, int n, uint32_t* tokens_out) {
-    OMX_REQUIRE(m && tokens_out, "omx_qwen3_decode: null argument");
+// n decode steps; logprobs != null: also the rings' entries of those steps (omx_qwen3_decode_logprobs, which has checked that they exist)
+static int decode_steps(omx_qwen3 m, int n, uint32_t* tokens_out, float* logprobs, uint32_t* top_ids, float* top_logprobs) {
     OMX_REQUIRE(n >= 0 && n <= m->ring_cap, "omx_qwen3_decode: n=%d out of range (1..%d per call)", n, m->ring_cap);
     if (n == 0) return 0;
     StepState st;
@@ -525,6 +559,45 @@ int omx_qwen3_decode(omx_qwen3 m, int n, uint32_t* tokens_out) {
     std::vector<uint32_t> ring(m->ring_cap);
     OMX_HIP_CHECK(hipMemcpy(ring.data(), m->out_ring, (size_t)m->ring_cap * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; ++i) tokens_out[i] = ring[(st.out_count + i) % m->ring_cap];
+    m->lp_valid = m->lp_top >= 0;
+    if (!logprobs) return 0;
+    const size_t top = (size_t)m->lp_top;
+    std::vector<float> lp(m->ring_cap), tlp(top_logprobs ? m->ring_cap * top : 0);
+    std::vector<uint32_t> ids(top_ids ? m->ring_cap * top : 0);
+    OMX_HIP_CHECK(hipMemcpy(lp.data(), m->lp_ring, lp.size() * 4, hipMemcpyDeviceToHost));
+    if (!tlp.empty()) OMX_HIP_CHECK(hipMemcpy(tlp.data(), m->top_lp_ring, tlp.size() * 4, hipMemcpyDeviceToHost));
+    if (!ids.empty()) OMX_HIP_CHECK(hipMemcpy(ids.data(), m->top_id_ring, ids.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; ++i) {
+        const size_t at = (size_t)((st.out_count + i) % m->ring_cap);
+        logprobs[i] = lp[at];
+        if (!tlp.empty()) memcpy(top_logprobs + i * top, tlp.data() + at * top, top * 4);
+        if (!ids.empty()) memcpy(top_ids + i * top, ids.data() + at * top, top * 4);
+    }
+    return 0;
+}
+
+int omx_qwen3_decode(omx_qwen3 m, int n, uint32_t* tokens_out) {
+    OMX_REQUIRE(m && tokens_out, "omx_qwen3_decode: null argument");
+    return decode_steps(m, n, tokens_out, nullptr, nullptr, nullptr);
+}
+
+int omx_qwen3_decode_logprobs(omx_qwen3 m, int n, uint32_t* tokens_out, float* logprobs, uint32_t* top_ids, float* top_logprobs) {
+    OMX_REQUIRE(m && tokens_out && logprobs, "omx_qwen3_decode_logprobs: null argument");
+    OMX_REQUIRE(m->lp_top >= 0, "omx_qwen3_decode_logprobs: log-probabilities are off (omx_qwen3_set_logprobs)");
+    return decode_steps(m, n, tokens_out, logprobs, top_ids, top_logprobs);
+}
+
+int omx_qwen3_last_logprobs(omx_qwen3 m, float* logprob, uint32_t* top_ids, float* top_logprobs) {
+    OMX_REQUIRE(m && logprob, "omx_qwen3_last_logprobs: null argument");
+    OMX_REQUIRE(m->lp_top >= 0, "omx_qwen3_last_logprobs: log-probabilities are off (omx_qwen3_set_logprobs)");
+    OMX_REQUIRE(m->lp_valid, "omx_qwen3_last_logprobs: no token has been sampled since omx_qwen3_set_logprobs / omx_qwen3_reset");
+    StepState st;
+    if (read_step_state(m, &st)) return 1;
+    OMX_REQUIRE(st.out_count >= 1, "omx_qwen3_last_logprobs: no token has been sampled yet");
+    const size_t at = (size_t)((st.out_count - 1) % m->ring_cap), top = (size_t)m->lp_top;
+    OMX_HIP_CHECK(hipMemcpy(logprob, m->lp_ring + at, 4, hipMemcpyDeviceToHost));
+    if (top_ids && top) OMX_HIP_CHECK(hipMemcpy(top_ids, m->top_id_ring + at * top, top * 4, hipMemcpyDeviceToHost));
+    if (top_logprobs && top) OMX_HIP_CHECK(hipMemcpy(top_logprobs, m->top_lp_ring + at * top, top * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

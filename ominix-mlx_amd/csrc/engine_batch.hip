@@ -405,6 +405,15 @@ struct omx_qwen3_batch_ {
     // the rows' own blocks at every group size measured (2, 4, 8 members), so by default no group is large enough
     int group_min = kMaxSlots + 1, group_rows = 8;
     float last_decode_ms = 0.f;                        // device time of the last decode call's steps (the model's event pair)
+    // per-token log-probabilities (omx_qwen3_batch_set_logprobs): lp_top = -1 off, else the alternatives per token.  The rings are laid
+    // out as the token ring is ([kRingSteps][kMaxSlots] and the same x lp_top); slot_lp / slot_ids / slot_top keep every slot's last
+    // values ([n_slots] and [n_slots, lp_top]), written by the same merge launch.  All allocated at the first switch-on, for
+    // OMX_LOGPROBS_MAX_TOP, with the scratch of the two launches over kMaxSlots rows.  lp_valid: the slot has sampled since the setting changed
+    int lp_top = -1;
+    float *lp_ring = nullptr, *top_lp_ring = nullptr, *slot_lp = nullptr, *slot_top = nullptr;
+    uint32_t *top_id_ring = nullptr, *slot_ids = nullptr;
+    uint8_t* lp_scratch = nullptr;
+    bool lp_valid[kMaxSlots] = {};
     std::vector<void*> owned;
 };
 
@@ -429,9 +438,29 @@ int clear_history(omx_qwen3_batch b, int slot) {
     return 0;
 }
 
+// after the sampler: the log-probabilities of the M tokens it just wrote at ring_at (and the rows' alternatives) over the same raw
+// rows, into the rings at the same offset and into the slots' last values
+int batch_logprobs(omx_qwen3_batch b, const bf16_t* logits, const int* rows, int M, const uint32_t* ring_at) {
+    if (b->lp_top < 0) return 0;
+    const size_t at = (size_t)(ring_at - b->ring), top = (size_t)b->lp_top;
+    LogprobTopOut o = {};
+    o.logprobs = b->lp_ring + at; o.top_ids = b->top_id_ring + at * top; o.top_lp = b->top_lp_ring + at * top;
+    o.row_slot = b->row_slot; o.slot_lp = b->slot_lp; o.slot_ids = b->slot_ids; o.slot_top = b->slot_top;
+    if (launch_logprob_top(o, b->lp_scratch, logits, b->m->V, ring_at, M, b->m->V, b->lp_top, b->m->stream)) return 1;
+    for (int r = 0; r < M; ++r) b->lp_valid[rows[r]] = true;
+    return 0;
+}
+
+int batch_sample_rows(omx_qwen3_batch b, const bf16_t* logits, const int* rows, int M, uint32_t* ring_at);
+
 // [per-row sample + advance] of logits[M, V] for slots rows[0..M) (row_slot already on the device): the plain kernel while no listed
-// slot filters, else every row under its own slot's rule (launch_batch_filtered; a plain row draws the same token there)
+// slot filters, else every row under its own slot's rule (launch_batch_filtered; a plain row draws the same token there); then,
+// where asked for, the drawn tokens' log-probabilities
 int batch_sample(omx_qwen3_batch b, const bf16_t* logits, const int* rows, int M, uint32_t* ring_at) {
+    return batch_sample_rows(b, logits, rows, M, ring_at) || batch_logprobs(b, logits, rows, M, ring_at);
+}
+
+int batch_sample_rows(omx_qwen3_batch b, const bf16_t* logits, const int* rows, int M, uint32_t* ring_at) {
     hipStream_t s = b->m->stream;
     const int V = b->m->V;
     bool any = false;
@@ -731,6 +760,13 @@ int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint
         OMX_HIP_CHECK(hipMemcpyAsync(first_token, &b->slots[src].pending, 4, hipMemcpyDeviceToHost, s));
         if (b->seen)   // the sibling continues src's sequence: src's history with it
             OMX_HIP_CHECK(hipMemcpyAsync(b->seen + (size_t)dst * V, b->seen + (size_t)src * V, (size_t)V, hipMemcpyDeviceToDevice, s));
+        if (b->lp_top >= 0) {   // ... and the values of the token it shares with src
+            const size_t top = (size_t)b->lp_top;
+            OMX_HIP_CHECK(hipMemcpyAsync(b->slot_lp + dst, b->slot_lp + src, 4, hipMemcpyDeviceToDevice, s));
+            if (top) OMX_HIP_CHECK(hipMemcpyAsync(b->slot_ids + dst * top, b->slot_ids + src * top, top * 4, hipMemcpyDeviceToDevice, s));
+            if (top) OMX_HIP_CHECK(hipMemcpyAsync(b->slot_top + dst * top, b->slot_top + src * top, top * 4, hipMemcpyDeviceToDevice, s));
+            b->lp_valid[dst] = b->lp_valid[src];
+        }
     }
     // one level deep: a fork of a child shares what the child shares with the root, and holds the rest in its own copy alone
     const bool child = b->shared_len[src] > 0 && b->owner[src] != src;
@@ -756,8 +792,10 @@ int omx_qwen3_batch_shared(omx_qwen3_batch b, int slot, int* owner, int* shared_
     return 0;
 }
 
-int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out) {
-    OMX_REQUIRE(b && slots && tokens_out, "omx_qwen3_batch_decode: null argument");
+// n_steps steps of the listed slots; logprobs != null: also the rings' entries of those steps (omx_qwen3_batch_decode_logprobs, which has
+// checked that they exist)
+static int batch_decode_steps(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out, float* logprobs,
+                              uint32_t* top_ids, float* top_logprobs) {
     OMX_REQUIRE(n_slots >= 1 && n_slots <= b->n_slots, "omx_qwen3_batch_decode: %d slots listed (1..%d)", n_slots, b->n_slots);
     OMX_REQUIRE(n_steps >= 0 && n_steps <= kRingSteps, "omx_qwen3_batch_decode: n_steps=%d out of range (0..%d per call)", n_steps, kRingSteps);
     omx_qwen3 m = b->m;
@@ -798,12 +836,66 @@ int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int
     }
     OMX_HIP_CHECK(hipEventRecord(m->ev1, s));
     OMX_HIP_CHECK(hipMemcpyAsync(tokens_out, b->ring, (size_t)n_steps * n_slots * 4, hipMemcpyDeviceToHost, s));
+    const size_t cells = (size_t)n_steps * n_slots, top = (size_t)std::max(b->lp_top, 0);
+    if (logprobs) OMX_HIP_CHECK(hipMemcpyAsync(logprobs, b->lp_ring, cells * 4, hipMemcpyDeviceToHost, s));
+    if (logprobs && top_ids && top) OMX_HIP_CHECK(hipMemcpyAsync(top_ids, b->top_id_ring, cells * top * 4, hipMemcpyDeviceToHost, s));
+    if (logprobs && top_logprobs && top) OMX_HIP_CHECK(hipMemcpyAsync(top_logprobs, b->top_lp_ring, cells * top * 4, hipMemcpyDeviceToHost, s));
     OMX_HIP_CHECK(hipStreamSynchronize(s));
     OMX_HIP_CHECK(hipEventElapsedTime(&b->last_decode_ms, m->ev0, m->ev1));
     for (int r = 0; r < n_slots; ++r) {
         b->pos[rows[r]] += n_steps;
         b->decoded[rows[r]] += n_steps;
     }
+    return 0;
+}
+
+int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out) {
+    OMX_REQUIRE(b && slots && tokens_out, "omx_qwen3_batch_decode: null argument");
+    return batch_decode_steps(b, slots, n_slots, n_steps, tokens_out, nullptr, nullptr, nullptr);
+}
+
+int omx_qwen3_batch_decode_logprobs(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out, float* logprobs,
+                                    uint32_t* top_ids, float* top_logprobs) {
+    OMX_REQUIRE(b && slots && tokens_out && logprobs, "omx_qwen3_batch_decode_logprobs: null argument");
+    OMX_REQUIRE(b->lp_top >= 0, "omx_qwen3_batch_decode_logprobs: log-probabilities are off (omx_qwen3_batch_set_logprobs)");
+    return batch_decode_steps(b, slots, n_slots, n_steps, tokens_out, logprobs, top_ids, top_logprobs);
+}
+
+int omx_qwen3_batch_set_logprobs(omx_qwen3_batch b, int top_n) {
+    OMX_REQUIRE(b, "omx_qwen3_batch_set_logprobs: null batch");
+    const int V = b->m->V;
+    OMX_REQUIRE(top_n >= -1 && top_n <= OMX_LOGPROBS_MAX_TOP && top_n <= V,
+                "omx_qwen3_batch_set_logprobs: top_n = %d is outside -1..min(%d, V = %d) (-1 = off, 0 = the drawn token only)", top_n,
+                OMX_LOGPROBS_MAX_TOP, V);
+    OMX_REQUIRE(top_n < 0 || (V % 8 == 0 && V <= (1 << 20)),
+                "omx_qwen3_batch_set_logprobs: vocabulary %d must be a multiple of 8 and at most 2^20 (omx_logprob_rows' shapes)", V);
+    if (top_n >= 0 && !b->lp_ring) {
+        const size_t cells = (size_t)kRingSteps * kMaxSlots, mt = OMX_LOGPROBS_MAX_TOP;
+        if (batch_alloc(b, &b->lp_ring, cells) || batch_alloc(b, &b->top_lp_ring, cells * mt) || batch_alloc(b, &b->top_id_ring, cells * mt) ||
+            batch_alloc(b, &b->slot_lp, (size_t)b->n_slots) || batch_alloc(b, &b->slot_top, b->n_slots * mt) ||
+            batch_alloc(b, &b->slot_ids, b->n_slots * mt) ||
+            batch_alloc(b, &b->lp_scratch, logprob_top_scratch_bytes(kMaxSlots, V, OMX_LOGPROBS_MAX_TOP)))
+            return 1;
+        OMX_HIP_CHECK(hipStreamSynchronize(b->m->stream));
+    }
+    if (top_n != b->lp_top) {
+        b->lp_top = top_n;
+        for (int s = 0; s < kMaxSlots; ++s) b->lp_valid[s] = false;   // (the slots' rows are laid out by top_n)
+    }
+    return 0;
+}
+
+int omx_qwen3_batch_last_logprobs(omx_qwen3_batch b, int slot, float* logprob, uint32_t* top_ids, float* top_logprobs) {
+    OMX_BATCH_SLOT("omx_qwen3_batch_last_logprobs");
+    OMX_REQUIRE(logprob, "omx_qwen3_batch_last_logprobs: null argument");
+    OMX_REQUIRE(b->lp_top >= 0, "omx_qwen3_batch_last_logprobs: log-probabilities are off (omx_qwen3_batch_set_logprobs)");
+    OMX_REQUIRE(b->lp_valid[slot], "omx_qwen3_batch_last_logprobs: slot %d has sampled no token since omx_qwen3_batch_set_logprobs", slot);
+    hipStream_t s = b->m->stream;
+    const size_t top = (size_t)b->lp_top;
+    OMX_HIP_CHECK(hipMemcpyAsync(logprob, b->slot_lp + slot, 4, hipMemcpyDeviceToHost, s));
+    if (top_ids && top) OMX_HIP_CHECK(hipMemcpyAsync(top_ids, b->slot_ids + slot * top, top * 4, hipMemcpyDeviceToHost, s));
+    if (top_logprobs && top) OMX_HIP_CHECK(hipMemcpyAsync(top_logprobs, b->slot_top + slot * top, top * 4, hipMemcpyDeviceToHost, s));
+    OMX_HIP_CHECK(hipStreamSynchronize(s));
     return 0;
 }
 
@@ -926,6 +1018,7 @@ int omx_qwen3_batch_reset(omx_qwen3_batch b, int slot) {
     b->pos[slot] = 0;
     b->prefilled[slot] = false;
     b->decoded[slot] = 0;
+    b->lp_valid[slot] = false;
     return 0;
 }
 

@@ -20,6 +20,7 @@
 #include "gemv.hpp"
 #include "random.hpp"
 #include "sample_filter.hpp"
+#include "logprob.hpp"
 #include "prefill.hpp"
 #include "quant.hpp"
 #include "launch_timing.hpp"
@@ -191,6 +192,15 @@ struct omx_qwen3_ {
     omx_sampling sampling = {0.f, 0, 1.f, 1.f, 0.f};
     uint8_t* seen = nullptr;
     uint8_t* sel = nullptr;
+
+    // per-token log-probabilities inside the step (omx_qwen3_set_logprobs): lp_top = -1 off, else the alternatives per token.  The rings
+    // lie beside out_ring ([ring_cap] and [ring_cap, lp_top]); they and the scratch of the two launches are allocated at the first
+    // switch-on, for OMX_LOGPROBS_MAX_TOP.  lp_valid: a token has been sampled since the setting changed
+    int lp_top = -1;
+    float *lp_ring = nullptr, *top_lp_ring = nullptr;
+    uint32_t* top_id_ring = nullptr;
+    void* lp_scratch = nullptr;
+    bool lp_valid = false;
 
     // batched-prefill activations (allocated on first use, sized for pf_cap tokens)
     int pf_cap = 0;

@@ -206,6 +206,17 @@ static int mark_sampled_token(omx_qwen3 m, hipStream_t s) {
     return launch_mark_seen(m->seen, m->V, m->st, s);
 }
 
+// after that: the log-probability of the token the finalize just wrote (and the row's alternatives) over the step's raw logits, into the
+// rings' entry of that token (omx_qwen3_set_logprobs).  Every argument is fixed: the target is the step state's word, the entry is
+// derived on the device from its count.
+static int add_step_logprobs(omx_qwen3 m, hipStream_t s) {
+    if (m->lp_top < 0) return 0;
+    LogprobTopOut o = {};
+    o.logprobs = m->lp_ring; o.top_ids = m->top_id_ring; o.top_lp = m->top_lp_ring;
+    o.ring_count = &m->st->out_count; o.ring_cap = m->ring_cap;
+    return launch_logprob_top(o, m->lp_scratch, m->logits, m->V, &m->st->cur_token, 1, m->V, m->lp_top, s);
+}
+
 // temperature sampling: replace the greedy per-block partials by those of logits / T + Gumbel noise, the noise
 // of vocabulary row v being word v of a V-word draw from the step's key (random.hip).  The greedy partials the
 // lm_head epilogue wrote are simply overwritten; sample_finalize_kernel / the TP max all-reduce are unchanged.
@@ -322,7 +333,7 @@ static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* re
 // The end of a step on the hidden row `h` (plus the pending f32 partial(s) the dense step has not folded into it yet) -- the residual
 // stream of a decode step, or the last row of a batched prompt (model.rs:423, 480-489, 733-735):
 // [final RMSNorm + lm_head GEMV + argmax partials] [sampler noise / filter] [finalize], then on one rank the sampled token joins the
-// penalties' history; tp: a rank holds a vocabulary shard -- its rows are numbered from its offset and the ranks' packed (logit, index)
+// penalties' history and, where asked for, its log-probability is taken from the row; tp: a rank holds a vocabulary shard -- its rows are numbered from its offset and the ranks' packed (logit, index)
 // keys meet in one unsigned max.  with_head = false (a prompt token whose logits nobody reads): advance to the next prompt token.
 // Every launch is a recording site: the AQL replay refuses a step with a launch that is none.
 int enqueue_step_tail(omx_qwen3 m, bool with_head, const bf16_t* h, const float* pending, int pending_n, bool tp) {
@@ -355,7 +366,7 @@ int enqueue_step_tail(omx_qwen3 m, bool with_head, const bf16_t* h, const float*
     OMX_LAUNCH(sample_finalize_kernel, 1, 256, 0, s, m->st, m->argmax_partials, m->n_argmax_partials, m->out_ring,
                m->ring_cap, tp ? m->argmax_key : nullptr);
     OMX_LAUNCH_CHECK();
-    if (!tp) return mark_sampled_token(m, s);
+    if (!tp) return mark_sampled_token(m, s) || add_step_logprobs(m, s);
     if (rank_allreduce(m, m->argmax_key, 1, kNcclUint64, kNcclMax)) return 1;
     OMX_LAUNCH(apply_token_kernel, 1, 1, 0, s, m->st, m->argmax_key, m->out_ring, m->ring_cap);
     OMX_LAUNCH_CHECK();
@@ -476,7 +487,7 @@ static int enqueue_step_quant(omx_qwen3 m, bool with_head) {
 int step_engine_mode(omx_qwen3 m) {
     const int mode = env_int("OMX_STEP_ENGINE", 0);    // (read per call: tests flip it between engines of one process)
     const omx_qwen3_config& c = m->cfg;
-    const bool ok = mode > 0 && !m->se_disabled && !m->filter_on && c.quant_bits == 0 && !m->f16 && c.num_experts == 0 && c.tp_size == 1 && c.ep_size <= 1 && m->allreduce == nullptr &&
+    const bool ok = mode > 0 && !m->se_disabled && !m->filter_on && m->lp_top < 0 && c.quant_bits == 0 && !m->f16 && c.num_experts == 0 && c.tp_size == 1 && c.ep_size <= 1 && m->allreduce == nullptr &&
            !c.attention_bias && m->se_gran != nullptr && m->cus > 0 &&
            step_engine_ok(c.hidden_size, m->H, m->Hkv, c.head_dim, m->I, m->attn_nsplit, m->cus);
     return ok ? (mode == 2 ? 2 : 1) : 0;
@@ -725,13 +736,13 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
 
 // The with-head step as AQL packets on the engine's own queue (aql_step.hpp): OMX_STEP_AQL=1 (agent-scope fences on every packet, the
 // semantics of the stream) or =2 (no fences between the packets of a replay -- the step's kernels hand every cross-kernel value over
-// with write-through stores and coherent loads).  Greedy single-rank dense / packed steps only: the sampler's and the MoE block's
-// launches are not recording sites.  Any failure leaves the engine on its hipGraph (and says why once on stderr with OMX_STEP_AQL_VERBOSE).
+// with write-through stores and coherent loads).  Greedy single-rank dense / packed steps only: the sampler's, the log-probability
+// launches and the MoE block's are not recording sites.  Any failure leaves the engine on its hipGraph (and says why once on stderr with OMX_STEP_AQL_VERBOSE).
 int step_aql_mode(omx_qwen3 m) {
     const int mode = env_int("OMX_STEP_AQL", 0);
     const omx_qwen3_config& c = m->cfg;
     if (mode <= 0 || m->aql_disabled || m->eager || m->allreduce != nullptr || c.tp_size > 1 || c.ep_size > 1 || c.num_experts > 0 ||
-        m->temperature != 0.f || m->filter_on || step_engine_mode(m) != 0)
+        m->temperature != 0.f || m->filter_on || m->lp_top >= 0 || step_engine_mode(m) != 0)
         return 0;
     return mode;
 }

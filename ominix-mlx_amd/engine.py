@@ -105,6 +105,10 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_prefill": (c_int, [c_void_p, ctypes.POINTER(c_uint32), c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_decode": (c_int, [c_void_p, c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_last_logits": (c_int, [c_void_p, c_void_p, c_int]),
+    # per-token log-probabilities of the tokens being generated, inside the step (csrc/logprob.hip's top-n form)
+    "omx_qwen3_set_logprobs": (c_int, [c_void_p, c_int]),
+    "omx_qwen3_decode_logprobs": (c_int, [c_void_p, c_int, ctypes.POINTER(c_uint32), ctypes.POINTER(c_float), c_void_p, c_void_p]),
+    "omx_qwen3_last_logprobs": (c_int, [c_void_p, ctypes.POINTER(c_float), c_void_p, c_void_p]),
     "omx_qwen3_last_decode_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "omx_qwen3_last_prefill_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "omx_qwen3_dequant_bytes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_size_t)]),
@@ -141,6 +145,10 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_batch_last_decode_ms": (c_int, [c_void_p, ctypes.POINTER(c_float)]),
     "omx_qwen3_batch_fork": (c_int, [c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_batch_shared": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "omx_qwen3_batch_set_logprobs": (c_int, [c_void_p, c_int]),
+    "omx_qwen3_batch_decode_logprobs": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_uint32), ctypes.POINTER(c_float),
+                                                c_void_p, c_void_p]),
+    "omx_qwen3_batch_last_logprobs": (c_int, [c_void_p, c_int, ctypes.POINTER(c_float), c_void_p, c_void_p]),
     # ... with its K/V storage chosen (kv_bits 8: MLX affine rows, quantised on append, read packed), and what reads the slabs back
     "omx_qwen3_batch_create_kv": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int, c_int]),
     "omx_qwen3_batch_kv_bytes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_size_t)]),
@@ -323,6 +331,8 @@ def expected_shape(c: Qwen3Config, name: str, formats=None):
 class Model:
     """qwen3_mlx::Model (dense Qwen3) resident on one MI355X (or one TP shard of it)."""
 
+    logprobs_top = None   # set_logprobs: alternatives reported per generated token (None = off)
+
     def __init__(self, *, hidden_size, num_hidden_layers, intermediate_size, num_attention_heads,
                  num_key_value_heads, head_dim, vocab_size, rms_norm_eps=1e-6, rope_theta=1e6,
                  tie_word_embeddings=False, rope_scaling=None, max_context=4096, tp_rank=0, tp_size=1, quantization=None,
@@ -494,10 +504,32 @@ class Model:
         check(lib.omx_qwen3_prefill(self._h, p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, ctypes.byref(first)))
         return first.value
 
-    def decode(self, n: int) -> np.ndarray:
+    def set_logprobs(self, top_n=None) -> None:
+        """Per-token log-probabilities inside the step (omx_qwen3_set_logprobs): None = off (default), 0 = the drawn token's only,
+        1..20 = with that many alternatives.  They are the log-softmax of the RAW logits row (what last_logits() returns): before
+        temperature, top-k / top-p and penalties, as score() reports them."""
+        check(lib.omx_qwen3_set_logprobs(self._h, -1 if top_n is None else int(top_n)))
+        self.logprobs_top = None if top_n is None or int(top_n) < 0 else int(top_n)
+
+    def decode(self, n: int, return_logprobs: bool = False):
+        """n further tokens, uint32 [n].  return_logprobs (after set_logprobs): (tokens, logprobs float32 [n]) and, with alternatives
+        on, (tokens, logprobs, top_ids uint32 [n, top_n], top_logprobs float32 [n, top_n])."""
         out = np.empty(n, dtype=np.uint32)
-        check(lib.omx_qwen3_decode(self._h, n, out.ctypes.data_as(ctypes.POINTER(c_uint32))))
-        return out
+        if not return_logprobs:
+            check(lib.omx_qwen3_decode(self._h, n, out.ctypes.data_as(ctypes.POINTER(c_uint32))))
+            return out
+        top = self.logprobs_top or 0
+        lp, ids, tlp = np.zeros(n, np.float32), np.zeros((n, top), np.uint32), np.zeros((n, top), np.float32)
+        check(lib.omx_qwen3_decode_logprobs(self._h, n, out.ctypes.data_as(ctypes.POINTER(c_uint32)), lp.ctypes.data_as(ctypes.POINTER(c_float)),
+                                            ids.ctypes.data if top else None, tlp.ctypes.data if top else None))
+        return (out, lp, ids, tlp) if top else (out, lp)
+
+    def last_logprobs(self):
+        """Of the most recently sampled token (after a prefill: its first token): logprob, or (logprob, top_ids, top_logprobs)."""
+        top = self.logprobs_top or 0
+        lp, ids, tlp = c_float(), np.zeros(top, np.uint32), np.zeros(top, np.float32)
+        check(lib.omx_qwen3_last_logprobs(self._h, ctypes.byref(lp), ids.ctypes.data if top else None, tlp.ctypes.data if top else None))
+        return (np.float32(lp.value), ids, tlp) if top else np.float32(lp.value)
 
     def verify(self, tokens) -> np.ndarray:
         """speculative.rs:132-161 `verify_draft_tokens`: all tokens in one batched pass on top of the cache; greedy token per position."""
@@ -640,6 +672,8 @@ class Batch:
     advances any subset of them with one weight stream per Linear.  The model's own prefill / decode / verify keep working beside it;
     calls on a model and its batches must not overlap (they share the model's stream and prompt scratch)."""
 
+    logprobs_top = None   # set_logprobs: alternatives reported per generated token (None = off)
+
     def __init__(self, model: Model, n_slots: int, max_context: int = 0, kv_bits: int = 0):
         self.model, self.n_slots, self.kv_bits = model, int(n_slots), int(kv_bits)
         self._h = c_void_p()
@@ -696,13 +730,37 @@ class Batch:
         check(lib.omx_qwen3_batch_shared(self._h, int(slot), ctypes.byref(owner), ctypes.byref(n)))
         return owner.value, n.value
 
-    def decode(self, n: int, slots=None) -> np.ndarray:
-        """n tokens for each of `slots` (default: all; distinct, prefilled) -> [n, len(slots)], columns in the listed order."""
+    def set_logprobs(self, top_n=None) -> None:
+        """Model.set_logprobs for the batch, one setting for all slots (omx_qwen3_batch_set_logprobs)."""
+        check(lib.omx_qwen3_batch_set_logprobs(self._h, -1 if top_n is None else int(top_n)))
+        self.logprobs_top = None if top_n is None or int(top_n) < 0 else int(top_n)
+
+    def decode(self, n: int, slots=None, return_logprobs: bool = False):
+        """n tokens for each of `slots` (default: all; distinct, prefilled) -> [n, len(slots)], columns in the listed order.
+        return_logprobs (after set_logprobs): (tokens, logprobs [n, len(slots)]) and, with alternatives on, (tokens, logprobs,
+        top_ids [n, len(slots), top_n], top_logprobs [n, len(slots), top_n])."""
         ids = np.ascontiguousarray(list(range(self.n_slots)) if slots is None else slots, dtype=np.int32).ravel()
         out = np.empty((int(n), ids.size), dtype=np.uint32)
-        check(lib.omx_qwen3_batch_decode(self._h, ids.ctypes.data_as(ctypes.POINTER(c_int)), ids.size, int(n),
-                                         out.ctypes.data_as(ctypes.POINTER(c_uint32))))
-        return out
+        if not return_logprobs:
+            check(lib.omx_qwen3_batch_decode(self._h, ids.ctypes.data_as(ctypes.POINTER(c_int)), ids.size, int(n),
+                                             out.ctypes.data_as(ctypes.POINTER(c_uint32))))
+            return out
+        top = self.logprobs_top or 0
+        lp = np.zeros((int(n), ids.size), np.float32)
+        tid, tlp = np.zeros((int(n), ids.size, top), np.uint32), np.zeros((int(n), ids.size, top), np.float32)
+        check(lib.omx_qwen3_batch_decode_logprobs(self._h, ids.ctypes.data_as(ctypes.POINTER(c_int)), ids.size, int(n),
+                                                  out.ctypes.data_as(ctypes.POINTER(c_uint32)), lp.ctypes.data_as(ctypes.POINTER(c_float)),
+                                                  tid.ctypes.data if top else None, tlp.ctypes.data if top else None))
+        return (out, lp, tid, tlp) if top else (out, lp)
+
+    def last_logprobs(self, slot: int):
+        """Of the slot's most recently sampled token (a prefill's or fork's first token, or its last step's): logprob, or
+        (logprob, top_ids, top_logprobs)."""
+        top = self.logprobs_top or 0
+        lp, ids, tlp = c_float(), np.zeros(top, np.uint32), np.zeros(top, np.float32)
+        check(lib.omx_qwen3_batch_last_logprobs(self._h, int(slot), ctypes.byref(lp), ids.ctypes.data if top else None,
+                                                tlp.ctypes.data if top else None))
+        return (np.float32(lp.value), ids, tlp) if top else np.float32(lp.value)
 
     def logits(self, slot: int) -> np.ndarray:
         """float32-widened bf16 logits of the last prefill or step the slot took part in."""
@@ -771,22 +829,44 @@ class Batch:
 class Generate:
     """qwen3_mlx::Generate (model.rs:743-844): iterator yielding sampled tokens; the first `next`
     prefills the prompt.  temp == 0 is the greedy path of sample() (model.rs:733-735); temp != 0 draws
-    categorical(logits / temp) (model.rs:736-739) from the key sequence seeded with `seed`."""
+    categorical(logits / temp) (model.rs:736-739) from the key sequence seeded with `seed`.
+    logprobs = k (0..20): the same tokens, and `.logprobs` (a float per token yielded so far) / `.top_logprobs` (per token, its k
+    alternatives as (id, logprob) pairs, best first) of the model's raw logits (Model.set_logprobs); None leaves the model's setting off."""
 
     def __init__(self, model: Model, temp: float, prompt_token, chunk: int = 16, seed: int = 0, *, top_k: int = 0, top_p: float = 1.0,
-                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0):
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, logprobs=None):
         model.set_sampler(temp, seed, top_k=top_k, top_p=top_p, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty)
+        if logprobs is not None or model.logprobs_top is not None:
+            model.set_logprobs(logprobs)
         self.model, self.prompt, self.chunk = model, np.asarray(prompt_token, dtype=np.uint32).ravel(), chunk
         self._prefilled = False
         self._buf = []
+        self._with_logprobs = logprobs is not None
+        self.logprobs, self.top_logprobs = [], []
 
     def __iter__(self) -> Iterator[int]:
         return self
 
+    def _record(self, lp, ids=(), tlp=()) -> None:
+        self.logprobs.append(float(lp))
+        self.top_logprobs.append([(int(i), float(v)) for i, v in zip(ids, tlp)])
+
     def __next__(self) -> int:
         if not self._prefilled:
             self._prefilled = True
-            return self.model.prefill(self.prompt)
+            first = self.model.prefill(self.prompt)
+            if self._with_logprobs:
+                last = self.model.last_logprobs()
+                self._record(*(last if isinstance(last, tuple) else (last,)))
+            return first
         if not self._buf:
-            self._buf = list(self.model.decode(self.chunk))
-        return int(self._buf.pop(0))
+            if self._with_logprobs:
+                toks, lp, *top = self.model.decode(self.chunk, return_logprobs=True)
+                ids, tlp = top if top else ([()] * len(toks), [()] * len(toks))
+                self._buf = list(zip(toks, lp, ids, tlp))
+            else:
+                self._buf = [(t,) for t in self.model.decode(self.chunk)]
+        tok, *rest = self._buf.pop(0)
+        if rest:
+            self._record(*rest)
+        return int(tok)

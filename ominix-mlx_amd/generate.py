@@ -91,10 +91,13 @@ def apply_chat_template_and_encode(tokenizer, model_template: str, conversations
 def generate_text(model, tokenizer, prompt: str, temperature: float = 0.7, max_tokens: int = 100, seed: int = 0,
                   emit: Optional[Callable[[str], None]] = None, flush_every: int = 10,
                   stop_token_ids: Optional[Iterable[int]] = None, prompt_ids: Optional[Sequence[int]] = None, *, top_k: int = 0,
-                  top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0) -> dict:
+                  top_p: float = 1.0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                  logprobs: Optional[int] = None) -> dict:
     """generate_qwen3.rs:31-101.  Returns {"text", "tokens", "prompt_tokens", "seconds", "tokens_per_sec"}; `emit` receives
     each decoded chunk as the example prints it.  `stop_token_ids` (not in the example, which always runs max_tokens)
-    ends the stream after such a token.  top_k / top_p / repetition_penalty / presence_penalty: Model.set_sampler's filters (off by default)."""
+    ends the stream after such a token.  top_k / top_p / repetition_penalty / presence_penalty: Model.set_sampler's filters (off by default).
+    logprobs = k (0..20): the dict also has "logprobs" (a float per token) and "top_logprobs" (per token, its k alternatives as
+    (id, logprob) pairs, best first), from the model's raw logits (Model.set_logprobs)."""
     from .engine import Generate
     ids = list(prompt_ids) if prompt_ids is not None else list(tokenizer.encode(prompt, add_special_tokens=True).ids)
     if not ids:
@@ -113,8 +116,10 @@ def generate_text(model, tokenizer, prompt: str, temperature: float = 0.7, max_t
                 emit(text)
             pending.clear()
 
-    for i, token in enumerate(Generate(model, temperature, ids, chunk=flush_every, seed=seed, top_k=top_k, top_p=top_p,
-                                       repetition_penalty=repetition_penalty, presence_penalty=presence_penalty)):
+    more = {} if logprobs is None else {"logprobs": int(logprobs)}
+    gen = Generate(model, temperature, ids, chunk=flush_every, seed=seed, top_k=top_k, top_p=top_p,
+                   repetition_penalty=repetition_penalty, presence_penalty=presence_penalty, **more)
+    for i, token in enumerate(gen):
         token = int(token)
         pending.append(token)
         all_tokens.append(token)
@@ -124,12 +129,15 @@ def generate_text(model, tokenizer, prompt: str, temperature: float = 0.7, max_t
             break
     flush()
     seconds = time.perf_counter() - start
-    return {"text": "".join(pieces), "tokens": all_tokens, "prompt_tokens": len(ids), "seconds": seconds,
-            "tokens_per_sec": len(all_tokens) / seconds if seconds > 0 else 0.0}
+    out = {"text": "".join(pieces), "tokens": all_tokens, "prompt_tokens": len(ids), "seconds": seconds,
+           "tokens_per_sec": len(all_tokens) / seconds if seconds > 0 else 0.0}
+    if logprobs is not None:
+        out["logprobs"], out["top_logprobs"] = list(gen.logprobs), list(gen.top_logprobs)
+    return out
 
 
 def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int, eos_ids: Iterable[int] = (), chunk: int = 16,
-                   n: int = 1, before_sibling=None) -> List[List[int]]:
+                   n: int = 1, before_sibling=None, return_logprobs: bool = False, best_of: Optional[int] = None):
     """Any number of token-id prompts over the slots of an `engine.Batch`: free slots are prefilled with waiting prompts, the active
     slots decode together `chunk` tokens at a time, a sequence retires at its first token in `eos_ids` (which it keeps) or at
     max_new_tokens -- what its slot decoded past that point inside the chunk is dropped -- and its slot is reset and handed to the next
@@ -144,13 +152,24 @@ def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int,
     the place to give the slot its sampler (`Batch.set_sampler(slot, temperature, seed + k)`).
     Samplers are the caller's: whatever `Batch.set_sampler` was given per slot -- its top_k / top_p / repetition_penalty /
     presence_penalty filters included -- applies to the prefill's first token, to a fork's and to every decoded one; a slot's penalty
-    history starts empty at its prefill or fork and is cleared by the reset that frees the slot."""
+    history starts empty at its prefill or fork and is cleared by the reset that frees the slot.
+    return_logprobs: returns (outputs, logprobs), logprobs[i][t] being the log-probability of outputs[i][t] under the model's raw
+    logits (`Batch.set_logprobs`, switched on with no alternatives if the batch has it off), truncated with the tokens.
+    best_of = m (n <= m <= batch.n_slots): m siblings are forked per prompt and the n with the highest mean token log-probability are
+    returned, best first, ties going to the lower sibling index."""
     if max_new_tokens < 1 or chunk < 1:
         raise ValueError("generate_batch: max_new_tokens and chunk must be positive")
     if n < 1 or n > batch.n_slots:
         raise ValueError(f"generate_batch: n = {n} completions per prompt need 1..{batch.n_slots} slots")
+    if best_of is not None and not n <= best_of <= batch.n_slots:
+        raise ValueError(f"generate_batch: best_of = {best_of} must be in n = {n}..{batch.n_slots} (the batch's slots)")
+    keep, n = n, (n if best_of is None else int(best_of))   # from here on n = the siblings decoded per prompt
+    with_lp = return_logprobs or best_of is not None
+    if with_lp and batch.logprobs_top is None:
+        batch.set_logprobs(0)
     eos = set(int(t) for t in eos_ids)
     outputs: List[List[int]] = [[] for _ in range(len(prompts) * n)]
+    logprobs: List[List[float]] = [[] for _ in range(len(prompts) * n)]
     waiting = list(range(len(prompts)))
     free = list(range(batch.n_slots))
     active = {}                                   # slot -> output index
@@ -185,6 +204,9 @@ def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int,
                     before_sibling(p, k, slot)
                 first = batch.prefill(slot, prompts[p]) if k == 0 else batch.fork(slots[0], slot, True)
                 outputs[p * n + k].append(int(first))
+                if with_lp:
+                    last = batch.last_logprobs(slot)
+                    logprobs[p * n + k].append(float(last[0] if isinstance(last, tuple) else last))
                 active[slot] = p * n + k
             for k, slot in reversed(list(enumerate(slots))):   # (the owner last: it is released with its last sibling)
                 if finished(p * n + k):           # EOS as the first token, or max_new_tokens == 1
@@ -193,16 +215,25 @@ def generate_batch(batch, prompts: Sequence[Sequence[int]], max_new_tokens: int,
             continue
         slots = sorted(active)
         steps = min(chunk, min(max_new_tokens - len(outputs[active[s]]) for s in slots))
-        tokens = batch.decode(steps, slots)
+        tokens, lps = batch.decode(steps, slots, return_logprobs=True)[:2] if with_lp else (batch.decode(steps, slots), None)
         for col, slot in enumerate(slots):
             i = active[slot]
             for step in range(steps):
                 outputs[i].append(int(tokens[step][col]))
+                if with_lp:
+                    logprobs[i].append(float(lps[step][col]))
                 if finished(i):
                     break
             if finished(i):
                 retire(slot, i)
-    return outputs
+    if best_of is not None:
+        order = []
+        for p in range(len(prompts)):
+            mean = lambda i: sum(logprobs[i]) / len(logprobs[i])
+            ranked = sorted(range(p * n, p * n + n), key=lambda i: (-mean(i), i))   # best first, ties to the lower sibling index
+            order.extend(ranked[:keep])
+        outputs, logprobs = [outputs[i] for i in order], [logprobs[i] for i in order]
+    return (outputs, logprobs) if return_logprobs else outputs
 
 
 def perplexity(model, ids: Sequence[int], ctx: int = 2048, stride: Optional[int] = None) -> dict:

@@ -294,6 +294,34 @@ def logprob_rows(logits: Tensor, targets: Tensor, V: Optional[int] = None, panel
     return lp, lse, greedy
 
 
+def logprob_rows_top(logits: Tensor, targets: Tensor, top_n: int, V: Optional[int] = None, panels: Optional[Sequence[int]] = None):
+    """logprob_rows with the row's top_n alternatives (omx_logprob_rows_top): returns (logprobs, lse, greedy, top_ids u32 [rows, top_n],
+    top_logprobs f32 [rows, top_n]); the first three carry logprob_rows' bits, entry j of a row is its j-th column by (logit
+    descending, column ascending).  panels: the two-phase form, as in logprob_rows; the same bits either way."""
+    rows, ld = logits.size // logits.shape[-1], logits.shape[-1]
+    V = ld if V is None else int(V)
+    top_n = int(top_n)
+    lp, lse, greedy = Tensor((rows,), FLOAT32), Tensor((rows,), FLOAT32), Tensor((rows,), UINT32)
+    ids, tlp = Tensor((rows, max(top_n, 1)), UINT32), Tensor((rows, max(top_n, 1)), FLOAT32)
+    if panels is None:
+        check(lib.omx_logprob_rows_top(lp.ptr, greedy.ptr, lse.ptr, ids.ptr, tlp.ptr, logits.ptr, ld, targets.ptr, rows, V, top_n,
+                                       logits.dtype, None))
+        return lp, lse, greedy, ids, tlp
+    if sum(int(p) for p in panels) != V:
+        raise OmxError(f"logprob_rows_top: panels {list(panels)} do not add up to V = {V}")
+    nch = (V + 1023) // 1024
+    part, arg, tgt = Tensor((rows, nch, 2), FLOAT32), Tensor((rows, nch), UINT32), Tensor((rows,), FLOAT32)
+    cand = Tensor((rows, nch, max(top_n, 1)), UINT32)
+    c0 = 0
+    for p in panels:
+        check(lib.omx_logprob_top_partial(part.ptr, arg.ptr, tgt.ptr, cand.ptr, logits.ptr + 2 * c0, ld, c0, int(p), targets.ptr, rows, V,
+                                          top_n, logits.dtype, None))
+        c0 += int(p)
+    check(lib.omx_logprob_top_merge(lp.ptr, greedy.ptr, lse.ptr, ids.ptr, tlp.ptr, part.ptr, arg.ptr, tgt.ptr, cand.ptr, targets.ptr, rows, V,
+                                    top_n, None))
+    return lp, lse, greedy, ids, tlp
+
+
 def cast(x: Tensor, dtype) -> Tensor:
     """mlx_rs as_dtype between bf16 / f16 / f32 (one rounding)."""
     out = Tensor(x.shape, dtype)

@@ -7,7 +7,8 @@
         One JSON line per row, then the table.  --batch-sizes 1 8 keeps those rows only (and drops the single-sequence and ragged rows).
         --temperature T [--top-k K] [--top-p P] [--presence-penalty Q]: every slot samples with these settings (Batch.set_sampler,
         seed = its slot) instead of greedily -- the cost of the per-slot filters is the difference between two such runs.  They
-        apply to --trace too.
+        apply to --trace too.  --logprobs K (0..20): per-token log-probabilities on (Model.set_logprobs / Batch.set_logprobs) in the
+        single-sequence row, every batch row and --trace -- the cost of the two extra launches is the difference to a run without it.
     rocprofv3 --kernel-trace --stats -f csv -d DIR -- python tools/batch_decode.py --trace --bits 0 [--ctx 2048] [--steps 16]
         8 slots prefilled, --steps steps at B = 8 and nothing else at that row count: the trace's last steps give the per-launch times
         of a B = 8 step (python tools/batch_decode.py --stats DIR [--steps 32] prints them; pass rocprofv3 -f csv).
@@ -45,6 +46,7 @@ ap.add_argument("--temperature", type=float, default=0.0, help="every slot's sam
 ap.add_argument("--top-k", type=int, default=0)
 ap.add_argument("--top-p", type=float, default=1.0)
 ap.add_argument("--presence-penalty", type=float, default=0.0)
+ap.add_argument("--logprobs", type=int, default=None, help="log-probabilities of the generated tokens with K alternatives (off by default)")
 args = ap.parse_args()
 ctx_list, args.ctx = args.ctx, args.ctx[0]
 
@@ -187,7 +189,10 @@ for bits in args.bits:
     m.synth_weights()
     fmt = f"{bits}-bit g64" if bits else "bf16"
     b = m.batch(8)
-    sampler = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, presence_penalty=args.presence_penalty)
+    if args.logprobs is not None:
+        m.set_logprobs(args.logprobs)
+        b.set_logprobs(args.logprobs)
+    sampler = dict(temperature=args.temperature, top_k=args.top_k, top_p=args.top_p, presence_penalty=args.presence_penalty, logprobs=args.logprobs)
     filters = {k: v for k, v, off in (("top_k", args.top_k, 0), ("top_p", args.top_p, 1.0), ("presence_penalty", args.presence_penalty, 0.0)) if v != off}
     if args.temperature != 0.0 or filters:
         for s in range(8):
