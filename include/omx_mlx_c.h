@@ -23,6 +23,15 @@
  *   - there is no CPU backend: mlx_default_cpu_stream_new reports an error;
  *   - mlx_matmul is implemented for bfloat16 and float32 operands (N-D broadcast, MLX dtype promotion; float32 on the exact-f32
  *     matrix cores), mlx_quantized_matmul for bfloat16 / float16 / float32 activations; other dtypes report an error.
+ * Array-op rules (stated in numpy in tests/mlx_ops_rule.py, held by tests/test_gpu_mlx_ops_sweep.py):
+ *   - binary ops promote as MLX does (mlx-rs/src/dtype.rs TypePromotion: int32 x uint32 -> int64, uint64 x signed -> float32, ...);
+ *     integer add / subtract / multiply and integer abs / square / sign / negative are exact in 64-bit integers and wrap in the result
+ *     dtype; mlx_divide of two non-float arrays is float32; float arithmetic is one float32 operation rounded once;
+ *   - gather indices (mlx_take, mlx_take_axis, mlx_take_along_axis) may be any integer dtype; negative ones count from the end and
+ *     what is still outside the axis is clamped into it, on every route;
+ *   - whole-array and long-line mlx_sum / mlx_mean add in a fixed block order (the same bits from run to run);
+ *   - mlx_var / mlx_std run in float32 whatever the input's dtype and round once into the result dtype;
+ *   - an exclusive mlx_cummax / mlx_cummin starts from the lowest / highest value of the array's own dtype.
  */
 #ifndef OMX_MLX_C_H
 #define OMX_MLX_C_H

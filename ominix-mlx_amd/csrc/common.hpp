@@ -137,6 +137,9 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
 // ---- host-side error plumbing (capi.cpp) ------------------------------------
 namespace omx {
 int set_error(const char* fmt, ...);   // formats into TLS slot, calls handler, returns 1
+// omx_take_rows with the table's row count: ids wrap (signed_ids) and are clamped into [0, n_rows) when n_rows > 0 (elementwise.hip)
+int take_rows_checked(void* out, const void* table, const uint32_t* ids, int64_t n_ids, int dim, omx_dtype dtype, int64_t n_rows,
+                      bool signed_ids, omx_stream stream);
 }
 #define OMX_HIP_CHECK(expr)                                                                   \
     do {                                                                                      \

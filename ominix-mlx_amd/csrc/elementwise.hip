@@ -93,9 +93,15 @@ static int launch_binary(void* out, const void* a, const void* b, int64_t n, hip
 // embedding gather: out[r,:] = table[ids[r],:]
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void take_rows_kernel(uint8_t* __restrict__ out, const uint8_t* __restrict__ table,
-                                                        const uint32_t* __restrict__ ids, int64_t row_bytes, bool vec) {
+                                                        const uint32_t* __restrict__ ids, int64_t row_bytes, bool vec, int64_t n_rows,
+                                                        bool signed_ids) {
     const int64_t r = blockIdx.x;
-    const uint8_t* src = table + (int64_t)ids[r] * row_bytes;
+    int64_t id = signed_ids ? (int64_t)(int32_t)ids[r] : (int64_t)ids[r];
+    if (n_rows > 0) {   // caller-supplied indices: negatives wrap, the rest is clamped into the table (as take_axis_kernel does)
+        if (id < 0) id += n_rows;
+        id = id < 0 ? 0 : (id >= n_rows ? n_rows - 1 : id);
+    }
+    const uint8_t* src = table + id * row_bytes;
     uint8_t* dst = out + r * row_bytes;
     if (vec) {
         for (int64_t i = threadIdx.x * 16; i < row_bytes; i += 256 * 16)
@@ -191,7 +197,17 @@ int omx_add(void* out, const void* a, const void* b, int64_t n, omx_dtype dtype,
 
 int omx_take_rows(void* out, const void* table, const uint32_t* ids, int64_t n_ids, int dim, omx_dtype dtype,
                   omx_stream stream) {
+    return omx::take_rows_checked(out, table, ids, n_ids, dim, dtype, 0, false, stream);
+}
+
+}  // extern "C"
+
+// the launcher behind omx_take_rows.  n_rows > 0: the table's row count, for ids that come from a caller (mlx_take_axis) -- negative
+// ids (signed_ids: the words are int32) wrap and out-of-range ones are clamped; n_rows == 0: the engine's own ids, read as they are
+int omx::take_rows_checked(void* out, const void* table, const uint32_t* ids, int64_t n_ids, int dim, omx_dtype dtype, int64_t n_rows,
+                           bool signed_ids, omx_stream stream) {
     OMX_REQUIRE(out && table && ids, "omx_take_rows: null tensor");
+    OMX_REQUIRE(n_rows >= 0, "omx_take_rows: negative row count");
     if (n_ids == 0 || dim == 0) return 0;
     size_t es = (dtype == OMX_FLOAT32 || dtype == OMX_UINT32 || dtype == OMX_INT32) ? 4
                 : (dtype == OMX_BFLOAT16 || dtype == OMX_FLOAT16)                   ? 2
@@ -200,10 +216,12 @@ int omx_take_rows(void* out, const void* table, const uint32_t* ids, int64_t n_i
     const int64_t row_bytes = (int64_t)dim * es;
     const bool vec = (row_bytes % 16 == 0) && omx::aligned16(out) && omx::aligned16(table);
     omx::take_rows_kernel<<<(unsigned)n_ids, 256, 0, (hipStream_t)stream>>>((uint8_t*)out, (const uint8_t*)table, ids,
-                                                                             row_bytes, vec);
+                                                                             row_bytes, vec, n_rows, signed_ids);
     OMX_LAUNCH_CHECK();
     return 0;
 }
+
+extern "C" {
 
 int omx_argmax(uint32_t* out, const void* logits, int64_t rows, int n, omx_dtype dtype, omx_stream stream) {
     OMX_REQUIRE(out && logits, "omx_argmax: null tensor");

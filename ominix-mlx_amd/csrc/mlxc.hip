@@ -13,6 +13,7 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/omx_mlx_c.h"
@@ -267,7 +268,9 @@ namespace {
 
 enum { OP_ADD, OP_SUB, OP_MUL, OP_DIV, OP_SIGMOID, OP_EXP, OP_NEG, OP_CAST };
 
-__global__ void binary_kernel(char* out, int odt, const char* a, int adt, const char* b, int bdt, Idx ix, size_t n, int op) {
+// integer operands (int_math) are combined in 64-bit integers and wrap in the result dtype, like binary2_kernel (mlxc_glue.hpp): a float32
+// round trip loses every value beyond 2^24.  Division never takes that route: MLX divides integers as float32.
+__global__ void binary_kernel(char* out, int odt, const char* a, int adt, const char* b, int bdt, Idx ix, size_t n, int op, bool int_math) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         size_t r = i;
         long long oa = 0, ob = 0;
@@ -276,6 +279,11 @@ __global__ void binary_kernel(char* out, int odt, const char* a, int adt, const 
             r /= ix.shape[d];
             oa += c * ix.sa[d];
             ob += c * ix.sb[d];
+        }
+        if (int_math) {
+            const unsigned long long x = (unsigned long long)ld_i(a, adt, oa), y = (unsigned long long)ld_i(b, bdt, ob);   // unsigned: wraps
+            st_i(out, odt, i, (long long)(op == OP_ADD ? x + y : op == OP_SUB ? x - y : x * y));
+            continue;
         }
         const float x = ld_f(a, adt, oa), y = ld_f(b, bdt, ob);
         float v;
@@ -301,6 +309,10 @@ __global__ void unary_kernel(char* out, int odt, const char* a, int adt, Idx ix,
             st_i(out, odt, i, ld_i(a, adt, oa));
             continue;
         }
+        if (op == OP_NEG && is_int_dt(adt) && is_int_dt(odt)) {    // integer negation: exact, wrapping in the dtype
+            st_i(out, odt, i, (long long)(0ull - (unsigned long long)ld_i(a, adt, oa)));
+            continue;
+        }
         const float x = ld_f(a, adt, oa);
         float v;
         switch (op) {
@@ -312,6 +324,14 @@ __global__ void unary_kernel(char* out, int odt, const char* a, int adt, Idx ix,
         st_f(out, odt, i, v);
     }
 }
+// exp(x - mx) without the rounding of the difference: d = fl(x - mx) is off by up to u |d|, which exp turns into that much RELATIVE error
+// (16 u for a probability of 1e-7); the two-sum below recovers the lost part e exactly and exp(d + e) = exp(d) (1 + e) to first order
+__device__ __forceinline__ float exp_shifted(float x, float mx) {
+    const float d = x - mx, ex = expf(d);
+    if (!(fabsf(d) < INFINITY)) return ex;          // (-inf entries, inf - inf: nothing to give back)
+    const float bb = d - x, e = (x - (d - bb)) - (mx + bb);
+    return fmaf(ex, e, ex);
+}
 // softmax over the last axis of a contiguous [rows, n]; one wave per row, fp32 inside (precise)
 __global__ __launch_bounds__(256) void softmax_kernel(char* out, const char* in, int dt, size_t rows, int n) {
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -321,9 +341,9 @@ __global__ __launch_bounds__(256) void softmax_kernel(char* out, const char* in,
     for (int i = lane; i < n; i += 64) mx = fmaxf(mx, ld_f(in, dt, row * n + i));
     mx = omx::wave_max(mx);
     float s = 0.f;
-    for (int i = lane; i < n; i += 64) s += expf(ld_f(in, dt, row * n + i) - mx);
+    for (int i = lane; i < n; i += 64) s += exp_shifted(ld_f(in, dt, row * n + i), mx);
     s = omx::wave_sum(s);
-    for (int i = lane; i < n; i += 64) st_f(out, dt, row * n + i, expf(ld_f(in, dt, row * n + i) - mx) / s);
+    for (int i = lane; i < n; i += 64) st_f(out, dt, row * n + i, exp_shifted(ld_f(in, dt, row * n + i), mx) / s);
 }
 
 unsigned grid_for(size_t n) { size_t b = (n + 255) / 256; return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b)); }
@@ -451,12 +471,24 @@ bool vec_ok(const Arr& t, size_t n) {       // a whole contiguous array of 16-by
            (t.dt == MLX_BFLOAT16 || t.dt == MLX_FLOAT16 || t.dt == MLX_FLOAT32);
 }
 
+// MLX's type promotion (mlx-rs/src/dtype.rs, TypePromotion): bool yields to anything; among floats f32 wins and f16 x bf16 is f32; a float
+// beats any integer; integers of one signedness take the wider; signed x unsigned takes the signed type that holds both (the signed one
+// if it is wider, else twice the unsigned width), and uint64 x signed is float32
 mlx_dtype promote(mlx_dtype a, mlx_dtype b) {
     if (a == b) return a;
+    if (a == MLX_BOOL) return b;
+    if (b == MLX_BOOL) return a;
+    if (a == MLX_COMPLEX64 || b == MLX_COMPLEX64) return MLX_COMPLEX64;
+    if (a == MLX_FLOAT64 || b == MLX_FLOAT64) return MLX_FLOAT64;
     if (is_float(a) && !is_float(b)) return a;
     if (is_float(b) && !is_float(a)) return b;
     if (is_float(a) && is_float(b)) return MLX_FLOAT32;   // bf16 x f16, half x f32
-    return dsize(a) >= dsize(b) ? a : b;
+    auto is_signed = [](mlx_dtype d) { return d == MLX_INT8 || d == MLX_INT16 || d == MLX_INT32 || d == MLX_INT64; };
+    if (is_signed(a) == is_signed(b)) return dsize(a) >= dsize(b) ? a : b;
+    const mlx_dtype sg = is_signed(a) ? a : b, us = is_signed(a) ? b : a;
+    if (dsize(us) == 8) return MLX_FLOAT32;
+    if (dsize(sg) > dsize(us)) return sg;
+    return dsize(us) == 1 ? MLX_INT16 : dsize(us) == 2 ? MLX_INT32 : MLX_INT64;
 }
 
 int binary(mlx_array* res, const mlx_array ha, const mlx_array hb, int op, const char* name) {
@@ -475,7 +507,8 @@ int binary(mlx_array* res, const mlx_array ha, const mlx_array hb, int op, const
         ix.sa[i] = (ia >= 0 && da != 1) ? (long long)a.strides[ia] : 0;
         ix.sb[i] = (ib >= 0 && db != 1) ? (long long)b.strides[ib] : 0;
     }
-    const mlx_dtype odt = promote(a.dt, b.dt);
+    mlx_dtype odt = promote(a.dt, b.dt);
+    if (op == OP_DIV && !is_float(odt)) odt = MLX_FLOAT32;   // MLX: the quotient of two integer (or bool) arrays is float32
     NEW_OR_FAIL(r, shape, odt);
     const size_t n_ = r->size();
     Rec rec;
@@ -493,7 +526,8 @@ int binary(mlx_array* res, const mlx_array ha, const mlx_array hb, int op, const
             if (q.a[0].dt == MLX_FLOAT16) return launch_binary_vec<OMX_FLOAT16>(q.a[0].ptr(), q.a[1].ptr(), q.a[2].ptr(), nv, q.i0);
             return launch_binary_vec<OMX_FLOAT32>(q.a[0].ptr(), q.a[1].ptr(), q.a[2].ptr(), nv, q.i0);
         } else if (n) {
-            binary_kernel<<<grid_for(n), 256, 0, g_stream>>>(q.a[0].ptr(), q.a[0].dt, q.a[1].ptr(), q.a[1].dt, q.a[2].ptr(), q.a[2].dt, ix, n, q.i0);
+            binary_kernel<<<grid_for(n), 256, 0, g_stream>>>(q.a[0].ptr(), q.a[0].dt, q.a[1].ptr(), q.a[1].dt, q.a[2].ptr(), q.a[2].dt, ix, n, q.i0,
+                                                               q.i0 != OP_DIV && is_int_dt(q.a[0].dt) && is_int_dt(q.a[1].dt) && is_int_dt(q.a[2].dt));
             OMX_LAUNCH_CHECK();
         }
         return 0;
@@ -1197,8 +1231,8 @@ int mlx_add(mlx_array* res, const mlx_array a, const mlx_array b, const mlx_stre
 int mlx_subtract(mlx_array* res, const mlx_array a, const mlx_array b, const mlx_stream) { return binary(res, a, b, OP_SUB, "mlx_subtract"); }
 int mlx_multiply(mlx_array* res, const mlx_array a, const mlx_array b, const mlx_stream) { return binary(res, a, b, OP_MUL, "mlx_multiply"); }
 int mlx_divide(mlx_array* res, const mlx_array a, const mlx_array b, const mlx_stream) { return binary(res, a, b, OP_DIV, "mlx_divide"); }
-int mlx_sigmoid(mlx_array* res, const mlx_array a, const mlx_stream) { return unary(res, a, OP_SIGMOID, a.ctx ? A(a)->dt : MLX_FLOAT32, "mlx_sigmoid"); }
-int mlx_exp(mlx_array* res, const mlx_array a, const mlx_stream) { return unary(res, a, OP_EXP, a.ctx ? A(a)->dt : MLX_FLOAT32, "mlx_exp"); }
+int mlx_sigmoid(mlx_array* res, const mlx_array a, const mlx_stream) { return unary(res, a, OP_SIGMOID, a.ctx && is_float(A(a)->dt) ? A(a)->dt : MLX_FLOAT32, "mlx_sigmoid"); }
+int mlx_exp(mlx_array* res, const mlx_array a, const mlx_stream) { return unary(res, a, OP_EXP, a.ctx && is_float(A(a)->dt) ? A(a)->dt : MLX_FLOAT32, "mlx_exp"); }
 int mlx_negative(mlx_array* res, const mlx_array a, const mlx_stream) { return unary(res, a, OP_NEG, a.ctx ? A(a)->dt : MLX_FLOAT32, "mlx_negative"); }
 int mlx_astype(mlx_array* res, const mlx_array a, mlx_dtype dtype, const mlx_stream) { return unary(res, a, OP_CAST, dtype, "mlx_astype"); }
 
@@ -1373,8 +1407,10 @@ int mlx_take_axis(mlx_array* res, const mlx_array a, const mlx_array indices, in
     REQ_ARR(a, "mlx_take_axis"); REQ_ARR(indices, "mlx_take_axis");
     int ax;
     if (norm_axis(axis, (int)A(a)->shape.size(), "mlx_take_axis", &ax)) return 1;
-    OMX_REQUIRE(A(indices)->dt == MLX_UINT32 || A(indices)->dt == MLX_INT32, "mlx_take_axis: indices must be (u)int32");
-    if (!(ax == 0 && A(a)->shape.size() == 2 && is_float(A(a)->dt))) return take_axis_general(res, *A(a), *A(indices), ax);
+    // any integer index dtype, as in MLX (uint32 // int32 promotes to int64: mixtral's token_order); the row gather below reads 32-bit words
+    OMX_REQUIRE(is_int_dt(A(indices)->dt) && A(indices)->dt != MLX_BOOL, "mlx_take_axis: indices must be integers");
+    const bool idx32 = A(indices)->dt == MLX_UINT32 || A(indices)->dt == MLX_INT32;
+    if (!(idx32 && ax == 0 && A(a)->shape.size() == 2 && is_float(A(a)->dt))) return take_axis_general(res, *A(a), *A(indices), ax);
     // row gather from a 2-D floating table (Embedding): 16-byte vector rows
     std::vector<int> shape = A(indices)->shape;
     shape.push_back(A(a)->shape[1]);
@@ -1384,7 +1420,10 @@ int mlx_take_axis(mlx_array* res, const mlx_array a, const mlx_array indices, in
     rec.run = [](Rec& q) -> int {
         Contig ct, ci;
         if (ct.init(q.a[1]) || ci.init(q.a[2])) return 1;
-        return omx_take_rows(q.a[0].ptr(), ct.a->ptr(), (const uint32_t*)ci.a->ptr(), (int64_t)ci.a->size(), ct.a->shape[1], to_omx(ct.a->dt), g_stream);
+        if (!ct.a->shape[0]) return q.a[0].size() ? set_error("mlx_take_axis: cannot take from an empty axis") : 0;
+        // the indices are the caller's: bounded by the table's row count, int32 ones wrap
+        return omx::take_rows_checked(q.a[0].ptr(), ct.a->ptr(), (const uint32_t*)ci.a->ptr(), (int64_t)ci.a->size(), ct.a->shape[1], to_omx(ct.a->dt),
+                                      ct.a->shape[0], ci.a->dt == MLX_INT32, g_stream);
     };
     if (record(std::move(rec))) { delete r; return 1; }
     return assign(res, r);

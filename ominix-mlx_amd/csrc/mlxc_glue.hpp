@@ -160,6 +160,15 @@ __global__ void unary2_kernel(char* out, int odt, const char* a, int adt, Idx ix
             r /= ix.shape[d];
             oa += c * ix.sa[d];
         }
+        const bool int_op = op == U2_ABS || op == U2_SQUARE || op == U2_SIGN || op == U2_FLOOR || op == U2_CEIL || op == U2_ROUND;
+        if (int_op && is_int_dt(adt) && is_int_dt(odt)) {               // abs / square / sign of an integer (floor / ceil / round: the identity)
+            const long long x = ld_i(a, adt, oa);                       // in 64-bit integers: exact beyond 2^24, wrapping in the dtype
+            const bool neg = x < 0 && adt != MLX_UINT64;
+            st_i(out, odt, i, op == U2_ABS ? (neg ? (long long)(0ull - (unsigned long long)x) : x)
+                            : op == U2_SQUARE ? (long long)((unsigned long long)x * (unsigned long long)x)
+                            : op == U2_SIGN ? (neg ? -1 : x != 0) : x);
+            continue;
+        }
         const float x = ld_f(a, adt, oa);
         st_f(out, odt, i, unary2_apply(op, x));
     }
@@ -224,6 +233,51 @@ __global__ void reduce_axis_kernel(char* out, int odt, const char* in, int idt, 
                 acc = mode == 2 ? acc + v : mode == 0 ? fmaxf(acc, v) : fminf(acc, v);
             }
             st_f(out, odt, i, mode == 2 ? acc / (float)n : (nan ? NAN : acc));
+        }
+    }
+}
+// ---- sum / mean of a few long contiguous lines [rows, n]: a block reduction in two passes instead of one thread's loop over the line.
+// The order is fixed by the shape alone (deterministic run to run): pass 1 gives block (row, c) the elements [c * 4096, (c + 1) * 4096),
+// every thread adds its 16 (stride 256, ascending) and the 256 sums meet in a shared-memory tree; pass 2, one block per row, does the
+// same over the row's partials.  T is float (float32 inside, like the loop it replaces) or long long (integer sums: exact).
+constexpr int kLongChunk = 4096;
+template <typename T>
+__device__ __forceinline__ T block_tree_sum(T v, T* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const T tot = sh[0];
+    __syncthreads();   // (sh is reused by the caller's next trip)
+    return tot;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void long_sum_partial_kernel(T* part, const char* in, int idt, size_t rows, int n, int chunks) {
+    __shared__ T sh[256];
+    for (size_t blk = blockIdx.x; blk < rows * (size_t)chunks; blk += gridDim.x) {
+        const size_t row = blk / chunks;
+        const int lo = (int)(blk % chunks) * kLongChunk, hi = n - lo < kLongChunk ? n : lo + kLongChunk;
+        T acc = 0;
+        for (int k = lo + (int)threadIdx.x; k < hi; k += 256) {
+            if (std::is_same<T, float>::value) acc += (T)ld_f(in, idt, row * n + k);
+            else acc += (T)ld_i(in, idt, row * n + k);
+        }
+        const T tot = block_tree_sum(acc, sh);
+        if (threadIdx.x == 0) part[blk] = tot;
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void long_sum_final_kernel(char* out, int odt, const T* part, size_t rows, int n, int chunks, bool mean) {
+    __shared__ T sh[256];
+    for (size_t row = blockIdx.x; row < rows; row += gridDim.x) {
+        T acc = 0;
+        for (int c = (int)threadIdx.x; c < chunks; c += 256) acc += part[row * chunks + c];
+        const T tot = block_tree_sum(acc, sh);
+        if (threadIdx.x == 0) {
+            if (std::is_same<T, float>::value) st_f(out, odt, row, mean ? (float)tot / (float)n : (float)tot);
+            else st_i(out, odt, row, (long long)tot);
         }
     }
 }
@@ -374,7 +428,7 @@ int binary2(mlx_array* res, const mlx_array ha, const mlx_array hb, int op, cons
 int unary2(mlx_array* res, const mlx_array ha, int op, const char* name) {
     REQ_ARR(ha, name);
     const Arr& a = *A(ha);
-    // abs / square / sign / floor / ceil / round keep an integer input's dtype in MLX; the float32 round trip is exact below 2^24
+    // abs / square / sign / floor / ceil / round keep an integer input's dtype in MLX (unary2_kernel handles those in 64-bit integers)
     const bool keeps = op == U2_ABS || op == U2_SQUARE || op == U2_SIGN || op == U2_FLOOR || op == U2_CEIL || op == U2_ROUND;
     const mlx_dtype odt = op >= U2_FIRST_PRED ? MLX_BOOL : (is_float(a.dt) || keeps) ? a.dt : MLX_FLOAT32;
     NEW_OR_FAIL(r, a.shape, odt);
@@ -433,6 +487,22 @@ Arr* view_with_shape(const Arr& s, const std::vector<int>& shape, const std::vec
     r->shape = shape;
     r->strides = strides;
     return r;
+}
+// a sum / mean takes the block reduction when its lines are contiguous, long and few (every whole-array form is one such line)
+bool long_lines(size_t outer, int n, size_t inner) { return inner == 1 && n >= kLongChunk && outer >= 1 && outer <= 256; }
+template <typename T>
+int long_sum(Arr* r, const Arr& in, size_t rows, int n, bool mean) {
+    const int chunks = (n + kLongChunk - 1) / kLongChunk;
+    const size_t blocks = rows * (size_t)chunks;
+    // 8 bytes per partial: room for either T.  Freed right after the launches below: that relies on everything in this layer running on
+    // the single in-order g_stream, so whoever the pool hands the block to next is queued behind them
+    NEW_OR_FAIL(part, std::vector<int>{(int)blocks}, MLX_INT64);
+    long_sum_partial_kernel<T><<<(unsigned)std::min<size_t>(blocks, 8192), 256, 0, g_stream>>>((T*)part->ptr(), in.ptr(), in.dt, rows, n, chunks);
+    long_sum_final_kernel<T><<<(unsigned)rows, 256, 0, g_stream>>>(r->ptr(), r->dt, (const T*)part->ptr(), rows, n, chunks, mean);
+    const hipError_t e = hipGetLastError();
+    delete part;
+    OMX_REQUIRE(e == hipSuccess, "long_sum: launch failed: %s", hipGetErrorString(e));
+    return 0;
 }
 
 }  // namespace
@@ -950,7 +1020,9 @@ int mlx_sum_axis(mlx_array* res, const mlx_array a, int axis, bool keepdims, con
     if (keepdims) shape[ax] = 1; else shape.erase(shape.begin() + ax);
     const mlx_dtype odt = s.dt == MLX_BOOL ? MLX_INT32 : s.dt;   // sums of booleans count
     NEW_OR_FAIL(r, shape, odt);
-    if (r->size()) {
+    if (r->size() && long_lines(outer, n, inner)) {
+        if (is_int_dt(s.dt) ? long_sum<long long>(r, *c.a, outer, n, false) : long_sum<float>(r, *c.a, outer, n, false)) { delete r; return 1; }
+    } else if (r->size()) {
         sum_axis_kernel<<<grid_for(r->size()), 256, 0, g_stream>>>(r->ptr(), odt, c.a->ptr(), s.dt, outer, n, inner);
         OMX_LAUNCH_CHECK();
     }
@@ -970,7 +1042,9 @@ static int reduce_axis(mlx_array* res, const mlx_array a, int axis, bool keepdim
     if (keepdims) shape[ax] = 1; else shape.erase(shape.begin() + ax);
     const mlx_dtype odt = (mode == 3 || mode == 4) ? MLX_BOOL : ((mode == 2 || mode == 5) && !is_float(s.dt)) ? MLX_FLOAT32 : s.dt;    // the mean of integers is float32 in MLX
     NEW_OR_FAIL(r, shape, odt);
-    if (r->size()) {
+    if (r->size() && mode == 2 && long_lines(outer, n, inner)) {
+        if (long_sum<float>(r, *c.a, outer, n, true)) { delete r; return 1; }
+    } else if (r->size()) {
         reduce_axis_kernel<<<grid_for(r->size()), 256, 0, g_stream>>>(r->ptr(), odt, c.a->ptr(), s.dt, outer, n, inner, mode);
         OMX_LAUNCH_CHECK();
     }

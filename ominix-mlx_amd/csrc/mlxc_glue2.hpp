@@ -29,18 +29,36 @@ __global__ void prod_axis_kernel(char* out, int odt, const char* in, int idt, si
         }
     }
 }
+// the lowest / highest value of an integer dtype, as ld_i would return it (uint64's highest is all ones)
+__device__ inline long long int_extreme(int dt, bool lowest) {
+    switch (dt) {
+        case MLX_BOOL: return lowest ? 0 : 1;
+        case MLX_UINT8: return lowest ? 0 : 0xFF;
+        case MLX_UINT16: return lowest ? 0 : 0xFFFF;
+        case MLX_UINT32: return lowest ? 0 : 0xFFFFFFFFll;
+        case MLX_UINT64: return lowest ? 0 : -1ll;
+        case MLX_INT8: return lowest ? -128 : 127;
+        case MLX_INT16: return lowest ? -32768 : 32767;
+        case MLX_INT32: return lowest ? -2147483648ll : 2147483647ll;
+        default: return lowest ? LLONG_MIN : LLONG_MAX;
+    }
+}
 // running sum / product / max / min along the middle axis (mode 0..3), optionally from the end, optionally exclusive
 __global__ void scan_axis_kernel(char* out, const char* in, int dt, size_t outer, int n, size_t inner, int mode, bool reverse, bool inclusive) {
     const size_t total = outer * inner;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
         const size_t o = i / inner, j = i % inner;
         if (is_int_dt(dt)) {
-            long long acc = mode == 0 ? 0 : mode == 1 ? 1 : mode == 2 ? LLONG_MIN : LLONG_MAX;
+            // an exclusive running max / min starts from the dtype's own lowest / highest value (st_i keeps the low bits only)
+            const bool u64 = dt == MLX_UINT64;   // (held in a long long: ordered as unsigned)
+            long long acc = mode == 0 ? 0 : mode == 1 ? 1 : int_extreme(dt, mode == 2);
             for (int t = 0; t < n; ++t) {
                 const int k = reverse ? n - 1 - t : t;
                 const size_t at = (o * n + k) * inner + j;
                 const long long v = ld_i(in, dt, at);
-                const long long nxt = mode == 0 ? acc + v : mode == 1 ? acc * v : mode == 2 ? (v > acc ? v : acc) : (v < acc ? v : acc);
+                const bool above = u64 ? (unsigned long long)v > (unsigned long long)acc : v > acc;
+                const bool below = u64 ? (unsigned long long)v < (unsigned long long)acc : v < acc;
+                const long long nxt = mode == 0 ? acc + v : mode == 1 ? acc * v : mode == 2 ? (above ? v : acc) : (below ? v : acc);
                 st_i(out, dt, at, inclusive ? nxt : acc);
                 acc = nxt;
             }
@@ -174,20 +192,24 @@ int mlx_prod(mlx_array* res, const mlx_array a, bool keepdims, const mlx_stream 
     return mlx_prod_axes(res, a, ax.data(), ax.size(), keepdims, s);
 }
 
-// var = sum((a - mean)^2) / (n - ddof) over the axes, in the input's float dtype (integers: float32)
-int mlx_var_axes(mlx_array* res, const mlx_array a, const int* axes, size_t axes_num, bool keepdims, int ddof, const mlx_stream s) {
-    REQ_ARR(a, "mlx_var_axes");
+// var = sum((a - mean)^2) / (n - ddof) over the axes.  The whole chain runs in float32 whatever the input's dtype (a bfloat16 mean or
+// difference would lose 16 bits at every step); var_f32 leaves the float32 value, the callers round it ONCE into the result dtype -- the
+// input's float dtype, float32 for integers -- std after the square root
+static int var_f32(mlx_array* res, const mlx_array a, const int* axes, size_t axes_num, bool keepdims, int ddof, const mlx_stream s) {
     Tmp af, mu, dev, sq, ssum, denom;
-    const mlx_dtype fdt = is_float(A(a)->dt) ? A(a)->dt : MLX_FLOAT32;
-    if (mlx_astype(&af, a, fdt, s)) return 1;
+    if (mlx_astype(&af, a, MLX_FLOAT32, s)) return 1;
     if (mlx_mean_axes(&mu, af, axes, axes_num, true, s) || mlx_subtract(&dev, af, mu, s) || mlx_multiply(&sq, dev, dev, s)) return 1;
     if (mlx_sum_axes(&ssum, sq, axes, axes_num, keepdims, s)) return 1;
     const size_t n_in = A(a)->size(), n_out = A(ssum.a)->size();
     const double n = n_out ? (double)n_in / (double)n_out : 0.0;
-    Tmp d32;
-    d32.a = f32_scalar((float)std::max(n - (double)ddof, 0.0));
-    if (mlx_astype(&denom, d32, fdt, s)) return 1;
+    denom.a = f32_scalar((float)std::max(n - (double)ddof, 0.0));
     return mlx_divide(res, ssum, denom, s);
+}
+int mlx_var_axes(mlx_array* res, const mlx_array a, const int* axes, size_t axes_num, bool keepdims, int ddof, const mlx_stream s) {
+    REQ_ARR(a, "mlx_var_axes");
+    Tmp v;
+    if (var_f32(&v, a, axes, axes_num, keepdims, ddof, s)) return 1;
+    return mlx_astype(res, v, is_float(A(a)->dt) ? A(a)->dt : MLX_FLOAT32, s);
 }
 int mlx_var_axis(mlx_array* res, const mlx_array a, int axis, bool keepdims, int ddof, const mlx_stream s) { return mlx_var_axes(res, a, &axis, 1, keepdims, ddof, s); }
 int mlx_var(mlx_array* res, const mlx_array a, bool keepdims, int ddof, const mlx_stream s) {
@@ -196,9 +218,10 @@ int mlx_var(mlx_array* res, const mlx_array a, bool keepdims, int ddof, const ml
     return mlx_var_axes(res, a, ax.data(), ax.size(), keepdims, ddof, s);
 }
 int mlx_std_axes(mlx_array* res, const mlx_array a, const int* axes, size_t axes_num, bool keepdims, int ddof, const mlx_stream s) {
-    Tmp v;
-    if (mlx_var_axes(&v, a, axes, axes_num, keepdims, ddof, s)) return 1;
-    return mlx_sqrt(res, v, s);
+    REQ_ARR(a, "mlx_std_axes");
+    Tmp v, r;
+    if (var_f32(&v, a, axes, axes_num, keepdims, ddof, s) || mlx_sqrt(&r, v, s)) return 1;
+    return mlx_astype(res, r, is_float(A(a)->dt) ? A(a)->dt : MLX_FLOAT32, s);
 }
 int mlx_std_axis(mlx_array* res, const mlx_array a, int axis, bool keepdims, int ddof, const mlx_stream s) { return mlx_std_axes(res, a, &axis, 1, keepdims, ddof, s); }
 int mlx_std(mlx_array* res, const mlx_array a, bool keepdims, int ddof, const mlx_stream s) {

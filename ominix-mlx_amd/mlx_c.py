@@ -414,7 +414,8 @@ def _check(status: int) -> None:
         raise OmxError(msg or "unknown mlx_* error")
 
 
-_NP = {FLOAT32: np.float32, UINT32: np.uint32, INT32: np.int32, BOOL: np.bool_, UINT8: np.uint8, FLOAT16: np.float16}
+_NP = {FLOAT32: np.float32, UINT32: np.uint32, INT32: np.int32, BOOL: np.bool_, UINT8: np.uint8, FLOAT16: np.float16,
+       INT8: np.int8, INT16: np.int16, UINT16: np.uint16, INT64: np.int64, UINT64: np.uint64}
 _STREAM = None
 
 
