@@ -324,6 +324,21 @@ int omx_qwen3_reset(omx_qwen3 m);                                  /* KVCache::r
 int omx_qwen3_offset(omx_qwen3 m, int* offset);                    /* KeyValueCache::offset           */
 /* Generate: prefill the prompt, return the first sampled token (model.rs:808-827)                   */
 int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_t* first_token);
+/* A prompt pass whose rows the caller can supply -- the reference's forward_embeddings(inputs_embeds, cache), the door every multimodal
+ * crate goes through (qwen3-asr-mlx/src/model.rs:720-769, 782: audio rows over the <|audio_pad|> positions).
+ *   embed_tokens:   get_token_embeddings (:726, :814) -- the model's own embedding rows of n ids, [n, hidden] in the activation dtype
+ *                   (bf16; float16 for a float16 model), written to DEVICE memory out_rows; the bits the prompt pass itself gathers.
+ *   prefill_embeds: omx_qwen3_prefill with rows [first_row, first_row + n_rows) of the pass overwritten, after the embedding gather and
+ *                   in one launch, by `rows` (DEVICE, [n_rows, hidden] of rows_dtype OMX_FLOAT32 / OMX_BFLOAT16 / OMX_FLOAT16, converted
+ *                   to the activation dtype round-to-nearest-even as as_dtype does, :759).  Everything else is omx_qwen3_prefill: the
+ *                   ids at the overridden positions are still required and range-checked (pass the pad token), the cache may be
+ *                   non-empty, the span may include the last row.  n_rows = 0 IS omx_qwen3_prefill (rows may be NULL).
+ * Refused by name with n_rows > 0: a span outside the prompt, NULL rows, another dtype; tensor-parallel, expert-parallel and sparse-MoE
+ * engines; and "InvalidConfig" where omx_qwen3_prefill would go token-serial, through the decode step, which reads the embedding table
+ * itself -- OMX_PREFILL_SERIAL=1, OMX_PREFILL_TAIL_STEP=1, n_prompt < 2, a float16 model with n_prompt <= 16.  n_rows < 0 is refused. */
+int omx_qwen3_embed_tokens(omx_qwen3 m, const uint32_t* ids, int n, void* out_rows);
+int omx_qwen3_prefill_embeds(omx_qwen3 m, const uint32_t* prompt, int n_prompt, const void* rows, omx_dtype rows_dtype, int first_row,
+                             int n_rows, uint32_t* first_token);
 /* Generate: n further greedy tokens (model.rs:828-841); tokens_out is a HOST buffer of n entries    */
 int omx_qwen3_decode(omx_qwen3 m, int n, uint32_t* tokens_out);
 /* copy the logits of the last executed step ([vocab_local] bf16) to a host buffer                  */
@@ -873,6 +888,35 @@ int omx_resample_sinc(const float* in, int64_t n_in, uint32_t src_rate, uint32_t
 int omx_whisper_mel_create(omx_mel_frontend* out, int sample_rate, int n_mels, int n_fft, int hop_length);
 int omx_whisper_mel_frames(omx_mel_frontend f, int64_t n_samples, int* n_frames);
 int omx_whisper_mel_forward(omx_mel_frontend f, const float* audio, int64_t n_samples, float* out, omx_stream stream);
+
+/* The Qwen3-ASR audio tower (qwen3-asr-mlx/src/encoder.rs:254-458, `AudioEncoder::forward_encoder`) in float32 -- the reference feeds a
+ * float32 mel into bf16 parameters that are never quantised, and MLX promotes every op to float32; the caller hands the weights
+ * widened to float32.  mel (what omx_whisper_mel_forward writes) -> chunks of 2 * n_window frames -> three 3x3 stride-2 convolutions +
+ * GELU -> conv_out + sinusoid of the position within the chunk -> pre-norm transformer layers with attention inside windows of
+ * 13 * (n_window_infer / (2 * n_window)) rows (the reference's [N, N] additive mask, never materialised) -> ln_post, proj1 + GELU, proj2.
+ *   create:  shape preconditions are named "InvalidConfig" errors: d_model % 64, head width d_model / heads = 64, n_window_infer a
+ *            multiple of the chunk, a chunk's rows <= max_source_positions, a window that fits the attention kernel (<= 118 rows).
+ *   load:    one tensor by its key behind "audio_tower." ("conv2d1.weight" [ds, 3, 3, 1], "layers.3.self_attn.q_proj.bias", ...),
+ *            float32 on the HOST; a missing key or a size the config does not imply is an error at forward.
+ *   tokens:  rows N a mel of n_frames makes (get_feat_extract_output_lengths, :76-80, with floor division).
+ *   forward: mel DEVICE f32 [n_mels, n_frames] -> out_rows DEVICE f32 [N, output_dim] on `stream`.  The handle owns its scratch and
+ *            grows it per role; a handle reused for another n_frames gives a fresh handle's bits.  A NaN / infinite mel is refused.
+ *   omx_window_attention_f32: the tower's attention alone -- q | k | v DEVICE f32 rows `ld` floats apart (the thirds of one stacked
+ *            projection), head h at column 64 h, scale 1; out token-major, rows `ldo` apart; windows of `window` rows from row 0. */
+typedef struct omx_qwen3_asr_encoder_* omx_qwen3_asr_encoder;
+typedef struct omx_qwen3_asr_encoder_config_ {
+    int n_mels, n_layers, n_heads, ffn_dim, d_model, max_source_positions, n_window, output_dim, n_window_infer, downsample_hidden_size;
+} omx_qwen3_asr_encoder_config;
+int omx_qwen3_asr_encoder_create(omx_qwen3_asr_encoder* out, const omx_qwen3_asr_encoder_config* cfg);
+int omx_qwen3_asr_encoder_load(omx_qwen3_asr_encoder e, const char* name, const float* host, const int64_t* shape, int ndim);
+int omx_qwen3_asr_encoder_tokens(omx_qwen3_asr_encoder e, int n_frames, int* n);
+int omx_qwen3_asr_encoder_forward(omx_qwen3_asr_encoder e, const float* mel, int n_frames, float* out_rows, omx_stream stream);
+int omx_qwen3_asr_encoder_destroy(omx_qwen3_asr_encoder e);
+/* test hook: n_elems floats of a stage of the LAST forward to the host -- "x1" / "x2" / "x3" the stem's layers [chunks, f, t, ds] (NHWC),
+ * "h" the hidden rows [N, d_model] (the assembled rows when the tower has no layers) */
+int omx_qwen3_asr_encoder_debug_read(omx_qwen3_asr_encoder e, const char* name, float* host, size_t n_elems);
+int omx_window_attention_f32(float* out, int64_t ldo, const float* q, const float* k, const float* v, int64_t ld, int n, int heads, int window,
+                             omx_stream stream);
 
 /* =====================================================================================
  * a13: Paraformer body pieces (funasr-mlx/src/paraformer.rs).

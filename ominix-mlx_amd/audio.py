@@ -8,7 +8,7 @@ import sys
 
 import numpy as np
 
-from . import check, lib, require_device
+from . import OmxError, check, lib, require_device
 from .ops import Tensor
 
 c_int, c_void_p, c_int64 = ctypes.c_int, ctypes.c_void_p, ctypes.c_int64
@@ -17,6 +17,13 @@ c_int, c_void_p, c_int64 = ctypes.c_int, ctypes.c_void_p, ctypes.c_int64
 class MelConfig(ctypes.Structure):
     _fields_ = [("sample_rate", c_int), ("n_mels", c_int), ("n_fft", c_int), ("hop_length", c_int),
                 ("lfr_m", c_int), ("lfr_n", c_int)]
+
+
+class AudioEncoderConfig(ctypes.Structure):
+    """AudioEncoderConfig (qwen3-asr-mlx/src/encoder.rs:14-72), the fields the tower's arithmetic reads"""
+    _fields_ = [("n_mels", c_int), ("n_layers", c_int), ("n_heads", c_int), ("ffn_dim", c_int), ("d_model", c_int),
+                ("max_source_positions", c_int), ("n_window", c_int), ("output_dim", c_int), ("n_window_infer", c_int),
+                ("downsample_hidden_size", c_int)]
 
 
 AUDIO_SIGNATURES = {
@@ -34,6 +41,14 @@ AUDIO_SIGNATURES = {
     "omx_apply_lfr": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "omx_resample_len": (c_int64, [c_int64, ctypes.c_uint32, ctypes.c_uint32]),
     "omx_resample_sinc": (c_int, [c_void_p, c_int64, ctypes.c_uint32, ctypes.c_uint32, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    # the Qwen3-ASR audio tower in float32 (csrc/audio_encoder.hip)
+    "omx_qwen3_asr_encoder_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(AudioEncoderConfig)]),
+    "omx_qwen3_asr_encoder_load": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(c_int64), c_int]),
+    "omx_qwen3_asr_encoder_tokens": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int)]),
+    "omx_qwen3_asr_encoder_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "omx_qwen3_asr_encoder_destroy": (c_int, [c_void_p]),
+    "omx_qwen3_asr_encoder_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
+    "omx_window_attention_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
 }
 for _n, (_r, _a) in AUDIO_SIGNATURES.items():
     _f = getattr(lib, _n)
@@ -98,6 +113,66 @@ class WhisperMelFrontend:
         out = Tensor((self.n_mels, nf.value), "f32")
         check(lib.omx_whisper_mel_forward(self._h, a.ptr, a.size, out.ptr, None))
         return out
+
+
+class AudioEncoder:
+    """qwen3-asr-mlx/src/encoder.rs:254-458 (`AudioEncoder::{new, forward_encoder}`) in float32 on the device: mel [n_mels, n_frames]
+    -> audio rows [N, output_dim].  Keyword names are config.json's `audio_config` keys, defaults the reference's (:43-53)."""
+
+    def __init__(self, num_mel_bins=128, encoder_layers=24, encoder_attention_heads=16, encoder_ffn_dim=4096, d_model=1024,
+                 max_source_positions=1500, n_window=50, output_dim=2048, n_window_infer=800, downsample_hidden_size=480, **_ignored):
+        require_device()
+        self.cfg = AudioEncoderConfig(num_mel_bins, encoder_layers, encoder_attention_heads, encoder_ffn_dim, d_model, max_source_positions,
+                                      n_window, output_dim, n_window_infer, downsample_hidden_size)
+        self._h = c_void_p()
+        check(lib.omx_qwen3_asr_encoder_create(ctypes.byref(self._h), ctypes.byref(self.cfg)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib.omx_qwen3_asr_encoder_destroy(self._h)
+            self._h = c_void_p()
+
+    def __del__(self):
+        if sys is not None and not sys.is_finalizing():
+            self.close()
+
+    def load_weights(self, weights) -> None:
+        """{key behind "audio_tower.": array}; bf16 checkpoints arrive widened (loader.read_safetensors' Bf16Bits are widened here)."""
+        for name, arr in weights.items():
+            if type(arr).__name__ == "Bf16Bits":
+                arr = (np.asarray(arr).astype(np.uint32) << np.uint32(16)).view(np.float32)
+            a = np.ascontiguousarray(arr, dtype=np.float32)
+            shape = (c_int64 * a.ndim)(*a.shape)
+            check(lib.omx_qwen3_asr_encoder_load(self._h, name.encode(), a.ctypes.data, shape, a.ndim))
+
+    def tokens(self, n_frames: int) -> int:
+        n = c_int()
+        check(lib.omx_qwen3_asr_encoder_tokens(self._h, int(n_frames), ctypes.byref(n)))
+        return n.value
+
+    def debug_read(self, name: str, shape) -> np.ndarray:
+        """A stage of the last forward ("x1" / "x2" / "x3" [chunks, f, t, ds], "h" [N, d_model]) as float32 (test hook)."""
+        out = np.empty(shape, np.float32)
+        check(lib.omx_qwen3_asr_encoder_debug_read(self._h, name.encode(), out.ctypes.data, out.size))
+        return out
+
+    def forward(self, mel) -> Tensor:
+        m = mel if isinstance(mel, Tensor) else Tensor.from_numpy(np.asarray(mel, np.float32), "f32")
+        if len(m.shape) != 2 or m.shape[0] != self.cfg.n_mels:
+            raise OmxError(f"ShapeMismatch: mel has shape {m.shape}, the tower expects [{self.cfg.n_mels}, n_frames]")
+        out = Tensor((self.tokens(m.shape[1]), self.cfg.output_dim), "f32")
+        check(lib.omx_qwen3_asr_encoder_forward(self._h, m.ptr, m.shape[1], out.ptr, None))
+        return out
+
+
+def window_attention_f32(qkv: Tensor, heads: int, window: int, n: int = None) -> Tensor:
+    """The tower's attention alone (omx_window_attention_f32): qkv f32 [N, ld >= 3 * heads * 64] holding q | k | v side by side from
+    column 0; -> [N, heads * 64]."""
+    d = heads * 64
+    N, ld = (qkv.shape[0] if n is None else n), qkv.shape[1]
+    out = Tensor((N, d), "f32")
+    check(lib.omx_window_attention_f32(out.ptr, d, qkv.ptr, qkv.ptr + 4 * d, qkv.ptr + 8 * d, ld, N, heads, window, None))
+    return out
 
 
 class SenseVoiceMelFrontend:

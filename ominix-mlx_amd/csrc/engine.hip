@@ -349,8 +349,8 @@ int omx_qwen3_offset(omx_qwen3 m, int* offset) {
     return 0;
 }
 
-int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_t* first_token) {
-    OMX_REQUIRE(m && prompt && first_token, "omx_qwen3_prefill: null argument");
+// omx_qwen3_prefill, and omx_qwen3_prefill_embeds (span: the caller's rows, which only the batched pass can take)
+static int prefill_prompt(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_t* first_token, const RowSpan* span) {
     OMX_REQUIRE(n_prompt >= 1, "omx_qwen3_prefill: empty prompt");
     int off = 0;
     if (omx_qwen3_offset(m, &off)) return 1;
@@ -358,6 +358,17 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
     for (int i = 0; i < n_prompt; ++i) OMX_REQUIRE(prompt[i] < (uint32_t)m->cfg.vocab_size, "omx_qwen3_prefill: token id %u out of range (vocab %d)", prompt[i], m->cfg.vocab_size);
     OMX_REQUIRE(n_prompt <= m->prompt_cap, "omx_qwen3_prefill: prompt of %d tokens exceeds max_context %d", n_prompt, m->prompt_cap);
     const bool serial_on = env_on("OMX_PREFILL_SERIAL");
+    if (span) {
+        // the token-serial forms read the embedding table inside the decode step: there is no row buffer to put the caller's rows in
+        OMX_REQUIRE(!serial_on, "InvalidConfig: omx_qwen3_prefill_embeds: OMX_PREFILL_SERIAL=1 sends the prompt through the decode step, which "
+                    "cannot take embedding rows; unset it");
+        OMX_REQUIRE(!env_on("OMX_PREFILL_TAIL_STEP"), "InvalidConfig: omx_qwen3_prefill_embeds: OMX_PREFILL_TAIL_STEP=1 sends the last token through "
+                    "the decode step, which cannot take embedding rows; unset it");
+        OMX_REQUIRE(n_prompt >= 2, "InvalidConfig: omx_qwen3_prefill_embeds: a one-row prompt goes through the decode step, which cannot take "
+                    "embedding rows; pass at least 2 rows");
+        OMX_REQUIRE(!(m->f16 && n_prompt <= 16), "InvalidConfig: omx_qwen3_prefill_embeds: a float16 model sends prompts of 16 rows or fewer "
+                    "through the decode step, which cannot take embedding rows (%d rows); pass at least 17", n_prompt);
+    }
     // tensor-parallel engines run the batched matrix-core prefill on their shards with two all-reduces per layer, expert-parallel ones
     // with one all-reduce of the MoE block's [T, hidden] partial per layer (round 3; token-serial before)
     // (float16 models: the batched pass exists for plain prompts -- dense and sparse-MoE models, on one rank or sharded (round 6: the
@@ -390,7 +401,7 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
         //  TP prompt ended with a whole decode step, 2 ms of a 24 ms prompt at TP 2)
         const bool tail_step = env_on("OMX_PREFILL_TAIL_STEP");
         const int nb = tail_step ? n_prompt - 1 : n_prompt;
-        if (prefill_prefix_batched(m, nb, st.pos, nullptr, !tail_step)) return 1;
+        if (prefill_prefix_batched(m, nb, st.pos, nullptr, !tail_step, false, nullptr, nullptr, span)) return 1;
         st.pos += n_prompt - 1;
         st.prompt_idx = n_prompt - 1;
         st.cur_token = prompt[n_prompt - 1];
@@ -409,6 +420,49 @@ int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_
     OMX_HIP_CHECK(hipEventElapsedTime(&m->last_prefill_ms, m->ev0, m->ev1));
     m->lp_valid = m->lp_top >= 0;
     return step_health(m);
+}
+
+int omx_qwen3_prefill(omx_qwen3 m, const uint32_t* prompt, int n_prompt, uint32_t* first_token) {
+    OMX_REQUIRE(m && prompt && first_token, "omx_qwen3_prefill: null argument");
+    return prefill_prompt(m, prompt, n_prompt, first_token, nullptr);
+}
+
+/* omx_qwen3_prefill with rows [first_row, first_row + n_rows) of the pass supplied by the caller instead of gathered from the embedding
+ * table -- what the reference's multimodal crates do through forward_embeddings(inputs_embeds, cache) (qwen3-asr-mlx/src/model.rs:720-769, 782:
+ * the audio tower's rows over the <|audio_pad|> positions).  One more launch in the pass; the ids, the cache append, the sampler, the
+ * log-probabilities and the penalty history are omx_qwen3_prefill's.  n_rows = 0 IS omx_qwen3_prefill. */
+int omx_qwen3_prefill_embeds(omx_qwen3 m, const uint32_t* prompt, int n_prompt, const void* rows, omx_dtype rows_dtype, int first_row,
+                             int n_rows, uint32_t* first_token) {
+    OMX_REQUIRE(m && prompt && first_token, "omx_qwen3_prefill_embeds: null argument");
+    OMX_REQUIRE(n_rows >= 0, "omx_qwen3_prefill_embeds: n_rows %d is negative", n_rows);
+    if (n_rows == 0) return prefill_prompt(m, prompt, n_prompt, first_token, nullptr);
+    OMX_REQUIRE(rows != nullptr, "omx_qwen3_prefill_embeds: null rows with n_rows %d", n_rows);
+    OMX_REQUIRE(rows_dtype == OMX_FLOAT32 || rows_dtype == OMX_BFLOAT16 || rows_dtype == OMX_FLOAT16,
+                "omx_qwen3_prefill_embeds: rows of dtype %d (float32, bfloat16 or float16)", (int)rows_dtype);
+    OMX_REQUIRE(first_row >= 0 && first_row <= n_prompt && n_rows <= n_prompt - first_row,
+                "omx_qwen3_prefill_embeds: rows [%d, %d + %d) lie outside the prompt of %d tokens", first_row, first_row, n_rows, n_prompt);
+    OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
+                "omx_qwen3_prefill_embeds: tensor-parallel / expert-parallel engines are not supported (single-rank models only)");
+    OMX_REQUIRE(m->cfg.num_experts == 0, "omx_qwen3_prefill_embeds: sparse-MoE models are not supported (dense models only)");
+    const RowSpan span = {rows, rows_dtype, first_row, n_rows};
+    return prefill_prompt(m, prompt, n_prompt, first_token, &span);
+}
+
+/* The model's own embedding rows of n ids, [n, hidden] in the activation dtype (bf16, or float16 for a float16 model), written to DEVICE
+ * memory -- the reference's get_token_embeddings (qwen3-asr-mlx/src/model.rs:726, 814).  The launches are the prompt pass's own, so the
+ * rows are the bits that pass would put in its row buffer.  The cache and the sampler are not touched. */
+int omx_qwen3_embed_tokens(omx_qwen3 m, const uint32_t* ids, int n, void* out_rows) {
+    OMX_REQUIRE(m && ids && out_rows, "omx_qwen3_embed_tokens: null argument");
+    OMX_REQUIRE(n >= 1 && n <= m->prompt_cap, "omx_qwen3_embed_tokens: %d ids (1..%d, the prompt buffer)", n, m->prompt_cap);
+    for (int i = 0; i < n; ++i) OMX_REQUIRE(ids[i] < (uint32_t)m->cfg.vocab_size, "omx_qwen3_embed_tokens: token id %u out of range (vocab %d)", ids[i], m->cfg.vocab_size);
+    OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
+                "omx_qwen3_embed_tokens: tensor-parallel / expert-parallel engines are not supported (single-rank models only)");
+    if (resolve_weights(m)) return 1;
+    if (m->cfg.quant_bits && prefill_reserve(m, n, /*dequant=*/false)) return 1;   // (the gather's scratch lies in the row buffers)
+    OMX_HIP_CHECK(hipMemcpyAsync(m->prompt_dev, ids, (size_t)n * 4, hipMemcpyHostToDevice, m->stream));
+    if (embed_rows(m, (bf16_t*)out_rows, n, /*rows_form=*/false)) return 1;
+    OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
+    return 0;
 }
 
 /* Speculative decoding (mlx-rs-core/src/speculative.rs).  `verify` is verify_draft_tokens (:132-161): the target model runs ALL n

@@ -106,6 +106,14 @@ struct RaggedRows {
     size_t sb_stride;
 };
 
+// Rows the caller of a prompt pass supplies in place of the embedding gather's (omx_qwen3_prefill_embeds): n rows of `hidden` elements
+// in device memory, float32 / bf16 / float16, for rows [first, first + n) of the pass
+struct RowSpan {
+    const void* rows;
+    omx_dtype dtype;
+    int first, n;
+};
+
 }  // namespace omx
 
 using namespace omx;
@@ -304,7 +312,8 @@ int prefill_reserve(omx_qwen3 m, int T, bool dequant = true);
 void dq_cache_prepare(omx_qwen3 m);
 int packed_rows(const QGemvArgs& g, int T, bf16_t* const* mout, int bits, int pro, int epi, hipStream_t s);
 int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc = nullptr, bool full_last = false, bool packed_rows_pass = false,
-                           const KvSlabs* kv = nullptr, const RaggedRows* rag = nullptr);
+                           const KvSlabs* kv = nullptr, const RaggedRows* rag = nullptr, const RowSpan* span = nullptr);
+int embed_rows(omx_qwen3 m, bf16_t* out, int T, bool rows_form);
 void launch_encoder_mask(bf16_t* mask, const uint8_t* am, int T, hipStream_t s);
 
 // engine_score.hip

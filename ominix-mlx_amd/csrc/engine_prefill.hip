@@ -51,6 +51,15 @@ __global__ __launch_bounds__(256) void qembed_rows_kernel(bf16_t* __restrict__ o
     qembed_row<BITS>(out + (size_t)blockIdx.x * hidden, table, scales, biases, ids[blockIdx.x], hidden, group);
 }
 
+// the caller's rows of omx_qwen3_prefill_embeds over the gathered ones: n elements of src (DT) converted to the activation dtype
+// (F16: float16, else bf16) with ONE round-to-nearest-even, as mlx's as_dtype does (qwen3-asr-mlx/src/model.rs:759); rows already in
+// the activation dtype pass through their float32 value unchanged, bit for bit (NaN payloads aside)
+template <int DT, bool F16>
+__global__ void override_rows_kernel(bf16_t* __restrict__ dst, const typename Elem<DT>::T* __restrict__ src, int64_t n) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = Act16<F16>::bits(Elem<DT>::ld(src + i));
+}
+
 }  // namespace
 
 namespace omx {
@@ -164,6 +173,52 @@ int packed_rows(const QGemvArgs& g, int T, bf16_t* const* mout, int bits, int pr
     return 0;
 }
 
+// The embedding rows of the T ids in prompt_dev into out [T, hidden], in the activation dtype -- the first launches of the batched pass
+// and all of omx_qwen3_embed_tokens: a bf16 / float16 table gathered, a packed table straight through qembed_rows_kernel (rows_form:
+// the verify pass of a packed model) or gathered and dequantised (pf_xn / pf_h2 as scratch: T <= pf_cap), bit-identical to each other
+int embed_rows(omx_qwen3 m, bf16_t* out, int T, bool rows_form) {
+    const int hd = m->cfg.hidden_size;
+    const bool f16 = m->f16;
+    hipStream_t s = m->stream;
+    if (m->cfg.quant_bits != 0 && rows_form) {
+        const int bits = m->q_embed.bits;      // the embedding's own format
+#define OMX_QEMB_ROWS(B) \
+        case B: OMX_LAUNCH(qembed_rows_kernel<B>, T, 256, 0, s, out, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->prompt_dev, hd, m->q_embed.group); break;
+        switch (bits) { OMX_QEMB_ROWS(2) OMX_QEMB_ROWS(3) OMX_QEMB_ROWS(4) OMX_QEMB_ROWS(5) OMX_QEMB_ROWS(6) OMX_QEMB_ROWS(8) }
+#undef OMX_QEMB_ROWS
+        OMX_LAUNCH_CHECK();
+        return 0;
+    }
+    if (m->cfg.quant_bits != 0) {
+        // QuantizedEmbedding::forward: gather the packed rows, dequantise (quantized.rs:192-203)
+        const int wpr = hd * m->q_embed.bits / 32, gpr = hd / m->q_embed.group;
+        uint32_t* rows_w = (uint32_t*)m->pf_xn;                       // scratch: [T, wpr] u32 fits in [T, hd] bf16
+        bf16_t* rows_s = m->pf_h2;
+        bf16_t* rows_b = m->pf_h2 + (size_t)T * gpr;
+        if (omx_take_rows(rows_w, m->q_embed.w, m->prompt_dev, T, wpr, OMX_FLOAT32, s)) return 1;
+        if (omx_take_rows(rows_s, m->q_embed.scales, m->prompt_dev, T, gpr, OMX_BFLOAT16, s)) return 1;
+        if (omx_take_rows(rows_b, m->q_embed.biases, m->prompt_dev, T, gpr, OMX_BFLOAT16, s)) return 1;
+        return launch_dequantize_bf16(out, (const uint32_t*)rows_w, rows_s, rows_b, T, hd, m->q_embed.group, m->q_embed.bits, f16, s, f16);
+    }
+    return omx_take_rows(out, m->embed, m->prompt_dev, T, hd, OMX_BFLOAT16, s);
+}
+
+static int launch_override_rows(bf16_t* dst, const void* src, omx_dtype dt, int64_t n, bool f16, hipStream_t s) {
+    const int grid = (int)std::min<int64_t>((n + 255) / 256, 1024);
+#define OMX_OVERRIDE(DT) \
+    do { if (f16) OMX_LAUNCH((override_rows_kernel<DT, true>), grid, 256, 0, s, dst, (const Elem<DT>::T*)src, n); \
+         else OMX_LAUNCH((override_rows_kernel<DT, false>), grid, 256, 0, s, dst, (const Elem<DT>::T*)src, n); } while (0)
+    switch (dt) {
+        case OMX_FLOAT32: OMX_OVERRIDE(OMX_FLOAT32); break;
+        case OMX_BFLOAT16: OMX_OVERRIDE(OMX_BFLOAT16); break;
+        case OMX_FLOAT16: OMX_OVERRIDE(OMX_FLOAT16); break;
+        default: OMX_REQUIRE(false, "prompt pass: caller rows of dtype %d (float32, bfloat16 or float16)", (int)dt);
+    }
+#undef OMX_OVERRIDE
+    OMX_LAUNCH_CHECK();
+    return 0;
+}
+
 // Batched prefill of T prompt tokens (all but the last one, which goes through the decode step so
 // that sampling stays in one place): fills the KV slabs of every layer.  Matrix-core path:
 //   RMSNorm rows -> q/k/v GEMM -> [per-head norm + RoPE + cache scatter] -> flash attention
@@ -175,8 +230,9 @@ int packed_rows(const QGemvArgs& g, int T, bf16_t* const* mout, int bits, int pr
 // kv: the slabs the rows are appended to and attend over (default: the model's own).
 // rag (omx_qwen3_batch_decode only): the T rows are T different sequences -- embedding, cache append and attention take their ragged
 // form (engine_batch.hip), every Linear is the launch the verify pass makes for T rows
+// span (omx_qwen3_prefill_embeds only): rows of the caller's that replace the gathered embedding rows before the first layer
 int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, bool full_last, bool packed_rows_pass, const KvSlabs* kv,
-                           const RaggedRows* rag) {
+                           const RaggedRows* rag, const RowSpan* span) {
     const omx_qwen3_config& c = m->cfg;
     // float16 checkpoints (round 4): the same pass in float16 -- weights dequantised to float16, the eight-wave GEMM kernel's float16
     // form, float16 norms / RoPE / slabs, the flash attention kernel's float16 form -- for
@@ -245,25 +301,14 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
     };
     if (rag) {
         if (launch_batch_embed(m, *rag, T, s)) return 1;
-    } else if (prow) {
-        const int bits = m->q_embed.bits;      // the embedding's own format
-#define OMX_QEMB_ROWS(B) \
-        case B: OMX_LAUNCH(qembed_rows_kernel<B>, T, 256, 0, s, m->pf_h, m->q_embed.w, m->q_embed.scales, m->q_embed.biases, m->prompt_dev, hd, m->q_embed.group); break;
-        switch (bits) { OMX_QEMB_ROWS(2) OMX_QEMB_ROWS(3) OMX_QEMB_ROWS(4) OMX_QEMB_ROWS(5) OMX_QEMB_ROWS(6) OMX_QEMB_ROWS(8) }
-#undef OMX_QEMB_ROWS
-        OMX_LAUNCH_CHECK();
-    } else if (quant) {
-        // QuantizedEmbedding::forward: gather the packed rows, dequantise (quantized.rs:192-203)
-        const int wpr = hd * m->q_embed.bits / 32, gpr = hd / m->q_embed.group;
-        uint32_t* rows_w = (uint32_t*)m->pf_xn;                       // scratch: [T, wpr] u32 fits in [T, hd] bf16
-        bf16_t* rows_s = m->pf_h2;
-        bf16_t* rows_b = m->pf_h2 + (size_t)T * gpr;
-        if (omx_take_rows(rows_w, m->q_embed.w, m->prompt_dev, T, wpr, OMX_FLOAT32, s)) return 1;
-        if (omx_take_rows(rows_s, m->q_embed.scales, m->prompt_dev, T, gpr, OMX_BFLOAT16, s)) return 1;
-        if (omx_take_rows(rows_b, m->q_embed.biases, m->prompt_dev, T, gpr, OMX_BFLOAT16, s)) return 1;
-        if (launch_dequantize_bf16(m->pf_h, (const uint32_t*)rows_w, rows_s, rows_b, T, hd, m->q_embed.group, m->q_embed.bits, f16, s, f16)) return 1;
-    } else if (omx_take_rows(m->pf_h, m->embed, m->prompt_dev, T, hd, OMX_BFLOAT16, s)) {
+    } else if (embed_rows(m, m->pf_h, T, prow)) {
         return 1;
+    }
+    if (span && span->n > 0) {
+        // omx_qwen3_prefill_embeds: rows [first, first + n) replaced by the caller's, in one launch -- everything below reads pf_h
+        OMX_REQUIRE(!rag && !enc && span->first >= 0 && span->first + span->n <= T, "prompt pass: caller rows [%d, %d) outside its %d rows",
+                    span->first, span->first + span->n, T);
+        if (launch_override_rows(m->pf_h + (size_t)span->first * hd, span->rows, span->dtype, (int64_t)span->n * hd, f16, s)) return 1;
     }
     bf16_t* h = m->pf_h;
     bf16_t* h2 = m->pf_h2;

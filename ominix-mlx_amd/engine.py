@@ -103,6 +103,9 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_reset": (c_int, [c_void_p]),
     "omx_qwen3_offset": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
     "omx_qwen3_prefill": (c_int, [c_void_p, ctypes.POINTER(c_uint32), c_int, ctypes.POINTER(c_uint32)]),
+    # a prompt pass over caller-supplied embedding rows (the reference's forward_embeddings), and the model's own rows
+    "omx_qwen3_embed_tokens": (c_int, [c_void_p, ctypes.POINTER(c_uint32), c_int, c_void_p]),
+    "omx_qwen3_prefill_embeds": (c_int, [c_void_p, ctypes.POINTER(c_uint32), c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_decode": (c_int, [c_void_p, c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_last_logits": (c_int, [c_void_p, c_void_p, c_int]),
     # per-token log-probabilities of the tokens being generated, inside the step (csrc/logprob.hip's top-n form)
@@ -498,10 +501,33 @@ class Model:
         check(lib.omx_qwen3_offset(self._h, ctypes.byref(v)))
         return v.value
 
-    def prefill(self, prompt) -> int:
+    def embed_tokens(self, ids):
+        """get_token_embeddings (qwen3-asr-mlx/src/model.rs:726): the model's own embedding rows of `ids`, a device Tensor
+        [n, hidden] in the activation dtype -- the bits the prompt pass gathers (omx_qwen3_embed_tokens)."""
+        from .ops import Tensor
+        p = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).ravel())
+        out = Tensor((p.size, self.cfg.hidden_size), "f16" if self.f16 else "bf16")
+        check(lib.omx_qwen3_embed_tokens(self._h, p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, out.ptr))
+        return out
+
+    def prefill(self, prompt, embeds=None, embeds_at: int = 0) -> int:
+        """The prompt's first sampled token.  embeds: rows [n_rows, hidden] that replace the embedding rows of positions
+        [embeds_at, embeds_at + n_rows) -- the reference's forward_embeddings (omx_qwen3_prefill_embeds): a device Tensor (f32, bf16 or
+        f16) or a float32 / float16 numpy array; the ids at those positions are still required (the pad token)."""
         p = np.ascontiguousarray(prompt, dtype=np.uint32)
         first = c_uint32()
-        check(lib.omx_qwen3_prefill(self._h, p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, ctypes.byref(first)))
+        if embeds is None:
+            check(lib.omx_qwen3_prefill(self._h, p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, ctypes.byref(first)))
+            return first.value
+        from .ops import Tensor
+        if not isinstance(embeds, Tensor):
+            a = np.asarray(embeds)
+            embeds = Tensor.from_numpy(a, "f16" if a.dtype == np.float16 else "f32")
+        if len(embeds.shape) != 2 or embeds.shape[1] != self.cfg.hidden_size:
+            raise OmxError(f"ShapeMismatch: embeds has shape {embeds.shape}, the model expects [n_rows, {self.cfg.hidden_size}]")
+        check(lib.omx_synchronize(None))   # the rows may come from ops on the null stream; the pass runs on the model's own
+        check(lib.omx_qwen3_prefill_embeds(self._h, p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, embeds.ptr if embeds.shape[0] else None,
+                                           embeds.dtype, int(embeds_at), embeds.shape[0], ctypes.byref(first)))
         return first.value
 
     def set_logprobs(self, top_n=None) -> None:
