@@ -602,7 +602,8 @@ int omx_qwen3_debug_trace_engine(omx_qwen3 m, unsigned long long* host, size_t n
 /* test hooks of the decode step's forms.  step_forms: what the NEXT step would take -- forms[0] = down + the next layer's q/k/v in one
  * launch (csrc/gemv_chain.hip, OMX_DOWN_QKV=0 turns it off), forms[1] = the O projection inside the attention launch, forms[2] = the
  * persistent-step mode, forms[3] = 1 once a give-up switched the first off for this engine, forms[4] = gate/up + SwiGLU inside the
- * attention launch (OMX_ATTN_GATEUP=0 turns it off), forms[5] = 1 once a give-up switched that off (forms holds six ints).  raise_give_up: sets, from the host, the word
+ * attention launch (OMX_ATTN_GATEUP=0 turns it off), forms[5] = 1 once a give-up switched that off, forms[6] = down + the next layer's q/k/v
+ * inside the attention launch as well, one launch per layer (OMX_ATTN_DOWN=0 turns it off; forms holds seven ints).  raise_give_up: sets, from the host, the word
  * a wait inside a launch raises when it gives up; the next omx_qwen3_decode then replays its steps on the next form of the ladder */
 int omx_qwen3_debug_step_forms(omx_qwen3 m, int* forms);
 int omx_qwen3_debug_raise_give_up(omx_qwen3 m);

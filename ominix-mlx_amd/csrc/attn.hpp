@@ -67,7 +67,21 @@ struct AttnStepArgs {
     bf16_t* gu_out;             // [gu_rows] = silu(gate . xn) * up . xn with the roundings of gemv_kernel<8, 1, 1, PRO_RMSNORM, EPI_SWIGLU>
     int gu_rows;
     uint64_t* hg;               // granules [o_rows / 2]: {two packed bf16 of the hidden row the O projection leaves, tag}
+    // ---- optional [down + residual] of the same layer and [RMSNorm + q/k/v] of the NEXT one behind gate/up (dn_w != null; gate/up's shape
+    //      with attn_step_down_ok): the arithmetic of gemv_chain.hip's down_qkv_kernel, the residual being the hidden row above ----
+    const bf16_t* dn_w;         // [o_rows, gu_rows] row-major (model.rs:266)
+    bf16_t* dn_out;             // [o_rows] = bf16(hidden row + bf16(dn_w . gu_out)): the residual stream leaving the layer (model.rs:327)
+    uint64_t* ag;               // granules [gu_rows / 2]: {two packed bf16 of gu_out, tag}
+    uint64_t* rg;               // granules [o_rows / 2]: {two packed bf16 of dn_out, tag}
+    const bf16_t* nq_w0;        // the next layer's stacked q | k | v matrices, [nq_n0 | nq_n1 | nq_rows - nq_n0 - nq_n1] rows of o_rows
+    const bf16_t* nq_w1;
+    const bf16_t* nq_w2;
+    int nq_n0, nq_n1, nq_rows;
+    const bf16_t* nq_norm_w;    // [o_rows] the next layer's input RMSNorm weight
+    const bf16_t* nq_bias;      // [nq_rows] or null (Qwen2 wiring)
+    bf16_t* nq_out;             // [nq_rows]: may be `qkv` itself -- every block has consumed its q/k/v long before the first row is stored
 };
+bool attn_step_down_ok(int o_rows, int gu_rows, int nq_rows);
 bool attn_step_oproj_ok(int H, int Hkv, int D, int nsplit, int o_rows);
 bool attn_step_gateup_ok(int H, int Hkv, int D, int nsplit, int o_rows, int gu_rows);
 bool attn_step_oproj_q4_ok(int H, int Hkv, int D, int nsplit, int o_rows, int group);

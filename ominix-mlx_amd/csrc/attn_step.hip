@@ -243,7 +243,10 @@ __device__ __forceinline__ void oproj_await_vector(const AttnStepArgs& a, u32x4*
 }
 
 // a pair in a register set reduced against the normalised row in LDS: gemv.hip's OMX_COMPUTE with NR = 2, then its SwiGLU epilogue
-__device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4 (*w)[kGuNV], const u32x4* xs, int pair, int lane) {
+// (DN: the value is parked in LDS at its ticket's slot as well, for the activation hop of down_qkv_phase)
+template <bool DN = false>
+__device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4 (*w)[kGuNV], const u32x4* xs, int pair, int lane,
+                                              uint16_t* park = nullptr) {
     typedef Act16<false> A;
     float acc[2] = {0.f, 0.f};
 #pragma unroll
@@ -260,7 +263,257 @@ __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4
     }
 #pragma unroll
     for (int r = 0; r < 2; ++r) acc[r] = wave_sum(acc[r]);
+    if constexpr (DN) {
+        if (lane == 0) {
+            const uint16_t v = epi_bits<EPI_SWIGLU, A>(acc[0], acc[1], (bf16_t)0, 0);
+            a.gu_out[pair] = v;
+            *park = v;
+        }
+    } else
     if (lane == 0) a.gu_out[pair] = epi_bits<EPI_SWIGLU, A>(acc[0], acc[1], (bf16_t)0, 0);
+}
+
+// ---- [down + residual] of the layer and [RMSNorm + q/k/v] of the NEXT layer behind gate/up (attn_step_kernel, DN) ----
+// The launch that ends a layer: gemv_chain.hip's down_qkv_kernel on the 256 blocks of this launch, bit for bit.  Two more hops: the
+// block's 48 activations leave as 24 granules {two packed bf16, tag} and every block sweeps all 6 144 into LDS; the 16 residual rows a
+// block finishes leave as 8 granules and every block sweeps the 2 048.  Block b owns down rows [b * kDnBlockRows, + kDnBlockRows): 32 units
+// of (row pair, K quarter), 12 KB each, drawn from a ticket counter in LDS into two register sets per wave.  The arithmetic is
+// gemv_kernel<6, 4, 2, PRO_NONE, EPI_RESIDUAL>'s -- a quarter is a dot8 chain over its six vectors per lane + wave_sum, the four partials are
+// added in quarter order from 0.f, bf16(resid + bf16(sum)) -- and gemv_kernel<8, 1, 2, PRO_RMSNORM, EPI_STORE>'s on three q/k/v rows per
+// wave.  A wave asks for its first two units and two of its three q/k/v rows -- they depend on nothing -- as soon as its last pair is
+// reduced, and for the third row as soon as its last unit is: 40 KB per wave stream through the activation hop.  Waves 0 and 4 bring the
+// activation vector in first, half each (nothing of their own in flight in front of the granules); wave 0 finishes the rows and brings the
+// residual row in, its q/k/v rows long landed.  Forms measured at Qwen3-8B shapes, ctx 2 k (EXPERIMENTS C-4; parent 347.6 tok/s):
+//   * wave 0 alone sweeping the activation vector in three passes of 32 granules per lane, all q/k/v rows asked for behind the last unit
+//     (wave 0's behind the row's sweep): 344.1; with two q/k/v rows up front as here: 343.7 -- more requests queued, longer round trips;
+//   * as here: 351.9; without the watch in front of the residual row's sweep: 350.6.
+constexpr int kDnInter = 12288, kDnBlockRows = 16, kDnNV = kDnInter / 512 / 4, kDnUnits = kDnBlockRows / 2 * 4, kDnQRows = 3;
+// LDS of the phase, in the (dead) split-merge area at the front: the activation vector, the K-quarter partials, the parked activations
+constexpr int kDnPartOff = kDnInter * 2, kDnParkOff = kDnPartOff + kDnBlockRows * 4 * 4, kDnLdsBytes = kDnParkOff + kGuBlockPairs * 2;
+// the phase's words behind gate/up's in LDS: the unit ticket counter; units reduced and q/k/v rows stored (TRACE)
+enum { kDnTicket = 4, kDnReduced = 5, kDnStored = 6, kDnWords = 8 };
+
+__device__ __forceinline__ int down_claim(int* sm_gu, int lane) {
+    int t = 0;
+    if (lane == 0) t = __hip_atomic_fetch_add(sm_gu + kDnTicket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    return __builtin_amdgcn_readfirstlane(t);
+}
+
+// unit `u` of the block = rows row_begin + 2 * (u / 4) + {0, 1}, K quarter u % 4, into a register set
+__device__ __forceinline__ void down_issue(const AttnStepArgs& a, u32x4 (*w)[kDnNV], int row_begin, int u, int lane) {
+    const u32x4* p = reinterpret_cast<const u32x4*>(a.dn_w) + (size_t)(row_begin + 2 * (u >> 2)) * (kDnInter / 8) + (u & 3) * (kDnNV * 64) + lane;
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+#pragma unroll
+        for (int j = 0; j < kDnNV; ++j) w[r][j] = ld_nt(p + (size_t)r * (kDnInter / 8) + j * 64);
+    }
+    __builtin_amdgcn_sched_barrier(0);   // keep the loads HERE: the scheduler would sink them to their use
+}
+
+// a unit in a register set reduced against its quarter of the activation vector in LDS: gemv_chain.hip's OMX_COMPUTE
+__device__ __forceinline__ void down_reduce(const u32x4 (*w)[kDnNV], const u32x4* xa, float* part, int u, int lane) {
+    typedef Act16<false> A;
+    float acc[2] = {0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < kDnNV; ++j) {
+        const u32x4 xp = xa[(u & 3) * (kDnNV * 64) + j * 64 + lane];
+        float xf[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            xf[2 * q] = A::lo(xp[q]);
+            xf[2 * q + 1] = A::hi(xp[q]);
+        }
+#pragma unroll
+        for (int r = 0; r < 2; ++r) acc[r] = dot8(w[r][j], xf, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) acc[r] = wave_sum(acc[r]);
+    if (lane == 0) {
+#pragma unroll
+        for (int r = 0; r < 2; ++r) part[(2 * (u >> 2) + r) * 4 + (u & 3)] = acc[r];
+    }
+}
+
+// a wave brings its share -- part `part` of NW -- of a vector of `N2` granules into LDS (natural element order): it watches one granule per
+// lane politely (the last of every GPL-th run of its share), then asks for all of its GPL granules per lane in ONE pass (a pass is a round trip
+// through a memory system that is busy with the weight streams: three passes of 32 cost the activation hop 8 us, EXPERIMENTS C-4) and
+// re-reads them until every tag matches
+template <int N2, int NW>
+__device__ __forceinline__ void sweep_vector(const AttnStepArgs& a, const uint64_t* gr, unsigned* sx, int part, unsigned tag, int lane) {
+    constexpr int GPL = N2 / NW / 64;   // granules per lane
+    static_assert(N2 % (NW * 64) == 0 && GPL <= 48, "whole lanes, at most 96 registers of granules");
+    gr += (size_t)part * (N2 / NW);
+    sx += part * (N2 / NW);
+    for (unsigned spins = 0; spins < kSpinLimit; ++spins) {
+        const unsigned long long g = ld_granule(gr + (size_t)lane * GPL + (GPL - 1));
+        if (__all((unsigned)(g >> 32) == tag)) break;
+        __builtin_amdgcn_s_sleep(4);
+    }
+    unsigned long long g[GPL];
+    for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) g[i] = ld_granule(gr + (size_t)i * 64 + lane);
+        bool ok = true;
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
+        if (__all(ok)) break;
+        if (spins >= kSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
+            if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(4);
+    }
+#pragma unroll
+    for (int i = 0; i < GPL; ++i) sx[i * 64 + lane] = (unsigned)g[i];
+}
+
+__device__ __forceinline__ const bf16_t* next_qkv_row(const AttnStepArgs& a, int row) {
+    // wave-uniform: which of the stacked matrices owns this row
+    if (row < a.nq_n0) return a.nq_w0 + (size_t)row * kGuHidden;
+    row -= a.nq_n0;
+    if (row < a.nq_n1) return a.nq_w1 + (size_t)row * kGuHidden;
+    row -= a.nq_n1;
+    return a.nq_w2 + (size_t)row * kGuHidden;
+}
+
+// Every wave of every block of a DN launch ends here, behind its last (gate, up) pair; `res2`: the residual pair of rows
+// 2 * (lane & 7) + {0, 1} of the block.  Every wave passes the same barriers on every path, the give-up included; they wait for LDS only.
+template <bool TRACE>
+__device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned char* sm_dn, u32x4* xs, float* red, int* sm_gu, unsigned res2,
+                                               unsigned tag, int lane, int wave, unsigned long long* tr) {
+    typedef Act16<false> A;
+    u32x4* xa = reinterpret_cast<u32x4*>(sm_dn);
+    float* part = reinterpret_cast<float*>(sm_dn + kDnPartOff);
+    const int blk = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
+    const int row_begin = blk * kDnBlockRows;
+    const int q_row0 = (blk * kWaves + __builtin_amdgcn_readfirstlane(wave)) * kDnQRows;   // (in scalar registers: so are the row pointers)
+    // the next layer's norm weight and bias: asked for before any weight row
+    constexpr int PV = kGuNV * 64 / 256;
+    u32x4 nwv[PV];
+#pragma unroll
+    for (int i = 0; i < PV; ++i) nwv[i] = *(reinterpret_cast<const u32x4*>(a.nq_norm_w) + (threadIdx.x & 255) + i * 256);
+    bf16_t ob[kDnQRows];
+#pragma unroll
+    for (int r = 0; r < kDnQRows; ++r) ob[r] = *(a.nq_bias ? a.nq_bias + min(q_row0 + r, a.nq_rows - 1) : a.nq_norm_w);   // (one load either way: no branch)
+    u32x4 dA[2][kDnNV], dB[2][kDnNV];
+    int tA = 0, tB = 0;
+    u32x4 qw[kDnQRows][kGuNV];
+    auto issue_qkv = [&](const int r0, const int r1) {
+#pragma unroll
+        for (int r = r0; r < r1; ++r) {
+            const u32x4* p = reinterpret_cast<const u32x4*>(next_qkv_row(a, min(q_row0 + r, a.nq_rows - 1)));   // clamp: surplus waves re-read the last row
+#pragma unroll
+            for (int j = 0; j < kGuNV; ++j) qw[r][j] = ld_nt(p + j * 64 + lane);
+        }
+        __builtin_amdgcn_sched_barrier(0);   // keep the loads HERE: the scheduler would sink them to their use
+    };
+    // (the two tickets a wave draws ahead of the loop are below kDnUnits, no check: sixteen of the 32)
+    // Measured (EXPERIMENTS C-4): the more weight requests are queued when the sweep starts, the longer each of its round trips -- the hop is
+    // kept short by its number of round trips, not by what is parked in front of it
+    const bool sweeper = (wave & (kWaves / 2 - 1)) == 0;   // waves 0 and 4 bring the activation vector in, half each
+    if (!sweeper) {
+        tA = down_claim(sm_gu, lane);
+        down_issue(a, dA, row_begin, tA, lane);
+        tB = down_claim(sm_gu, lane);
+        down_issue(a, dB, row_begin, tB, lane);
+        issue_qkv(0, kDnQRows - 1);
+    }
+    lds_barrier();   // the block's 48 activations are parked
+    if (sweeper) {
+        if (wave == 0 && lane < kGuBlockPairs / 2)
+            st_granule_u32(a.ag + (size_t)blk * (kGuBlockPairs / 2) + lane, tag, reinterpret_cast<const unsigned*>(sm_dn + kDnParkOff)[lane]);
+        sweep_vector<kDnInter / 2, 2>(a, a.ag, reinterpret_cast<unsigned*>(xa), __builtin_amdgcn_readfirstlane(wave) / (kWaves / 2), tag, lane);
+        if (TRACE && threadIdx.x == 0) tr[11] = wall_clock64();
+        tA = down_claim(sm_gu, lane);
+        down_issue(a, dA, row_begin, tA, lane);
+        tB = down_claim(sm_gu, lane);
+        down_issue(a, dB, row_begin, tB, lane);
+        issue_qkv(0, kDnQRows - 1);
+    }
+    lds_barrier();   // the activation vector is in LDS
+    down_reduce(dA, xa, part, tA, lane);
+    if (TRACE && threadIdx.x == 0) tr[12] = wall_clock64();
+    // the loop of gateup_phase: wave-uniform branches over two named sets, the ticket of a refill drawn one reduce ahead
+    int n_reduced = 1;
+    int nA = down_claim(sm_gu, lane), nB;
+    for (;;) {
+        if (nA >= kDnUnits) {
+            down_reduce(dB, xa, part, tB, lane);
+            ++n_reduced;
+            break;
+        }
+        tA = nA;
+        down_issue(a, dA, row_begin, tA, lane);
+        nB = down_claim(sm_gu, lane);
+        down_reduce(dB, xa, part, tB, lane);
+        if (nB >= kDnUnits) {
+            down_reduce(dA, xa, part, tA, lane);
+            n_reduced += 2;
+            break;
+        }
+        tB = nB;
+        down_issue(a, dB, row_begin, tB, lane);
+        nA = down_claim(sm_gu, lane);
+        down_reduce(dA, xa, part, tA, lane);
+        n_reduced += 2;
+    }
+    if (TRACE && lane == 0) __hip_atomic_fetch_add(sm_gu + kDnReduced, n_reduced, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    issue_qkv(kDnQRows - 1, kDnQRows);   // the wave's last row, into the registers its down sets have left
+    lds_barrier();   // every K-quarter partial of the block's 16 rows is in LDS
+    if (wave == 0) {
+        if (lane < kDnBlockRows / 2) {
+            // rows 2 * lane and 2 * lane + 1 of the block: the pair leaves twice, to the ping-pong buffer (the next attention launch reads it
+            // as its residual) and as a tagged granule for the q/k/v rows of every block
+            float v[2] = {0.f, 0.f};
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+#pragma unroll
+                for (int w = 0; w < 4; ++w) v[e] += part[(2 * lane + e) * 4 + w];
+            }
+            const uint32_t o2 = (uint32_t)epi_bits<EPI_RESIDUAL, A>(v[0], 0.f, (bf16_t)(res2 & 0xFFFFu), 0) |
+                                ((uint32_t)epi_bits<EPI_RESIDUAL, A>(v[1], 0.f, (bf16_t)(res2 >> 16), 0) << 16);
+            reinterpret_cast<uint32_t*>(a.dn_out)[row_begin / 2 + lane] = o2;
+            st_granule_u32(a.rg + row_begin / 2 + lane, tag, o2);
+        }
+        sweep_vector<kGuHidden / 2, 1>(a, a.rg, reinterpret_cast<unsigned*>(xs), 0, tag, lane);
+        if (TRACE && lane == 0) tr[13] = wall_clock64();
+    }
+    lds_barrier();   // the residual row is in LDS
+    rmsnorm_in_lds<A, PV>(xs, red, nwv, kGuHidden, a.eps, threadIdx.x < 256);
+    float acc[kDnQRows];
+#pragma unroll
+    for (int r = 0; r < kDnQRows; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int j = 0; j < kGuNV; ++j) {
+        const u32x4 xp = xs[j * 64 + lane];
+        float xf[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            xf[2 * q] = A::lo(xp[q]);
+            xf[2 * q + 1] = A::hi(xp[q]);
+        }
+#pragma unroll
+        for (int r = 0; r < kDnQRows; ++r) acc[r] = dot8(qw[r][j], xf, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < kDnQRows; ++r) acc[r] = wave_sum(acc[r]);
+    if (lane == 0) {
+        int stored = 0;
+#pragma unroll
+        for (int r = 0; r < kDnQRows; ++r)
+            if (q_row0 + r < a.nq_rows) {
+                a.nq_out[q_row0 + r] = A::bits(a.nq_bias ? acc[r] + A::val(ob[r]) : acc[r]);
+                ++stored;
+            }
+        if (TRACE) __hip_atomic_fetch_add(sm_gu + kDnStored, stored, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    if constexpr (TRACE) {   // when the block's rows were stored; the units it reduced | the q/k/v rows it stored << 32
+        lds_barrier();
+        if (threadIdx.x == 0) {
+            tr[14] = wall_clock64();
+            tr[15] = (unsigned long long)sm_gu[kDnReduced] | (unsigned long long)sm_gu[kDnStored] << 32;
+        }
+    }
 }
 
 // Every wave of every block ends here.  `pub_rows` > 0: the block's O rows [pub_row0, + pub_rows) are parked in sm_pub (a block of O
@@ -278,11 +531,13 @@ __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4
 //     0's first and the others' second pair behind the hidden row's sweep as well: 347.5; the first pair of waves 1..7 moved up behind
 //     the ATTENTION VECTOR's sweep on top of that: 343.9, slower than the parent -- that sweep feeds the O rows every block waits for;
 //   * wave 0's second pair asked for as soon as the row is in LDS instead of behind the norm: 342.7 against 346.4.
-template <bool TRACE>
+template <bool TRACE, bool DN = false>
 __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, float* red, int* sm_gu, const uint16_t* sm_pub, unsigned tag,
-                                             int lane, int wave, int pub_row0, int pub_rows, unsigned long long* tr) {
+                                             int lane, int wave, int pub_row0, int pub_rows, unsigned long long* tr,
+                                             unsigned char* sm_dn = nullptr) {
     typedef Act16<false> A;
     const int pair0 = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * kGuBlockPairs;
+    uint16_t* park = DN ? reinterpret_cast<uint16_t*>(sm_dn + kDnParkOff) : nullptr;   // DN: the block's values by ticket
     constexpr int PV = kGuNV * 64 / 256;              // vectors of the row per thread of the first four waves
     u32x4 nwv[PV];
 #pragma unroll
@@ -341,17 +596,21 @@ __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, f
         gateup_issue(a, wB, pair0 + tB, lane);
     }
     lds_barrier();
+    // DN: the raw hidden row is the down rows' residual.  The pair a finishing thread of down_qkv_phase needs is read now, before the norm
+    // overwrites the row (its first barrier waits for this read); the plain `o_out` another block stored is not visible inside the launch
+    unsigned res2 = 0;
+    if constexpr (DN) res2 = reinterpret_cast<const unsigned*>(xs)[(pair0 / kGuBlockPairs) * (kDnBlockRows / 2) + (lane & (kDnBlockRows / 2 - 1))];
     rmsnorm_in_lds<A, PV>(xs, red, nwv, kGuHidden, a.eps, threadIdx.x < 256);
     // Wave 0 asks for its second pair only now: the norm's last barrier waits for every load of the first four waves (hipcc drains in
     // front of it), and a pair asked for when the row was in LDS would hold the whole block for its round trip.  (Two arms with an asm
     // text of their own: merged, the wait in front of the first reduce would drain wave 0's second pair.)
     if (wave == 0) {
         gateup_issue(a, wB, pair0 + tB, lane);
-        gateup_reduce(a, wA, xs, pair0 + tA, lane);
+        gateup_reduce<DN>(a, wA, xs, pair0 + tA, lane, park + tA);
         if (TRACE && threadIdx.x == 0) tr[7] = wall_clock64();
         asm volatile("; first pair reduced: wave 0, its second pair just asked for" ::: "memory");
     } else {
-        gateup_reduce(a, wA, xs, pair0 + tA, lane);
+        gateup_reduce<DN>(a, wA, xs, pair0 + tA, lane, park + tA);
         asm volatile("; first pair reduced: the second pair came in through the hop" ::: "memory");
     }
     // Both sets are in flight.  A set is reduced and refilled with the pair of the wave's next ticket -- or, with no pair left, the other
@@ -363,23 +622,23 @@ __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, f
     int nA = gateup_claim(sm_gu, lane), nB;
     for (;;) {
         if (nA >= kGuBlockPairs) {
-            gateup_reduce(a, wB, xs, pair0 + tB, lane);
+            gateup_reduce<DN>(a, wB, xs, pair0 + tB, lane, park + tB);
             ++n_reduced;
             break;
         }
         tA = nA;
         gateup_issue(a, wA, pair0 + tA, lane);
         nB = gateup_claim(sm_gu, lane);
-        gateup_reduce(a, wB, xs, pair0 + tB, lane);
+        gateup_reduce<DN>(a, wB, xs, pair0 + tB, lane, park + tB);
         if (nB >= kGuBlockPairs) {
-            gateup_reduce(a, wA, xs, pair0 + tA, lane);
+            gateup_reduce<DN>(a, wA, xs, pair0 + tA, lane, park + tA);
             n_reduced += 2;
             break;
         }
         tB = nB;
         gateup_issue(a, wB, pair0 + tB, lane);
         nA = gateup_claim(sm_gu, lane);
-        gateup_reduce(a, wA, xs, pair0 + tA, lane);
+        gateup_reduce<DN>(a, wA, xs, pair0 + tA, lane, park + tA);
         n_reduced += 2;
     }
     if constexpr (TRACE) {   // when wave 0 and wave 7 reduced their last pair, and how many pairs the block reduced
@@ -391,6 +650,7 @@ __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, f
         lds_barrier();
         if (threadIdx.x == 0) tr[10] = (unsigned long long)sm_gu[kGuReduced];
     }
+    if constexpr (DN) down_qkv_phase<TRACE>(a, sm_dn, xs, red, sm_gu, res2, tag, lane, wave, tr);
 }
 
 // The O-projection phase of a non-consumer block (attn_step_kernel, NVW > 0): R weight rows per wave go out NOW -- the block's
@@ -538,8 +798,9 @@ __device__ __forceinline__ void oproj_phase_q4(const AttnStepArgs& a, u32x4* sm_
 }
 
 
-template <int D, int GT, bool TRACE, int NVW, bool F16 = false, bool GU = false>
+template <int D, int GT, bool TRACE, int NVW, bool F16 = false, bool GU = false, bool DN = false>
 __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs a) {
+    static_assert(!DN || GU, "down + the next q/k/v follow gate/up only");
     static_assert(!F16 || NVW == 0, "the O projection rides in the launch for bfloat16 models only");
     static_assert(!GU || (NVW == kGuNV && D == 128), "gate/up follows the bf16 O projection of hidden 4096 only");
     typedef Act16<F16> A16;
@@ -566,7 +827,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
     unsigned long long* tr = TRACE ? a.trace + ((size_t)split * a.Hkv + kvh) * kAttnTraceWords : nullptr;
     if (TRACE && threadIdx.x == 0) tr[0] = wall_clock64();
     if constexpr (GU) {   // (every wave passes the barrier below before it draws a ticket)
-        if (threadIdx.x < kGuWords) sm_gu[threadIdx.x] = 0;
+        if (threadIdx.x < (DN ? kDnWords : kGuWords)) sm_gu[threadIdx.x] = 0;
     }
 
     bf16_t* Kb = a.k + (size_t)kvh * a.kv_head_stride;
@@ -777,7 +1038,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
             uint16_t* sm_pub = reinterpret_cast<uint16_t*>(sm_l);   // (the split merge is done with sm_m / sm_l: a block barrier ago)
             if (rows == 2) oproj_phase<NV, 2, true>(a, sm_x, tag, lane, wave, o_row0, otr, sm_pub, pub_row0);
             else oproj_phase<NV, 3, true>(a, sm_x, tag, lane, wave, o_row0, otr, sm_pub, pub_row0);
-            gateup_phase<TRACE>(a, sm_x, sm_m, sm_gu, sm_pub, tag, lane, wave, pub_row0, pub_rows, otr);
+            gateup_phase<TRACE, DN>(a, sm_x, sm_m, sm_gu, sm_pub, tag, lane, wave, pub_row0, pub_rows, otr, smem);
             return;
         } else
         if constexpr (QO) {
@@ -810,7 +1071,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
     if constexpr (GU) {
         // the consumer blocks take their share of the pairs once their heads are merged and published (block-uniform: split < G here)
         lds_barrier();
-        gateup_phase<TRACE>(a, sm_x, sm_m, sm_gu, nullptr, tag, lane, wave, 0, 0, TRACE ? tr : nullptr);
+        gateup_phase<TRACE, DN>(a, sm_x, sm_m, sm_gu, nullptr, tag, lane, wave, 0, 0, TRACE ? tr : nullptr, smem);
     }
 }
 
@@ -864,6 +1125,14 @@ bool attn_step_gateup_ok(int H, int Hkv, int D, int nsplit, int o_rows, int gu_r
     return oproj_rows_per_wave(H, Hkv, nsplit, o_rows) == 3 && (o_rows - waves * 2) % kWaves == 0;
 }
 
+// ... and [down + residual] + the next layer's [RMSNorm + q/k/v] behind that: gate/up's shape (256 blocks, hidden 4096) with sixteen down
+// rows a block over the intermediate size the units are cut for, and three q/k/v rows a wave covering the next layer's rows exactly as
+// gemv_chain.hip's waves do
+bool attn_step_down_ok(int o_rows, int gu_rows, int nq_rows) {
+    const int waves = 256 * kWaves;
+    return o_rows == 256 * kDnBlockRows && gu_rows == kDnInter && nq_rows > (kDnQRows - 1) * waves && nq_rows <= kDnQRows * waves;
+}
+
 int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
     AttnStepArgs a = a_in;
     const int G = a.H / a.Hkv;
@@ -891,6 +1160,10 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
         OMX_REQUIRE(a.o_w && a.o_out && !a.o_out_f32 && !a.f16 && a.gu_up && a.gu_norm_w && a.gu_out && a.hg &&
                         attn_step_gateup_ok(a.H, a.Hkv, D, a.nsplit, a.o_rows, a.gu_rows),
                     "decode attention + gate/up: shape does not qualify (%d blocks, %d O rows, %d pairs)", a.Hkv * a.nsplit, a.o_rows, a.gu_rows);
+    if (a.dn_w)
+        OMX_REQUIRE(a.gu_gate && a.dn_out && a.ag && a.rg && a.nq_w0 && a.nq_w1 && a.nq_w2 && a.nq_norm_w && a.nq_out &&
+                        a.nq_n0 > 0 && a.nq_n1 > 0 && a.nq_rows > a.nq_n0 + a.nq_n1 && attn_step_down_ok(a.o_rows, a.gu_rows, a.nq_rows),
+                    "decode attention + down + q/k/v: shape does not qualify (%d rows, %d pairs, %d q/k/v rows)", a.o_rows, a.gu_rows, a.nq_rows);
     const dim3 grid(a.Hkv, a.nsplit), block(kBlock);
     const int gt = G <= 1 ? 1 : G <= 2 ? 2 : G <= 4 ? 4 : 8;
 #define OMX_ATTN_LAUNCH(DD, GG, TT, NN)                                                                                  \
@@ -910,13 +1183,24 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
         OMX_LAUNCH_CHECK();                                                                                              \
         return 0;                                                                                                        \
     }
+#define OMX_ATTN_LAUNCH_DN(TT)                                                                                           \
+    {                                                                                                                    \
+        OMX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_step_kernel<128, 4, TT, kGuNV, false, true, true>,           \
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                      \
+        OMX_LAUNCH_TIMED((attn_step_kernel<128, 4, TT, kGuNV, false, true, true>), grid, block, shmem, s, a);            \
+        OMX_LAUNCH_CHECK();                                                                                              \
+        return 0;                                                                                                        \
+    }
 #define OMX_ATTN_STEP_CASE(DD, GG)                                                                                       \
     if (D == DD && gt == GG) {                                                                                           \
         const size_t shmem = ((size_t)kWaves * (64 / (DD / 8)) * GG * DD + 2 * kWaves * GG) * sizeof(float) +            \
                              (size_t)(GG + 1) * (DD / 8) * 16 + (size_t)nvw * 64 * 16 + (qo ? (size_t)nvw * 64 : 0) +    \
-                             (a.gu_gate ? kGuWords * sizeof(int) : 0);                                                   \
+                             (a.dn_w ? kDnWords * sizeof(int) : a.gu_gate ? kGuWords * sizeof(int) : 0);                 \
         if (a.gu_gate) {   /* gate/up behind the O projection: one shape (attn_step_gateup_ok) */                         \
             if constexpr (DD == 128 && GG == 4) {                                                                        \
+                static_assert(kDnLdsBytes <= kWaves * 4 * 4 * 128 * 4, "the down phase lives in the split-merge area");  \
+                if (a.dn_w && a.trace) OMX_ATTN_LAUNCH_DN(true)                                                          \
+                if (a.dn_w) OMX_ATTN_LAUNCH_DN(false)                                                                    \
                 if (a.trace) OMX_ATTN_LAUNCH_GU(true)                                                                    \
                 OMX_ATTN_LAUNCH_GU(false)                                                                                \
             }                                                                                                            \
@@ -954,6 +1238,7 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
     OMX_ATTN_STEP_CASE(128, 1) OMX_ATTN_STEP_CASE(128, 2) OMX_ATTN_STEP_CASE(128, 4) OMX_ATTN_STEP_CASE(128, 8)
     OMX_ATTN_STEP_CASE(64, 1) OMX_ATTN_STEP_CASE(64, 2) OMX_ATTN_STEP_CASE(64, 4) OMX_ATTN_STEP_CASE(64, 8)
 #undef OMX_ATTN_STEP_CASE
+#undef OMX_ATTN_LAUNCH_DN
 #undef OMX_ATTN_LAUNCH_GU
 #undef OMX_ATTN_LAUNCH
     return set_error("decode attention: head_dim %d unsupported (64 or 128)", D);

@@ -812,7 +812,8 @@ extern "C" int omx_bench_gemv_warm(int N, int K, int pro, int epi, int n_copies,
 /* which in-launch folds the NEXT step of this engine would take, as the step itself decides (environment switches read now):
  * forms[0] = down + the next layer's q/k/v in one launch, forms[1] = the O projection inside the attention launch, forms[2] = the
  * persistent-step mode; forms[3] = 1 once a give-up switched the first fold off for this engine; forms[4] = gate/up + SwiGLU inside the
- * attention launch (of any layer), forms[5] = 1 once a give-up switched THAT off */
+ * attention launch (of any layer), forms[5] = 1 once a give-up switched THAT off, forms[6] = down + the next layer's q/k/v inside the
+ * attention launch as well (of any layer) */
 extern "C" int omx_qwen3_debug_step_forms(omx_qwen3 m, int* forms) {
     OMX_REQUIRE(m && forms, "omx_qwen3_debug_step_forms: null argument");
     forms[0] = omx::down_takes_qkv(m) ? 1 : 0;
@@ -822,6 +823,8 @@ extern "C" int omx_qwen3_debug_step_forms(omx_qwen3 m, int* forms) {
     forms[4] = 0;
     for (int l = 0; l < m->cfg.num_hidden_layers; ++l) forms[4] |= omx::attention_takes_gateup(m, l) ? 1 : 0;
     forms[5] = m->gateup_disabled ? 1 : 0;
+    forms[6] = 0;
+    for (int l = 0; l < m->cfg.num_hidden_layers; ++l) forms[6] |= omx::attention_takes_down(m, l) ? 1 : 0;
     return 0;
 }
 

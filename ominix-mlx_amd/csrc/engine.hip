@@ -141,7 +141,7 @@ int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) {
     }
     if (dev_alloc(m, &m->rope_cur, (size_t)D) || dev_alloc(m, &m->attn_gran, attn_step_ws_granules(m->H, D)) ||
         dev_alloc(m, &m->attn_xg, (size_t)m->H * D / 2 + 8) || dev_alloc(m, &m->chain_gran, (size_t)c.hidden_size / 2 + 8) ||
-        dev_alloc(m, &m->gateup_gran, (size_t)c.hidden_size / 2 + 8))
+        dev_alloc(m, &m->gateup_gran, (size_t)c.hidden_size / 2 + 8) || dev_alloc(m, &m->act_gran, (size_t)m->I / 2 + 8))
         return 1;
     if (dev_alloc(m, &m->step_seq, 16) || dev_alloc(m, &m->wait_abort, 16)) return 1;
     {
@@ -724,7 +724,9 @@ int omx_qwen3_stream(omx_qwen3 m, omx_stream* s) {
  * host receives [layers][attn splits][kv heads][16] = {block start, loads landed + q/k normed and roped, own chunk done, granules
  * stored, gathered and merged (consumer blocks), attention vector swept, O rows stored, partials parked; with gate/up in the launch
  * (csrc/attn_step.hip gateup_phase): [4] of an O block the hidden row swept, [7] first pair reduced, [8] / [9] last pair of wave 0 / of
- * wave 7 reduced, [10] NOT a stamp: the pairs the block's waves reduced (48 each); the rest 0}; *blocks = splits * kv heads */
+ * wave 7 reduced, [10] NOT a stamp: the pairs the block's waves reduced (48 each); with down + the next q/k/v in the launch as well
+ * (down_qkv_phase): [11] activation vector swept, [12] first down unit of wave 0 reduced, [13] residual row swept, [14] q/k/v rows stored,
+ * [15] NOT a stamp: the down units the block reduced (32) | the q/k/v rows it stored (24) << 32; the rest 0}; *blocks = splits * kv heads */
 int omx_qwen3_debug_trace_step(omx_qwen3 m, unsigned long long* host, size_t n_words, int* blocks) {
     OMX_REQUIRE(m && host && blocks, "omx_qwen3_debug_trace_step: null argument");
     StepState st;
@@ -755,7 +757,9 @@ int omx_qwen3_debug_trace_step(omx_qwen3 m, unsigned long long* host, size_t n_w
  * layer and its duration is split between `down` and `qkv` in proportion to their algorithmic bytes: the q/k/v pairs of layers 1 .. L-1
  * are never armed and never read, no class comes back as 0 and the classes still sum to the step.
  * Where gate/up + SwiGLU rides in the attention launch (attention_takes_gateup), that launch is booked on the attention class and its
- * duration is split the same way between `attention` (the K/V rows read at this position + the O matrix) and `gate_up`. */
+ * duration is split the same way between `attention` (the K/V rows read at this position + the O matrix) and `gate_up`.
+ * Where that launch is the layer's only one (attention_takes_down: + down + the next layer's q/k/v), the down pair of the layer is never
+ * armed either and the duration is split four ways, `down` and `qkv` taking their bytes' share as well. */
 int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
     OMX_REQUIRE(m && us && steps > 0, "omx_qwen3_time_step_kernels: bad arguments");
     OMX_REQUIRE(!m->cfg.quant_bits && m->cfg.num_experts == 0 && m->allreduce == nullptr, "omx_qwen3_time_step_kernels: dense bf16 single-rank models only");
@@ -791,11 +795,18 @@ int omx_qwen3_time_step_kernels(omx_qwen3 m, int steps, float* us) {
                 if (chain && l > 0 && l < L && k == KC_QKV) continue;   // done inside the previous layer's down launch
                 const bool gateup = l < L && !engine && !hybrid && attention_takes_gateup(m, l);
                 if (gateup && k == KC_GATE_UP) continue;         // done inside the layer's attention launch
+                const bool down = gateup && chain && attention_takes_down(m, l);
+                if (down && k == KC_DOWN) continue;              // likewise
                 OMX_HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
                 if (gateup && k == KC_ATTN) {   // one launch for two classes: shared by bytes
                     const double attn_bytes = 2.0 * m->Hkv * m->cfg.head_dim * (st.pos + 1) + o_bytes;
-                    sum[KC_GATE_UP] += ms * 1e3 * (gu_bytes / (gu_bytes + attn_bytes));
-                    ms *= (float)(attn_bytes / (gu_bytes + attn_bytes));
+                    const double all_bytes = gu_bytes + attn_bytes + (down ? down_bytes + qkv_bytes : 0.0);
+                    sum[KC_GATE_UP] += ms * 1e3 * (gu_bytes / all_bytes);
+                    if (down) {
+                        sum[KC_DOWN] += ms * 1e3 * (down_bytes / all_bytes);
+                        sum[KC_QKV] += ms * 1e3 * (qkv_bytes / all_bytes);
+                    }
+                    ms *= (float)(attn_bytes / all_bytes);
                 }
                 if (chain && l < L - 1 && k == KC_DOWN) {   // one launch for two classes: shared by bytes
                     sum[KC_QKV] += ms * 1e3 * (qkv_bytes / (qkv_bytes + down_bytes));

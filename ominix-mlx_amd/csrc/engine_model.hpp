@@ -170,6 +170,7 @@ struct omx_qwen3_ {
     uint64_t* attn_xg = nullptr;          // the merged attention vector as granules (O projection in the attention launch)
     uint64_t* chain_gran = nullptr;       // the residual row as granules (down + the next layer's q/k/v in one launch, gemv_chain.hip)
     uint64_t* gateup_gran = nullptr;      // the hidden row behind the O projection as granules (gate/up inside the attention launch)
+    uint64_t* act_gran = nullptr;         // the activation vector as granules (down + the next layer's q/k/v inside the attention launch)
     int attn_chunk = 0, attn_nsplit = 0, graph_tk_max = 0;
     unsigned long long* attn_trace = nullptr;   // set for one eager step by omx_qwen3_debug_trace_step
     bf16_t* verify_logits = nullptr;            // [verify_cap, V]: every row's logits of the last omx_qwen3_verify
@@ -294,6 +295,7 @@ bool attention_takes_oproj(omx_qwen3 m, int layer);
 bool any_layer_takes_oproj(omx_qwen3 m);
 bool down_takes_qkv(omx_qwen3 m);
 bool attention_takes_gateup(omx_qwen3 m, int layer);
+bool attention_takes_down(omx_qwen3 m, int layer);
 int step_engine_mode(omx_qwen3 m);
 bool step_engine_takes(omx_qwen3 m);
 int step_aql_mode(omx_qwen3 m);

@@ -280,6 +280,17 @@ bool attention_takes_gateup(omx_qwen3 m, int layer) {
     return attn_step_gateup_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size, m->I);
 }
 
+// [down + residual] of layer `layer` and [RMSNorm + q/k/v] of layer + 1 inside that launch as well (csrc/attn_step.hip, down_qkv_phase): layers
+// 0 .. L-2 are ONE launch each.  Both folds it joins must be on -- it inherits their gates: dense bf16, single rank, the launch-per-op form,
+// no rows-per-wave override, the 4096 / 12288 / 32 / 8 / 128 shape on 256 resident blocks, a q/k/v bias allowed -- and a give-up that
+// switches either off switches this off with it; OMX_ATTN_DOWN=0 keeps the two launches per layer
+bool attention_takes_down(omx_qwen3 m, int layer) {
+    const bool off = env_off("OMX_ATTN_DOWN");         // (read per call: tests flip it between engines of one process)
+    const omx_qwen3_config& c = m->cfg;
+    if (off || !m->act_gran || layer + 1 >= c.num_hidden_layers || !attention_takes_gateup(m, layer) || !down_takes_qkv(m)) return false;
+    return attn_step_down_ok(c.hidden_size, m->I, (m->H + 2 * m->Hkv) * c.head_dim);
+}
+
 // OMX_PEER_FUSED: a GEMV whose blocks poll their peers' stores must be resident as a whole -- a block waiting for a peer's row while
 // that peer's matching block waits for a free CU behind OUR unscheduled blocks never finishes (it gives up after 2^23 polls and voids
 // the step).  The streaming kernels hold at least two 4-wave blocks per CU (<= 256 VGPRs, a few KB of LDS); beyond that the standalone
@@ -291,8 +302,10 @@ static bool peer_fused_fits(omx_qwen3 m, int N, int K) {
 // the attention launch of layer l of a decode step (both the bf16 and the packed-weight step use the bf16 KV kernels);
 // resid / out != null: the layer's O projection + residual rides in the same launch (attention_takes_oproj); gateup: and its
 // [RMSNorm + gate/up + SwiGLU] behind that (attention_takes_gateup)
+// down: and the layer's [down + residual] (into `resid`'s buffer: the ping-pong partner of the row the O projection leaves) + the next
+// layer's [RMSNorm + q/k/v] behind that (attention_takes_down)
 static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* resid = nullptr, bf16_t* out = nullptr, float* out_f32 = nullptr,
-                             bool gateup = false) {
+                             bool gateup = false, bool down = false) {
     const omx_qwen3_config& c = m->cfg;
     const int D = c.head_dim;
     const LayerW& L = m->layers[l];
@@ -326,6 +339,14 @@ static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* re
     if (gateup) {
         a.gu_gate = L.gate; a.gu_up = L.up; a.gu_norm_w = L.post_ln; a.gu_out = m->act; a.gu_rows = m->I;
         a.hg = m->gateup_gran;
+    }
+    if (down) {
+        const LayerW& Ln = m->layers[l + 1];
+        a.dn_w = L.down; a.dn_out = const_cast<bf16_t*>(resid);   // every O row has consumed its residual before the first down row exists
+        a.ag = m->act_gran; a.rg = m->chain_gran;
+        a.nq_w0 = Ln.q; a.nq_w1 = Ln.k; a.nq_w2 = Ln.v;
+        a.nq_n0 = m->H * D; a.nq_n1 = m->Hkv * D; a.nq_rows = (m->H + 2 * m->Hkv) * D;
+        a.nq_norm_w = Ln.in_ln; a.nq_bias = Ln.qkv_bias; a.nq_out = m->qkv;
     }
     return launch_attn_step(a, D, s);
 }
@@ -615,7 +636,9 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
         time_next_launch(m, l, KC_ATTN);
         // [q/k RMSNorm + RoPE + cache append + split-KV SDPA + merge]  model.rs:172-210
         const bool gateup = fused_o && !tp && !pending && attention_takes_gateup(m, l);
-        if (enqueue_attention(m, l, s, fused_o ? h : nullptr, fused_o && !tp ? hn : nullptr, fused_o && tp ? m->partial_a : nullptr, gateup)) return 1;
+        const bool down = gateup && chain && attention_takes_down(m, l);   // ... + down + the next layer's q/k/v: the layer's only launch
+        if (enqueue_attention(m, l, s, fused_o ? h : nullptr, fused_o && !tp ? hn : nullptr, fused_o && tp ? m->partial_a : nullptr, gateup, down)) return 1;
+        if (down) continue;   // h: the residual stream leaving the layer (the down rows went into the buffer the layer entered on)
         if (fused_o && tp) {   // the rank's f32 partial of the O projection came out of the attention launch
             if (allreduce_sum(m, m->partial_a, hd)) return 1;
             pending = m->partial_a;

@@ -673,10 +673,10 @@ class Model:
 
     def step_forms(self) -> dict:
         """Which in-launch folds the next decode step would take (test hook, omx_qwen3_debug_step_forms)."""
-        f = (c_int * 6)()
+        f = (c_int * 7)()
         check(lib.omx_qwen3_debug_step_forms(self._h, f))
         return {"down_qkv": bool(f[0]), "attn_oproj": bool(f[1]), "step_engine": int(f[2]), "down_qkv_gave_up": bool(f[3]),
-                "attn_gateup": bool(f[4]), "attn_gateup_gave_up": bool(f[5])}
+                "attn_gateup": bool(f[4]), "attn_gateup_gave_up": bool(f[5]), "attn_down": bool(f[6])}
 
     def raise_give_up(self) -> None:
         """Set, from the host, the word a wait inside a launch raises when it gives up (test hook of the fallback ladder)."""

@@ -29,7 +29,11 @@ names = ["block start", "loads landed, q/k normed+roped", "own chunk done", "gra
 # Hop three is hidden when "first pair reduced" follows "hidden row swept" by less than a weight round trip.
 # Stamps 8 and 9: wave 0 and wave 7 done with their last pair (the pairs are drawn from a ticket counter in the block: the two end
 # together); word 10 is a count, not a stamp: the pairs the block's waves reduced (48).
+# down + the next layer's q/k/v inside the launch as well (OMX_ATTN_DOWN, layers 0 .. L-2): stamp 11 the activation vector swept into
+# LDS (hop four), 12 the first down unit of wave 0 -- the sweeping wave -- reduced, 13 the residual row swept (hop five), 14 the block's
+# q/k/v rows stored; word 15 is a count: the down units the block reduced (32) | the q/k/v rows it stored (24) << 32.
 gateup = m.step_forms()["attn_gateup"]
+down = m.step_forms()["attn_down"]
 n_cons = H   # consumer blocks: one per query head, the launch's first blocks
 events = [(ev, nm, slice(None)) for ev, nm in enumerate(names)]
 if gateup:
@@ -38,10 +42,15 @@ if gateup:
     events.insert(7, (4, "gate/up: hidden row swept into LDS (O blocks)", slice(n_cons, None)))
     events.append((8, "gate/up: last pair of wave 0 reduced", slice(None)))
     events.append((9, "gate/up: last pair of wave 7 reduced", slice(None)))
-print(f"{nb} blocks per launch, {L} layers, ctx {ctx}, gate/up in the launch: {gateup}")
+if down:
+    events.append((11, "down: activation vector swept into LDS", slice(None)))
+    events.append((12, "down: first unit reduced (wave 0)", slice(None)))
+    events.append((13, "q/k/v: residual row swept into LDS", slice(None)))
+    events.append((14, "q/k/v: rows stored", slice(None)))
+print(f"{nb} blocks per launch, {L} layers, ctx {ctx}, gate/up in the launch: {gateup}, down + next q/k/v in the launch: {down}")
 for ev, nm, blocks in events:
     rows = []
-    for l in range(1, L):
+    for l in range(1, L - 1 if ev >= 11 else L):
         t0 = t[l, :, 0][t[l, :, 0] > 0].min()
         v = t[l, blocks, ev]
         v = v[v > 0]
@@ -50,10 +59,13 @@ for ev, nm, blocks in events:
     if rows:
         allv = np.concatenate(rows)
         print(f"  {nm:48s} median {np.median(allv):6.2f} us   p90 {np.percentile(allv, 90):6.2f}   max(median over layers) "
-              f"{np.median([r.max() for r in rows]):6.2f}   n/layer {allv.size // (L - 1)}")
+              f"{np.median([r.max() for r in rows]):6.2f}   n/layer {allv.size // len(rows)}")
 if gateup:
     tail = (t[1:, :, 8] - t[1:, :, 9]) / 100.0
     print(f"  wave 0 behind wave 7 at the end of a block: median {np.median(tail):6.2f} us   p90 {np.percentile(tail, 90):6.2f}   "
           f"max {tail.max():6.2f}")
     print(f"  pairs reduced per block: min {t[:, :, 10].min()}   max {t[:, :, 10].max()}")
+if down:
+    u, r = t[:L - 1, :, 15] & 0xFFFFFFFF, t[:L - 1, :, 15] >> 32
+    print(f"  down units reduced per block: min {u.min()}   max {u.max()};   q/k/v rows stored per block: min {r.min()}   max {r.max()}")
 m.close()
