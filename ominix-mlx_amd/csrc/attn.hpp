@@ -1,6 +1,7 @@
 // Attention launchers shared by the per-op ABI (sdpa.hip) and the decode engine.
 #pragma once
 #include "common.hpp"
+#include "gemv.hpp"
 
 namespace omx {
 
@@ -73,13 +74,10 @@ struct AttnStepArgs {
     bf16_t* dn_out;             // [o_rows] = bf16(hidden row + bf16(dn_w . gu_out)): the residual stream leaving the layer (model.rs:327)
     uint64_t* ag;               // granules [gu_rows / 2]: {two packed bf16 of gu_out, tag}
     uint64_t* rg;               // granules [o_rows / 2]: {two packed bf16 of dn_out, tag}
-    const bf16_t* nq_w0;        // the next layer's stacked q | k | v matrices, [nq_n0 | nq_n1 | nq_rows - nq_n0 - nq_n1] rows of o_rows
-    const bf16_t* nq_w1;
-    const bf16_t* nq_w2;
-    int nq_n0, nq_n1, nq_rows;
+    StackedRows nq;             // the next layer's stacked q | k | v matrices, rows of o_rows
     const bf16_t* nq_norm_w;    // [o_rows] the next layer's input RMSNorm weight
-    const bf16_t* nq_bias;      // [nq_rows] or null (Qwen2 wiring)
-    bf16_t* nq_out;             // [nq_rows]: may be `qkv` itself -- every block has consumed its q/k/v long before the first row is stored
+    const bf16_t* nq_bias;      // [nq.rows] or null (Qwen2 wiring)
+    bf16_t* nq_out;             // [nq.rows]: may be `qkv` itself -- every block has consumed its q/k/v long before the first row is stored
 };
 bool attn_step_down_ok(int o_rows, int gu_rows, int nq_rows);
 bool attn_step_oproj_ok(int H, int Hkv, int D, int nsplit, int o_rows);

@@ -42,7 +42,6 @@ namespace {
 
 constexpr int kBlock = 512;
 constexpr int kWaves = 8;
-constexpr unsigned kSpinLimit = 1u << 15;   // gather passes (~1 us each) before a consumer gives up
 
 template <int N>
 __device__ __forceinline__ float swap_halves(float v) {     // value of lane (l ^ N/2) of the aligned N-lane group
@@ -94,7 +93,7 @@ __device__ __forceinline__ void gather_head(const AttnStepArgs& a, const uint64_
             all = all && ok_b[b];
         }
         if (all) break;
-        if (spins >= kSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
+        if (spins >= kGranuleSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
             if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
         }
@@ -154,16 +153,6 @@ __device__ __forceinline__ float dot8_16(const u32x4 a, const u32x4 b) {
     return d;
 }
 
-// the O GEMV's accumulation (gemv.hip dot8): lo then hi of each dword, one fma chain
-__device__ __forceinline__ float dot8_chain(const u32x4 w, const u32x4 xp, float acc) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        acc = fmaf(bf16lo(w[i]), bf16lo(xp[i]), acc);
-        acc = fmaf(bf16hi(w[i]), bf16hi(xp[i]), acc);
-    }
-    return acc;
-}
-
 constexpr int kORows = 4;   // most O-projection rows a wave holds (attn_step_oproj_ok)
 
 // ---- [RMSNorm + gate/up + SwiGLU] of the layer behind the O projection (attn_step_kernel, GU > 0) ----
@@ -197,6 +186,7 @@ __device__ __forceinline__ void gateup_issue(const AttnStepArgs& a, u32x4 (*w)[k
 }
 
 // the merged attention vector: awaited, then swept from its granules into LDS (natural element order); a block-wide step.
+// (Written out, not sweep_granules: all 512 threads share the sweep and meet in __syncthreads_and between passes.)
 // (With gate/up in the launch, the first pair of waves 1..7 asked for right behind a peeled first pass of this sweep, tags read behind a
 //  counted wait: measured SLOWER than asking once the O rows are consumed -- EXPERIMENTS C-3 -- and not in the tree.)
 template <int NVW>
@@ -207,7 +197,7 @@ __device__ __forceinline__ void oproj_await_vector(const AttnStepArgs& a, u32x4*
     if (wave == 0) {
         constexpr int SEGS = NVW * 8;                                  // consumer waves: H * D / 64
         const uint64_t* probe = a.xg + (size_t)min(lane, SEGS - 1) * 32 + 31;
-        for (unsigned spins = 0; spins < kSpinLimit; ++spins) {
+        for (unsigned spins = 0; spins < kGranuleSpinLimit; ++spins) {
             const unsigned long long g = ld_granule(probe);
             if (__all((unsigned)(g >> 32) == tag)) break;
             __builtin_amdgcn_s_sleep(4);
@@ -234,7 +224,7 @@ __device__ __forceinline__ void oproj_await_vector(const AttnStepArgs& a, u32x4*
             }
         }
         if (__syncthreads_and(done)) break;                          // also orders the LDS writes before the reads below
-        if (spins >= kSpinLimit) {
+        if (spins >= kGranuleSpinLimit) {
             if (threadIdx.x == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             break;
         }
@@ -242,27 +232,14 @@ __device__ __forceinline__ void oproj_await_vector(const AttnStepArgs& a, u32x4*
     }
 }
 
-// a pair in a register set reduced against the normalised row in LDS: gemv.hip's OMX_COMPUTE with NR = 2, then its SwiGLU epilogue
+// a pair in a register set reduced against the normalised row in LDS: rows_dot with NR = 2, then gemv.hip's SwiGLU epilogue
 // (DN: the value is parked in LDS at its ticket's slot as well, for the activation hop of down_qkv_phase)
 template <bool DN = false>
 __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4 (*w)[kGuNV], const u32x4* xs, int pair, int lane,
                                               uint16_t* park = nullptr) {
     typedef Act16<false> A;
-    float acc[2] = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < kGuNV; ++j) {
-        const u32x4 xp = xs[j * 64 + lane];
-        float xf[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            xf[2 * q] = A::lo(xp[q]);
-            xf[2 * q + 1] = A::hi(xp[q]);
-        }
-#pragma unroll
-        for (int r = 0; r < 2; ++r) acc[r] = dot8(w[r][j], xf, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) acc[r] = wave_sum(acc[r]);
+    float acc[2];
+    rows_dot<false, 2, kGuNV>(w, xs, lane, acc);
     if constexpr (DN) {
         if (lane == 0) {
             const uint16_t v = epi_bits<EPI_SWIGLU, A>(acc[0], acc[1], (bf16_t)0, 0);
@@ -312,68 +289,12 @@ __device__ __forceinline__ void down_issue(const AttnStepArgs& a, u32x4 (*w)[kDn
 
 // a unit in a register set reduced against its quarter of the activation vector in LDS: gemv_chain.hip's OMX_COMPUTE
 __device__ __forceinline__ void down_reduce(const u32x4 (*w)[kDnNV], const u32x4* xa, float* part, int u, int lane) {
-    typedef Act16<false> A;
-    float acc[2] = {0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < kDnNV; ++j) {
-        const u32x4 xp = xa[(u & 3) * (kDnNV * 64) + j * 64 + lane];
-        float xf[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            xf[2 * q] = A::lo(xp[q]);
-            xf[2 * q + 1] = A::hi(xp[q]);
-        }
-#pragma unroll
-        for (int r = 0; r < 2; ++r) acc[r] = dot8(w[r][j], xf, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < 2; ++r) acc[r] = wave_sum(acc[r]);
+    float acc[2];
+    rows_dot<false, 2, kDnNV>(w, xa + (u & 3) * (kDnNV * 64), lane, acc);
     if (lane == 0) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) part[(2 * (u >> 2) + r) * 4 + (u & 3)] = acc[r];
     }
-}
-
-// a wave brings its share -- part `part` of NW -- of a vector of `N2` granules into LDS (natural element order): it watches one granule per
-// lane politely (the last of every GPL-th run of its share), then asks for all of its GPL granules per lane in ONE pass (a pass is a round trip
-// through a memory system that is busy with the weight streams: three passes of 32 cost the activation hop 8 us, EXPERIMENTS C-4) and
-// re-reads them until every tag matches
-template <int N2, int NW>
-__device__ __forceinline__ void sweep_vector(const AttnStepArgs& a, const uint64_t* gr, unsigned* sx, int part, unsigned tag, int lane) {
-    constexpr int GPL = N2 / NW / 64;   // granules per lane
-    static_assert(N2 % (NW * 64) == 0 && GPL <= 48, "whole lanes, at most 96 registers of granules");
-    gr += (size_t)part * (N2 / NW);
-    sx += part * (N2 / NW);
-    for (unsigned spins = 0; spins < kSpinLimit; ++spins) {
-        const unsigned long long g = ld_granule(gr + (size_t)lane * GPL + (GPL - 1));
-        if (__all((unsigned)(g >> 32) == tag)) break;
-        __builtin_amdgcn_s_sleep(4);
-    }
-    unsigned long long g[GPL];
-    for (unsigned spins = 0;; ++spins) {
-#pragma unroll
-        for (int i = 0; i < GPL; ++i) g[i] = ld_granule(gr + (size_t)i * 64 + lane);
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
-        if (__all(ok)) break;
-        if (spins >= kSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
-            if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
-        __builtin_amdgcn_s_sleep(4);
-    }
-#pragma unroll
-    for (int i = 0; i < GPL; ++i) sx[i * 64 + lane] = (unsigned)g[i];
-}
-
-__device__ __forceinline__ const bf16_t* next_qkv_row(const AttnStepArgs& a, int row) {
-    // wave-uniform: which of the stacked matrices owns this row
-    if (row < a.nq_n0) return a.nq_w0 + (size_t)row * kGuHidden;
-    row -= a.nq_n0;
-    if (row < a.nq_n1) return a.nq_w1 + (size_t)row * kGuHidden;
-    row -= a.nq_n1;
-    return a.nq_w2 + (size_t)row * kGuHidden;
 }
 
 // Every wave of every block of a DN launch ends here, behind its last (gate, up) pair; `res2`: the residual pair of rows
@@ -394,14 +315,14 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
     for (int i = 0; i < PV; ++i) nwv[i] = *(reinterpret_cast<const u32x4*>(a.nq_norm_w) + (threadIdx.x & 255) + i * 256);
     bf16_t ob[kDnQRows];
 #pragma unroll
-    for (int r = 0; r < kDnQRows; ++r) ob[r] = *(a.nq_bias ? a.nq_bias + min(q_row0 + r, a.nq_rows - 1) : a.nq_norm_w);   // (one load either way: no branch)
+    for (int r = 0; r < kDnQRows; ++r) ob[r] = *(a.nq_bias ? a.nq_bias + min(q_row0 + r, a.nq.rows - 1) : a.nq_norm_w);   // (one load either way: no branch)
     u32x4 dA[2][kDnNV], dB[2][kDnNV];
     int tA = 0, tB = 0;
     u32x4 qw[kDnQRows][kGuNV];
     auto issue_qkv = [&](const int r0, const int r1) {
 #pragma unroll
         for (int r = r0; r < r1; ++r) {
-            const u32x4* p = reinterpret_cast<const u32x4*>(next_qkv_row(a, min(q_row0 + r, a.nq_rows - 1)));   // clamp: surplus waves re-read the last row
+            const u32x4* p = reinterpret_cast<const u32x4*>(a.nq.row_ptr(min(q_row0 + r, a.nq.rows - 1), kGuHidden));   // clamp: surplus waves re-read the last row
 #pragma unroll
             for (int j = 0; j < kGuNV; ++j) qw[r][j] = ld_nt(p + j * 64 + lane);
         }
@@ -422,7 +343,7 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
     if (sweeper) {
         if (wave == 0 && lane < kGuBlockPairs / 2)
             st_granule_u32(a.ag + (size_t)blk * (kGuBlockPairs / 2) + lane, tag, reinterpret_cast<const unsigned*>(sm_dn + kDnParkOff)[lane]);
-        sweep_vector<kDnInter / 2, 2>(a, a.ag, reinterpret_cast<unsigned*>(xa), __builtin_amdgcn_readfirstlane(wave) / (kWaves / 2), tag, lane);
+        sweep_granules<kDnInter / 2, 2>(a.ag, reinterpret_cast<unsigned*>(xa), __builtin_amdgcn_readfirstlane(wave) / (kWaves / 2), tag, lane, a.abort_flag);
         if (TRACE && threadIdx.x == 0) tr[11] = wall_clock64();
         tA = down_claim(sm_gu, lane);
         down_issue(a, dA, row_begin, tA, lane);
@@ -434,6 +355,7 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
     down_reduce(dA, xa, part, tA, lane);
     if (TRACE && threadIdx.x == 0) tr[12] = wall_clock64();
     // the loop of gateup_phase: wave-uniform branches over two named sets, the ticket of a refill drawn one reduce ahead
+    // (written out at both places: hipcc's counted waits depend on the two named register sets, EXPERIMENTS C-3)
     int n_reduced = 1;
     int nA = down_claim(sm_gu, lane), nB;
     for (;;) {
@@ -464,44 +386,22 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
         if (lane < kDnBlockRows / 2) {
             // rows 2 * lane and 2 * lane + 1 of the block: the pair leaves twice, to the ping-pong buffer (the next attention launch reads it
             // as its residual) and as a tagged granule for the q/k/v rows of every block
-            float v[2] = {0.f, 0.f};
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) v[e] += part[(2 * lane + e) * 4 + w];
-            }
-            const uint32_t o2 = (uint32_t)epi_bits<EPI_RESIDUAL, A>(v[0], 0.f, (bf16_t)(res2 & 0xFFFFu), 0) |
-                                ((uint32_t)epi_bits<EPI_RESIDUAL, A>(v[1], 0.f, (bf16_t)(res2 >> 16), 0) << 16);
+            const uint32_t o2 = residual_pair<A, 4>(part + 2 * lane * 4, res2);
             reinterpret_cast<uint32_t*>(a.dn_out)[row_begin / 2 + lane] = o2;
             st_granule_u32(a.rg + row_begin / 2 + lane, tag, o2);
         }
-        sweep_vector<kGuHidden / 2, 1>(a, a.rg, reinterpret_cast<unsigned*>(xs), 0, tag, lane);
+        sweep_granules<kGuHidden / 2, 1>(a.rg, reinterpret_cast<unsigned*>(xs), 0, tag, lane, a.abort_flag);
         if (TRACE && lane == 0) tr[13] = wall_clock64();
     }
     lds_barrier();   // the residual row is in LDS
     rmsnorm_in_lds<A, PV>(xs, red, nwv, kGuHidden, a.eps, threadIdx.x < 256);
     float acc[kDnQRows];
-#pragma unroll
-    for (int r = 0; r < kDnQRows; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int j = 0; j < kGuNV; ++j) {
-        const u32x4 xp = xs[j * 64 + lane];
-        float xf[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            xf[2 * q] = A::lo(xp[q]);
-            xf[2 * q + 1] = A::hi(xp[q]);
-        }
-#pragma unroll
-        for (int r = 0; r < kDnQRows; ++r) acc[r] = dot8(qw[r][j], xf, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < kDnQRows; ++r) acc[r] = wave_sum(acc[r]);
+    rows_dot<false, kDnQRows, kGuNV>(qw, xs, lane, acc);
     if (lane == 0) {
         int stored = 0;
 #pragma unroll
         for (int r = 0; r < kDnQRows; ++r)
-            if (q_row0 + r < a.nq_rows) {
+            if (q_row0 + r < a.nq.rows) {
                 a.nq_out[q_row0 + r] = A::bits(a.nq_bias ? acc[r] + A::val(ob[r]) : acc[r]);
                 ++stored;
             }
@@ -553,8 +453,9 @@ __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, f
     lds_barrier();   // every wave is done with the attention vector in `xs` and has parked its O rows
     if (wave == 0) {
         if (lane < pub_rows / 2) st_granule_u32(a.hg + pub_row0 / 2 + lane, tag, reinterpret_cast<const unsigned*>(sm_pub)[lane]);
+        // (written out, not sweep_granules: the first pass is straight-line, its tags read behind a counted wait)
         constexpr int GPL = kGuHidden / 2 / 64;       // granules per lane
-        for (unsigned spins = 0; spins < kSpinLimit; ++spins) {   // politely: one granule of every eighth producer, a sleep between looks
+        for (unsigned spins = 0; spins < kGranuleSpinLimit; ++spins) {   // politely: one granule of every eighth producer, a sleep between looks
             const unsigned long long g = ld_granule(a.hg + (size_t)lane * GPL + (GPL - 1));
             if (__all((unsigned)(g >> 32) == tag)) break;
             __builtin_amdgcn_s_sleep(4);
@@ -578,7 +479,7 @@ __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, f
 #pragma unroll
                 for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
                 if (__all(ok)) break;
-                if (spins >= kSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
+                if (spins >= kGranuleSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
                     if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     break;
                 }
@@ -618,6 +519,7 @@ __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, f
     // stay counted (a refill skipped under a condition makes the wait that follows drain the set in flight).  The ticket of a refill is
     // drawn one reduce AHEAD (nA, nB): the LDS round trip hides behind the reduce, and with the draw at the loop's head hipcc drained the
     // set in flight there (s_waitcnt vmcnt(0) in front of the draw's first VALU write): 346.4 against 347.5 tok/s, EXPERIMENTS C-3
+    // (written out here and in down_qkv_phase, not a template over the sets: the counted waits depend on the two NAMED sets)
     int n_reduced = 1;
     int nA = gateup_claim(sm_gu, lane), nB;
     for (;;) {
@@ -679,16 +581,7 @@ __device__ __forceinline__ void oproj_phase(const AttnStepArgs& a, u32x4* sm_x, 
     oproj_await_vector<NVW>(a, sm_x, tag, lane, wave);
     if (tr && threadIdx.x == 0) tr[5] = wall_clock64();
     float acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NVW; ++j) {
-        const u32x4 xp = sm_x[j * 64 + lane];
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[r] = dot8_chain(ow[r][j], xp, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
+    rows_dot<false, R, NVW>(ow, sm_x, lane, acc);
     if (lane == 0) {
 #pragma unroll
         for (int r = 0; r < R; ++r)
@@ -1133,6 +1026,16 @@ bool attn_step_down_ok(int o_rows, int gu_rows, int nq_rows) {
     return o_rows == 256 * kDnBlockRows && gu_rows == kDnInter && nq_rows > (kDnQRows - 1) * waves && nq_rows <= kDnQRows * waves;
 }
 
+// one instantiation's launch: the dynamic-LDS attribute where the block needs more than the default 48 KB, the (timed or recorded) launch
+template <int D, int GT, bool TRACE, int NVW, bool F16 = false, bool GU = false, bool DN = false>
+static int launch_instance(dim3 grid, size_t shmem, hipStream_t s, const AttnStepArgs& a) {
+    if (shmem > 48 * 1024)
+        OMX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_step_kernel<D, GT, TRACE, NVW, F16, GU, DN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    OMX_LAUNCH_TIMED((attn_step_kernel<D, GT, TRACE, NVW, F16, GU, DN>), grid, dim3(kBlock), shmem, s, a);
+    OMX_LAUNCH_CHECK();
+    return 0;
+}
+
 int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
     AttnStepArgs a = a_in;
     const int G = a.H / a.Hkv;
@@ -1161,36 +1064,11 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
                         attn_step_gateup_ok(a.H, a.Hkv, D, a.nsplit, a.o_rows, a.gu_rows),
                     "decode attention + gate/up: shape does not qualify (%d blocks, %d O rows, %d pairs)", a.Hkv * a.nsplit, a.o_rows, a.gu_rows);
     if (a.dn_w)
-        OMX_REQUIRE(a.gu_gate && a.dn_out && a.ag && a.rg && a.nq_w0 && a.nq_w1 && a.nq_w2 && a.nq_norm_w && a.nq_out &&
-                        a.nq_n0 > 0 && a.nq_n1 > 0 && a.nq_rows > a.nq_n0 + a.nq_n1 && attn_step_down_ok(a.o_rows, a.gu_rows, a.nq_rows),
-                    "decode attention + down + q/k/v: shape does not qualify (%d rows, %d pairs, %d q/k/v rows)", a.o_rows, a.gu_rows, a.nq_rows);
-    const dim3 grid(a.Hkv, a.nsplit), block(kBlock);
+        OMX_REQUIRE(a.gu_gate && a.dn_out && a.ag && a.rg && a.nq.w0 && a.nq.w1 && a.nq.w2 && a.nq_norm_w && a.nq_out &&
+                        a.nq.n0 > 0 && a.nq.n1 > 0 && a.nq.rows > a.nq.n0 + a.nq.n1 && attn_step_down_ok(a.o_rows, a.gu_rows, a.nq.rows),
+                    "decode attention + down + q/k/v: shape does not qualify (%d rows, %d pairs, %d q/k/v rows)", a.o_rows, a.gu_rows, a.nq.rows);
+    const dim3 grid(a.Hkv, a.nsplit);
     const int gt = G <= 1 ? 1 : G <= 2 ? 2 : G <= 4 ? 4 : 8;
-#define OMX_ATTN_LAUNCH(DD, GG, TT, NN)                                                                                  \
-    {                                                                                                                    \
-        if (shmem > 48 * 1024)                                                                                           \
-            OMX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_step_kernel<DD, GG, TT, NN>,                            \
-                                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                  \
-        OMX_LAUNCH_TIMED((attn_step_kernel<DD, GG, TT, NN>), grid, block, shmem, s, a);                                  \
-        OMX_LAUNCH_CHECK();                                                                                              \
-        return 0;                                                                                                        \
-    }
-#define OMX_ATTN_LAUNCH_GU(TT)                                                                                           \
-    {                                                                                                                    \
-        OMX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_step_kernel<128, 4, TT, kGuNV, false, true>,                 \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                      \
-        OMX_LAUNCH_TIMED((attn_step_kernel<128, 4, TT, kGuNV, false, true>), grid, block, shmem, s, a);                  \
-        OMX_LAUNCH_CHECK();                                                                                              \
-        return 0;                                                                                                        \
-    }
-#define OMX_ATTN_LAUNCH_DN(TT)                                                                                           \
-    {                                                                                                                    \
-        OMX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_step_kernel<128, 4, TT, kGuNV, false, true, true>,           \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));                      \
-        OMX_LAUNCH_TIMED((attn_step_kernel<128, 4, TT, kGuNV, false, true, true>), grid, block, shmem, s, a);            \
-        OMX_LAUNCH_CHECK();                                                                                              \
-        return 0;                                                                                                        \
-    }
 #define OMX_ATTN_STEP_CASE(DD, GG)                                                                                       \
     if (D == DD && gt == GG) {                                                                                           \
         const size_t shmem = ((size_t)kWaves * (64 / (DD / 8)) * GG * DD + 2 * kWaves * GG) * sizeof(float) +            \
@@ -1199,48 +1077,38 @@ int launch_attn_step(const AttnStepArgs& a_in, int D, hipStream_t s) {
         if (a.gu_gate) {   /* gate/up behind the O projection: one shape (attn_step_gateup_ok) */                         \
             if constexpr (DD == 128 && GG == 4) {                                                                        \
                 static_assert(kDnLdsBytes <= kWaves * 4 * 4 * 128 * 4, "the down phase lives in the split-merge area");  \
-                if (a.dn_w && a.trace) OMX_ATTN_LAUNCH_DN(true)                                                          \
-                if (a.dn_w) OMX_ATTN_LAUNCH_DN(false)                                                                    \
-                if (a.trace) OMX_ATTN_LAUNCH_GU(true)                                                                    \
-                OMX_ATTN_LAUNCH_GU(false)                                                                                \
+                if (a.dn_w && a.trace) return launch_instance<128, 4, true, kGuNV, false, true, true>(grid, shmem, s, a); \
+                if (a.dn_w) return launch_instance<128, 4, false, kGuNV, false, true, true>(grid, shmem, s, a);          \
+                if (a.trace) return launch_instance<128, 4, true, kGuNV, false, true>(grid, shmem, s, a);                \
+                return launch_instance<128, 4, false, kGuNV, false, true>(grid, shmem, s, a);                            \
             }                                                                                                            \
             return set_error("decode attention + gate/up: no instantiation for head_dim %d, group %d", DD, GG);         \
         }                                                                                                                \
         if (a.trace && !qo) {   /* timeline builds: the plain kernel and the widest fused one */                        \
-            if (nvw == 0) OMX_ATTN_LAUNCH(DD, GG, true, 0)                                                               \
-            if (nvw == 8) OMX_ATTN_LAUNCH(DD, GG, true, 8)                                                               \
+            if (nvw == 0) return launch_instance<DD, GG, true, 0>(grid, shmem, s, a);                                    \
+            if (nvw == 8) return launch_instance<DD, GG, true, 8>(grid, shmem, s, a);                                    \
             return set_error("decode attention: no traced instantiation for H*D = %d", a.H * DD);                       \
         }                                                                                                                \
         if (qo) {                                                                                                        \
-            if (nvw == 4) OMX_ATTN_LAUNCH(DD, GG, false, 104)                                                            \
-            OMX_ATTN_LAUNCH(DD, GG, false, 108)                                                                          \
+            if (nvw == 4) return launch_instance<DD, GG, false, 104>(grid, shmem, s, a);                                 \
+            return launch_instance<DD, GG, false, 108>(grid, shmem, s, a);                                               \
         }                                                                                                                \
         if (a.f16) {   /* a float16 checkpoint's model: float16 q / k / v, cache and output; D = 128, no O projection in the launch */ \
             if constexpr (DD == 128) {                                                                                   \
-                if (nvw == 0) {                                                                                          \
-                    if (shmem > 48 * 1024)                                                                               \
-                        OMX_HIP_CHECK(hipFuncSetAttribute((const void*)attn_step_kernel<DD, GG, false, 0, true>,        \
-                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));      \
-                    OMX_LAUNCH_TIMED((attn_step_kernel<DD, GG, false, 0, true>), grid, block, shmem, s, a);              \
-                    OMX_LAUNCH_CHECK();                                                                                  \
-                    return 0;                                                                                            \
-                }                                                                                                        \
+                if (nvw == 0) return launch_instance<DD, GG, false, 0, true>(grid, shmem, s, a);                         \
             }                                                                                                            \
             return set_error("decode attention: float16 models take head_dim 128 without the O projection in the launch"); \
         }                                                                                                                \
-        if (nvw == 0) OMX_ATTN_LAUNCH(DD, GG, false, 0)                                                                  \
-        if (nvw == 1) OMX_ATTN_LAUNCH(DD, GG, false, 1)                                                                  \
-        if (nvw == 2) OMX_ATTN_LAUNCH(DD, GG, false, 2)                                                                  \
-        if (nvw == 4) OMX_ATTN_LAUNCH(DD, GG, false, 4)                                                                  \
-        if (nvw == 7) OMX_ATTN_LAUNCH(DD, GG, false, 7)                                                                  \
-        OMX_ATTN_LAUNCH(DD, GG, false, 8)                                                                                \
+        if (nvw == 0) return launch_instance<DD, GG, false, 0>(grid, shmem, s, a);                                       \
+        if (nvw == 1) return launch_instance<DD, GG, false, 1>(grid, shmem, s, a);                                       \
+        if (nvw == 2) return launch_instance<DD, GG, false, 2>(grid, shmem, s, a);                                       \
+        if (nvw == 4) return launch_instance<DD, GG, false, 4>(grid, shmem, s, a);                                       \
+        if (nvw == 7) return launch_instance<DD, GG, false, 7>(grid, shmem, s, a);                                       \
+        return launch_instance<DD, GG, false, 8>(grid, shmem, s, a);                                                     \
     }
     OMX_ATTN_STEP_CASE(128, 1) OMX_ATTN_STEP_CASE(128, 2) OMX_ATTN_STEP_CASE(128, 4) OMX_ATTN_STEP_CASE(128, 8)
     OMX_ATTN_STEP_CASE(64, 1) OMX_ATTN_STEP_CASE(64, 2) OMX_ATTN_STEP_CASE(64, 4) OMX_ATTN_STEP_CASE(64, 8)
 #undef OMX_ATTN_STEP_CASE
-#undef OMX_ATTN_LAUNCH_DN
-#undef OMX_ATTN_LAUNCH_GU
-#undef OMX_ATTN_LAUNCH
     return set_error("decode attention: head_dim %d unsupported (64 or 128)", D);
 }
 

@@ -255,14 +255,28 @@ bool any_layer_takes_oproj(omx_qwen3 m) {
     return false;
 }
 
+// what the folds of the dense step share: dense bf16 weights, a single rank without a communicator, no experts, the launch-per-op form
+static bool dense_bf16_single_rank_per_op(omx_qwen3 m) {
+    const omx_qwen3_config& c = m->cfg;
+    if (c.quant_bits != 0 || m->f16 || c.num_experts > 0 || c.tp_size > 1 || c.ep_size > 1 || m->allreduce != nullptr) return false;
+    return step_engine_mode(m) == 0;
+}
+
+// a layer's stacked q | k | v matrices as the kernels that stream them take them
+static StackedRows qkv_rows(omx_qwen3 m, int layer) {
+    const LayerW& L = m->layers[layer];
+    const int D = m->cfg.head_dim;
+    return StackedRows{L.q, L.k, L.v, m->H * D, m->Hkv * D, (m->H + 2 * m->Hkv) * D};
+}
+
 // down + residual of a layer and [RMSNorm + q/k/v] of the next one as ONE launch (csrc/gemv_chain.hip): the dense bf16 step of a single rank
 // on its launch-per-op form, no rows-per-wave override of the two GEMVs it stands for, a shape the kernel has a register layout for and a
 // grid that is resident as a whole (every workgroup of that launch waits on all others); OMX_DOWN_QKV=0 keeps the two launches
 bool down_takes_qkv(omx_qwen3 m) {
     const bool off = env_off("OMX_DOWN_QKV");          // (read per call: tests flip it between engines of one process)
     const omx_qwen3_config& c = m->cfg;
-    if (off || m->chain_disabled || c.quant_bits != 0 || m->f16 || c.num_experts > 0 || c.tp_size > 1 || c.ep_size > 1 || m->allreduce != nullptr) return false;
-    if (step_engine_mode(m) != 0 || env_int("OMX_GEMV_RPW_QKV", 0) != 0 || env_int("OMX_GEMV_RPW_DOWN", 0) != 0) return false;
+    if (off || m->chain_disabled || !dense_bf16_single_rank_per_op(m)) return false;
+    if (env_int("OMX_GEMV_RPW_QKV", 0) != 0 || env_int("OMX_GEMV_RPW_DOWN", 0) != 0) return false;
     if (!m->chain_gran || !gemv_chain_ok(c.hidden_size, m->I, (m->H + 2 * m->Hkv) * c.head_dim)) return false;
     return gemv_chain_grid(c.hidden_size) <= kGemvChainBlocksPerCU * m->cus;
 }
@@ -274,8 +288,8 @@ bool down_takes_qkv(omx_qwen3 m) {
 bool attention_takes_gateup(omx_qwen3 m, int layer) {
     const bool off = env_off("OMX_ATTN_GATEUP");       // (read per call: tests flip it between engines of one process)
     const omx_qwen3_config& c = m->cfg;
-    if (off || m->gateup_disabled || c.quant_bits != 0 || m->f16 || c.num_experts > 0 || c.tp_size > 1 || c.ep_size > 1 || m->allreduce != nullptr) return false;
-    if (step_engine_mode(m) != 0 || env_int("OMX_GEMV_RPW_O", 0) != 0 || env_int("OMX_GEMV_RPW_GU", 0) != 0) return false;
+    if (off || m->gateup_disabled || !dense_bf16_single_rank_per_op(m)) return false;
+    if (env_int("OMX_GEMV_RPW_O", 0) != 0 || env_int("OMX_GEMV_RPW_GU", 0) != 0) return false;
     if (!m->gateup_gran || m->cus < 256 || !attention_takes_oproj(m, layer)) return false;
     return attn_step_gateup_ok(m->H, m->Hkv, c.head_dim, m->attn_nsplit, c.hidden_size, m->I);
 }
@@ -344,8 +358,7 @@ static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* re
         const LayerW& Ln = m->layers[l + 1];
         a.dn_w = L.down; a.dn_out = const_cast<bf16_t*>(resid);   // every O row has consumed its residual before the first down row exists
         a.ag = m->act_gran; a.rg = m->chain_gran;
-        a.nq_w0 = Ln.q; a.nq_w1 = Ln.k; a.nq_w2 = Ln.v;
-        a.nq_n0 = m->H * D; a.nq_n1 = m->Hkv * D; a.nq_rows = (m->H + 2 * m->Hkv) * D;
+        a.nq = qkv_rows(m, l + 1);
         a.nq_norm_w = Ln.in_ln; a.nq_bias = Ln.qkv_bias; a.nq_out = m->qkv;
     }
     return launch_attn_step(a, D, s);
@@ -617,10 +630,10 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
         const LayerW& L = m->layers[l];
         if (!(chain && l > 0)) {   // [RMSNorm + QKV GEMV]  model.rs:168-170,324
             GemvArgs a = {};
-            a.w0 = L.q; a.n0 = m->H * D;
-            a.w1 = L.k; a.n1 = m->Hkv * D;
-            a.w2 = L.v; a.n2 = m->Hkv * D;
-            a.N = (m->H + 2 * m->Hkv) * D;
+            const StackedRows q = qkv_rows(m, l);
+            a.w0 = q.w0; a.w1 = q.w1; a.w2 = q.w2;
+            a.n0 = q.n0; a.n1 = q.n1; a.n2 = q.rows - q.n0 - q.n1;
+            a.N = q.rows;
             a.K = hd;
             a.x = h; a.x_partial = pending; a.x_partial_n = pending_n; a.x_out = pending ? hn : nullptr;
             a.norm_w = L.in_ln; a.eps = c.rms_norm_eps;
@@ -723,10 +736,7 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             a.x = m->act; a.resid = h; a.out = hn;
             a.xg = m->chain_gran; a.seq_ptr = m->step_seq; a.abort_flag = m->wait_abort;
             a.tag_mul = (unsigned)c.num_hidden_layers; a.tag_add = (unsigned)l + 1u;
-            a.w0 = Ln.q; a.n0 = m->H * D;
-            a.w1 = Ln.k; a.n1 = m->Hkv * D;
-            a.w2 = Ln.v; a.n2 = m->Hkv * D;
-            a.NQ = (m->H + 2 * m->Hkv) * D;
+            a.qkv = qkv_rows(m, l + 1);
             a.norm_w = Ln.in_ln; a.eps = c.rms_norm_eps;
             a.out_bias = Ln.qkv_bias;
             a.qkv_out = m->qkv;

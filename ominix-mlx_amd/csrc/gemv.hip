@@ -158,17 +158,7 @@ __global__ __launch_bounds__(kBlock, OMX_GEMV_MINWAVES) void gemv_kernel(const G
 #define OMX_COMPUTE(WB, R0)                                                                        \
     {                                                                                              \
         float acc[NR];                                                                             \
-        _Pragma("unroll") for (int r = 0; r < NR; ++r) acc[r] = 0.f;                               \
-        _Pragma("unroll") for (int j = 0; j < NVW; ++j) {                                          \
-            const u32x4 xp = xs[koff + j * 64 + lane];                                             \
-            float xf[8];                                                                           \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                        \
-                xf[2 * q] = A::lo(xp[q]);                                                          \
-                xf[2 * q + 1] = A::hi(xp[q]);                                                      \
-            }                                                                                      \
-            _Pragma("unroll") for (int r = 0; r < NR; ++r) acc[r] = dot8<F16>(WB[r][j], xf, acc[r]); \
-        }                                                                                          \
-        _Pragma("unroll") for (int r = 0; r < NR; ++r) acc[r] = wave_sum(acc[r]);                  \
+        rows_dot<F16, NR, NVW>(WB, xs + koff, lane, acc);                                          \
         if (lane == 0) {                                                                           \
             _Pragma("unroll") for (int r = 0; r < RB; ++r) {                                       \
                 const int row = (R0) + r;                                                          \

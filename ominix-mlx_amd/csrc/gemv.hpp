@@ -95,10 +95,25 @@ GemvRoute gemv_route(const GemvArgs& a, int pro, int epi);
 // true when launch_gemv has a kernel for contraction width K (K not a multiple of 512 only without a prologue)
 bool gemv_k_supported(int K, bool needs_full_vectors);
 
+// up to three row-stacked matrices sharing K, as the decode step hands a layer's q | k | v to the kernels that stream them behind
+// something else (gemv_chain.hip, attn_step.hip); n2 = rows - n0 - n1
+struct StackedRows {
+    const bf16_t *w0, *w1, *w2;
+    int n0, n1, rows;
+    // wave-uniform: the start of row `row` in the matrix that owns it
+    __device__ __forceinline__ const bf16_t* row_ptr(int row, int K) const {
+        if (row < n0) return w0 + (size_t)row * K;
+        row -= n0;
+        if (row < n1) return w1 + (size_t)row * K;
+        row -= n1;
+        return w2 + (size_t)row * K;
+    }
+};
+
 // ---- down GEMV + residual of a layer and [RMSNorm + q/k/v GEMV] of the NEXT layer as one launch (gemv_chain.hip) ----
 // Phase A is gemv_kernel<NVW, 4, 2, PRO_NONE, EPI_RESIDUAL> on (w_down, x, resid) -> out; the same bf16 row also leaves as tagged
 // granules (granule.hpp).  Every wave then requests its rows of the stacked q/k/v matrices, the block awaits and sweeps the row and
-// finishes with the arithmetic of gemv_kernel<NVW, 1, 2, PRO_RMSNORM, EPI_STORE> on (w0 | w1 | w2, norm_w, eps, out_bias) -> qkv_out.
+// finishes with the arithmetic of gemv_kernel<NVW, 1, 2, PRO_RMSNORM, EPI_STORE> on (qkv, norm_w, eps, out_bias) -> qkv_out.
 struct GemvChainArgs {
     const bf16_t* w_down;       // [N, K]
     int N, K;                   // hidden rows, intermediate columns
@@ -109,12 +124,11 @@ struct GemvChainArgs {
     const unsigned* seq_ptr;    // step sequence number; tag = seq * tag_mul + tag_add (tag_add = layer + 1)
     unsigned tag_mul, tag_add;
     unsigned* abort_flag;       // raised when a wait gives up
-    const bf16_t *w0, *w1, *w2; // the next layer's q / k / v, [n*, N]
-    int n0, n1, n2, NQ;         // NQ = n0 + n1 + n2
+    StackedRows qkv;            // the next layer's q | k | v, rows of N
     const bf16_t* norm_w;       // [N] the next layer's input RMSNorm weight
     float eps;
-    const bf16_t* out_bias;     // optional [NQ]
-    bf16_t* qkv_out;            // [NQ]
+    const bf16_t* out_bias;     // optional [qkv.rows]
+    bf16_t* qkv_out;            // [qkv.rows]
 };
 // a register layout exists: hidden 4096, intermediate 12288 (Qwen3-8B), 4097..6144 q/k/v rows (three per wave)
 bool gemv_chain_ok(int hidden, int inter, int n_qkv);

@@ -31,16 +31,6 @@ constexpr int kWaves = 4;
 constexpr int kSplit = 4;     // phase A: waves sharing one row
 constexpr int kRowsA = 8;     // phase A: rows per workgroup (resolve_rpw of a K-split kernel)
 constexpr int kRB = 2;        // phase A: rows per register batch
-constexpr unsigned kSpinLimit = 1u << 15;   // passes (~1 us each) before a wait gives up
-
-__device__ __forceinline__ const bf16_t* qkv_row_ptr(const GemvChainArgs& a, int row, int K) {
-    // wave-uniform: which of the stacked matrices owns this row
-    if (row < a.n0) return a.w0 + (size_t)row * K;
-    row -= a.n0;
-    if (row < a.n1) return a.w1 + (size_t)row * K;
-    row -= a.n1;
-    return a.w2 + (size_t)row * K;
-}
 
 // NVA = 16-byte vectors per lane per row per wave of phase A (K = NVA * 4 * 512); NVB = vectors per lane per row of phase B
 // (N = NVB * 512); RQ = q/k/v rows a wave holds
@@ -70,17 +60,7 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
 #define OMX_COMPUTE(WB, R0)                                                                        \
     {                                                                                              \
         float acc[kRB];                                                                            \
-        _Pragma("unroll") for (int r = 0; r < kRB; ++r) acc[r] = 0.f;                              \
-        _Pragma("unroll") for (int j = 0; j < NVA; ++j) {                                          \
-            const u32x4 xp = xs[koff + j * 64 + lane];                                             \
-            float xf[8];                                                                           \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                        \
-                xf[2 * q] = A::lo(xp[q]);                                                          \
-                xf[2 * q + 1] = A::hi(xp[q]);                                                      \
-            }                                                                                      \
-            _Pragma("unroll") for (int r = 0; r < kRB; ++r) acc[r] = dot8(WB[r][j], xf, acc[r]);   \
-        }                                                                                          \
-        _Pragma("unroll") for (int r = 0; r < kRB; ++r) acc[r] = wave_sum(acc[r]);                 \
+        rows_dot<false, kRB, NVA>(WB, xs + koff, lane, acc);                                       \
         if (lane == 0) {                                                                           \
             _Pragma("unroll") for (int r = 0; r < kRB; ++r) part[((R0) + r - row_begin) * kSplit + wave] = acc[r]; \
         }                                                                                          \
@@ -117,14 +97,7 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
     if (threadIdx.x < kRowsA / 2) {
         // rows 2t and 2t + 1 of the workgroup: K-quarter partials in wave order, bf16(resid + bf16(sum)) -- then the pair leaves twice:
         // to the ping-pong buffer (the attention launch reads it as its residual) and as a tagged granule for phase B of every workgroup
-        float v[2] = {0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-#pragma unroll
-            for (int w = 0; w < kSplit; ++w) v[e] += part[(2 * threadIdx.x + e) * kSplit + w];
-        }
-        const uint32_t o2 = (uint32_t)epi_bits<EPI_RESIDUAL, A>(v[0], 0.f, (bf16_t)(res2 & 0xFFFFu), 0) |
-                            ((uint32_t)epi_bits<EPI_RESIDUAL, A>(v[1], 0.f, (bf16_t)(res2 >> 16), 0) << 16);
+        const uint32_t o2 = residual_pair<A, kSplit>(part + 2 * threadIdx.x * kSplit, res2);
         reinterpret_cast<uint32_t*>(a.out)[row_begin / 2 + threadIdx.x] = o2;
         st_granule_u32(a.xg + row_begin / 2 + threadIdx.x, tag, o2);
     }
@@ -138,12 +111,12 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
     for (int i = 0; i < PVB; ++i) nwv[i] = *(reinterpret_cast<const u32x4*>(a.norm_w) + threadIdx.x + i * kBlock);
     bf16_t ob[RQ];
 #pragma unroll
-    for (int r = 0; r < RQ; ++r) ob[r] = *(a.out_bias ? a.out_bias + min(q_row0 + r, a.NQ - 1) : a.norm_w);   // (one load either way: no branch)
+    for (int r = 0; r < RQ; ++r) ob[r] = *(a.out_bias ? a.out_bias + min(q_row0 + r, a.qkv.rows - 1) : a.norm_w);   // (one load either way: no branch)
     u32x4 qw[RQ][NVB];
 #define OMX_ISSUE_QKV()                                                                                                   \
     {                                                                                                                     \
         _Pragma("unroll") for (int r = 0; r < RQ; ++r) {                                                                  \
-            const u32x4* p = reinterpret_cast<const u32x4*>(qkv_row_ptr(a, min(q_row0 + r, a.NQ - 1), N)); /* clamp: surplus waves re-read the last row */ \
+            const u32x4* p = reinterpret_cast<const u32x4*>(a.qkv.row_ptr(min(q_row0 + r, a.qkv.rows - 1), N)); /* clamp: surplus waves re-read the last row */ \
             _Pragma("unroll") for (int j = 0; j < NVB; ++j) qw[r][j] = ld_nt(p + j * 64 + lane);                          \
         }                                                                                                                 \
         __builtin_amdgcn_sched_barrier(0); /* keep the loads HERE: the scheduler would sink them to their use */          \
@@ -154,84 +127,23 @@ __global__ __launch_bounds__(kBlock, 2) void down_qkv_kernel(const GemvChainArgs
     //      which queue behind the other waves' 3/4 of the matrix: the hop costs the launch nothing while it is shorter than that stream.
     //      (Measured, EXPERIMENTS C-3: wave 0 asking for its rows right BEHIND a peeled first pass of the sweep, tags read behind
     //      s_waitcnt vmcnt(24) -- 344.26 / 344.44 tok/s against 344.29 / 344.44, 230 VGPRs instead of 138: nothing, not in the tree.) ----
-    unsigned* sx = reinterpret_cast<unsigned*>(xs);   // the raw row, natural element order
     if (wave != 0) {
         OMX_ISSUE_QKV();
     } else {
-        constexpr int GPL = N / 2 / 64;               // granules per lane
-        for (unsigned spins = 0; spins < kSpinLimit; ++spins) {
-            const unsigned long long g = ld_granule(a.xg + (size_t)lane * GPL + (GPL - 1));
-            if (__all((unsigned)(g >> 32) == tag)) break;
-            __builtin_amdgcn_s_sleep(4);
-        }
-        unsigned long long g[GPL];
-        bool done = false;
-        for (unsigned spins = 0;; ++spins) {
-#pragma unroll
-            for (int i = 0; i < GPL; ++i) g[i] = ld_granule(a.xg + (size_t)i * 64 + lane);   // (every pass re-reads all: one wave-wide round)
-            bool ok = true;
-#pragma unroll
-            for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
-            done = __all(ok);
-            if (done) break;
-            if (spins >= kSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
-                if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(4);
-        }
-#pragma unroll
-        for (int i = 0; i < GPL; ++i) sx[i * 64 + lane] = (unsigned)g[i];
+        sweep_granules<N / 2, 1>(a.xg, reinterpret_cast<unsigned*>(xs), 0, tag, lane, a.abort_flag);   // the raw row, natural element order
         OMX_ISSUE_QKV();
     }
 #undef OMX_ISSUE_QKV
     // (barriers of this phase wait for LDS only: the q/k/v rows stay in flight across them)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    // RMS-normalise into LDS (gemv.hip, PRO_RMSNORM): thread t owns vectors t, t + 256 (in place: nobody else touches them).
-    // (The same sequence is rmsnorm_in_lds of gemv_parts.hpp, which attn_step.hip calls; it stays written out here because calling the
-    //  helper reorders this kernel's instruction stream -- EXPERIMENTS C-2 -- and the kernel's measured form is kept.)
-    {
-        float ss = 0.f;
-        u32x4 xv[PVB];
-#pragma unroll
-        for (int i = 0; i < PVB; ++i) {
-            xv[i] = xs[threadIdx.x + i * kBlock];
-            ss = sumsq8<A>(xv[i], ss);
-        }
-        // block_sum<4> (common.hpp) with LDS-only barriers: wave sums, then the four of them added in wave order from 0.f
-        ss = wave_sum(ss);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (lane == 0) red[wave] = ss;
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        ss = 0.f;
-#pragma unroll
-        for (int i = 0; i < kWaves; ++i) ss += red[i];
-        const float rstd = 1.0f / sqrtf(ss / (float)N + a.eps);
-#pragma unroll
-        for (int i = 0; i < PVB; ++i) xs[threadIdx.x + i * kBlock] = norm8<A>(xv[i], nwv[i], rstd);
-        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-    }
+    lds_barrier();
+    // RMS-normalise in LDS (gemv.hip, PRO_RMSNORM): thread t owns vectors t, t + 256
+    rmsnorm_in_lds<A, PVB>(xs, red, nwv, N, a.eps, true);
     float acc[RQ];
-#pragma unroll
-    for (int r = 0; r < RQ; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int j = 0; j < NVB; ++j) {
-        const u32x4 xp = xs[j * 64 + lane];
-        float xf[8];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            xf[2 * q] = A::lo(xp[q]);
-            xf[2 * q + 1] = A::hi(xp[q]);
-        }
-#pragma unroll
-        for (int r = 0; r < RQ; ++r) acc[r] = dot8(qw[r][j], xf, acc[r]);
-    }
-#pragma unroll
-    for (int r = 0; r < RQ; ++r) acc[r] = wave_sum(acc[r]);
+    rows_dot<false, RQ, NVB>(qw, xs, lane, acc);
     if (lane == 0) {
 #pragma unroll
         for (int r = 0; r < RQ; ++r)
-            if (q_row0 + r < a.NQ) a.qkv_out[q_row0 + r] = A::bits(a.out_bias ? acc[r] + A::val(ob[r]) : acc[r]);
+            if (q_row0 + r < a.qkv.rows) a.qkv_out[q_row0 + r] = A::bits(a.out_bias ? acc[r] + A::val(ob[r]) : acc[r]);
     }
 }
 
@@ -247,8 +159,9 @@ bool gemv_chain_ok(int hidden, int inter, int n_qkv) {
 int gemv_chain_grid(int hidden) { return hidden / kRowsA; }
 
 int launch_gemv_chain(const GemvChainArgs& a, hipStream_t s) {
-    OMX_REQUIRE(gemv_chain_ok(a.N, a.K, a.NQ) && a.NQ == a.n0 + a.n1 + a.n2, "down + q/k/v: no register layout for hidden %d, intermediate %d, %d q/k/v rows", a.N, a.K, a.NQ);
-    OMX_REQUIRE(a.w_down && a.x && a.resid && a.out && a.xg && a.seq_ptr && a.abort_flag && a.w0 && a.norm_w && a.qkv_out && a.tag_add >= 1u,
+    OMX_REQUIRE(gemv_chain_ok(a.N, a.K, a.qkv.rows) && a.qkv.n0 >= 0 && a.qkv.n1 >= 0 && a.qkv.rows >= a.qkv.n0 + a.qkv.n1,
+                "down + q/k/v: no register layout for hidden %d, intermediate %d, %d q/k/v rows", a.N, a.K, a.qkv.rows);
+    OMX_REQUIRE(a.w_down && a.x && a.resid && a.out && a.xg && a.seq_ptr && a.abort_flag && a.qkv.w0 && a.norm_w && a.qkv_out && a.tag_add >= 1u,
                 "down + q/k/v: missing argument");
     const size_t shmem = (size_t)(kInter / 8) * 16 + 32 + (size_t)kRowsA * 2 * kSplit * 4;
     OMX_LAUNCH_TIMED((down_qkv_kernel<kInter / 512 / kSplit, kHidden / 512, kRQ>), dim3(gemv_chain_grid(a.N)), dim3(kBlock), shmem, s, a);

@@ -1,8 +1,17 @@
 // The arithmetic that the decode GEMV kernels share, each piece written ONCE: gemv.hip (bf16 / float16 weights), quant.hip (packed
-// weights, VALU), qgemv_mfma.hip (packed 4-bit, matrix cores), qgemv_rows.hip (packed, a handful of rows) and gemv_chain.hip (down +
-// q/k/v in one launch) must agree bit for bit -- the VALU-against-rows comparison is exact and token equality across the routes rests on
-// it -- so they call these instead of carrying a copy.  Everything here is inlined straight-line code on values: no pointer, no branch
-// enters a kernel's streaming loop through it.  A = Act16<F16> (act16.hpp): bfloat16, or float16 with the same rounding points.
+// weights, VALU), qgemv_mfma.hip (packed 4-bit, matrix cores), qgemv_rows.hip (packed, a handful of rows), gemv_chain.hip (down +
+// q/k/v in one launch) and attn_step.hip (O, gate/up, down and the next q/k/v inside the attention launch) must agree bit for bit -- the
+// VALU-against-rows comparison is exact and token equality across the routes and the step's forms rests on it -- so they call these
+// instead of carrying a copy.  Everything here is inlined straight-line code on values: no pointer, no branch enters a kernel's
+// streaming loop through it.  A = Act16<F16> (act16.hpp): bfloat16, or float16 with the same rounding points.
+// Who calls what:
+//   dot8                     rows_dot below; gemv.hip (gemv_generic_kernel, whose rows are not held in registers)
+//   rows_dot                 gemv.hip (gemv_kernel's OMX_COMPUTE); gemv_chain.hip (phase A's OMX_COMPUTE, the q/k/v rows); attn_step.hip
+//                            (oproj_phase, gateup_reduce, down_reduce, the q/k/v rows of down_qkv_phase)
+//   residual_pair            gemv_chain.hip (down_qkv_kernel); attn_step.hip (down_qkv_phase)
+//   sumsq8 / norm8           the prologues of gemv.hip, qgemv_body.inc (quant.hip), qgemv_mfma.hip, qgemv_rows.hip; rmsnorm_in_lds below
+//   rmsnorm_in_lds           gemv_chain.hip (down_qkv_kernel); attn_step.hip (gateup_phase, down_qkv_phase)
+//   epi_bits                 every row epilogue of the files above; residual_pair below
 // (The packed kernels' unpack and activation staging are beside qfield in quant.hpp; argmax_key is in common.hpp.)
 #pragma once
 #include "act16.hpp"
@@ -23,6 +32,30 @@ __device__ __forceinline__ float dot8(const u32x4 w, const float (&xf)[8], float
         acc = fmaf(A::hi(w[i]), xf[2 * i + 1], acc);
     }
     return acc;
+}
+
+// ---- NR rows held in registers (NV 16-byte vectors per lane each) against a vector in LDS: the reduce of every decode GEMV ----
+// xs is already advanced to the caller's K slice.  acc[r] = the wave's sum of row r: zeroed, the dot8 chain over j = 0..NV-1 on
+// xs[j * 64 + lane] unpacked lo then hi of each dword, wave_sum.  What happens to acc stays with the caller.
+template <bool F16, int NR, int NV>
+__device__ __forceinline__ void rows_dot(const u32x4 (*w)[NV], const u32x4* xs, int lane, float (&acc)[NR]) {
+    typedef Act16<F16> A;
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+        const u32x4 xp = xs[j * 64 + lane];
+        float xf[8];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            xf[2 * q] = A::lo(xp[q]);
+            xf[2 * q + 1] = A::hi(xp[q]);
+        }
+#pragma unroll
+        for (int r = 0; r < NR; ++r) acc[r] = dot8<F16>(w[r][j], xf, acc[r]);
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = wave_sum(acc[r]);
 }
 
 // ---- RMSNorm prologue on one packed 16-byte vector (eight elements) ----
@@ -96,6 +129,20 @@ __device__ __forceinline__ uint16_t epi_bits(float v0, float v1, uint16_t resid_
         return A::bits(A::rnd(g * sg) * u);
     }
     return A::bits(v0);
+}
+
+// ---- the finish of a PAIR of K-split EPI_RESIDUAL rows: part_of_pair = [2][KSPLIT] partials, res2 = the two residuals packed ----
+// each row's partials added in wave order from 0.f, bf16(resid + bf16(sum)) on the low and the high half, one dword out
+template <class A, int KSPLIT>
+__device__ __forceinline__ uint32_t residual_pair(const float* part_of_pair, uint32_t res2) {
+    float v[2] = {0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+#pragma unroll
+        for (int w = 0; w < KSPLIT; ++w) v[e] += part_of_pair[e * KSPLIT + w];
+    }
+    return (uint32_t)epi_bits<EPI_RESIDUAL, A>(v[0], 0.f, (uint16_t)(res2 & 0xFFFFu), 0) |
+           ((uint32_t)epi_bits<EPI_RESIDUAL, A>(v[1], 0.f, (uint16_t)(res2 >> 16), 0) << 16);
 }
 
 // ---- expert parallelism: only experts [lo, lo + n) live on this rank (n == 0: all of them) ----
