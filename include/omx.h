@@ -919,6 +919,56 @@ int omx_qwen3_asr_encoder_debug_read(omx_qwen3_asr_encoder e, const char* name, 
 int omx_window_attention_f32(float* out, int64_t ldo, const float* q, const float* k, const float* v, int64_t ld, int n, int heads, int window,
                              omx_stream stream);
 
+/* The vision towers of Moxin-VLM (moxin-vlm-mlx/src/vision.rs `ViTEncoder::forward`, :259-310) and its projector (projector.rs:34-40) in
+ * float32 -- the reference feeds a float32 image into bf16 parameters and casts nothing, MLX promotes every op to float32; the caller
+ * hands the weights widened to float32.  image [S, S, 3] in [0, 1] -> (x - mean) / std -> P x P stride-P convolution (im2col + the
+ * float32 matrix-core GEMM) -> CLS | registers | patches + pos_embed -> blocks 0 .. depth - 2 (pre-norm, eps 1e-6, exact GELU,
+ * optional LayerScale) -> the patch rows; the final norm is never applied, as in the reference.
+ *   config:  every field of ViTConfig, the three-channel mean / std of the tower's image preparation (lib.rs:427-440), and the
+ *            checkpoint prefix the error texts name ("vision_backbone.featurizer").
+ *   create:  "InvalidConfig" by name: head width other than 64 / 72, embed_dim != heads * width, image size no multiple of the patch,
+ *            more than 1024 rows.
+ *   load:    one tensor by its key behind the prefix ("patch_embed.proj.weight" [O, 3, P, P] as the checkpoint holds it, "pos_embed",
+ *            "cls_token", "reg_token" or "register_tokens", "blocks.3.attn.qkv.weight", "blocks.3.ls1.gamma" or ".scale_factor", ...),
+ *            float32 on the HOST.  A missing key ("WeightNotFound: <key>"), a size the config does not imply, or a pos_embed of
+ *            neither num_patches nor num_patches + 1 rows is an error at forward, before any launch.  Biases are optional.
+ *   tokens:  rows of the sequence (CLS + registers + patches) and rows that come out (patches).
+ *   forward: image DEVICE f32 [S, S, 3] -> out_rows DEVICE f32 [patches, embed_dim], rows `ldo` floats apart (two towers fill the two
+ *            column ranges of one buffer).  The handle owns its scratch and reuses it; a reused handle gives a fresh handle's bits.  A
+ *            NaN / infinite image is refused.
+ *   debug_read (test hook): a stage of the LAST forward -- "col" [patches, 3 P P], "patches" [patches, dim], "h" [tokens, dim] (the
+ *            assembled rows when no block runs, else the last block's rows after its attention residual), and of the last block "ln1",
+ *            "qkv" [tokens, 3 dim], "attn", "ln2", "mlp" [tokens, intermediate].
+ *   omx_vit_attention_f32: the towers' attention alone -- unmasked softmax(q k^T width^-0.5) v in float32 on the f32 matrix cores;
+ *            q | k | v DEVICE rows `ld` floats apart, head h at column h * width, out token-major.  width 64 or 72, 1 <= n <= 1024,
+ *            anything else is refused by name.  Fixed summation order: the same input gives the same bits.
+ *   omx_gemm_f32_epilogue: out [M, N] = resid + col_scale * gelu?(a [M, K] . w [N, K]^T + bias) through the float32 GEMM's fused
+ *            epilogues (test hook and building block); bias, resid, col_scale optional, all contiguous.
+ *   omx_vlm_projector_*: fc1 -> gelu -> fc2 -> gelu -> fc3 with keys "fc1.weight", "fc1.bias", ...; widths are read from the weights. */
+typedef struct omx_vit_encoder_* omx_vit_encoder;
+typedef struct omx_vlm_projector_* omx_vlm_projector;
+typedef struct omx_vit_config_ {
+    int embed_dim, depth, num_heads, head_dim, intermediate_dim, has_cls_token, num_registers, has_layer_scale, patch_size, image_size;
+    float mean[3], std[3];
+    char key_prefix[128];
+} omx_vit_config;
+int omx_vit_encoder_create(omx_vit_encoder* out, const omx_vit_config* cfg);
+int omx_vit_encoder_load(omx_vit_encoder e, const char* name, const float* host, const int64_t* shape, int ndim);
+int omx_vit_encoder_tokens(omx_vit_encoder e, int* n_tokens, int* n_rows);
+int omx_vit_encoder_forward(omx_vit_encoder e, const float* image, float* out_rows, int64_t ldo, omx_stream stream);
+int omx_vit_encoder_launches(omx_vit_encoder e, int* n);   /* launches the last forward enqueued, split-K reduce launches not counted */
+int omx_vit_encoder_debug_read(omx_vit_encoder e, const char* name, float* host, size_t n_elems);
+int omx_vit_encoder_destroy(omx_vit_encoder e);
+int omx_vit_attention_f32(float* out, int64_t ldo, const float* q, const float* k, const float* v, int64_t ld, int n, int heads, int width,
+                          omx_stream stream);
+int omx_gemm_f32_epilogue(float* out, const float* a, const float* w, const float* bias, const float* resid, const float* col_scale, int M, int N, int K,
+                          int gelu, omx_stream stream);
+int omx_vlm_projector_create(omx_vlm_projector* out);
+int omx_vlm_projector_load(omx_vlm_projector p, const char* name, const float* host, const int64_t* shape, int ndim);
+int omx_vlm_projector_dims(omx_vlm_projector p, int* in_dim, int* out_dim);
+int omx_vlm_projector_forward(omx_vlm_projector p, const float* x, int rows, float* out, omx_stream stream);
+int omx_vlm_projector_destroy(omx_vlm_projector p);
+
 /* =====================================================================================
  * a13: Paraformer body pieces (funasr-mlx/src/paraformer.rs).
  *   omx_sanm_encoder_layer  SanmEncoderLayer::forward :618-634 = LayerNorm(1e-5) -> SanmAttention (:496-532:

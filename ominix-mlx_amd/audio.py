@@ -26,6 +26,14 @@ class AudioEncoderConfig(ctypes.Structure):
                 ("downsample_hidden_size", c_int)]
 
 
+class ViTConfig(ctypes.Structure):
+    """ViTConfig (moxin-vlm-mlx/src/vision.rs:26-37) plus the tower's image statistics (lib.rs:427-440) and the checkpoint prefix the
+    error texts name.  It lives here, beside the audio tower's, because its entry points are bound in AUDIO_SIGNATURES (vision.py uses them)."""
+    _fields_ = [("embed_dim", c_int), ("depth", c_int), ("num_heads", c_int), ("head_dim", c_int), ("intermediate_dim", c_int),
+                ("has_cls_token", c_int), ("num_registers", c_int), ("has_layer_scale", c_int), ("patch_size", c_int), ("image_size", c_int),
+                ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3), ("key_prefix", ctypes.c_char * 128)]
+
+
 AUDIO_SIGNATURES = {
     "omx_mel_frontend_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(MelConfig)]),
     "omx_mel_frontend_destroy": (c_int, [c_void_p]),
@@ -49,6 +57,21 @@ AUDIO_SIGNATURES = {
     "omx_qwen3_asr_encoder_destroy": (c_int, [c_void_p]),
     "omx_qwen3_asr_encoder_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
     "omx_window_attention_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    # the Moxin-VLM vision towers and projector in float32 (csrc/vit_encoder.hip; the classes are in vision.py)
+    "omx_vit_encoder_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(ViTConfig)]),
+    "omx_vit_encoder_load": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(c_int64), c_int]),
+    "omx_vit_encoder_tokens": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "omx_vit_encoder_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "omx_vit_encoder_launches": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "omx_vit_encoder_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
+    "omx_vit_encoder_destroy": (c_int, [c_void_p]),
+    "omx_vit_attention_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "omx_gemm_f32_epilogue": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "omx_vlm_projector_create": (c_int, [ctypes.POINTER(c_void_p)]),
+    "omx_vlm_projector_load": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(c_int64), c_int]),
+    "omx_vlm_projector_dims": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "omx_vlm_projector_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
+    "omx_vlm_projector_destroy": (c_int, [c_void_p]),
 }
 for _n, (_r, _a) in AUDIO_SIGNATURES.items():
     _f = getattr(lib, _n)

@@ -94,7 +94,7 @@ int launch_gemm_bf16_swiglu(bf16_t* out_plain, int ld_plain, bf16_t* out_act, in
 int launch_gemm_bf16_grouped(bf16_t* out, const bf16_t* x, const bf16_t* w, int max_rows, int N, int K,
                              const GroupedDesc& g, int max_tiles, hipStream_t s);
 
-// float32 GEMM on the f32-input matrix cores (gemm_f32.hip): out[b] = alpha * A[b] . B[b] (+ bias) (relu) (+ resid), strided and
+// float32 GEMM on the f32-input matrix cores (gemm_f32.hip): out[b] = alpha * A[b] . B[b] (+ bias) (relu) (gelu) (* col_scale) (+ resid), strided and
 // batched; B is [N, K] row-major (b_nn = 0, nn::Linear) or [K, N] row-major (b_nn = 1)
 struct GemmF32 {
     const float* a; const float* b; const float* bias; const float* resid; float* out;
@@ -108,6 +108,10 @@ struct GemmF32 {
     // *defer_partial [splits][M][N] (the split-K scratch of the stream, valid until the stream's next GEMM) with *defer_splits >= 1
     const float** defer_partial = nullptr;
     int* defer_splits = nullptr;
+    // the vision towers' epilogues (vit_encoder.hip), off by default: exact-erf GELU after the bias, and a per-column factor [N]
+    // (LayerScale) applied before the residual: out = resid + col_scale * (alpha A.B + bias).  Neither goes with a deferred epilogue.
+    int gelu = 0;
+    const float* col_scale = nullptr;
 };
 int launch_gemm_f32(const GemmF32& p, hipStream_t s);
 

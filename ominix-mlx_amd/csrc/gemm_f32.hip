@@ -3,7 +3,9 @@
 // (funasr-mlx/src/paraformer.rs:496-532, 560-570, 618-634, 981-1053: f32 weights converted from PyTorch, f32 activations):
 // 0.17 TFLOP for 30 s of audio, GEMMs of 200-500 rows -- so these kernels are built for SMALL problems (64 x 64 tiles so that a
 // [501, 512] output still gives 64 blocks, split-K when even that leaves the chip idle), not for a roofline number.
-//   out[b][m, n] = alpha * sum_k A[b][m, k] * B[b](k, n) (+ bias[n]) (relu) (+ resid[m, n])
+//   out[b][m, n] = alpha * sum_k A[b][m, k] * B[b](k, n) (+ bias[n]) (relu) (gelu) (* col_scale[n]) (+ resid[m, n])
+//   (gelu: the exact erf form; col_scale: a LayerScale factor per column, applied before the residual -- both off for every caller
+//    older than the vision towers, whose arithmetic is the same instructions as before)
 //   B(k, n) = B[n * ldb + k]   ("NT": an nn::Linear weight [N, K], mlx-rs/src/nn/linear.rs:87-92)    or
 //           = B[k * ldb + n]   ("NN": P . V of the explicit attention, paraformer.rs:513-515)
 // Three kernels, newest last:
@@ -27,7 +29,15 @@ struct F32Args {
     int64_t lda, ldb, ldc, ldr, sa, sb, sc;   // leading dimensions and per-batch strides (elements)
     int batch, splits, relu, b_nn;
     float alpha;
+    int gelu; const float* col_scale;
 };
+
+// what follows alpha, bias and relu in every epilogue: nn::gelu (mlx-rs/src/nn/activation.rs:164) in its exact form, then the column factor
+__device__ __forceinline__ float f32_tail(const F32Args& g, float v, int col) {
+    if (g.gelu) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
+    if (g.col_scale) v *= g.col_scale[col];
+    return v;
+}
 
 // stage one [64 rows x 64 k] operand tile held k-contiguous in memory (A, or B in NT form) into registers: thread t covers
 // row t / 16 (+ 16 i), k quad t % 16
@@ -138,6 +148,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const F32Args g) {
             float v = acc[r] * g.alpha;
             if (g.bias) v += g.bias[col];
             if (g.relu) v = fmaxf(v, 0.f);
+            v = f32_tail(g, v, col);
             if (g.resid) v += g.resid[(int64_t)row * g.ldr + col];
             g.out[(int64_t)bz * g.sc + (int64_t)row * g.ldc + col] = v;
         }
@@ -248,6 +259,7 @@ __global__ __launch_bounds__(256) void gemm_f32_small_kernel(const F32Args g) {
             float v = acc[r] * g.alpha;
             if (g.bias) v += g.bias[col];
             if (g.relu) v = fmaxf(v, 0.f);
+            v = f32_tail(g, v, col);
             if (g.resid) v += g.resid[(int64_t)row * g.ldr + col];
             g.out[(int64_t)bz * g.sc + (int64_t)row * g.ldc + col] = v;
         }
@@ -495,6 +507,7 @@ __global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(const F32Args g) {
             v *= g.alpha;
             if (g.bias) v += *reinterpret_cast<const f32x4*>(g.bias + col);
             if (g.relu) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
+            if (g.gelu || g.col_scale) { v[0] = f32_tail(g, v[0], col); v[1] = f32_tail(g, v[1], col + 1); v[2] = f32_tail(g, v[2], col + 2); v[3] = f32_tail(g, v[3], col + 3); }
             if (g.resid) v += *reinterpret_cast<const f32x4*>(g.resid + (int64_t)row * g.ldr + col);
             *reinterpret_cast<f32x4*>(dst) = v;
         } else {
@@ -504,6 +517,7 @@ __global__ __launch_bounds__(256) void gemm_f32_pipe_kernel(const F32Args g) {
                 float x = v[e] * g.alpha;
                 if (g.bias) x += g.bias[col + e];
                 if (g.relu) x = fmaxf(x, 0.f);
+                x = f32_tail(g, x, col + e);
                 if (g.resid) x += g.resid[(int64_t)row * g.ldr + col + e];
                 dst[e] = x;
             }
@@ -523,6 +537,7 @@ __global__ __launch_bounds__(256) void gemm_f32_reduce_kernel(const F32Args g) {
         v *= g.alpha;
         if (g.bias) v += g.bias[col];
         if (g.relu) v = fmaxf(v, 0.f);
+        v = f32_tail(g, v, col);
         if (g.resid) v += g.resid[(int64_t)row * g.ldr + col];
         g.out[(int64_t)bz * g.sc + (int64_t)row * g.ldc + col] = v;
     }
@@ -533,11 +548,11 @@ __global__ __launch_bounds__(256) void gemm_f32_reduce_kernel(const F32Args g) {
 int launch_gemm_f32(const GemmF32& p, hipStream_t s) {
     OMX_REQUIRE(p.a && p.b && p.out && p.M > 0 && p.N > 0 && p.K > 0 && p.batch >= 1, "gemm_f32: bad arguments (M=%d N=%d K=%d)", p.M, p.N, p.K);
     F32Args g = {p.a, p.b, p.bias, p.resid, p.out, nullptr, p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.ldr ? p.ldr : p.ldc, p.sa, p.sb, p.sc,
-                 p.batch, 1, p.relu, p.b_nn, p.alpha};
+                 p.batch, 1, p.relu, p.b_nn, p.alpha, p.gelu, p.col_scale};
     const bool defer = p.defer_partial && p.defer_splits;      // the caller applies the epilogue (and whatever follows) in its own launch
     if (defer) {
         OMX_REQUIRE(p.batch == 1 && p.ldc == p.N, "gemm_f32: a deferred epilogue takes one dense [M, N] product");
-        g.bias = nullptr; g.resid = nullptr; g.relu = 0; g.alpha = 1.0f;
+        g.bias = nullptr; g.resid = nullptr; g.relu = 0; g.alpha = 1.0f; g.gelu = 0; g.col_scale = nullptr;
     }
     const int gx = (p.N + TN - 1) / TN, gy = (p.M + TM - 1) / TM, tiles = gx * gy * p.batch, ktiles = (p.K + TK - 1) / TK;
     // split K while the tile grid leaves most of the chip idle and every split keeps >= 2 K tiles: a wave's tile is a chain of
