@@ -457,6 +457,11 @@ int omx_qwen3_batch_destroy(omx_qwen3_batch b);
 int omx_qwen3_batch_set_sampler(omx_qwen3_batch b, int slot, float temperature, uint64_t seed);
 int omx_qwen3_batch_set_sampling(omx_qwen3_batch b, int slot, const omx_sampling* p, uint64_t seed);
 int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, uint32_t* first_token);
+/* omx_qwen3_batch_prefill with rows [first_row, first_row + n_rows) of the pass supplied by the caller: omx_qwen3_prefill_embeds' span
+ * (DEVICE rows, f32 / bf16 / f16, cast once to nearest even), its refusals and their texts, on the slot's own cache (bf16 or kv_bits = 8).
+ * A packed model's prompt of 8 rows or fewer takes the few-row packed launches, which cannot take rows: refused as "InvalidConfig". */
+int omx_qwen3_batch_prefill_embeds(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, const void* rows, omx_dtype rows_dtype,
+                                   int first_row, int n_rows, uint32_t* first_token);
 int omx_qwen3_batch_decode(omx_qwen3_batch b, const int* slots, int n_slots, int n_steps, uint32_t* tokens_out);
 int omx_qwen3_batch_logits(omx_qwen3_batch b, int slot, void* host_bf16, int n);
 int omx_qwen3_batch_offset(omx_qwen3_batch b, int slot, int* offset);
@@ -919,6 +924,41 @@ int omx_qwen3_asr_encoder_debug_read(omx_qwen3_asr_encoder e, const char* name, 
 int omx_window_attention_f32(float* out, int64_t ldo, const float* q, const float* k, const float* v, int64_t ld, int n, int heads, int window,
                              omx_stream stream);
 
+/* The audio tower of Fun-ASR-Nano (funasr-nano-mlx/src/sensevoice_encoder.rs:453-478 `SenseVoiceEncoder::forward`, then adaptor.rs:247-261
+ * `AudioAdaptor::forward`) in float32, over UP TO 8 UTTERANCES AT ONCE: their LFR rows stacked into one [sum T, lfr_dim] tensor, every GEMM
+ * and LayerNorm over all rows, attention and the FSMN memory block stopping at utterance boundaries, positions restarting at 1.
+ *   x + PE(t + 1) (no scale) -> encoders0 (lfr_dim -> output_size, no attention residual) -> num_blocks - 1 encoders -> after_norm ->
+ *   tp_blocks tp_encoders -> tp_norm -> linear1 + ReLU -> linear2 -> n_layer pre-norm blocks (8 heads, FFN bottleneck 256) -> [sum T, llm_dim]
+ *   create:  "InvalidConfig" by name: head width other than 128 (output_size / attention_heads, or llm_dim / 8), an even or > 31
+ *            kernel_size, widths that are no multiple of 4.
+ *   load:    one tensor by its key after the reference's key map (model.rs:350-374): "encoder.encoders0.0.self_attn.linear_q_k_v.weight",
+ *            "encoder.tp_encoders.3.self_attn.fsmn.weight" [dim, 1, k], "encoder.after_norm.bias", "adaptor.linear1.weight",
+ *            "adaptor.blocks.0.self_attn.linear_q.weight", ...; float32 on the HOST.  Keys with another prefix are refused; the shape is
+ *            checked against the config at once ("ShapeMismatch"); a missing key is "WeightNotFound" at forward.  The adaptor's
+ *            linear_q / k / v are stacked into one [3 llm_dim, llm_dim] product at the first forward.
+ *   forward: lfr_rows DEVICE f32 [sum T, lfr_dim]; seg HOST int[n_utt + 1], the row offsets (seg[0] = 0, increasing); out_rows DEVICE f32
+ *            [sum T, llm_dim].  1 <= n_utt <= 8, every utterance 1..512 rows (30 s of audio make 501; 512 is the one-launch attention's
+ *            key limit): anything else is refused by name before the first launch.  A GEMM's split of K depends on its row count, so the
+ *            last bits of an utterance's rows may depend on what shares the pass.
+ *   omx_segment_attention_f32: the tower's attention alone -- out = softmax(q k^T / sqrt(128)) v per head of width 128 and per utterance,
+ *            one launch; q | k | v DEVICE f32 rows ld* floats apart, head h at column 128 h.
+ *   omx_sanm_segment_layer_f32: one SenseVoiceEncoderLayer (:368-384) over stacked utterances, x [sum T, in_dim] -> out [sum T, dim];
+ *            in_dim != dim is the first layer's form (no attention residual).  Declared with omx_sanm_layer_weights below. */
+typedef struct omx_funasr_nano_encoder_* omx_funasr_nano_encoder;
+typedef struct omx_funasr_nano_encoder_config_ {
+    int lfr_dim, output_size, attention_heads, linear_units, num_blocks, tp_blocks, kernel_size;   /* SenseVoiceEncoderConfig */
+    int encoder_dim, ffn_dim, llm_dim, n_layer;                                                     /* AdaptorConfig */
+} omx_funasr_nano_encoder_config;
+int omx_funasr_nano_encoder_create(omx_funasr_nano_encoder* out, const omx_funasr_nano_encoder_config* cfg);
+int omx_funasr_nano_encoder_load(omx_funasr_nano_encoder e, const char* name, const float* host, const int64_t* shape, int ndim);
+int omx_funasr_nano_encoder_forward(omx_funasr_nano_encoder e, const float* lfr_rows, const int* seg, int n_utt, float* out_rows, omx_stream stream);
+int omx_funasr_nano_encoder_destroy(omx_funasr_nano_encoder e);
+/* test hook: n_elems floats of a stage of the LAST forward to the host -- "pos" [sum T, lfr_dim] (rows + positions), "after_norm" and
+ * "tp_norm" [sum T, output_size], "linear2" [sum T, llm_dim] (the adaptor before its blocks; the blocks' output is out_rows) */
+int omx_funasr_nano_encoder_debug_read(omx_funasr_nano_encoder e, const char* name, float* host, size_t n_elems);
+int omx_segment_attention_f32(float* out, const float* q, const float* k, const float* v, int64_t ldq, int64_t ldkv, int64_t ldo, const int* seg,
+                              int n_utt, int heads, omx_stream stream);
+
 /* The vision towers of Moxin-VLM (moxin-vlm-mlx/src/vision.rs `ViTEncoder::forward`, :259-310) and its projector (projector.rs:34-40) in
  * float32 -- the reference feeds a float32 image into bf16 parameters and casts nothing, MLX promotes every op to float32; the caller
  * hands the weights widened to float32.  image [S, S, 3] in [0, 1] -> (x - mean) / std -> P x P stride-P convolution (im2col + the
@@ -994,6 +1034,9 @@ int omx_sanm_encoder_layer(void* out, const void* x, const omx_sanm_layer_weight
 int omx_sanm_encoder_stack(void* out, const void* x, const omx_sanm_layer_weights* layers, int n_layers, int T, int in_dim, int dim, int heads,
                            int ffn_dim, int kernel_size, const void* after_norm_w, const void* after_norm_b, void* act0, void* act1, void* nrm0,
                            void* nrm1, omx_dtype dtype, omx_stream stream);
+/* one SenseVoiceEncoderLayer over stacked utterances (float32; see omx_funasr_nano_encoder above): seg HOST int[n_utt + 1] */
+int omx_sanm_segment_layer_f32(float* out, const float* x, const omx_sanm_layer_weights* w, const int* seg, int n_utt, int in_dim, int dim,
+                               int heads, int ffn_dim, int kernel_size, omx_stream stream);
 int omx_cif_fire(float* frames, int* counts, const float* hidden, const float* alphas, int batch, int T, int H,
                  float threshold, float tail_threshold, int max_frames, omx_stream stream);
 /* SanmEncoder::forward prologue (paraformer.rs:691-703): out [T, dim] = mel f32 [T, dim] * sqrt(512) + sinusoidal

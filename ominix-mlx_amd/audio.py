@@ -26,6 +26,12 @@ class AudioEncoderConfig(ctypes.Structure):
                 ("downsample_hidden_size", c_int)]
 
 
+class FunASRNanoEncoderConfig(ctypes.Structure):
+    """SenseVoiceEncoderConfig (funasr-nano-mlx/src/sensevoice_encoder.rs:20-70) and AdaptorConfig (adaptor.rs:12-53)"""
+    _fields_ = [("lfr_dim", c_int), ("output_size", c_int), ("attention_heads", c_int), ("linear_units", c_int), ("num_blocks", c_int),
+                ("tp_blocks", c_int), ("kernel_size", c_int), ("encoder_dim", c_int), ("ffn_dim", c_int), ("llm_dim", c_int), ("n_layer", c_int)]
+
+
 class ViTConfig(ctypes.Structure):
     """ViTConfig (moxin-vlm-mlx/src/vision.rs:26-37) plus the tower's image statistics (lib.rs:427-440) and the checkpoint prefix the
     error texts name.  It lives here, beside the audio tower's, because its entry points are bound in AUDIO_SIGNATURES (vision.py uses them)."""
@@ -57,6 +63,14 @@ AUDIO_SIGNATURES = {
     "omx_qwen3_asr_encoder_destroy": (c_int, [c_void_p]),
     "omx_qwen3_asr_encoder_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
     "omx_window_attention_f32": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    # the Fun-ASR-Nano audio tower over stacked utterances in float32 (csrc/sensevoice_encoder.hip)
+    "omx_funasr_nano_encoder_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(FunASRNanoEncoderConfig)]),
+    "omx_funasr_nano_encoder_load": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(c_int64), c_int]),
+    "omx_funasr_nano_encoder_forward": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_int), c_int, c_void_p, c_void_p]),
+    "omx_funasr_nano_encoder_destroy": (c_int, [c_void_p]),
+    "omx_funasr_nano_encoder_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
+    "omx_segment_attention_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, ctypes.POINTER(c_int), c_int, c_int,
+                                          c_void_p]),
     # the Moxin-VLM vision towers and projector in float32 (csrc/vit_encoder.hip; the classes are in vision.py)
     "omx_vit_encoder_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(ViTConfig)]),
     "omx_vit_encoder_load": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(c_int64), c_int]),
@@ -186,6 +200,78 @@ class AudioEncoder:
         out = Tensor((self.tokens(m.shape[1]), self.cfg.output_dim), "f32")
         check(lib.omx_qwen3_asr_encoder_forward(self._h, m.ptr, m.shape[1], out.ptr, None))
         return out
+
+
+def _seg_offsets(lengths):
+    """row offsets int[n + 1] of utterances of the given row counts"""
+    off = np.zeros(len(lengths) + 1, np.int64)
+    off[1:] = np.cumsum(np.asarray(lengths, np.int64))
+    return (c_int * len(off))(*[int(v) for v in off]), int(off[-1])
+
+
+class FunASRNanoEncoder:
+    """funasr-nano-mlx's audio tower in float32 on the device: SenseVoiceEncoder::forward (sensevoice_encoder.rs:453-478) followed by
+    AudioAdaptor::forward (adaptor.rs:247-261), over up to 8 utterances in one pass.  Keyword names are config.yaml's
+    `audio_encoder_conf` / `audio_adaptor_conf` keys, defaults the reference's."""
+
+    MAX_UTTERANCES, MAX_ROWS = 8, 512
+
+    def __init__(self, lfr_dim=560, output_size=512, attention_heads=4, linear_units=2048, num_blocks=50, tp_blocks=20, kernel_size=11,
+                 encoder_dim=512, ffn_dim=2048, llm_dim=1024, n_layer=2, **_ignored):
+        require_device()
+        self.cfg = FunASRNanoEncoderConfig(lfr_dim, output_size, attention_heads, linear_units, num_blocks, tp_blocks, kernel_size,
+                                           encoder_dim, ffn_dim, llm_dim, n_layer)
+        self._h = c_void_p()
+        check(lib.omx_funasr_nano_encoder_create(ctypes.byref(self._h), ctypes.byref(self.cfg)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib.omx_funasr_nano_encoder_destroy(self._h)
+            self._h = c_void_p()
+
+    def __del__(self):
+        if sys is not None and not sys.is_finalizing():
+            self.close()
+
+    def load_weights(self, weights) -> None:
+        """{key after the reference's key map ("encoder.…" / "adaptor.…"): array}; bf16 tensors (loader's Bf16Bits) are widened here."""
+        for name, arr in weights.items():
+            if type(arr).__name__ == "Bf16Bits":
+                arr = (np.asarray(arr).astype(np.uint32) << np.uint32(16)).view(np.float32)
+            a = np.ascontiguousarray(arr, dtype=np.float32)
+            shape = (c_int64 * a.ndim)(*a.shape)
+            check(lib.omx_funasr_nano_encoder_load(self._h, name.encode(), a.ctypes.data, shape, a.ndim))
+
+    def debug_read(self, name: str, shape) -> np.ndarray:
+        """A stage of the last forward ("pos", "after_norm", "tp_norm", "linear2") as float32 (test hook)."""
+        out = np.empty(shape, np.float32)
+        check(lib.omx_funasr_nano_encoder_debug_read(self._h, name.encode(), out.ctypes.data, out.size))
+        return out
+
+    def forward(self, lfr_rows, lengths=None) -> Tensor:
+        """lfr_rows: f32 [sum T, lfr_dim] (Tensor or numpy), the utterances' LFR rows stacked; lengths: their row counts (default: one
+        utterance).  -> Tensor f32 [sum T, llm_dim], utterance u at rows [sum(lengths[:u]), sum(lengths[:u + 1]))."""
+        x = lfr_rows if isinstance(lfr_rows, Tensor) else Tensor.from_numpy(np.ascontiguousarray(lfr_rows, np.float32), "f32")
+        if len(x.shape) != 2 or x.shape[1] != self.cfg.lfr_dim:
+            raise OmxError(f"ShapeMismatch: lfr_rows has shape {x.shape}, the tower expects [rows, {self.cfg.lfr_dim}]")
+        lengths = [x.shape[0]] if lengths is None else [int(v) for v in lengths]
+        seg, total = _seg_offsets(lengths)
+        if total != x.shape[0]:
+            raise OmxError(f"ShapeMismatch: the utterances hold {total} rows, lfr_rows has {x.shape[0]}")
+        out = Tensor((max(total, 1), self.cfg.llm_dim), "f32")
+        check(lib.omx_funasr_nano_encoder_forward(self._h, x.ptr, seg, len(lengths), out.ptr, None))
+        return out
+
+
+def segment_attention_f32(qkv: Tensor, heads: int, lengths) -> Tensor:
+    """The tower's attention alone (omx_segment_attention_f32): qkv f32 [sum T, ld >= 3 * heads * 128] holding q | k | v side by side from
+    column 0, utterances of `lengths` rows stacked; -> [sum T, heads * 128]."""
+    d = heads * 128
+    ld = qkv.shape[1]
+    seg, total = _seg_offsets(lengths)
+    out = Tensor((max(total, 1), d), "f32")
+    check(lib.omx_segment_attention_f32(out.ptr, qkv.ptr, qkv.ptr + 4 * d, qkv.ptr + 8 * d, ld, ld, d, seg, len(lengths), heads, None))
+    return out
 
 
 def window_attention_f32(qkv: Tensor, heads: int, window: int, n: int = None) -> Tensor:

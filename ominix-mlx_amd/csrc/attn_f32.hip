@@ -25,10 +25,13 @@ namespace {
 
 constexpr int AF_ROWS = 16, AF_HD = 128, AF_SLOT = AF_ROWS * AF_HD + 2 * AF_ROWS;
 
-template <int NT>
+// SEG (launch_attn_f32_seg): blockIdx.x counts the query tiles of ALL utterances of `segs`, utterance after utterance, each utterance's last
+// tile partial.  The block finds its utterance [lo, hi), takes query rows from lo + 16 * (its tile within the utterance) and sees keys
+// lo .. hi - 1 only; past that it is the kernel below on one utterance, instruction for instruction.  No key split in this form.
+template <int NT, bool SEG>
 __global__ __launch_bounds__(256) void attn_f32_kernel(float* __restrict__ out, const float* __restrict__ q, const float* __restrict__ k,
                                                        const float* __restrict__ v, int64_t ldq, int64_t ldkv, int64_t ldo, int Tq, int Tk_all,
-                                                       float scale, float* __restrict__ part) {
+                                                       float scale, float* __restrict__ part, SegTable segs) {
     constexpr int KW = NT * 16;            // keys per wave
     constexpr int KP = 4 * KW;             // padded key count
     constexpr int S_LD = KP + 4;
@@ -36,7 +39,26 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(float* __restrict__ out, 
     __shared__ __attribute__((aligned(16))) float S[S_FLOATS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = lane & 15, g = lane >> 4;
-    const int m0 = blockIdx.x * AF_ROWS, head = blockIdx.y;
+    int m0 = blockIdx.x * AF_ROWS;
+    const int head = blockIdx.y;
+    if constexpr (SEG) {
+        int t = blockIdx.x, lo = 0, hi = 0;
+        bool found = false;
+#pragma unroll
+        for (int u = 0; u < kMaxSegments; ++u) {
+            if (u < segs.n && !found) {
+                const int nt_u = (segs.off[u + 1] - segs.off[u] + AF_ROWS - 1) / AF_ROWS;
+                if (t < nt_u) { found = true; lo = segs.off[u]; hi = segs.off[u + 1]; }
+                else t -= nt_u;
+            }
+        }
+        if (!found) return;                    // (the grid is exactly the tiles of segs: never taken)
+        m0 = lo + t * AF_ROWS;
+        Tq = hi;                               // the tile's rows end with its utterance
+        k += (int64_t)lo * ldkv;
+        v += (int64_t)lo * ldkv;
+        Tk_all = hi - lo;
+    }
     const int key0 = wave * KW;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // key split (gridDim.z > 1): this block sees only keys [KP z, KP (z + 1)) -- k / v rebased, Tk = its share.  Everything down to the
@@ -262,11 +284,41 @@ int launch_attn_f32(float* out, const float* q, const float* k, const float* v, 
     const int row_tiles = (Tq + AF_ROWS - 1) / AF_ROWS;
     const dim3 grid(row_tiles, heads, split);
     const int width = split > 1 ? nt : (Tk <= 128 ? 2 : Tk <= 256 ? 4 : 8);
-    if (width == 2) attn_f32_kernel<2><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, Tq, Tk, scale, part);
-    else if (width == 4) attn_f32_kernel<4><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, Tq, Tk, scale, part);
-    else attn_f32_kernel<8><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, Tq, Tk, scale, part);
+    const SegTable none = {};
+    if (width == 2) attn_f32_kernel<2, false><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, Tq, Tk, scale, part, none);
+    else if (width == 4) attn_f32_kernel<4, false><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, Tq, Tk, scale, part, none);
+    else attn_f32_kernel<8, false><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, Tq, Tk, scale, part, none);
     OMX_LAUNCH_CHECK();
     if (split > 1) attn_f32_combine_kernel<<<tiles, 256, 0, s>>>(out, part, split, ldo, Tq, row_tiles);
+    OMX_LAUNCH_CHECK();
+    return 0;
+}
+
+int launch_attn_f32_seg(float* out, const float* q, const float* k, const float* v, int64_t ldq, int64_t ldkv, int64_t ldo, const SegTable& sg,
+                        int heads, float scale, hipStream_t s) {
+    OMX_REQUIRE(out && q && k && v && heads >= 1, "segment attention: bad arguments (heads=%d)", heads);
+    OMX_REQUIRE(sg.n >= 1 && sg.n <= kMaxSegments, "segment attention: %d utterances (1..%d)", sg.n, kMaxSegments);
+    OMX_REQUIRE(sg.off[0] == 0, "segment attention: the first utterance must start at row 0 (starts at %d)", sg.off[0]);
+    int tiles = 0, longest = 0;
+    for (int u = 0; u < sg.n; ++u) {
+        const int len = sg.off[u + 1] - sg.off[u];
+        OMX_REQUIRE(len >= 1 && len <= kMaxSegmentRows, "segment attention: utterance %d has %d rows (1..%d: the one-launch attention's key limit)", u,
+                    len, kMaxSegmentRows);
+        tiles += (len + AF_ROWS - 1) / AF_ROWS;
+        longest = len > longest ? len : longest;
+    }
+    const int64_t total = sg.off[sg.n];
+    OMX_REQUIRE(total * ldq < (1ll << 28) && total * ldkv < (1ll << 28), "segment attention: %lld rows of %lld floats exceed the kernel's 32-bit offsets",
+                (long long)total, (long long)(ldq > ldkv ? ldq : ldkv));
+    OMX_REQUIRE(ldq >= 128 * (int64_t)heads && ldkv >= 128 * (int64_t)heads && ldo >= 128 * (int64_t)heads, "segment attention: rows shorter than heads x 128");
+    OMX_REQUIRE(!((ldq | ldkv | ldo) & 3) && aligned16(out) && aligned16(q) && aligned16(k) && aligned16(v),
+                "segment attention: operands must be 16-byte aligned with row strides that are multiples of 4 floats");
+    // every block takes the width of the longest utterance: a shorter one's surplus key tiles are computed and dropped (their probabilities
+    // are written as 0), which costs less than a launch per width
+    const dim3 grid(tiles, heads, 1);
+    if (longest <= 128) attn_f32_kernel<2, true><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, 0, 0, scale, nullptr, sg);
+    else if (longest <= 256) attn_f32_kernel<4, true><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, 0, 0, scale, nullptr, sg);
+    else attn_f32_kernel<8, true><<<grid, 256, 0, s>>>(out, q, k, v, ldq, ldkv, ldo, 0, 0, scale, nullptr, sg);
     OMX_LAUNCH_CHECK();
     return 0;
 }

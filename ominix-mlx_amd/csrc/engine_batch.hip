@@ -672,7 +672,8 @@ int omx_qwen3_batch_set_sampling(omx_qwen3_batch b, int slot, const omx_sampling
     return 0;
 }
 
-int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, uint32_t* first_token) {
+// omx_qwen3_batch_prefill, and omx_qwen3_batch_prefill_embeds (span: the caller's rows over the gathered ones, as omx_qwen3_prefill_embeds)
+static int batch_prefill_prompt(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, uint32_t* first_token, const RowSpan* span) {
     OMX_BATCH_SLOT("omx_qwen3_batch_prefill");
     OMX_REQUIRE(prompt && first_token, "omx_qwen3_batch_prefill: null argument");
     OMX_REQUIRE(n_prompt >= 1, "omx_qwen3_batch_prefill: empty prompt");
@@ -683,18 +684,21 @@ int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt,
         OMX_REQUIRE(prompt[i] < (uint32_t)m->cfg.vocab_size, "omx_qwen3_batch_prefill: token id %u out of range (vocab %d)", prompt[i], m->cfg.vocab_size);
     OMX_REQUIRE(n_prompt <= m->prompt_cap, "omx_qwen3_batch_prefill: prompt of %d tokens exceeds the model's prompt buffer (%d)", n_prompt, m->prompt_cap);
     OMX_REQUIRE(!m->filter_on, "omx_qwen3_batch_prefill: filtered sampling (omx_qwen3_set_sampling) is on; call omx_qwen3_set_sampler first");
+    // a handful of rows of a packed model: the packed rows launches, as the verify pass (nothing dequantised); else the prompt pass's GEMMs
+    const bool prow = m->cfg.quant_bits != 0 && n_prompt <= 8;
+    // (those launches gather and unpack the embedding rows in their own form: there is no row buffer to put the caller's rows in)
+    OMX_REQUIRE(!(span && prow), "InvalidConfig: omx_qwen3_batch_prefill_embeds: a packed model sends prompts of 8 rows or fewer through the "
+                "few-row packed launches, which cannot take embedding rows (%d rows); pass at least 9", n_prompt);
     if (resolve_weights(m)) return 1;
     if (off == 0 && lower_share(b, slot, 0)) return 1;   // rows from 0 on are rewritten: nobody shares them any more
     if (clear_history(b, slot)) return 1;                // the penalties see the tokens sampled since THIS prefill (as omx_qwen3_prefill)
     hipStream_t s = m->stream;
-    // a handful of rows of a packed model: the packed rows launches, as the verify pass (nothing dequantised); else the prompt pass's GEMMs
-    const bool prow = m->cfg.quant_bits != 0 && n_prompt <= 8;
     if (m->cfg.quant_bits && !prow) dq_cache_prepare(m);
     if (prefill_reserve(m, n_prompt, !prow)) return 1;
     OMX_HIP_CHECK(hipMemcpyAsync(m->prompt_dev, prompt, (size_t)n_prompt * 4, hipMemcpyHostToDevice, s));
     const KvSlabs kv = b->kv_bits ? KvSlabs{b->stage_k.data(), b->stage_v.data(), b->cap, b->slot8[slot].data()}
                                   : KvSlabs{b->slot_k[slot].data(), b->slot_v[slot].data(), b->cap};
-    if (prefill_prefix_batched(m, n_prompt, off, nullptr, /*full_last=*/true, prow, &kv)) return 1;
+    if (prefill_prefix_batched(m, n_prompt, off, nullptr, /*full_last=*/true, prow, &kv, nullptr, span)) return 1;
     // the last row through the head and the slot's sampler: the sample launch turns pos = off + n - 1 into off + n
     BatchSlot v = {};
     v.pos = off + n_prompt - 1;
@@ -708,6 +712,33 @@ int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt,
     b->prefilled[slot] = true;
     b->decoded[slot] = 0;
     return 0;
+}
+
+int omx_qwen3_batch_prefill(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, uint32_t* first_token) {
+    return batch_prefill_prompt(b, slot, prompt, n_prompt, first_token, nullptr);
+}
+
+/* omx_qwen3_batch_prefill with rows [first_row, first_row + n_rows) of the pass supplied by the caller (omx_qwen3_prefill_embeds' span, its
+ * refusals and their texts): what a multimodal model needs to decode several clips together.  The slot's cache append (bf16 or kv_bits = 8),
+ * sampler, penalty history and log-probabilities are omx_qwen3_batch_prefill's.  n_rows = 0 IS omx_qwen3_batch_prefill. */
+int omx_qwen3_batch_prefill_embeds(omx_qwen3_batch b, int slot, const uint32_t* prompt, int n_prompt, const void* rows, omx_dtype rows_dtype,
+                                   int first_row, int n_rows, uint32_t* first_token) {
+    OMX_REQUIRE(b && prompt && first_token, "omx_qwen3_batch_prefill_embeds: null argument");
+    OMX_REQUIRE(n_rows >= 0, "omx_qwen3_batch_prefill_embeds: n_rows %d is negative", n_rows);
+    if (n_rows == 0) return batch_prefill_prompt(b, slot, prompt, n_prompt, first_token, nullptr);
+    omx_qwen3 m = b->m;
+    OMX_REQUIRE(rows != nullptr, "omx_qwen3_batch_prefill_embeds: null rows with n_rows %d", n_rows);
+    OMX_REQUIRE(rows_dtype == OMX_FLOAT32 || rows_dtype == OMX_BFLOAT16 || rows_dtype == OMX_FLOAT16,
+                "omx_qwen3_batch_prefill_embeds: rows of dtype %d (float32, bfloat16 or float16)", (int)rows_dtype);
+    OMX_REQUIRE(first_row >= 0 && first_row <= n_prompt && n_rows <= n_prompt - first_row,
+                "omx_qwen3_batch_prefill_embeds: rows [%d, %d + %d) lie outside the prompt of %d tokens", first_row, first_row, n_rows, n_prompt);
+    OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
+                "omx_qwen3_batch_prefill_embeds: tensor-parallel / expert-parallel engines are not supported (single-rank models only)");
+    OMX_REQUIRE(m->cfg.num_experts == 0, "omx_qwen3_batch_prefill_embeds: sparse-MoE models are not supported (dense models only)");
+    OMX_REQUIRE(n_prompt >= 2, "InvalidConfig: omx_qwen3_batch_prefill_embeds: a one-row prompt goes through the decode step, which cannot take "
+                "embedding rows; pass at least 2 rows");
+    const RowSpan span = {rows, rows_dtype, first_row, n_rows};
+    return batch_prefill_prompt(b, slot, prompt, n_prompt, first_token, &span);
 }
 
 int omx_qwen3_batch_fork(omx_qwen3_batch b, int src, int dst, int resample, uint32_t* first_token) {

@@ -129,6 +129,25 @@ struct AttnLayout {
 // float32 attention of the explicit form in one launch (attn_f32.hip): head width 128, no mask, Tk <= 512.  -1 = not this kernel's shape.
 int launch_attn_f32(float* out, const float* q, const float* k, const float* v, int64_t ldq, int64_t ldkv, int64_t ldo, int Tq, int Tk, int heads,
                     float scale, hipStream_t s);
+// Several utterances stacked along the rows of one tensor: utterance u is rows [off[u], off[u + 1]), 1 <= n <= 8.  Passed to kernels by value
+// (40 bytes of kernel arguments): a block finds its utterance with a few scalar compares, nothing is uploaded.
+struct SegTable {
+    int n;
+    int off[9];
+};
+constexpr int kMaxSegments = 8, kMaxSegmentRows = 512;
+// lo / hi: the first row of `row`'s utterance and the row behind its last
+__device__ __forceinline__ void seg_bounds(const SegTable& sg, int row, int& lo, int& hi) {
+    lo = sg.off[0];
+    hi = sg.off[1];
+#pragma unroll
+    for (int u = 1; u < kMaxSegments; ++u)
+        if (u < sg.n && row >= sg.off[u]) { lo = sg.off[u]; hi = sg.off[u + 1]; }
+}
+// launch_attn_f32 over stacked utterances in ONE launch: a query tile lies inside one utterance and reads that utterance's keys only.
+// Every utterance 1..512 rows (the kernel's key limit); anything else is an error -- there is no other path.
+int launch_attn_f32_seg(float* out, const float* q, const float* k, const float* v, int64_t ldq, int64_t ldkv, int64_t ldo, const SegTable& sg,
+                        int heads, float scale, hipStream_t s);
 int launch_attn_prefill(bf16_t* out, const bf16_t* q, const bf16_t* k, const bf16_t* v, int B, int H, int Hkv, int Tq,
                         int Tk, int D, int64_t kv_batch_stride, int64_t kv_head_stride, float scale, int mask_mode,
                         const void* mask, hipStream_t s, bool out_token_major = false,

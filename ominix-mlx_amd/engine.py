@@ -140,6 +140,7 @@ ENGINE_SIGNATURES = {
     "omx_qwen3_batch_set_sampler": (c_int, [c_void_p, c_int, ctypes.c_float, ctypes.c_uint64]),
     "omx_qwen3_batch_set_sampling": (c_int, [c_void_p, c_int, ctypes.POINTER(Sampling), ctypes.c_uint64]),
     "omx_qwen3_batch_prefill": (c_int, [c_void_p, c_int, ctypes.POINTER(c_uint32), c_int, ctypes.POINTER(c_uint32)]),
+    "omx_qwen3_batch_prefill_embeds": (c_int, [c_void_p, c_int, ctypes.POINTER(c_uint32), c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_batch_decode": (c_int, [c_void_p, ctypes.POINTER(c_int), c_int, c_int, ctypes.POINTER(c_uint32)]),
     "omx_qwen3_batch_logits": (c_int, [c_void_p, c_int, c_void_p, c_int]),
     "omx_qwen3_batch_offset": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int)]),
@@ -732,11 +733,26 @@ class Batch:
         p = Sampling(temperature, top_k, top_p, repetition_penalty, presence_penalty)
         check(lib.omx_qwen3_batch_set_sampling(self._h, int(slot), ctypes.byref(p), int(seed) & 0xFFFFFFFFFFFFFFFF))
 
-    def prefill(self, slot: int, prompt) -> int:
-        """The prompt onto the slot's cache (appended to what the slot holds); returns the slot's first sampled token."""
+    def prefill(self, slot: int, prompt, embeds=None, embeds_at: int = 0) -> int:
+        """The prompt onto the slot's cache (appended to what the slot holds); returns the slot's first sampled token.  embeds / embeds_at:
+        Model.prefill's -- rows [n_rows, hidden] (a device Tensor, f32 / bf16 / f16, or a float32 / float16 numpy array) that replace the
+        embedding rows of positions [embeds_at, embeds_at + n_rows) (omx_qwen3_batch_prefill_embeds), with Model.prefill's refusals."""
         p = np.ascontiguousarray(prompt, dtype=np.uint32)
         first = c_uint32()
-        check(lib.omx_qwen3_batch_prefill(self._h, int(slot), p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, ctypes.byref(first)))
+        if embeds is None:
+            check(lib.omx_qwen3_batch_prefill(self._h, int(slot), p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size, ctypes.byref(first)))
+            return first.value
+        from .ops import Tensor
+        if not isinstance(embeds, Tensor):
+            a = np.asarray(embeds)
+            embeds = Tensor.from_numpy(a, "f16" if a.dtype == np.float16 else "f32")
+        hidden = self.model.cfg.hidden_size
+        if len(embeds.shape) != 2 or embeds.shape[1] != hidden:
+            raise OmxError(f"ShapeMismatch: embeds has shape {embeds.shape}, the model expects [n_rows, {hidden}]")
+        check(lib.omx_synchronize(None))   # the rows may come from ops on the null stream; the pass runs on the model's own
+        check(lib.omx_qwen3_batch_prefill_embeds(self._h, int(slot), p.ctypes.data_as(ctypes.POINTER(c_uint32)), p.size,
+                                                 embeds.ptr if embeds.shape[0] else None, embeds.dtype, int(embeds_at), embeds.shape[0],
+                                                 ctypes.byref(first)))
         return first.value
 
     def fork(self, src: int, dst: int, resample: bool = True) -> int:

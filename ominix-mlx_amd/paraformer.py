@@ -46,6 +46,8 @@ PARAFORMER_SIGNATURES = {
     "omx_sanm_encoder_layer": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SanmLayerWeights), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "omx_sanm_encoder_stack": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SanmLayerWeights), c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "omx_sanm_segment_layer_f32": (c_int, [c_void_p, c_void_p, ctypes.POINTER(SanmLayerWeights), ctypes.POINTER(c_int), c_int, c_int, c_int, c_int,
+                                           c_int, c_int, c_void_p]),
     "omx_cif_fire": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int, c_void_p]),
 }
 for _n, (_r, _a) in PARAFORMER_SIGNATURES.items():
@@ -71,6 +73,17 @@ class SanmEncoderLayer:
         out = Tensor(tuple(x.shape[:-1]) + (self.dim,), x.dtype)
         check(lib.omx_sanm_encoder_layer(out.ptr, x.ptr, ctypes.byref(self.w), T, self.in_dim, self.dim, self.heads, self.ffn_dim,
                                          self.kernel_size, out.dtype, None))
+        return out
+
+    def forward_segments(self, x: Tensor, lengths) -> Tensor:
+        """The SenseVoice form of the layer (funasr-nano-mlx/src/sensevoice_encoder.rs:368-384) over utterances of `lengths` rows stacked
+        in x [sum T, in_dim], float32: attention and the FSMN block stop at utterance boundaries (omx_sanm_segment_layer_f32)."""
+        off = np.zeros(len(lengths) + 1, np.int64)
+        off[1:] = np.cumsum(np.asarray(lengths, np.int64))
+        seg = (c_int * len(off))(*[int(v) for v in off])
+        out = Tensor((x.shape[0], self.dim), "f32")
+        check(lib.omx_sanm_segment_layer_f32(out.ptr, x.ptr, ctypes.byref(self.w), seg, len(lengths), self.in_dim, self.dim, self.heads,
+                                             self.ffn_dim, self.kernel_size, None))
         return out
 
 
