@@ -1009,6 +1009,66 @@ int omx_vlm_projector_dims(omx_vlm_projector p, int* in_dim, int* out_dim);
 int omx_vlm_projector_forward(omx_vlm_projector p, const float* x, int rows, float* out, omx_stream stream);
 int omx_vlm_projector_destroy(omx_vlm_projector p);
 
+/* The vision side of DeepSeek-OCR-2 (deepseek-ocr2-mlx/src/vision.rs `ImageEncoderViT::forward` :385-431, qwen2_encoder.rs
+ * `Qwen2Encoder::forward_vision` :198-244) in float32, for the reason given above: a float32 image meets bf16 parameters, nothing is cast.
+ * The caller hands the weights widened to float32, by their checkpoint keys behind the prefix.
+ *   omx_sam_attention_f32: SAM's attention alone over `images` stacked images of a gh x gw grid.  qkv DEVICE rows `ld` floats apart hold
+ *            q | k | v side by side, head h at column 64 h; out [images * gh * gw, heads * 64] token-major in image order.
+ *            s = (q . k) / 8 + q . Rh[qh, kh] + q . Rw[qw, kw] (q unscaled in the bias), R[a, b] = T[a - b + g - 1] with T = rel_pos_*
+ *            [len, 64] resampled nearest-neighbour when len != 2 g - 1 (vision.rs:186-196).  window 0: every key of the image, any
+ *            count -- an online softmax on the float32 matrix cores, nothing of N x N is written to memory, the bias comes from
+ *            [64, gh + gw] tables a block builds in LDS.  window > 0: the grid zero-padded to multiples of the window and cut into
+ *            windows (:271-326) with g = window; the rows are read in place, a padded position reads pad_qkv [3 * heads * 64] (the qkv
+ *            Linear's bias) as its q | k | v, takes part as a key and is dropped as a query; pad_qkv is required when a grid side is no
+ *            multiple of the window.  width other than 64 is refused by name.  Fixed summation order: the same bits twice.
+ *   omx_prefix_causal_attention_f32: `images` stacked sequences of n_rows; qkv rows hold `heads` query heads, then kv_heads key heads,
+ *            then kv_heads value heads of 64; query head h reads key/value head h / (heads / kv_heads); row i sees keys
+ *            j < max(n_prefix, i + 1) of its own sequence (qwen2_encoder.rs:249-288); scale 1 / 8; any n_rows.
+ *   omx_sam_encoder_*: images DEVICE f32 [n, S, S, 3] in [-1, 1], S a multiple of the patch -> out_rows DEVICE f32 [n * (S / P / 4)^2,
+ *            net_3's rows].  16 x 16 patch convolution + bias, + pos_embed (gathered nearest-neighbour where its grid differs, :435-454),
+ *            the blocks (LayerNorm 1e-6, attention as above -- global on global_attn_indexes, windowed elsewhere --, tanh GELU), neck
+ *            and the two stride-2 convolutions; neck and output widths are read from the weights.  keep_stages: keep a copy of the rows
+ *            after the positions and after every block for debug_read (tests).  tokens: the grid side, the rows per image that come out
+ *            and their width.  scratch_bytes: the device scratch the handle holds after its last forward (the split-K workspace the
+ *            GEMMs share per stream is not the handle's).  debug_read stages: "patches", "h0", "block<N>" [n * G * G, embed_dim],
+ *            "neck" [n * G * G, neck width], "out".
+ *   omx_vcf_encoder_*: x DEVICE f32 [n * n_img, hidden] (the SAM rows) -> out_rows DEVICE f32 [n * n_query, hidden]: per image its rows
+ *            followed by query_768 (n_img == 144) or query_1024 (otherwise), `layers` Qwen2 layers (RMSNorm, q | k | v with bias in one
+ *            stacked GEMM, RoPE over the full 64 dims at positions 0 .. L - 1, the prefix-causal attention with n_prefix = n_img,
+ *            SwiGLU MLP), the final RMSNorm, the query rows.  debug_read stages: "layer<N>" [n * L, hidden] (keep_stages), "out". */
+typedef struct omx_sam_encoder_* omx_sam_encoder;
+typedef struct omx_vcf_encoder_* omx_vcf_encoder;
+typedef struct omx_sam_config_ {
+    int embed_dim, depth, num_heads, mlp_dim, window, patch_size, n_global, keep_stages;
+    int global_attn_indexes[16];
+    char key_prefix[128];
+} omx_sam_config;
+typedef struct omx_vcf_config_ {
+    int hidden, layers, heads, kv_heads, intermediate, keep_stages;
+    float rope_theta, eps;
+    char key_prefix[128];
+} omx_vcf_config;
+int omx_sam_attention_f32(float* out, int64_t ldo, const float* qkv, int64_t ld, int images, int gh, int gw, int heads, int width, int window,
+                          const float* rel_pos_h, int len_h, const float* rel_pos_w, int len_w, const float* pad_qkv, omx_stream stream);
+int omx_prefix_causal_attention_f32(float* out, int64_t ldo, const float* qkv, int64_t ld, int images, int n_rows, int heads, int kv_heads, int width,
+                                    int n_prefix, omx_stream stream);
+int omx_sam_encoder_create(omx_sam_encoder* out, const omx_sam_config* cfg);
+int omx_sam_encoder_load(omx_sam_encoder e, const char* name, const float* host, const int64_t* shape, int ndim);
+int omx_sam_encoder_tokens(omx_sam_encoder e, int image_size, int* grid, int* n_rows, int* out_dim);
+int omx_sam_encoder_forward(omx_sam_encoder e, const float* images, int n_images, int image_size, float* out_rows, omx_stream stream);
+int omx_sam_encoder_launches(omx_sam_encoder e, int* n);   /* launches the last forward enqueued, split-K reduce launches not counted */
+int omx_sam_encoder_scratch_bytes(omx_sam_encoder e, size_t* bytes);
+int omx_sam_encoder_debug_read(omx_sam_encoder e, const char* name, float* host, size_t n_elems);
+int omx_sam_encoder_destroy(omx_sam_encoder e);
+int omx_vcf_encoder_create(omx_vcf_encoder* out, const omx_vcf_config* cfg);
+int omx_vcf_encoder_load(omx_vcf_encoder e, const char* name, const float* host, const int64_t* shape, int ndim);
+int omx_vcf_encoder_tokens(omx_vcf_encoder e, int n_img, int* n_query, int* seq_len);
+int omx_vcf_encoder_forward(omx_vcf_encoder e, const float* x, int n_images, int n_img, float* out_rows, omx_stream stream);
+int omx_vcf_encoder_launches(omx_vcf_encoder e, int* n);
+int omx_vcf_encoder_scratch_bytes(omx_vcf_encoder e, size_t* bytes);
+int omx_vcf_encoder_debug_read(omx_vcf_encoder e, const char* name, float* host, size_t n_elems);
+int omx_vcf_encoder_destroy(omx_vcf_encoder e);
+
 /* =====================================================================================
  * a13: Paraformer body pieces (funasr-mlx/src/paraformer.rs).
  *   omx_sanm_encoder_layer  SanmEncoderLayer::forward :618-634 = LayerNorm(1e-5) -> SanmAttention (:496-532:

@@ -40,6 +40,18 @@ class ViTConfig(ctypes.Structure):
                 ("mean", ctypes.c_float * 3), ("std", ctypes.c_float * 3), ("key_prefix", ctypes.c_char * 128)]
 
 
+class SamConfig(ctypes.Structure):
+    """The SAM ViT-B tower of DeepSeek-OCR-2 (deepseek-ocr2-mlx/src/vision.rs:492-496; omx_sam_config of include/omx.h)"""
+    _fields_ = [("embed_dim", c_int), ("depth", c_int), ("num_heads", c_int), ("mlp_dim", c_int), ("window", c_int), ("patch_size", c_int),
+                ("n_global", c_int), ("keep_stages", c_int), ("global_attn_indexes", c_int * 16), ("key_prefix", ctypes.c_char * 128)]
+
+
+class VcfConfig(ctypes.Structure):
+    """The visual-causal-flow encoder of DeepSeek-OCR-2 (qwen2_encoder.rs:305-311; omx_vcf_config of include/omx.h)"""
+    _fields_ = [("hidden", c_int), ("layers", c_int), ("heads", c_int), ("kv_heads", c_int), ("intermediate", c_int), ("keep_stages", c_int),
+                ("rope_theta", ctypes.c_float), ("eps", ctypes.c_float), ("key_prefix", ctypes.c_char * 128)]
+
+
 AUDIO_SIGNATURES = {
     "omx_mel_frontend_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(MelConfig)]),
     "omx_mel_frontend_destroy": (c_int, [c_void_p]),
@@ -86,6 +98,26 @@ AUDIO_SIGNATURES = {
     "omx_vlm_projector_dims": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "omx_vlm_projector_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "omx_vlm_projector_destroy": (c_int, [c_void_p]),
+    # the DeepSeek-OCR-2 vision side in float32 (csrc/sam_encoder.hip, csrc/vcf_encoder.hip; the classes are in vision.py)
+    "omx_sam_attention_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                      c_void_p, c_void_p]),
+    "omx_prefix_causal_attention_f32": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "omx_sam_encoder_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(SamConfig)]),
+    "omx_sam_encoder_load": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(c_int64), c_int]),
+    "omx_sam_encoder_tokens": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "omx_sam_encoder_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "omx_sam_encoder_launches": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "omx_sam_encoder_scratch_bytes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_size_t)]),
+    "omx_sam_encoder_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
+    "omx_sam_encoder_destroy": (c_int, [c_void_p]),
+    "omx_vcf_encoder_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(VcfConfig)]),
+    "omx_vcf_encoder_load": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.POINTER(c_int64), c_int]),
+    "omx_vcf_encoder_tokens": (c_int, [c_void_p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "omx_vcf_encoder_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "omx_vcf_encoder_launches": (c_int, [c_void_p, ctypes.POINTER(c_int)]),
+    "omx_vcf_encoder_scratch_bytes": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_size_t)]),
+    "omx_vcf_encoder_debug_read": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
+    "omx_vcf_encoder_destroy": (c_int, [c_void_p]),
 }
 for _n, (_r, _a) in AUDIO_SIGNATURES.items():
     _f = getattr(lib, _n)

@@ -110,6 +110,7 @@ struct GemmF32 {
     int* defer_splits = nullptr;
     // the vision towers' epilogues (vit_encoder.hip), off by default: exact-erf GELU after the bias, and a per-column factor [N]
     // (LayerScale) applied before the residual: out = resid + col_scale * (alpha A.B + bias).  Neither goes with a deferred epilogue.
+    // gelu: 1 the exact erf form; 2 the tanh form (nn::gelu_approximate, the SAM tower of sam_encoder.hip)
     int gelu = 0;
     const float* col_scale = nullptr;
 };

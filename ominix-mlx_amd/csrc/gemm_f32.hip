@@ -34,6 +34,8 @@ struct F32Args {
 
 // what follows alpha, bias and relu in every epilogue: nn::gelu (mlx-rs/src/nn/activation.rs:164) in its exact form, then the column factor
 __device__ __forceinline__ float f32_tail(const F32Args& g, float v, int col) {
+    // gelu == 2: nn::gelu_approximate (activation.rs:168-177), the tanh form the SAM tower's MLP uses (sam_encoder.hip)
+    if (g.gelu == 2) v = 0.5f * v * (1.0f + tanhf(0.79788456080286535588f * (v + 0.044715f * (v * v * v)))); else
     if (g.gelu) v = 0.5f * v * (1.0f + erff(v * 0.70710678118654752440f));
     if (g.col_scale) v *= g.col_scale[col];
     return v;
