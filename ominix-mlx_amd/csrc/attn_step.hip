@@ -257,13 +257,22 @@ __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4
 // of (row pair, K quarter), 12 KB each, drawn from a ticket counter in LDS into two register sets per wave.  The arithmetic is
 // gemv_kernel<6, 4, 2, PRO_NONE, EPI_RESIDUAL>'s -- a quarter is a dot8 chain over its six vectors per lane + wave_sum, the four partials are
 // added in quarter order from 0.f, bf16(resid + bf16(sum)) -- and gemv_kernel<8, 1, 2, PRO_RMSNORM, EPI_STORE>'s on three q/k/v rows per
-// wave.  A wave asks for its first two units and two of its three q/k/v rows -- they depend on nothing -- as soon as its last pair is
-// reduced, and for the third row as soon as its last unit is: 40 KB per wave stream through the activation hop.  Waves 0 and 4 bring the
-// activation vector in first, half each (nothing of their own in flight in front of the granules); wave 0 finishes the rows and brings the
-// residual row in, its q/k/v rows long landed.  Forms measured at Qwen3-8B shapes, ctx 2 k (EXPERIMENTS C-4; parent 347.6 tok/s):
+// wave.  The block's 24 activation granules are stored FIRST, behind the barrier that follows the block's last pair; only then does a
+// non-sweeper wave ask for its first two units and the first of its three q/k/v rows -- they depend on nothing --, for its second row
+// directly behind the sweepers' pass and for the third as soon as its last unit is reduced: 40 KB per wave stream through the activation
+// hop.  Waves 0 and 4 bring the activation vector in first, half each, in one straight-line pass (nothing of their own in flight in front
+// of the granules; one down unit behind them, the tags read behind a counted wait); wave 0 finishes the rows and brings the residual row
+// in, its q/k/v rows long landed.  Forms measured at Qwen3-8B shapes, ctx 2 k (EXPERIMENTS C-4; parent 347.6 tok/s):
 //   * wave 0 alone sweeping the activation vector in three passes of 32 granules per lane, all q/k/v rows asked for behind the last unit
-//     (wave 0's behind the row's sweep): 344.1; with two q/k/v rows up front as here: 343.7 -- more requests queued, longer round trips;
-//   * as here: 351.9; without the watch in front of the residual row's sweep: 350.6.
+//     (wave 0's behind the row's sweep): 344.1; with two q/k/v rows up front: 343.7 -- more requests queued, longer round trips;
+//   * waves 0 and 4 sweeping half each in one pass: 351.9; without the watch in front of the residual row's sweep: 350.6.
+// Issue order around the hop (EXPERIMENTS C-5, mean tok/s against the parent's of the same interleaved set):
+//   * both rows behind the sweepers' pass, two units in front: 354.07 against 353.96; one unit in front, the second behind the pass with the
+//     rows: 351.85; two units + one row in front, one row behind the pass: 354.42 (set 1), 352.90 against 351.25 (set 2) -- no gain alone;
+//   * the first down unit into the register set that gate/up's loop leaves free: 353.73; the third q/k/v row ahead of the last unit's
+//     reduce: 352.68; all three together: 353.49 against 353.96 -- not in the tree;
+//   * the activation granules stored before the block's own requests (they used to queue behind the other waves' 240 KB): 355.37 against
+//     351.25; with two units + one row in front and one row behind the pass, as here: 355.98 (set 2), 356.64 against 351.67 (set 3).
 constexpr int kDnInter = 12288, kDnBlockRows = 16, kDnNV = kDnInter / 512 / 4, kDnUnits = kDnBlockRows / 2 * 4, kDnQRows = 3;
 // LDS of the phase, in the (dead) split-merge area at the front: the activation vector, the K-quarter partials, the parked activations
 constexpr int kDnPartOff = kDnInter * 2, kDnParkOff = kDnPartOff + kDnBlockRows * 4 * 4, kDnLdsBytes = kDnParkOff + kGuBlockPairs * 2;
@@ -332,24 +341,63 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
     // Measured (EXPERIMENTS C-4): the more weight requests are queued when the sweep starts, the longer each of its round trips -- the hop is
     // kept short by its number of round trips, not by what is parked in front of it
     const bool sweeper = (wave & (kWaves / 2 - 1)) == 0;   // waves 0 and 4 bring the activation vector in, half each
-    if (!sweeper) {
-        tA = down_claim(sm_gu, lane);
-        down_issue(a, dA, row_begin, tA, lane);
-        tB = down_claim(sm_gu, lane);
-        down_issue(a, dB, row_begin, tB, lane);
-        issue_qkv(0, kDnQRows - 1);
-    }
     lds_barrier();   // the block's 48 activations are parked
+    // publish FIRST: every block's sweep waits for the slowest block's granules, and stored behind the block's own 240 KB of fresh weight
+    // requests they became visible late (the sweep was done at 55.9 us; with this order at 48.8, EXPERIMENTS C-5)
+    if (wave == 0 && lane < kGuBlockPairs / 2)
+        st_granule_u32(a.ag + (size_t)blk * (kGuBlockPairs / 2) + lane, tag, reinterpret_cast<const unsigned*>(sm_dn + kDnParkOff)[lane]);
+    lds_barrier();   // the block's granules are in the CU's queue: what the block asks for now is behind them
     if (sweeper) {
-        if (wave == 0 && lane < kGuBlockPairs / 2)
-            st_granule_u32(a.ag + (size_t)blk * (kGuBlockPairs / 2) + lane, tag, reinterpret_cast<const unsigned*>(sm_dn + kDnParkOff)[lane]);
-        sweep_granules<kDnInter / 2, 2>(a.ag, reinterpret_cast<unsigned*>(xa), __builtin_amdgcn_readfirstlane(wave) / (kWaves / 2), tag, lane, a.abort_flag);
+        // (written out, not sweep_granules: the first pass is straight-line, its tags read behind a counted wait -- gateup_phase's pattern)
+        constexpr int HALF = kDnInter / 2 / 2, GPL = HALF / 64;   // the granules of a sweeper's half, per lane
+        const int half = __builtin_amdgcn_readfirstlane(wave) / (kWaves / 2);
+        const uint64_t* gr = a.ag + (size_t)half * HALF;
+        for (unsigned spins = 0; spins < kGranuleSpinLimit; ++spins) {   // politely: one granule per lane, a sleep between looks
+            const unsigned long long g = ld_granule(gr + (size_t)lane * GPL + (GPL - 1));
+            if (__all((unsigned)(g >> 32) == tag)) break;
+            __builtin_amdgcn_s_sleep(4);
+        }
+        unsigned long long g[GPL];
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) g[i] = ld_granule(gr + (size_t)i * 64 + lane);
+        __builtin_amdgcn_sched_barrier(0);
+        lds_barrier();   // the sweep is in the CU's queue: what the block asks for now is behind it
+        tA = down_claim(sm_gu, lane);
+        down_issue(a, dA, row_begin, tA, lane);   // (one unit: with two, or with the rows, behind 96 registers of granules the kernel spills)
+        unsigned bad = 0;
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) bad |= (unsigned)(g[i] >> 32) ^ tag;
+        asm volatile("; activation vector: tags read behind the first down unit" : "+v"(bad));
+        if (!__all(bad == 0)) {
+            for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+                for (int i = 0; i < GPL; ++i) g[i] = ld_granule(gr + (size_t)i * 64 + lane);
+                bool ok = true;
+#pragma unroll
+                for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
+                if (__all(ok)) break;
+                if (spins >= kGranuleSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
+                    if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(4);
+            }
+        }
+        unsigned* sx = reinterpret_cast<unsigned*>(xa) + half * HALF;   // natural element order
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) sx[i * 64 + lane] = (unsigned)g[i];
         if (TRACE && threadIdx.x == 0) tr[11] = wall_clock64();
+        tB = down_claim(sm_gu, lane);   // into the registers the granules have left
+        down_issue(a, dB, row_begin, tB, lane);
+        issue_qkv(0, kDnQRows - 1);
+    } else {
         tA = down_claim(sm_gu, lane);
         down_issue(a, dA, row_begin, tA, lane);
         tB = down_claim(sm_gu, lane);
         down_issue(a, dB, row_begin, tB, lane);
-        issue_qkv(0, kDnQRows - 1);
+        issue_qkv(0, 1);
+        lds_barrier();
+        issue_qkv(1, kDnQRows - 1);   // the second row directly behind the sweepers' pass: it cannot delay it
     }
     lds_barrier();   // the activation vector is in LDS
     down_reduce(dA, xa, part, tA, lane);
