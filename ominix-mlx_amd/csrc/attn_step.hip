@@ -257,12 +257,17 @@ __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4
 // of (row pair, K quarter), 12 KB each, drawn from a ticket counter in LDS into two register sets per wave.  The arithmetic is
 // gemv_kernel<6, 4, 2, PRO_NONE, EPI_RESIDUAL>'s -- a quarter is a dot8 chain over its six vectors per lane + wave_sum, the four partials are
 // added in quarter order from 0.f, bf16(resid + bf16(sum)) -- and gemv_kernel<8, 1, 2, PRO_RMSNORM, EPI_STORE>'s on three q/k/v rows per
-// wave.  The block's 24 activation granules are stored FIRST, behind the barrier that follows the block's last pair; only then does a
-// non-sweeper wave ask for its first two units and the first of its three q/k/v rows -- they depend on nothing --, for its second row
-// directly behind the sweepers' pass and for the third as soon as its last unit is reduced: 40 KB per wave stream through the activation
-// hop.  Waves 0 and 4 bring the activation vector in first, half each, in one straight-line pass (nothing of their own in flight in front
-// of the granules; one down unit behind them, the tags read behind a counted wait); wave 0 finishes the rows and brings the residual row
-// in, its q/k/v rows long landed.  Forms measured at Qwen3-8B shapes, ctx 2 k (EXPERIMENTS C-4; parent 347.6 tok/s):
+// wave.  What is asked for where:
+//   * hop four (activation vector): the block's 24 activation granules are stored FIRST, behind the barrier that follows the block's last
+//     pair; only then does a non-sweeper wave ask for its first two down units -- they depend on nothing -- and NOTHING else: 24 KB per
+//     wave stream through the hop.  Waves 0 and 4 bring the activation vector in, half each, in one straight-line pass (nothing of their
+//     own in flight in front of the granules; one down unit behind them, the tags read behind a counted wait);
+//   * hop five (residual row): behind the block's last unit wave 0 finishes the 16 rows and stores their 8 granules, asks for the whole
+//     residual row at once -- no watch: an optimistic straight-line pass right behind the publish -- and the block meets at an LDS-only
+//     barrier; behind it every wave asks for all three of its q/k/v rows (192 KB per block), which stream while the row crosses and is
+//     normalised.  Wave 0 reads the tags behind a counted wait (its rows stay in flight); a tag that is not there yet sends it into the
+//     draining retry loop, behind the rows.  Until C-6 two of the three rows were asked for around hop four, which did not want them,
+//     and hop five idled HBM.  Forms measured at Qwen3-8B shapes, ctx 2 k (EXPERIMENTS C-4; parent 347.6 tok/s):
 //   * wave 0 alone sweeping the activation vector in three passes of 32 granules per lane, all q/k/v rows asked for behind the last unit
 //     (wave 0's behind the row's sweep): 344.1; with two q/k/v rows up front: 343.7 -- more requests queued, longer round trips;
 //   * waves 0 and 4 sweeping half each in one pass: 351.9; without the watch in front of the residual row's sweep: 350.6.
@@ -272,7 +277,13 @@ __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4
 //   * the first down unit into the register set that gate/up's loop leaves free: 353.73; the third q/k/v row ahead of the last unit's
 //     reduce: 352.68; all three together: 353.49 against 353.96 -- not in the tree;
 //   * the activation granules stored before the block's own requests (they used to queue behind the other waves' 240 KB): 355.37 against
-//     351.25; with two units + one row in front and one row behind the pass, as here: 355.98 (set 2), 356.64 against 351.67 (set 3).
+//     351.25; with two units + one row in front and one row behind the pass (the tree until C-6): 355.98 (set 2), 356.64 against 351.67 (set 3).
+// The rows moved to hop five (EXPERIMENTS C-6, mean tok/s of four runs; parent 358.41 in set 1, 355.62 in set 2):
+//   * A, publish -> watch -> pass -> barrier -> three rows: 361.60; B, the same without the watch, as here: 368.33 (set 1), 365.89 (set 2);
+//   * C, the rows of waves 1..7 right behind a barrier that follows the publish, wave 0 watch -> pass -> its rows: 366.56, 364.17; C without
+//     the watch: 361.22 (set 2) -- the rows in front of the optimistic pass delay it, and a miss costs a second pass;
+//   * E, row 0 left in front of hop four, on A / B / C: 362.51 / 367.09 / 365.62 (set 1), on B 364.35 (set 2) -- row 0 carries 1.2-1.5 of B's 10;
+//   * D, a third named down set through hop four: 256 VGPRs and 332 bytes of scratch -- not run.
 constexpr int kDnInter = 12288, kDnBlockRows = 16, kDnNV = kDnInter / 512 / 4, kDnUnits = kDnBlockRows / 2 * 4, kDnQRows = 3;
 // LDS of the phase, in the (dead) split-merge area at the front: the activation vector, the K-quarter partials, the parked activations
 constexpr int kDnPartOff = kDnInter * 2, kDnParkOff = kDnPartOff + kDnBlockRows * 4 * 4, kDnLdsBytes = kDnParkOff + kGuBlockPairs * 2;
@@ -328,9 +339,9 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
     u32x4 dA[2][kDnNV], dB[2][kDnNV];
     int tA = 0, tB = 0;
     u32x4 qw[kDnQRows][kGuNV];
-    auto issue_qkv = [&](const int r0, const int r1) {
+    auto issue_qkv = [&]() {
 #pragma unroll
-        for (int r = r0; r < r1; ++r) {
+        for (int r = 0; r < kDnQRows; ++r) {
             const u32x4* p = reinterpret_cast<const u32x4*>(a.nq.row_ptr(min(q_row0 + r, a.nq.rows - 1), kGuHidden));   // clamp: surplus waves re-read the last row
 #pragma unroll
             for (int j = 0; j < kGuNV; ++j) qw[r][j] = ld_nt(p + j * 64 + lane);
@@ -389,15 +400,12 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
         if (TRACE && threadIdx.x == 0) tr[11] = wall_clock64();
         tB = down_claim(sm_gu, lane);   // into the registers the granules have left
         down_issue(a, dB, row_begin, tB, lane);
-        issue_qkv(0, kDnQRows - 1);
     } else {
         tA = down_claim(sm_gu, lane);
         down_issue(a, dA, row_begin, tA, lane);
         tB = down_claim(sm_gu, lane);
         down_issue(a, dB, row_begin, tB, lane);
-        issue_qkv(0, 1);
-        lds_barrier();
-        issue_qkv(1, kDnQRows - 1);   // the second row directly behind the sweepers' pass: it cannot delay it
+        lds_barrier();   // (the sweepers' barrier behind their pass)
     }
     lds_barrier();   // the activation vector is in LDS
     down_reduce(dA, xa, part, tA, lane);
@@ -428,18 +436,52 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
         n_reduced += 2;
     }
     if (TRACE && lane == 0) __hip_atomic_fetch_add(sm_gu + kDnReduced, n_reduced, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    issue_qkv(kDnQRows - 1, kDnQRows);   // the wave's last row, into the registers its down sets have left
     lds_barrier();   // every K-quarter partial of the block's 16 rows is in LDS
+    // publish FIRST, as at the head of the phase: every block's sweep waits for the slowest block's granules
+    if (wave == 0 && lane < kDnBlockRows / 2) {
+        // rows 2 * lane and 2 * lane + 1 of the block: the pair leaves twice, to the ping-pong buffer (the next attention launch reads it
+        // as its residual) and as a tagged granule for the q/k/v rows of every block
+        const uint32_t o2 = residual_pair<A, 4>(part + 2 * lane * 4, res2);
+        reinterpret_cast<uint32_t*>(a.dn_out)[row_begin / 2 + lane] = o2;
+        st_granule_u32(a.rg + row_begin / 2 + lane, tag, o2);
+    }
     if (wave == 0) {
-        if (lane < kDnBlockRows / 2) {
-            // rows 2 * lane and 2 * lane + 1 of the block: the pair leaves twice, to the ping-pong buffer (the next attention launch reads it
-            // as its residual) and as a tagged granule for the q/k/v rows of every block
-            const uint32_t o2 = residual_pair<A, 4>(part + 2 * lane * 4, res2);
-            reinterpret_cast<uint32_t*>(a.dn_out)[row_begin / 2 + lane] = o2;
-            st_granule_u32(a.rg + row_begin / 2 + lane, tag, o2);
+        // (written out, not sweep_granules: the first pass is straight-line, its tags read behind a counted wait -- gateup_phase's pattern)
+        // No watch: the optimistic pass goes out right behind the publish, so the block's 192 KB of q/k/v rows are asked for at once and
+        // stream while the row crosses; a pass that came too early is repeated behind them (measured against the watched forms, C-6)
+        constexpr int GPL = kGuHidden / 2 / 64;   // granules per lane
+        unsigned long long g[GPL];
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) g[i] = ld_granule(a.rg + (size_t)i * 64 + lane);
+        __builtin_amdgcn_sched_barrier(0);
+        lds_barrier();   // the publish and the sweep are in the CU's queue: what the block asks for now is behind them
+        issue_qkv();
+        unsigned bad = 0;
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) bad |= (unsigned)(g[i] >> 32) ^ tag;
+        asm volatile("; residual row: tags read behind wave 0's q/k/v rows" : "+v"(bad));
+        if (!__all(bad == 0)) {
+            for (unsigned spins = 0;; ++spins) {
+#pragma unroll
+                for (int i = 0; i < GPL; ++i) g[i] = ld_granule(a.rg + (size_t)i * 64 + lane);
+                bool ok = true;
+#pragma unroll
+                for (int i = 0; i < GPL; ++i) ok &= (unsigned)(g[i] >> 32) == tag;
+                if (__all(ok)) break;
+                if (spins >= kGranuleSpinLimit) {   // a producer never showed up: void result, loud flag, no hang
+                    if (lane == 0) __hip_atomic_store(a.abort_flag, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    break;
+                }
+                __builtin_amdgcn_s_sleep(4);
+            }
         }
-        sweep_granules<kGuHidden / 2, 1>(a.rg, reinterpret_cast<unsigned*>(xs), 0, tag, lane, a.abort_flag);
+        unsigned* sx = reinterpret_cast<unsigned*>(xs);   // the raw row, natural element order
+#pragma unroll
+        for (int i = 0; i < GPL; ++i) sx[i * 64 + lane] = (unsigned)g[i];
         if (TRACE && lane == 0) tr[13] = wall_clock64();
+    } else {
+        lds_barrier();
+        issue_qkv();   // all three rows, into the registers the wave's down sets have left
     }
     lds_barrier();   // the residual row is in LDS
     rmsnorm_in_lds<A, PV>(xs, red, nwv, kGuHidden, a.eps, threadIdx.x < 256);

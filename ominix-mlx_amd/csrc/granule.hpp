@@ -3,9 +3,9 @@
 // A producer writes a granule with ONE relaxed agent-scope 8-byte store (write-through: no store-ack wait, no arrival counter, no flag);
 // a consumer re-reads it with relaxed agent-scope loads until the tag matches (cdna_hip_programming.md Guideline 16, form R2).  The tag
 // is derived from the step sequence number, so nothing has to be reset between launches.
-// Who calls what: st_granule* / ld_granule -- attn_step.hip, gemv_chain.hip; sweep_granules -- attn_step.hip
-// (down_qkv_phase: the residual row; the activation vector's sweep, half per sweeping wave, is this text written out there for its first
-// pass's counted wait) and gemv_chain.hip (wave 0 of down_qkv_kernel: the residual row); kGranuleSpinLimit -- every bounded wait of those two files.
+// Who calls what: st_granule* / ld_granule -- attn_step.hip, gemv_chain.hip; sweep_granules -- gemv_chain.hip (wave 0 of
+// down_qkv_kernel: the residual row; attn_step.hip's down_qkv_phase writes this text out for the activation vector, half per sweeping wave,
+// and for the residual row, for the first pass's counted wait); kGranuleSpinLimit -- every bounded wait of those two files.
 #pragma once
 #include "common.hpp"
 
