@@ -277,6 +277,17 @@ typedef struct omx_qwen3_config_ {
 typedef struct omx_qwen3_* omx_qwen3;
 
 int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg);
+/* DeepSeek-V2 family layer plan (cfg->moe_mode 2; deepseek-ocr2-mlx/src/lib.rs:988): layers [0, first_k_dense_replace) carry a dense SwiGLU
+ * MLP of intermediate_size ("mlp.{gate,up,down}_proj"), the rest the float32 router "mlp.gate", the stacks "mlp.switch_mlp.*" and --
+ * n_shared_experts > 0 -- one shared MLP "mlp.shared_experts.{gate,up,down}_proj" of width n_shared_experts * moe_intermediate_size
+ * added to the routed sum; the router's weights are multiplied by routed_scaling_factor (omx_moe_deepseek_forward).  bf16, single
+ * rank, no attention_bias.  The plan travels beside omx_qwen3_config, whose layout stays as it is; omx_qwen3_create on a mode-2 config
+ * is the plan {0, 0, 1.0} (every layer routes, no shared experts).  Modes 0 / 1 take no plan: all three zero (the factor 0 or 1). */
+typedef struct omx_qwen3_deepseek_plan_ {
+    int first_k_dense_replace, n_shared_experts;
+    float routed_scaling_factor;
+} omx_qwen3_deepseek_plan;
+int omx_qwen3_create_deepseek(omx_qwen3* out, const omx_qwen3_config* cfg, const omx_qwen3_deepseek_plan* plan);
 int omx_qwen3_destroy(omx_qwen3 m);
 /* register a weight by HF key name; `ptr` is this rank's shard (column-split q/k/v/gate/up/lm_head rows,
  * row-split o/down columns), bf16 (packed u32 / bf16 scales, biases for a quantized checkpoint), contiguous, `nbytes` long: the
@@ -750,6 +761,34 @@ int omx_moe_experts(void* y, const void* x_rows, const uint32_t* expert_ids, int
                     const void* w_up, const void* w_down, int hidden, int inter, int n_experts, omx_stream stream);
 int omx_moe_combine(void* out, const void* y_slots, const void* scores, int n_tokens, int hidden, int top_k,
                     omx_stream stream);
+
+/* DeepSeek-V2 family block (deepseek-ocr2-mlx/src/lib.rs:162-299 MoEGate::route + MoE::forward): routed experts plus shared experts
+ * under a third routing arithmetic ("mode 2") -- float32 gate logits (nothing rounded to bf16), softmax over all experts, top-k
+ * (descending, ties to the lower index), division by (sum + 1e-20) where norm_topk_prob && top_k > 1, then routed_scaling_factor; the
+ * weights stay float32.  out = bf16( bf16(sum_j f32(bf16 y_j) * w_j) + bf16(shared_experts(x)) ).
+ *   w_gate / w_up [n_experts + stack_tail, inter, hidden], w_down [n_experts + stack_tail, hidden, inter], bf16: the routed experts and,
+ *     where stack_tail == n_shared, the shared MLP behind them as n_shared pseudo-experts of width inter (gate / up: its row blocks,
+ *     down: its column blocks).  A token is then top_k + n_shared slots of the expert-selected GEMVs: four launches per block.
+ *   sh_gate / sh_up [n_shared * inter, hidden], sh_down [hidden, n_shared * inter] (optional): the shared MLP whole, for more rows than
+ *     32 slots hold (n_tokens * (top_k + n_shared) > 32) and for OMX_MOE_SHARED_SLOTS=0.
+ * omx_moe_deepseek_form names the launch sequence a call takes: 0 slots, 1 separate GEMVs, 2 grouped GEMMs, -1 none (weights missing).
+ * inds_out [n_tokens, top_k] u32 and weights_out [n_tokens, top_k] float32 are optional. */
+int omx_moe_deepseek_form(int n_tokens, int hidden, int inter, int top_k, int n_shared, int stack_tail, int have_separate);
+int omx_moe_deepseek_workspace_bytes(int n_tokens, int hidden, int inter, int n_experts, int top_k, int n_shared, size_t* bytes);
+int omx_moe_deepseek_forward(void* out, const void* x, const void* gate_w, const void* w_gate, const void* w_up, const void* w_down,
+                             int stack_tail, const void* sh_gate, const void* sh_up, const void* sh_down, int n_tokens, int hidden,
+                             int inter, int n_experts, int top_k, int n_shared, int norm_topk_prob, float routed_scaling_factor,
+                             uint32_t* inds_out, float* weights_out, omx_stream stream);
+/* decoder-block form: out = resid + block(rmsnorm(x) * norm_w); xn [n_tokens, hidden] receives the normalised rows */
+int omx_moe_deepseek_block_forward(void* out, const void* resid, const void* x, const void* norm_w, float eps, void* xn,
+                                   const void* gate_w, const void* w_gate, const void* w_up, const void* w_down, int stack_tail,
+                                   const void* sh_gate, const void* sh_up, const void* sh_down, int n_tokens, int hidden, int inter,
+                                   int n_experts, int top_k, int n_shared, int norm_topk_prob, float routed_scaling_factor,
+                                   omx_stream stream);
+/* the mode-2 router alone (norm_w optional: the block's RMSNorm folded in, rows left in xn) */
+int omx_moe_route_deepseek(uint32_t* inds_out, float* weights_out, const void* x, const void* gate_w, const void* norm_w, float eps,
+                           void* xn, int n_tokens, int hidden, int n_experts, int top_k, int norm_topk_prob,
+                           float routed_scaling_factor, omx_stream stream);
 
 /* =====================================================================================
  * a14 (+ a9): FLUX.2-klein DiT / MMDiT forward -- FluxKlein::forward_with_rope

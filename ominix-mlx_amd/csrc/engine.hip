@@ -38,9 +38,20 @@ __global__ void rope_table_kernel(float* cos_t, float* sin_t, int cap, int half,
 
 extern "C" {
 
-int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) {
+int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) { return omx_qwen3_create_deepseek(out, cfg, nullptr); }
+
+int omx_qwen3_create_deepseek(omx_qwen3* out, const omx_qwen3_config* cfg, const omx_qwen3_deepseek_plan* plan) {
     OMX_REQUIRE(out && cfg, "omx_qwen3_create: null argument");
-    const omx_qwen3_config& c = *cfg;
+    EngineConfig with_plan;
+    static_cast<omx_qwen3_config&>(with_plan) = *cfg;
+    if (plan) {
+        with_plan.first_k_dense_replace = plan->first_k_dense_replace;
+        with_plan.n_shared_experts = plan->n_shared_experts;
+        with_plan.routed_scaling_factor = plan->routed_scaling_factor;
+    } else if (cfg->num_experts > 0 && cfg->moe_mode == 2) {
+        with_plan.routed_scaling_factor = 1.f;
+    }
+    const EngineConfig& c = with_plan;
     OMX_REQUIRE(c.tp_size >= 1 && c.tp_rank >= 0 && c.tp_rank < c.tp_size, "InvalidConfig: tp rank %d of %d", c.tp_rank, c.tp_size);
     OMX_REQUIRE(c.hidden_size > 0 && c.hidden_size % 64 == 0, "InvalidConfig: hidden_size %d must be a multiple of 64", c.hidden_size);
     OMX_REQUIRE(c.head_dim == 64 || c.head_dim == 128, "InvalidConfig: head_dim %d (64 or 128 supported)", c.head_dim);
@@ -80,11 +91,25 @@ int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) {
     OMX_REQUIRE(!c.float16_weights || !c.attention_bias, "InvalidConfig: float16_weights with attention_bias (dense float16 Qwen2) is not supported");
     OMX_REQUIRE(!c.float16_weights || c.head_dim == 128, "InvalidConfig: float16_weights needs head_dim 128 (got %d)", c.head_dim);
     m->f16 = c.quant_scales_f16 || c.float16_weights;
+    // DeepSeek-V2 family (moe_mode 2): a dense prefix, shared experts, a scaled float32 router -- bf16 on one rank
+    const bool ds = c.num_experts > 0 && c.moe_mode == 2;
+    OMX_REQUIRE(ds || (c.first_k_dense_replace == 0 && c.n_shared_experts == 0 && (c.routed_scaling_factor == 0.f || c.routed_scaling_factor == 1.f)),
+                "InvalidConfig: first_k_dense_replace %d, n_shared_experts %d and routed_scaling_factor %g belong to moe_mode 2 (deepseek) with experts",
+                c.first_k_dense_replace, c.n_shared_experts, (double)c.routed_scaling_factor);
+    OMX_REQUIRE(!ds || !c.quant_bits, "InvalidConfig: moe_mode 2 (deepseek) with quant_bits %d is not supported (bf16 checkpoints)", c.quant_bits);
+    OMX_REQUIRE(!ds || !c.float16_weights, "InvalidConfig: moe_mode 2 (deepseek) with float16_weights is not supported");
+    OMX_REQUIRE(!ds || !c.attention_bias, "InvalidConfig: moe_mode 2 (deepseek) with attention_bias is not supported");
+    OMX_REQUIRE(!ds || c.tp_size <= 1, "InvalidConfig: moe_mode 2 (deepseek) with tp_size %d is not supported (single rank)", c.tp_size);
+    OMX_REQUIRE(!ds || m->cfg.ep_size <= 1, "InvalidConfig: moe_mode 2 (deepseek) with ep_size %d is not supported (single rank)", m->cfg.ep_size);
+    OMX_REQUIRE(!ds || (c.first_k_dense_replace >= 0 && c.first_k_dense_replace <= c.num_hidden_layers && c.n_shared_experts >= 0 &&
+                        c.n_shared_experts <= 8 && c.routed_scaling_factor > 0.f),
+                "InvalidConfig: moe_mode 2 (deepseek): first_k_dense_replace %d of %d layers, n_shared_experts %d (0..8), routed_scaling_factor %g (> 0)",
+                c.first_k_dense_replace, c.num_hidden_layers, c.n_shared_experts, (double)c.routed_scaling_factor);
     m->H = c.num_attention_heads / c.tp_size;
     m->Hkv = c.num_key_value_heads >= c.tp_size ? c.num_key_value_heads / c.tp_size : 1;
     m->I = c.intermediate_size / c.tp_size;
     m->V = c.vocab_size / c.tp_size;
-    OMX_REQUIRE(c.num_experts > 0 || m->I % 64 == 0, "InvalidConfig: per-rank intermediate %d must be a multiple of 64", m->I);
+    OMX_REQUIRE(!any_dense_layer(c) || m->I % 64 == 0, "InvalidConfig: per-rank intermediate %d must be a multiple of 64", m->I);
     OMX_REQUIRE(!c.quant_bits || (c.hidden_size % 512 == 0 && (m->H * c.head_dim) % 512 == 0 && (c.num_experts > 0 || m->I % 512 == 0)),
                 "InvalidConfig: quantized checkpoints need hidden %d, attention width %d and intermediate %d to be multiples of 512", c.hidden_size, m->H * c.head_dim, m->I);
     OMX_REQUIRE(!c.attention_bias || !c.quant_bits, "InvalidConfig: attention_bias (Qwen2) runs on bf16 checkpoints");
@@ -120,13 +145,14 @@ int omx_qwen3_create(omx_qwen3* out, const omx_qwen3_config* cfg) {
                     "InvalidConfig: expert parallel rank %d of %d over %d experts", c.ep_rank, c.ep_size, c.num_experts);
         OMX_REQUIRE(!c.quant_bits || c.moe_intermediate_size % 512 == 0, "InvalidConfig: quantised experts need moe_intermediate_size %% 512 == 0 (%d)", c.moe_intermediate_size);
         OMX_REQUIRE(c.num_experts_per_tok >= 1 && c.num_experts_per_tok <= c.num_experts && c.moe_intermediate_size > 0 &&
-                        c.moe_intermediate_size % 64 == 0 && (c.moe_mode == 0 || c.moe_mode == 1) && (c.tp_size > 1 || m->H * D >= c.hidden_size),
+                        c.moe_intermediate_size % 64 == 0 && (c.moe_mode == 0 || c.moe_mode == 1 || c.moe_mode == 2) && (c.tp_size > 1 || m->H * D >= c.hidden_size),
                     "InvalidConfig: experts %d top-%d moe_intermediate_size %d mode %d", c.num_experts, c.num_experts_per_tok,
                     c.moe_intermediate_size, c.moe_mode);
         // the MoE block takes its scratch from the library workspace: size it ONCE for the largest batch (a whole-context
         // prefill) so that the pointers captured in the step graph never move
         size_t need = 0;
         omx_moe_workspace_bytes(m->cap, c.hidden_size, c.moe_intermediate_size, c.num_experts, c.num_experts_per_tok, &need);
+        if (ds) omx_moe_deepseek_workspace_bytes(m->cap, c.hidden_size, c.moe_intermediate_size, c.num_experts, c.num_experts_per_tok, c.n_shared_experts, &need);
         void* ws = nullptr;
         if (get_workspace(&ws, need)) return 1;
         if (c.ep_size > 1 && get_workspace_aux(&ws, need, m->stream)) return 1;   // the expert-parallel block's per-stream scratch (moe.hip)
@@ -261,10 +287,11 @@ int omx_qwen3_set_sampling(omx_qwen3 m, const omx_sampling* p, uint64_t seed) {
  * token (enqueue_step_tail), over the raw logits row.  They are launch sites of the captured step: the graphs are dropped. */
 int omx_qwen3_set_logprobs(omx_qwen3 m, int top_n) {
     OMX_REQUIRE(m, "omx_qwen3_set_logprobs: null model");
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     OMX_REQUIRE(top_n < 0 || (c.tp_size <= 1 && c.ep_size <= 1 && m->allreduce == nullptr),
                 "omx_qwen3_set_logprobs: tensor / expert parallel models are not supported (tp_size %d, ep_size %d: a rank holds a "
                 "vocabulary shard, the row's log-sum-exp would need an all-reduce)", c.tp_size, c.ep_size);
+    OMX_REQUIRE(top_n < 0 || !(c.num_experts > 0 && c.moe_mode == 2), "omx_qwen3_set_logprobs: moe_mode 2 (deepseek) models are not supported");
     OMX_REQUIRE(top_n < 0 || !m->f16, "omx_qwen3_set_logprobs: float16 models (float16 weights or float16 triplets) are not supported: the row reduction "
                 "reads bfloat16 logits");
     OMX_REQUIRE(top_n >= -1 && top_n <= OMX_LOGPROBS_MAX_TOP && top_n <= m->V,
@@ -443,7 +470,8 @@ int omx_qwen3_prefill_embeds(omx_qwen3 m, const uint32_t* prompt, int n_prompt, 
                 "omx_qwen3_prefill_embeds: rows [%d, %d + %d) lie outside the prompt of %d tokens", first_row, first_row, n_rows, n_prompt);
     OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
                 "omx_qwen3_prefill_embeds: tensor-parallel / expert-parallel engines are not supported (single-rank models only)");
-    OMX_REQUIRE(m->cfg.num_experts == 0, "omx_qwen3_prefill_embeds: sparse-MoE models are not supported (dense models only)");
+    // (moe_mode 2, the DeepSeek-V2 family: the decoder of an image-to-text model, whose prompt IS caller rows -- accepted)
+    OMX_REQUIRE(m->cfg.num_experts == 0 || m->cfg.moe_mode == 2, "omx_qwen3_prefill_embeds: sparse-MoE models are not supported (dense models only)");
     const RowSpan span = {rows, rows_dtype, first_row, n_rows};
     return prefill_prompt(m, prompt, n_prompt, first_token, &span);
 }
@@ -480,6 +508,7 @@ int omx_qwen3_verify(omx_qwen3 m, const uint32_t* tokens, int n, uint32_t* greed
     OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
                 "omx_qwen3_verify: tensor / expert parallel models are not supported (single-rank models only)");
     const bool packed = m->cfg.quant_bits != 0;
+    OMX_REQUIRE(!(m->cfg.num_experts > 0 && m->cfg.moe_mode == 2), "omx_qwen3_verify: moe_mode 2 (deepseek) models are not supported");
     OMX_REQUIRE(!m->cfg.float16_weights, "omx_qwen3_verify: dense float16 models (float16_weights) are not supported; speculative verify runs "
                 "on bf16 weights or bf16-scale packed weights");
     OMX_REQUIRE(!packed || !m->cfg.quant_scales_f16,
@@ -860,12 +889,15 @@ int omx_qwen3_decode_path(omx_qwen3 m, int* path) {
 
 int omx_qwen3_step_bytes(omx_qwen3 m, int ctx, double* bytes) {
     OMX_REQUIRE(m && bytes, "omx_qwen3_step_bytes: null argument");
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const double D = c.head_dim, hd = c.hidden_size;
     // 2 B x [L (h H D + 2 h Hkv D + H D h + 3 h I) + V h] + ctx (2 L Hkv D 2 B) + KV write
     // sparse MoE: the router plus the top-k experts' three matrices are what one token streams
     const double moe_i = c.tp_size > 1 && c.num_experts > 0 ? m->moe_I : c.moe_intermediate_size;   // (expert tensor parallel: this rank's columns)
-    const double ffn = c.num_experts > 0 ? hd * c.num_experts + 3.0 * hd * moe_i * c.num_experts_per_tok : 3.0 * hd * m->I;
+    // (mode 2: the shared experts stream with every token, and the first first_k_dense_replace layers are dense)
+    const double ffn_moe = hd * c.num_experts + 3.0 * hd * moe_i * (c.num_experts_per_tok + (c.moe_mode == 2 ? c.n_shared_experts : 0));
+    const double n_dense = c.num_experts == 0 ? c.num_hidden_layers : (c.moe_mode == 2 ? c.first_k_dense_replace : 0);
+    const double ffn = (n_dense * 3.0 * hd * m->I + (c.num_hidden_layers - n_dense) * ffn_moe) / c.num_hidden_layers;   // mean over the layer plan
     const double per_layer = hd * m->H * D + 2.0 * hd * m->Hkv * D + m->H * D * hd + ffn;
     // bytes per weight element: bf16 = 2; quantized = bits/8 packed + (scale + bias) bf16 per group
     const double bpe = c.quant_bits ? c.quant_bits / 8.0 + 4.0 / c.quant_group : 2.0;

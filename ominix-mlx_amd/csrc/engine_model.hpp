@@ -39,6 +39,10 @@ constexpr int kNcclFloat32 = 7, kNcclUint64 = 5, kNcclBfloat16 = 9, kNcclSum = 0
 struct LayerW {
     const bf16_t *q, *k, *v, *o, *gate, *up, *down, *q_norm, *k_norm, *in_ln, *post_ln;
     const bf16_t *moe_gate, *moe_wg, *moe_wu, *moe_wd;   // sparse-MoE feed-forward (router + stacked experts)
+    // moe_mode 2: the shared MLP whole (checkpoint tensors), and how many pseudo-experts it contributes behind the routed experts of
+    // moe_wg / moe_wu / moe_wd (0: those are the checkpoint's stacks; n_shared_experts: owned copies with the split shared MLP appended)
+    const bf16_t *sh_gate, *sh_up, *sh_down;
+    int moe_tail;
     const bf16_t *q_bias, *k_bias, *v_bias, *qkv_bias;   // Qwen2: projection biases; qkv_bias = the three concatenated (owned)
 };
 
@@ -48,6 +52,16 @@ struct LayerQ {
     QMat q, k, v, o, gate, up, down;
     QMat moe_router, moe_g, moe_u, moe_d;   // sparse-MoE feed-forward: quantised router and expert stacks
 };
+
+// which feed-forward layer l carries: modes 0 / 1 put experts in every layer, mode 2 (DeepSeek-V2 family) behind a dense prefix
+// the engine's configuration: the caller's omx_qwen3_config and, behind it, the DeepSeek-V2 family layer plan of omx_qwen3_create_deepseek
+// (zeros for every other model)
+struct EngineConfig : omx_qwen3_config {
+    int first_k_dense_replace = 0, n_shared_experts = 0;
+    float routed_scaling_factor = 0.f;
+};
+inline bool layer_is_moe(const EngineConfig& c, int l) { return c.num_experts > 0 && (c.moe_mode != 2 || l >= c.first_k_dense_replace); }
+inline bool any_dense_layer(const EngineConfig& c) { return c.num_experts == 0 || (c.moe_mode == 2 && c.first_k_dense_replace > 0); }
 
 // kernel classes timed by omx_qwen3_time_step_kernels: an event pair armed for the launch that follows (launch_timing.hpp)
 enum { KC_QKV = 0, KC_ATTN, KC_O, KC_GATE_UP, KC_DOWN, KC_HEAD, KC_ENGINE, KC_COUNT };
@@ -119,7 +133,7 @@ struct RowSpan {
 using namespace omx;
 
 struct omx_qwen3_ {
-    omx_qwen3_config cfg;
+    EngineConfig cfg;
     // float16 activations: a packed checkpoint with float16 triplets, or a dense float16 one -- the model then runs in float16 end to
     // end (embedding row, norms, RoPE, K/V slabs, every rounding point, logits, sampler); every float16 branch keys on this
     bool f16 = false;

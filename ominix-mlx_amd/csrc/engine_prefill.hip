@@ -70,7 +70,7 @@ void launch_encoder_mask(bf16_t* mask, const uint8_t* am, int T, hipStream_t s) 
 // here, on the host, AHEAD of a prompt's device-timed region (a hipMalloc between the launches leaves the device idle for its duration)
 // dequant = false: the row buffers only (the verify pass of a packed model dequantises no weight: qgemv_rows.hip)
 int prefill_reserve(omx_qwen3 m, int T, bool dequant) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const int hd = c.hidden_size, D = c.head_dim, H = m->H, Hkv = m->Hkv, I = m->I;
     if (T > m->pf_cap) {
         OMX_HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -101,7 +101,7 @@ int prefill_reserve(omx_qwen3 m, int T, bool dequant) {
 // ONE allocation, made once per model -- host time (~0.03 s per GB) that omx_qwen3_prefill spends ahead of its device-timed region.
 void dq_cache_prepare(omx_qwen3 m) {
     if (m->dq_cache_mode >= 0) return;
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const size_t hd = c.hidden_size, D = c.head_dim, H = m->H, Hkv = m->Hkv, I = m->I;
     const size_t per_layer = (H * D * hd * 2 + 2 * Hkv * D * hd + (c.num_experts == 0 ? 3 * I * hd : 0)) * 2;
     size_t free_b = 0, total_b = 0;
@@ -233,7 +233,7 @@ static int launch_override_rows(bf16_t* dst, const void* src, omx_dtype dt, int6
 // span (omx_qwen3_prefill_embeds only): rows of the caller's that replace the gathered embedding rows before the first layer
 int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, bool full_last, bool packed_rows_pass, const KvSlabs* kv,
                            const RaggedRows* rag, const RowSpan* span) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     // float16 checkpoints (round 4): the same pass in float16 -- weights dequantised to float16, the eight-wave GEMM kernel's float16
     // form, float16 norms / RoPE / slabs, the flash attention kernel's float16 form -- for
     // plain prompts of a dense model, also on tensor-parallel shards (each rank's float16 partial products summed in f32); encode /
@@ -433,10 +433,19 @@ int prefill_prefix_batched(omx_qwen3 m, int T, int off, const EncodeOpts* enc, b
         if (!(w = W(L.o, &Q.o, H * D)) || row_split(h2, m->pf_attn, w, h, H * D)) return 1;
         GemmSegs gu = {};
         gu.w_gate = L.gate; gu.w_up = L.up; gu.out_act = m->pf_g; gu.half = I; gu.ld_act = I; gu.act_mode = 1;
-        const bool gu_norm = !f16 && c.num_experts == 0 && seg_gemm && gemm_segmented_preferred(T, hd, gu) && gemv_rows_takes_norm(T, hd, gu);
-        if (!gu_norm && omx_rms_norm(m->pf_xn, h2, L.post_ln, T, hd, c.rms_norm_eps, act_dt, s)) return 1;
+        const bool gu_norm = !f16 && !layer_is_moe(c, l) && seg_gemm && gemm_segmented_preferred(T, hd, gu) && gemv_rows_takes_norm(T, hd, gu);
+        const bool ds_moe = layer_is_moe(c, l) && c.moe_mode == 2;      // (its router launch normalises the rows itself)
+        if (!gu_norm && !ds_moe && omx_rms_norm(m->pf_xn, h2, L.post_ln, T, hd, c.rms_norm_eps, act_dt, s)) return 1;
         if (gu_norm) { gu.pre_norm_w = L.post_ln; gu.pre_norm_eps = c.rms_norm_eps; }
-        if (c.num_experts > 0) {   // sparse-MoE feed-forward over all T rows (grouped MFMA GEMM route), then the residual
+        if (ds_moe) {   // DeepSeek-V2 family: float32 router, routed + shared experts, the residual in the combine
+            if (omx_moe_deepseek_block_forward(h, h2, h2, L.post_ln, c.rms_norm_eps, m->pf_xn, L.moe_gate, L.moe_wg, L.moe_wu, L.moe_wd, L.moe_tail,
+                                               L.sh_gate, L.sh_up, L.sh_down, T, hd, c.moe_intermediate_size, c.num_experts, c.num_experts_per_tok,
+                                               c.n_shared_experts, c.norm_topk_prob, c.routed_scaling_factor, s))
+                return 1;
+            if (tap_out(l)) return 1;
+            continue;
+        }
+        if (layer_is_moe(c, l)) {   // sparse-MoE feed-forward over all T rows (grouped MFMA GEMM route), then the residual
             if (quant && (c.ep_size > 1 || c.tp_size > 1)) {
                 // packed stacks under expert parallelism / expert tensor parallelism (round 5): this rank's stacks dequantised per call, the
                 // bf16 batched form, ONE all-reduce of the [T, hidden] f32 partial (the exchange combine stays a bf16-checkpoint path)

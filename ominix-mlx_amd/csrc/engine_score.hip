@@ -65,6 +65,7 @@ int omx_qwen3_score(omx_qwen3 m, const uint32_t* tokens, int n, const uint32_t* 
     OMX_REQUIRE(m, "omx_qwen3_score: null model");
     OMX_REQUIRE(m->allreduce == nullptr && m->cfg.tp_size <= 1 && m->cfg.ep_size <= 1,
                 "omx_qwen3_score: tensor / expert parallel models are not supported (the vocabulary is sharded; single-rank models only)");
+    OMX_REQUIRE(!(m->cfg.num_experts > 0 && m->cfg.moe_mode == 2), "omx_qwen3_score: moe_mode 2 (deepseek) models are not supported");
     OMX_REQUIRE(!m->f16, "omx_qwen3_score: float16 models (float16 weights or float16 triplets) are not supported; bf16 activations only");
     OMX_REQUIRE(n >= 1, "omx_qwen3_score: %d tokens (at least 1)", n);
     OMX_REQUIRE(tokens && targets && logprobs, "omx_qwen3_score: null argument");

@@ -223,7 +223,7 @@ static int add_step_logprobs(omx_qwen3 m, hipStream_t s) {
 static int add_sampling_noise(omx_qwen3 m, hipStream_t s) {
     if (m->filter_on) return add_filtered_sampling(m, s);
     if (m->temperature == 0.f) return 0;
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const int tp = c.tp_size > 1 ? c.tp_size : 1;
     if (launch_rng_next(m->rng, s)) return 1;
     return launch_sample_noise(m->argmax_partials, m->n_argmax_partials, m->logits, m->rng + 2, m->V, c.tp_rank * m->V,
@@ -234,7 +234,7 @@ static int add_sampling_noise(omx_qwen3 m, hipStream_t s) {
 // O matrix is 4-bit --, single rank, a shape the kernel has a register layout for; OMX_ATTN_OPROJ=0 keeps the two launches
 bool attention_takes_oproj(omx_qwen3 m, int layer) {
     const bool off = env_off("OMX_ATTN_OPROJ");        // (read per call: tests flip it between engines of one process)
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     // (tensor parallel: the rank's heads and columns -- the launch then leaves the f32 partial for the all-reduce)
     // every block of that launch waits on others: all Hkv * nsplit of them must be resident, one per CU
     if (off || m->oproj_disabled || m->Hkv * m->attn_nsplit > m->cus) return false;
@@ -257,7 +257,7 @@ bool any_layer_takes_oproj(omx_qwen3 m) {
 
 // what the folds of the dense step share: dense bf16 weights, a single rank without a communicator, no experts, the launch-per-op form
 static bool dense_bf16_single_rank_per_op(omx_qwen3 m) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     if (c.quant_bits != 0 || m->f16 || c.num_experts > 0 || c.tp_size > 1 || c.ep_size > 1 || m->allreduce != nullptr) return false;
     return step_engine_mode(m) == 0;
 }
@@ -274,7 +274,7 @@ static StackedRows qkv_rows(omx_qwen3 m, int layer) {
 // grid that is resident as a whole (every workgroup of that launch waits on all others); OMX_DOWN_QKV=0 keeps the two launches
 bool down_takes_qkv(omx_qwen3 m) {
     const bool off = env_off("OMX_DOWN_QKV");          // (read per call: tests flip it between engines of one process)
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     if (off || m->chain_disabled || !dense_bf16_single_rank_per_op(m)) return false;
     if (env_int("OMX_GEMV_RPW_QKV", 0) != 0 || env_int("OMX_GEMV_RPW_DOWN", 0) != 0) return false;
     if (!m->chain_gran || !gemv_chain_ok(c.hidden_size, m->I, (m->H + 2 * m->Hkv) * c.head_dim)) return false;
@@ -287,7 +287,7 @@ bool down_takes_qkv(omx_qwen3 m) {
 // plan of these heads has 256 blocks) and that grid resident as a whole.  A q/k/v bias (Qwen2 wiring) does not touch gate/up and is allowed; OMX_ATTN_GATEUP=0 keeps the two launches
 bool attention_takes_gateup(omx_qwen3 m, int layer) {
     const bool off = env_off("OMX_ATTN_GATEUP");       // (read per call: tests flip it between engines of one process)
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     if (off || m->gateup_disabled || !dense_bf16_single_rank_per_op(m)) return false;
     if (env_int("OMX_GEMV_RPW_O", 0) != 0 || env_int("OMX_GEMV_RPW_GU", 0) != 0) return false;
     if (!m->gateup_gran || m->cus < 256 || !attention_takes_oproj(m, layer)) return false;
@@ -300,7 +300,7 @@ bool attention_takes_gateup(omx_qwen3 m, int layer) {
 // switches either off switches this off with it; OMX_ATTN_DOWN=0 keeps the two launches per layer
 bool attention_takes_down(omx_qwen3 m, int layer) {
     const bool off = env_off("OMX_ATTN_DOWN");         // (read per call: tests flip it between engines of one process)
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     if (off || !m->act_gran || layer + 1 >= c.num_hidden_layers || !attention_takes_gateup(m, layer) || !down_takes_qkv(m)) return false;
     return attn_step_down_ok(c.hidden_size, m->I, (m->H + 2 * m->Hkv) * c.head_dim);
 }
@@ -320,7 +320,7 @@ static bool peer_fused_fits(omx_qwen3 m, int N, int K) {
 // layer's [RMSNorm + q/k/v] behind that (attention_takes_down)
 static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* resid = nullptr, bf16_t* out = nullptr, float* out_f32 = nullptr,
                              bool gateup = false, bool down = false) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const int D = c.head_dim;
     const LayerW& L = m->layers[l];
     AttnStepArgs a = {};
@@ -371,7 +371,7 @@ static int enqueue_attention(omx_qwen3 m, int l, hipStream_t s, const bf16_t* re
 // keys meet in one unsigned max.  with_head = false (a prompt token whose logits nobody reads): advance to the next prompt token.
 // Every launch is a recording site: the AQL replay refuses a step with a launch that is none.
 int enqueue_step_tail(omx_qwen3 m, bool with_head, const bf16_t* h, const float* pending, int pending_n, bool tp) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     hipStream_t s = m->stream;
     if (!with_head) {
         OMX_LAUNCH(feed_prompt_kernel, 1, 1, 0, s, m->st, m->prompt_dev);
@@ -409,7 +409,7 @@ int enqueue_step_tail(omx_qwen3 m, bool with_head, const bf16_t* h, const float*
 
 // the same step on a quantized checkpoint: packed-weight GEMVs (quant.hip) with the prologues / epilogues of the bf16 step
 static int enqueue_step_quant(omx_qwen3 m, bool with_head) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     hipStream_t s = m->stream;
     const int hd = c.hidden_size, D = c.head_dim;
     const bool sf16 = c.quant_scales_f16 != 0;
@@ -520,7 +520,7 @@ static int enqueue_step_quant(omx_qwen3 m, bool with_head) {
 // segment of the engine: two launches per layer instead of four, the weight stream of three ops crossing its two edges without a stop.
 int step_engine_mode(omx_qwen3 m) {
     const int mode = env_int("OMX_STEP_ENGINE", 0);    // (read per call: tests flip it between engines of one process)
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const bool ok = mode > 0 && !m->se_disabled && !m->filter_on && m->lp_top < 0 && c.quant_bits == 0 && !m->f16 && c.num_experts == 0 && c.tp_size == 1 && c.ep_size <= 1 && m->allreduce == nullptr &&
            !c.attention_bias && m->se_gran != nullptr && m->cus > 0 &&
            step_engine_ok(c.hidden_size, m->H, m->Hkv, c.head_dim, m->I, m->attn_nsplit, m->cus);
@@ -533,7 +533,7 @@ bool step_engine_takes(omx_qwen3 m) { return step_engine_mode(m) != 0; }
 // seg_layer = i: one segment of the hybrid step -- [gate/up, down] of layer i - 1 on the post-attention residual in m->h2, the new residual
 // to m->h; [RMSNorm + q/k/v] of layer i into m->qkv
 static int enqueue_step_engine(omx_qwen3 m, hipStream_t s, int seg_layer = -1) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const int D = c.head_dim, hd = c.hidden_size;
     StepEngineArgs a = {};
     a.layers = m->se_layers;
@@ -573,7 +573,7 @@ inline void time_next_launch(omx_qwen3 m, int layer, int cls) {
 
 // the hybrid step (step_engine_mode == 2): per layer [engine segment] [attention + o]; m->h = residual entering a layer, m->h2 = after attention
 static int enqueue_step_hybrid(omx_qwen3 m, bool with_head) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     hipStream_t s = m->stream;
     const int hd = c.hidden_size, D = c.head_dim, L = c.num_hidden_layers;
     OMX_LAUNCH(embed_kernel, 2, 256, 0, s, m->h, m->embed, m->st, hd, m->step_seq, m->rope_cur, m->rope_cos, m->rope_sin, D / 2);
@@ -602,7 +602,7 @@ static int enqueue_step_hybrid(omx_qwen3 m, bool with_head) {
 // tuning knob: OMX_GEMV_RPW_<QKV|O|GU|DOWN>=n overrides the rows-per-wave (per block for K-split kernels) heuristic of gemv.hip
 int enqueue_step(omx_qwen3 m, bool with_head) {
     if (m->cfg.quant_bits) return enqueue_step_quant(m, with_head);
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     hipStream_t s = m->stream;
     const int hd = c.hidden_size, D = c.head_dim;
     const bool ep = c.ep_size > 1;                               // expert parallel: attention replicated, one all-reduce per MoE block
@@ -623,7 +623,8 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
     int pending_n = 1;                //   ... how many f32 vectors `pending` holds (summed in order by the consumer's prologue)
     // MoE block without its weighted-sum launch (the next GEMV folds the experts' outputs in): every block of that GEMV reads top_k
     // extra f32 vectors, so by default only for top-2 routing (Mixtral-8x7B: 206.4 -> 207.9 tok/s); OMX_MOE_FOLD=1 forces it, 0 disables
-    const bool moe_fold = env_on("OMX_MOE_FOLD", c.num_experts_per_tok <= 2) && c.num_experts > 0 && !ep && !tp;
+    // (not mode 2: its combine adds the shared experts and rounds at other points)
+    const bool moe_fold = env_on("OMX_MOE_FOLD", c.num_experts_per_tok <= 2) && c.num_experts > 0 && c.moe_mode != 2 && !ep && !tp;
     // layers 0 .. L-2 end with [down + residual + the next layer's RMSNorm + q/k/v] in one launch: layers 1 .. L-1 find their q/k/v done
     const bool chain = !engine && down_takes_qkv(m);
     for (int l = 0; l < (engine ? 0 : c.num_hidden_layers); ++l) {
@@ -701,7 +702,17 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
             pending = m->partial_b;
             continue;
         }
-        if (c.num_experts > 0) {
+        if (layer_is_moe(c, l) && c.moe_mode == 2) {
+            // DeepSeek-V2 family: [RMSNorm + float32 router] [gate/up + SwiGLU over top_k + n_shared slots] [down, float32 rows]
+            // [weighted sum + shared experts + residual]  (deepseek-ocr2-mlx/src/lib.rs:224-298); a dense layer of the plan falls through
+            if (omx_moe_deepseek_block_forward(hn, h, h, L.post_ln, c.rms_norm_eps, m->moe_xn, L.moe_gate, L.moe_wg, L.moe_wu, L.moe_wd,
+                                               L.moe_tail, L.sh_gate, L.sh_up, L.sh_down, 1, hd, c.moe_intermediate_size, c.num_experts,
+                                               c.num_experts_per_tok, c.n_shared_experts, c.norm_topk_prob, c.routed_scaling_factor, s))
+                return 1;
+            std::swap(h, hn);
+            continue;
+        }
+        if (layer_is_moe(c, l)) {
             // [RMSNorm] [router] [expert gate/up + SwiGLU] [expert down] [weighted sum] [+ residual]
             // (qwen3_moe.rs:475-503 / mixtral model.rs:296-308, :343-344)
             if (moe_fold) {   // ... without the last two launches: the down GEMVs store the weighted outputs, the next GEMV folds them in
@@ -773,7 +784,7 @@ int enqueue_step(omx_qwen3 m, bool with_head) {
 // launches and the MoE block's are not recording sites.  Any failure leaves the engine on its hipGraph (and says why once on stderr with OMX_STEP_AQL_VERBOSE).
 int step_aql_mode(omx_qwen3 m) {
     const int mode = env_int("OMX_STEP_AQL", 0);
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     if (mode <= 0 || m->aql_disabled || m->eager || m->allreduce != nullptr || c.tp_size > 1 || c.ep_size > 1 || c.num_experts > 0 ||
         m->temperature != 0.f || m->filter_on || m->lp_top >= 0 || step_engine_mode(m) != 0)
         return 0;

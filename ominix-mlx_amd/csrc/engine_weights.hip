@@ -21,7 +21,7 @@ std::pair<int, int> quant_format_of(omx_qwen3 m, const std::string& prefix) {
 // The packed Linear / embedding the forward reads at module path `prefix` of a dense model: its contraction width K, or 0 for a path
 // that names none (layer index out of range, a norm, an lm_head the tied model does not have)
 static int packed_module_k(omx_qwen3 m, const std::string& prefix) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     if (prefix == "model.embed_tokens") return c.hidden_size;
     if (prefix == "lm_head") return c.tie_word_embeddings ? 0 : c.hidden_size;
     if (prefix.compare(0, 13, "model.layers.") != 0) return 0;
@@ -43,7 +43,7 @@ int resolve_weights(omx_qwen3 m) {
         m->dq_cache.clear();          // (the slab stays: the same shapes come back)
         m->dq_cache_bytes = 0;
     }
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const bool quant = c.quant_bits != 0;
     const int D = c.head_dim, hd = c.hidden_size;
     auto get = [&](const std::string& n, const bf16_t** out) -> int {
@@ -104,7 +104,7 @@ int resolve_weights(omx_qwen3 m) {
             OMX_HIP_CHECK(hipMemcpyAsync(cat + nq + nk, L.v_bias, nk * 2, hipMemcpyDeviceToDevice, m->stream));
             L.qkv_bias = cat;
         }
-        if (c.num_experts > 0) {
+        if (layer_is_moe(c, i)) {
             const std::string mp = p + (c.moe_mode == 0 ? "block_sparse_moe." : "mlp.");
             // (expert tensor parallel: this rank's columns of every expert; expert parallel: this rank's experts)
             const int Im = c.tp_size > 1 ? m->moe_I : c.moe_intermediate_size;
@@ -112,6 +112,28 @@ int resolve_weights(omx_qwen3 m) {
             if (lin(mp + "gate", E, &L.moe_gate, &Q.moe_router, hd) || lin(mp + "switch_mlp.gate_proj", Im, &L.moe_wg, &Q.moe_g, hd, El) ||
                 lin(mp + "switch_mlp.up_proj", Im, &L.moe_wu, &Q.moe_u, hd, El) || lin(mp + "switch_mlp.down_proj", hd, &L.moe_wd, &Q.moe_d, Im, El))
                 return 1;
+            if (c.moe_mode == 2 && c.n_shared_experts > 0) {
+                if (get(mp + "shared_experts.gate_proj.weight", &L.sh_gate) || get(mp + "shared_experts.up_proj.weight", &L.sh_up) ||
+                    get(mp + "shared_experts.down_proj.weight", &L.sh_down))
+                    return 1;
+                // the decode form streams the shared MLP as n_shared pseudo-experts BEHIND the routed ones, through the same two
+                // expert-selected launches: stacks of E + n_shared matrices, the tail being the shared gate / up row blocks and the
+                // shared down projection's column blocks (moe.hip).  OMX_MOE_SHARED_SLOTS=0: the checkpoint's stacks as they are.
+                if (!env_off("OMX_MOE_SHARED_SLOTS")) {
+                    const size_t ns = c.n_shared_experts, per = (size_t)Im * hd, routed = (size_t)E * per;
+                    bf16_t *wg = nullptr, *wu = nullptr, *wd = nullptr;
+                    if (dev_alloc(m, &wg, routed + ns * per) || dev_alloc(m, &wu, routed + ns * per) || dev_alloc(m, &wd, routed + ns * per)) return 1;
+                    OMX_HIP_CHECK(hipMemcpyAsync(wg, L.moe_wg, routed * 2, hipMemcpyDeviceToDevice, m->stream));
+                    OMX_HIP_CHECK(hipMemcpyAsync(wu, L.moe_wu, routed * 2, hipMemcpyDeviceToDevice, m->stream));
+                    OMX_HIP_CHECK(hipMemcpyAsync(wd, L.moe_wd, routed * 2, hipMemcpyDeviceToDevice, m->stream));
+                    OMX_HIP_CHECK(hipMemcpyAsync(wg + routed, L.sh_gate, ns * per * 2, hipMemcpyDeviceToDevice, m->stream));
+                    OMX_HIP_CHECK(hipMemcpyAsync(wu + routed, L.sh_up, ns * per * 2, hipMemcpyDeviceToDevice, m->stream));
+                    for (size_t j = 0; j < ns; ++j)      // pseudo-expert j of down: columns [j Im, (j + 1) Im) of [hidden, ns Im]
+                        OMX_HIP_CHECK(hipMemcpy2DAsync(wd + routed + j * per, (size_t)Im * 2, L.sh_down + j * Im, ns * Im * 2, (size_t)Im * 2, hd,
+                                                       hipMemcpyDeviceToDevice, m->stream));
+                    L.moe_wg = wg; L.moe_wu = wu; L.moe_wd = wd; L.moe_tail = (int)ns;
+                }
+            }
         } else if (lin(p + "mlp.gate_proj", m->I, &L.gate, &Q.gate, hd) || lin(p + "mlp.up_proj", m->I, &L.up, &Q.up, hd) ||
                    lin(p + "mlp.down_proj", hd, &L.down, &Q.down, m->I)) {
             return 1;
@@ -136,7 +158,7 @@ int resolve_weights(omx_qwen3 m) {
     } else if (get("lm_head.weight", &m->lm_head)) {
         return 1;
     }
-    if (m->cfg.num_experts == 0) {   // layer table of the persistent step (step_engine.hip)
+    if (m->cfg.num_experts == 0) {   // layer table of the persistent step (step_engine.hip; it stands down for any model with experts)
         m->se_layers_host.resize(m->cfg.num_hidden_layers);
         for (int i = 0; i < m->cfg.num_hidden_layers; ++i) {
             const LayerW& L = m->layers[i];
@@ -156,7 +178,7 @@ int resolve_weights(omx_qwen3 m) {
 // bytes the forward will read behind checkpoint tensor `name` on THIS rank (after the TP / EP slicing), 0 for a name it does not
 // use; mirrors resolve_weights above (and engine.py expected_shape, which reports the same thing as a shape)
 static size_t expected_weight_bytes(omx_qwen3 m, const std::string& name) {
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const size_t hd = c.hidden_size, D = c.head_dim, H = m->H, Hkv = m->Hkv, I = m->I, Im = c.tp_size > 1 && c.num_experts > 0 ? m->moe_I : c.moe_intermediate_size;   // (expert tensor parallel: this rank's columns)
     const size_t E = c.num_experts, El = c.ep_size > 1 ? E / c.ep_size : E;
     static const char* kSuffix[] = {".weight", ".scales", ".biases", ".bias"};
@@ -184,6 +206,16 @@ static size_t expected_weight_bytes(omx_qwen3 m, const std::string& name) {
     const size_t dot = stem.find('.', 13);
     if (dot == std::string::npos) return 0;
     const std::string sub = stem.substr(dot + 1);
+    const bool ds = E > 0 && c.moe_mode == 2;
+    const int layer = atoi(stem.c_str() + 13);
+    if (ds) {   // the per-layer plan: a name the layer does not read has no expected size
+        const bool dense_name = sub == "mlp.gate_proj" || sub == "mlp.up_proj" || sub == "mlp.down_proj";
+        const bool moe_name = sub == "mlp.gate" || sub.compare(0, 15, "mlp.switch_mlp.") == 0 || sub.compare(0, 19, "mlp.shared_experts.") == 0;
+        if ((dense_name && layer_is_moe(c, layer)) || (moe_name && !layer_is_moe(c, layer))) return 0;
+        const size_t Ws = (size_t)c.n_shared_experts * Im;
+        if (Ws > 0 && (sub == "mlp.shared_experts.gate_proj" || sub == "mlp.shared_experts.up_proj")) return lin(Ws, hd);
+        if (Ws > 0 && sub == "mlp.shared_experts.down_proj") return lin(hd, Ws);
+    }
     if (sub == "self_attn.q_proj") return lin(H * D, hd);
     if (sub == "self_attn.k_proj" || sub == "self_attn.v_proj") return lin(Hkv * D, hd);
     if (sub == "self_attn.o_proj") return lin(hd, H * D);
@@ -221,7 +253,7 @@ int omx_qwen3_set_weight(omx_qwen3 m, const char* name, const void* ptr, size_t 
 // follow the format.
 int omx_qwen3_set_quant_format(omx_qwen3 m, const char* prefix, int bits, int group_size) {
     OMX_REQUIRE(m && prefix, "omx_qwen3_set_quant_format: null argument");
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     OMX_REQUIRE(c.quant_bits != 0, "omx_qwen3_set_quant_format: %s: the model has no base quantization (a bf16 / float16 checkpoint)", prefix);
     OMX_REQUIRE(c.num_experts == 0, "omx_qwen3_set_quant_format: %s: per-matrix formats with experts (num_experts %d) are not supported", prefix, c.num_experts);
     OMX_REQUIRE(c.tp_size <= 1 && c.ep_size <= 1, "omx_qwen3_set_quant_format: %s: per-matrix formats under tensor / expert parallelism (tp_size %d, ep_size %d) are not supported",
@@ -271,7 +303,7 @@ static int synth_weights_impl(omx_qwen3 m, uint32_t base_seed, bool peaked) {
     OMX_REQUIRE(!peaked || (m->cfg.quant_bits == 0 && !m->cfg.float16_weights && !m->cfg.tie_word_embeddings),
                 "omx_qwen3_synth_weights_peaked: bf16 checkpoints with an untied lm_head only");
     OMX_REQUIRE(!m->cfg.quant_scales_f16, "omx_qwen3_synth_weights: the device generator quantises in bf16; a float16-scale model takes uploaded triplets");
-    const omx_qwen3_config& c = m->cfg;
+    const EngineConfig& c = m->cfg;
     const int D = c.head_dim, hd = c.hidden_size, r = c.tp_rank;
     const float amp_w = (float)(0.02 * sqrt(3.0)), amp_n = (float)(0.01 * sqrt(3.0));   // == oracle/synth.py
     // logical tensor [rows_full, cols_full]; this rank holds rows [row0, row0+rows) x cols [col0, col0+cols)
@@ -383,10 +415,15 @@ static int synth_weights_impl(omx_qwen3 m, uint32_t base_seed, bool peaked) {
                                  make(p + "self_attn.k_proj.bias", 1, Hk, Hk_all, 0, kv_row0, false) ||
                                  make(p + "self_attn.v_proj.bias", 1, Hk, Hk_all, 0, kv_row0, false)))
             return 1;
-        if (c.num_experts > 0) {
+        if (layer_is_moe(c, i)) {
             const std::string mp = p + (c.moe_mode == 0 ? "block_sparse_moe." : "mlp.");
             const int64_t E = c.num_experts, Im = c.moe_intermediate_size;
             const int64_t El = c.ep_size > 1 ? E / c.ep_size : E, e0 = c.ep_size > 1 ? c.ep_rank * El : 0;   // this rank's experts
+            const int64_t Ws = c.moe_mode == 2 ? (int64_t)c.n_shared_experts * Im : 0;                        // the shared MLP (mode 2)
+            if (Ws > 0 && (make(mp + "shared_experts.gate_proj.weight", Ws, hd, hd, 0, 0, false) ||
+                           make(mp + "shared_experts.up_proj.weight", Ws, hd, hd, 0, 0, false) ||
+                           make(mp + "shared_experts.down_proj.weight", hd, Ws, Ws, 0, 0, false)))
+                return 1;
             if (c.tp_size > 1) {
                 // expert tensor parallel: rows [r I_l, +I_l) of every expert's gate / up, the same columns of its down projection
                 const int64_t Il = m->moe_I;

@@ -29,11 +29,27 @@ namespace {
 constexpr int kRouterThreads = 1024;
 constexpr int kRouterXnMax = 8192;   // widest hidden size whose normalised row the few-experts path keeps in LDS
 static int router_threads(int n_experts, int hidden) { return (n_experts <= 8 && hidden <= 4096 && (hidden & 511) == 0) ? 512 : kRouterThreads; }
+// the routing arithmetics differ in what happens to a finished gate dot product: modes 0 / 1 round it to bf16 (the gate Linear's
+// output array) and leave bf16 scores; mode 2 (DS, DeepSeek-V2 family) keeps it float32 and leaves float32 weights
+struct RouterDS {
+    float scale = 1.f;           // routed_scaling_factor
+    int n_tail = 0;              // shared pseudo-experts named behind each token's k routed entries of inds
+    float* weights = nullptr;    // [n_tokens, k] float32
+};
+template <bool DS>
+__device__ __forceinline__ float router_logit(float v) { return DS ? v : round_bf16(v); }
+template <bool DS>
+__device__ __forceinline__ void router_select(const float* s_logit, int t, int lane, int E, int k, int mode, int renorm, uint32_t* inds,
+                                              bf16_t* scores, const RouterDS& ds) {
+    if constexpr (DS) route_from_logits_f32(s_logit, t, lane, E, k, renorm, ds.scale, ds.n_tail, inds, ds.weights);
+    else route_from_logits(s_logit, t, lane, E, k, mode, renorm, inds, scores);
+}
+template <bool DS>
 __global__ __launch_bounds__(kRouterThreads) void moe_router_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ gate_w,
                                                                     int h, int E, int k, int mode, int renorm,
                                                                     uint32_t* __restrict__ inds, bf16_t* __restrict__ scores,
                                                                     const bf16_t* __restrict__ norm_w = nullptr, float eps = 0.f,
-                                                                    bf16_t* __restrict__ xn_out = nullptr) {
+                                                                    bf16_t* __restrict__ xn_out = nullptr, RouterDS ds = RouterDS()) {
     __shared__ float s_logit[kMaxExperts];
     __shared__ float s_red[kRouterThreads / 64];
     __shared__ __attribute__((aligned(16))) bf16_t s_xn[kRouterXnMax];
@@ -117,11 +133,11 @@ __global__ __launch_bounds__(kRouterThreads) void moe_router_kernel(const bf16_t
                 }
             }
             const float v = wave_sum(acc);
-            if (lane == 0) s_logit[wave] = round_bf16(v);
+            if (lane == 0) s_logit[wave] = router_logit<DS>(v);
         }
         __syncthreads();
         if (wave != 0) return;
-        route_from_logits(s_logit, t, lane, E, k, mode, renorm, inds, scores);
+        router_select<DS>(s_logit, t, lane, E, k, mode, renorm, inds, scores, ds);
         return;
     }
     for (int e0 = wave; e0 < E; e0 += 4 * n_waves) {
@@ -143,12 +159,12 @@ __global__ __launch_bounds__(kRouterThreads) void moe_router_kernel(const bf16_t
         for (int u = 0; u < 4; ++u) {
             const float v = wave_sum(acc[u]);
             const int e = e0 + u * n_waves;
-            if (lane == 0 && e < E) s_logit[e] = round_bf16(v);   // the gate Linear's output is a bf16 array
+            if (lane == 0 && e < E) s_logit[e] = router_logit<DS>(v);   // the gate Linear's output is a bf16 array
         }
     }
     __syncthreads();
     if (wave != 0) return;
-    route_from_logits(s_logit, t, lane, E, k, mode, renorm, inds, scores);
+    router_select<DS>(s_logit, t, lane, E, k, mode, renorm, inds, scores, ds);
 }
 
 // logits [n_tokens, E] already computed (quantised router: qgemv on the packed gate): selection only, one wave per token
@@ -255,6 +271,66 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(bf16_t* __restrict__ o
         } else {
 #pragma unroll
             for (int q = 0; q < 4; ++q) o[q] = A16::pack(acc[2 * q], acc[2 * q + 1]);
+        }
+        *reinterpret_cast<u32x4*>(out + (size_t)t * h + i) = o;
+    }
+}
+
+// The DeepSeek block's tail (MoE::forward, deepseek-ocr2-mlx/src/lib.rs:285-295) with float32 routing weights:
+//   moe    = bf16( sum_j f32(bf16(y_j)) * w_j )      over the k routed slots in slot order, no rounding of the products
+//   shared = bf16( shared MLP's down projection )    one rounding, as the reference's single down_proj
+//   out    = bf16(moe + shared), or bf16(resid + that) inside a decoder block
+// SLOTS: y holds float32 rows, k + n_sh per token -- the routed slots, then the shared MLP's n_sh pseudo-experts whose float32 rows add up
+// to its down projection.  Otherwise y holds bf16 rows (k per token, through pos_of_slot after the expert sort) and `shared` bf16 rows.
+template <bool SLOTS>
+__global__ __launch_bounds__(256) void moe_combine_shared_kernel(bf16_t* __restrict__ out, const void* __restrict__ y_,
+                                                                 const float* __restrict__ weights, const uint32_t* __restrict__ pos_of_slot,
+                                                                 const bf16_t* __restrict__ shared, const bf16_t* __restrict__ resid, int h,
+                                                                 int k, int n_sh) {
+    const int t = blockIdx.x;
+    for (int i = threadIdx.x * 8; i < h; i += 256 * 8) {
+        float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sh[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if constexpr (SLOTS) {
+            const float* y = reinterpret_cast<const float*>(y_) + (size_t)t * (k + n_sh) * h + i;
+            for (int j = 0; j < k; ++j) {
+                const float w = weights[(size_t)t * k + j];
+                const f32x4 a = *reinterpret_cast<const f32x4*>(y + (size_t)j * h), b = *reinterpret_cast<const f32x4*>(y + (size_t)j * h + 4);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { acc[q] += round_bf16(a[q]) * w; acc[4 + q] += round_bf16(b[q]) * w; }
+            }
+            for (int j = k; j < k + n_sh; ++j) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(y + (size_t)j * h), b = *reinterpret_cast<const f32x4*>(y + (size_t)j * h + 4);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { sh[q] += a[q]; sh[4 + q] += b[q]; }
+            }
+        } else {
+            const bf16_t* y = reinterpret_cast<const bf16_t*>(y_);
+            for (int j = 0; j < k; ++j) {
+                const size_t slot = (size_t)t * k + j;
+                const size_t p = pos_of_slot ? pos_of_slot[slot] : slot;
+                const float w = weights[slot];
+                const u32x4 v = *reinterpret_cast<const u32x4*>(y + p * h + i);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { acc[2 * q] += bf16lo(v[q]) * w; acc[2 * q + 1] += bf16hi(v[q]) * w; }
+            }
+            if (shared) {
+                const u32x4 v = *reinterpret_cast<const u32x4*>(shared + (size_t)t * h + i);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) { sh[2 * q] = bf16lo(v[q]); sh[2 * q + 1] = bf16hi(v[q]); }
+            }
+        }
+        const bool has_sh = SLOTS ? n_sh > 0 : shared != nullptr;
+        float r[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q) r[q] = has_sh ? round_bf16(round_bf16(acc[q]) + round_bf16(sh[q])) : round_bf16(acc[q]);
+        u32x4 o;
+        if (resid) {
+            const u32x4 rs = *reinterpret_cast<const u32x4*>(resid + (size_t)t * h + i);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = pack_bf16(bf16lo(rs[q]) + r[2 * q], bf16hi(rs[q]) + r[2 * q + 1]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) o[q] = pack_bf16(r[2 * q], r[2 * q + 1]);
         }
         *reinterpret_cast<u32x4*>(out + (size_t)t * h + i) = o;
     }
@@ -382,7 +458,7 @@ static int moe_forward_impl(void* out, const void* x, const void* gate_w, const 
                              router_threads(n_experts, hidden) == 512 && rf_env && rf_env[0] == '1';
     const void* x_raw = x;
     if (!route_fused) {
-        moe_router_kernel<<<n_tokens, router_threads(n_experts, hidden), 0, s>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts, top_k, mode,
+        moe_router_kernel<false><<<n_tokens, router_threads(n_experts, hidden), 0, s>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts, top_k, mode,
                                                               norm_topk_prob, inds, scores, bf ? (const bf16_t*)bf->norm_w : nullptr,
                                                               bf ? bf->eps : 0.f, bf ? (bf16_t*)bf->xn : nullptr);
         OMX_LAUNCH_CHECK();
@@ -517,6 +593,202 @@ extern "C" int omx_moe_block_partials(float* partials, const void* x, const void
     bf.norm_w = norm_w; bf.eps = eps; bf.xn = xn; bf.resid = x; bf.partials = partials;
     return moe_forward_impl(partials, x, gate_w, w_gate, w_up, w_down, nullptr, 1, hidden, inter, n_experts, top_k, mode, norm_topk_prob,
                             nullptr, nullptr, stream, &bf);
+}
+
+/* ---- DeepSeek-V2 family block (deepseek-ocr2-mlx/src/lib.rs:162-299): float32 router (mode 2), routed experts, shared experts ----
+ * Three forms, chosen by the row count (omx_moe_deepseek_form):
+ *   0  slots     n_tokens * (top_k + n_shared) <= 32 and the stacks carry the shared MLP as n_shared trailing pseudo-experts of width
+ *                `inter` (gate / up: row blocks, down: column blocks): router, ONE gate/up + fused_swiglu launch and ONE down launch over
+ *                top_k + n_shared slots per token (float32 rows), combine.  Four launches.  OMX_MOE_SHARED_SLOTS=0 stands it down.
+ *   1  separate  n_tokens * top_k <= 32: the routed slots as today's expert-selected GEMVs, the shared MLP as two GEMVs of its own.
+ *   2  grouped   more rows: counting sort + grouped matrix-core GEMMs for the routed slots, the shared MLP as ordinary GEMMs.
+ * Every form rounds where the reference does (moe_combine_shared_kernel); form 0 adds the shared down projection's n_shared column
+ * blocks in float32 before its one rounding, so it may differ from the other two in that sum's last bit. */
+static bool deepseek_slots_wanted() {
+    const char* e = getenv("OMX_MOE_SHARED_SLOTS");
+    return !(e && e[0] == '0');
+}
+extern "C" int omx_moe_deepseek_form(int n_tokens, int hidden, int inter, int top_k, int n_shared, int stack_tail, int have_separate) {
+    const bool gemv_ok = omx::gemv_k_supported(hidden, false) && omx::gemv_k_supported(inter, false);
+    if (gemv_ok && n_shared > 0 && stack_tail == n_shared && deepseek_slots_wanted() && n_tokens * (top_k + n_shared) <= 32) return 0;
+    if (n_shared > 0 && !have_separate) return -1;
+    return gemv_ok && n_tokens * top_k <= 32 ? 1 : 2;
+}
+
+extern "C" int omx_moe_deepseek_workspace_bytes(int n_tokens, int hidden, int inter, int n_experts, int top_k, int n_shared, size_t* bytes) {
+    OMX_REQUIRE(bytes, "omx_moe_deepseek_workspace_bytes: null argument");
+    const size_t S = (size_t)top_k + n_shared, slots = (size_t)n_tokens * S, tiles = slots / 128 + n_experts + 1;
+    const size_t sh = (size_t)n_tokens * std::max(n_shared, 1) * inter;
+    *bytes = slots * 4 * 4 + (size_t)(n_experts + 2) * 4 + tiles * 8 + 16 * 256 +    // plan + weights
+             slots * (size_t)inter * 2 * 2 + slots * (size_t)hidden * 4 +             // gate/up (act in place), y (float32 in the slot form)
+             sh * 2 * 2 + (size_t)n_tokens * hidden * 2;                               // the shared MLP's gate/up and rows
+    return 0;
+}
+
+static int moe_deepseek_impl(void* out, const void* resid, const void* x, const void* norm_w, float eps, void* xn, const void* gate_w,
+                             const void* w_gate, const void* w_up, const void* w_down, int stack_tail, const void* sh_gate, const void* sh_up,
+                             const void* sh_down, int n_tokens, int hidden, int inter, int n_experts, int top_k, int n_shared,
+                             int norm_topk_prob, float scale, uint32_t* inds_out, float* weights_out, omx_stream stream) {
+    using namespace omx;
+    OMX_REQUIRE(out && x && gate_w && w_gate && w_up && w_down, "omx_moe_deepseek_forward: null tensor");
+    OMX_REQUIRE(!norm_w || xn, "omx_moe_deepseek_forward: norm_w needs the xn scratch");
+    OMX_REQUIRE(n_tokens >= 0 && hidden > 0 && inter > 0 && hidden % 64 == 0 && inter % 64 == 0,
+                "omx_moe_deepseek_forward: hidden=%d and intermediate=%d must be multiples of 64", hidden, inter);
+    OMX_REQUIRE(n_experts >= 1 && n_experts <= kMaxExperts && top_k >= 1 && top_k <= kMaxTopK && top_k <= n_experts,
+                "omx_moe_deepseek_forward: n_experts=%d (max %d), top_k=%d (max %d)", n_experts, kMaxExperts, top_k, kMaxTopK);
+    OMX_REQUIRE(n_shared >= 0 && n_shared <= 8 && (stack_tail == 0 || stack_tail == n_shared),
+                "omx_moe_deepseek_forward: n_shared_experts=%d (0..8), %d pseudo-experts behind the stacks (0 or n_shared_experts)", n_shared, stack_tail);
+    const bool have_sep = sh_gate && sh_up && sh_down;
+    const int form = omx_moe_deepseek_form(n_tokens, hidden, inter, top_k, n_shared, stack_tail, have_sep);
+    OMX_REQUIRE(form >= 0, "omx_moe_deepseek_forward: %d rows with %d shared experts need the shared MLP's own matrices (the stacks' pseudo-experts "
+                "serve at most 32 slots)", n_tokens, n_shared);
+    if (n_tokens == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const int n_tail = form == 0 ? n_shared : 0, S = top_k + n_tail, slots = n_tokens * S, routed = n_tokens * top_k;
+    const int max_tiles = routed / 128 + n_experts + 1;
+    size_t need = 0;
+    omx_moe_deepseek_workspace_bytes(n_tokens, hidden, inter, n_experts, top_k, n_shared, &need);
+    void* ws = nullptr;
+    if (get_workspace(&ws, need)) return 1;
+    char* p = (char*)ws;
+    auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) & ~(size_t)255; return r; };
+    const size_t all = (size_t)n_tokens * (top_k + n_shared);
+    uint32_t* inds = (uint32_t*)take(all * 4);
+    uint32_t* row_src = (uint32_t*)take(all * 4);
+    uint32_t* pos_of_slot = (uint32_t*)take(all * 4);
+    float* weights = (float*)take(all * 4);
+    int* seg_start = (int*)take((size_t)(n_experts + 2) * 4);
+    int* tile_expert = (int*)take((size_t)max_tiles * 4);
+    int* tile_m0 = (int*)take((size_t)max_tiles * 4);
+    int* n_tiles = (int*)take(256);
+    bf16_t* gbuf = (bf16_t*)take(all * inter * 2);
+    bf16_t* ubuf = (bf16_t*)take(all * inter * 2);
+    void* ybuf = take(all * hidden * 4);
+    const size_t sh_w = (size_t)std::max(n_shared, 1) * inter;
+    bf16_t* sg = (bf16_t*)take((size_t)n_tokens * sh_w * 2);
+    bf16_t* su = (bf16_t*)take((size_t)n_tokens * sh_w * 2);
+    bf16_t* srow = (bf16_t*)take((size_t)n_tokens * hidden * 2);
+
+    RouterDS ds;
+    ds.scale = scale; ds.n_tail = n_tail; ds.weights = weights;
+    moe_router_kernel<true><<<n_tokens, router_threads(n_experts, hidden), 0, s>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts, top_k, 2,
+                                                                                    norm_topk_prob, inds, nullptr, (const bf16_t*)norm_w, eps,
+                                                                                    norm_w ? (bf16_t*)xn : nullptr, ds);
+    OMX_LAUNCH_CHECK();
+    if (norm_w) x = xn;
+    const bf16_t* shared_rows = nullptr;
+    if (form <= 1) {
+        GemvArgs a = {};
+        a.w0 = (const bf16_t*)w_gate; a.w1 = (const bf16_t*)w_up; a.n0 = inter; a.N = inter; a.K = hidden;
+        a.x = (const bf16_t*)x; a.out = gbuf;
+        a.n_batch = slots; a.x_div = S; a.x_bstride = hidden; a.out_bstride_bytes = (size_t)inter * 2;
+        a.w_sel = inds; a.w_estride = (size_t)inter * hidden; a.swiglu_single_round = 1;
+        if (launch_gemv(a, PRO_NONE, EPI_SWIGLU, s)) return 1;
+        GemvArgs d = {};
+        d.w0 = (const bf16_t*)w_down; d.n0 = hidden; d.N = hidden; d.K = inter;
+        d.x = gbuf; d.out = ybuf;
+        d.n_batch = slots; d.x_div = 1; d.x_bstride = inter;
+        d.w_sel = inds; d.w_estride = (size_t)hidden * inter;
+        d.out_bstride_bytes = (size_t)hidden * (form == 0 ? 4 : 2);
+        if (launch_gemv(d, PRO_NONE, form == 0 ? EPI_F32 : EPI_STORE, s)) return 1;
+        if (form == 1 && n_shared > 0) {   // the shared MLP on its own: gate/up + fused_swiglu, down (bf16 rows: its one rounding)
+            const int W = n_shared * inter;
+            GemvArgs g = {};
+            g.w0 = (const bf16_t*)sh_gate; g.w1 = (const bf16_t*)sh_up; g.n0 = W; g.N = W; g.K = hidden;
+            g.x = (const bf16_t*)x; g.out = sg;
+            g.n_batch = n_tokens; g.x_div = 1; g.x_bstride = hidden; g.out_bstride_bytes = (size_t)W * 2; g.swiglu_single_round = 1;
+            if (launch_gemv(g, PRO_NONE, EPI_SWIGLU, s)) return 1;
+            GemvArgs sd = {};
+            sd.w0 = (const bf16_t*)sh_down; sd.n0 = hidden; sd.N = hidden; sd.K = W;
+            sd.x = sg; sd.out = srow;
+            sd.n_batch = n_tokens; sd.x_div = 1; sd.x_bstride = W; sd.out_bstride_bytes = (size_t)hidden * 2;
+            if (launch_gemv(sd, PRO_NONE, EPI_STORE, s)) return 1;
+            shared_rows = srow;
+        }
+        if (form == 0)
+            moe_combine_shared_kernel<true><<<n_tokens, 256, 0, s>>>((bf16_t*)out, ybuf, weights, nullptr, nullptr, (const bf16_t*)resid, hidden,
+                                                                     top_k, n_shared);
+        else
+            moe_combine_shared_kernel<false><<<n_tokens, 256, 0, s>>>((bf16_t*)out, ybuf, weights, nullptr, shared_rows, (const bf16_t*)resid,
+                                                                      hidden, top_k, 0);
+        OMX_LAUNCH_CHECK();
+    } else {
+        const int tile_rows = moe_tile_rows(routed, n_experts, hidden, inter);
+        moe_plan_kernel<<<1, 1024, 0, s>>>(inds, routed, n_experts, top_k, seg_start, row_src, pos_of_slot, tile_expert, tile_m0, n_tiles, tile_rows);
+        OMX_LAUNCH_CHECK();
+        GroupedDesc g;
+        g.tile_expert = tile_expert; g.tile_m0 = tile_m0; g.seg_start = seg_start; g.n_tiles = n_tiles;
+        g.row_src = row_src; g.w_estride = (size_t)inter * hidden;
+        if (tile_rows == 256) {
+            if (grouped_glu_256((bf16_t*)ybuf, gbuf, (const bf16_t*)x, (const bf16_t*)w_gate, (const bf16_t*)w_up, (const bf16_t*)w_down, routed, hidden,
+                                inter, n_experts, g, s))
+                return 1;
+        } else {
+            if (launch_gemm_bf16_grouped(gbuf, (const bf16_t*)x, (const bf16_t*)w_gate, routed, inter, hidden, g, max_tiles, s)) return 1;
+            if (launch_gemm_bf16_grouped(ubuf, (const bf16_t*)x, (const bf16_t*)w_up, routed, inter, hidden, g, max_tiles, s)) return 1;
+            if (omx_fused_swiglu(gbuf, ubuf, gbuf, (int64_t)routed * inter, OMX_BFLOAT16, stream)) return 1;
+            g.row_src = nullptr;
+            g.w_estride = (size_t)hidden * inter;
+            if (launch_gemm_bf16_grouped((bf16_t*)ybuf, gbuf, (const bf16_t*)w_down, routed, hidden, inter, g, max_tiles, s)) return 1;
+        }
+        if (n_shared > 0) {   // shared_experts(x): an ordinary MLP over all rows (lib.rs:148-159)
+            const int W = n_shared * inter;
+            if (launch_gemm_bf16(sg, (const bf16_t*)x, (const bf16_t*)sh_gate, nullptr, n_tokens, W, hidden, s)) return 1;
+            if (launch_gemm_bf16(su, (const bf16_t*)x, (const bf16_t*)sh_up, nullptr, n_tokens, W, hidden, s)) return 1;
+            if (omx_fused_swiglu(sg, su, sg, (int64_t)n_tokens * W, OMX_BFLOAT16, stream)) return 1;
+            if (launch_gemm_bf16(srow, sg, (const bf16_t*)sh_down, nullptr, n_tokens, hidden, W, s)) return 1;
+            shared_rows = srow;
+        }
+        moe_combine_shared_kernel<false><<<n_tokens, 256, 0, s>>>((bf16_t*)out, ybuf, weights, pos_of_slot, shared_rows, (const bf16_t*)resid, hidden,
+                                                                  top_k, 0);
+        OMX_LAUNCH_CHECK();
+    }
+    if (inds_out)
+        OMX_HIP_CHECK(hipMemcpy2DAsync(inds_out, (size_t)top_k * 4, inds, (size_t)S * 4, (size_t)top_k * 4, n_tokens, hipMemcpyDeviceToDevice, s));
+    if (weights_out) OMX_HIP_CHECK(hipMemcpyAsync(weights_out, weights, (size_t)routed * 4, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+/* out = moe(x) + shared_experts(x).  w_gate / w_up [E + stack_tail, inter, hidden], w_down [E + stack_tail, hidden, inter]: the routed
+ * experts, then (stack_tail == n_shared) the shared MLP split into pseudo-experts; sh_* (optional): the shared MLP whole, gate / up
+ * [n_shared * inter, hidden], down [hidden, n_shared * inter].  inds_out [n_tokens, top_k] / weights_out [n_tokens, top_k] float32. */
+extern "C" int omx_moe_deepseek_forward(void* out, const void* x, const void* gate_w, const void* w_gate, const void* w_up, const void* w_down,
+                                        int stack_tail, const void* sh_gate, const void* sh_up, const void* sh_down, int n_tokens, int hidden,
+                                        int inter, int n_experts, int top_k, int n_shared, int norm_topk_prob, float routed_scaling_factor,
+                                        uint32_t* inds_out, float* weights_out, omx_stream stream) {
+    return moe_deepseek_impl(out, nullptr, x, nullptr, 0.f, nullptr, gate_w, w_gate, w_up, w_down, stack_tail, sh_gate, sh_up, sh_down, n_tokens,
+                             hidden, inter, n_experts, top_k, n_shared, norm_topk_prob, routed_scaling_factor, inds_out, weights_out, stream);
+}
+
+/* decoder-block form: out = resid + block(rmsnorm(x) * norm_w) -- the norm in the router launch, the residual in the combine launch */
+extern "C" int omx_moe_deepseek_block_forward(void* out, const void* resid, const void* x, const void* norm_w, float eps, void* xn,
+                                              const void* gate_w, const void* w_gate, const void* w_up, const void* w_down, int stack_tail,
+                                              const void* sh_gate, const void* sh_up, const void* sh_down, int n_tokens, int hidden, int inter,
+                                              int n_experts, int top_k, int n_shared, int norm_topk_prob, float routed_scaling_factor,
+                                              omx_stream stream) {
+    OMX_REQUIRE(resid && norm_w && xn, "omx_moe_deepseek_block_forward: null tensor");
+    return moe_deepseek_impl(out, resid, x, norm_w, eps, xn, gate_w, w_gate, w_up, w_down, stack_tail, sh_gate, sh_up, sh_down, n_tokens, hidden,
+                             inter, n_experts, top_k, n_shared, norm_topk_prob, routed_scaling_factor, nullptr, nullptr, stream);
+}
+
+/* the mode-2 router alone: inds_out [n_tokens, top_k], weights_out [n_tokens, top_k] float32; norm_w (optional) folds the block's RMSNorm
+ * in and leaves the normalised rows in xn */
+extern "C" int omx_moe_route_deepseek(uint32_t* inds_out, float* weights_out, const void* x, const void* gate_w, const void* norm_w, float eps,
+                                      void* xn, int n_tokens, int hidden, int n_experts, int top_k, int norm_topk_prob,
+                                      float routed_scaling_factor, omx_stream stream) {
+    using namespace omx;
+    OMX_REQUIRE(inds_out && weights_out && x && gate_w && (!norm_w || xn), "omx_moe_route_deepseek: null tensor");
+    OMX_REQUIRE(n_experts >= 1 && n_experts <= kMaxExperts && top_k >= 1 && top_k <= kMaxTopK && top_k <= n_experts,
+                "omx_moe_route_deepseek: n_experts=%d (max %d), top_k=%d (max %d)", n_experts, kMaxExperts, top_k, kMaxTopK);
+    OMX_REQUIRE(hidden > 0 && hidden % 64 == 0, "omx_moe_route_deepseek: hidden=%d must be a multiple of 64", hidden);
+    if (n_tokens <= 0) return 0;
+    RouterDS ds;
+    ds.scale = routed_scaling_factor; ds.weights = weights_out;
+    moe_router_kernel<true><<<n_tokens, router_threads(n_experts, hidden), 0, (hipStream_t)stream>>>(
+        (const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts, top_k, 2, norm_topk_prob, inds_out, nullptr, (const bf16_t*)norm_w, eps,
+        norm_w ? (bf16_t*)xn : nullptr, ds);
+    OMX_LAUNCH_CHECK();
+    return 0;
 }
 
 /* decoder-block form on a quantised checkpoint (mixtral-mlx/src/model.rs:560-600: gate = QuantizedLinear, switch_mlp =
@@ -720,7 +992,7 @@ extern "C" int omx_moe_block_partial_ep(float* partial, const void* x, const voi
     bf16_t* gbuf = (bf16_t*)take((size_t)slots * inter * 2);
     bf16_t* ubuf = (bf16_t*)take((size_t)slots * inter * 2);
     bf16_t* ybuf = (bf16_t*)take((size_t)slots * hidden * 2);
-    moe_router_kernel<<<n_tokens, router_threads(n_experts, hidden), 0, s>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts, top_k, mode,
+    moe_router_kernel<false><<<n_tokens, router_threads(n_experts, hidden), 0, s>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts, top_k, mode,
                                                           norm_topk_prob, inds, scores, (const bf16_t*)norm_w, eps, norm_w ? (bf16_t*)xn : nullptr);
     OMX_LAUNCH_CHECK();
     if (!decode) {
@@ -818,7 +1090,7 @@ extern "C" int omx_moe_block_partial_tp(float* y_partial, uint32_t* route_inds, 
     void* ws = nullptr;
     if (get_workspace_aux(&ws, ((size_t)slots * inter * 2 + 256), s)) return 1;
     bf16_t* gbuf = (bf16_t*)ws;
-    moe_router_kernel<<<n_tokens, router_threads(n_experts, hidden), 0, s>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts, top_k, mode,
+    moe_router_kernel<false><<<n_tokens, router_threads(n_experts, hidden), 0, s>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts, top_k, mode,
                                                           norm_topk_prob, route_inds, (bf16_t*)route_scores, (const bf16_t*)norm_w, eps, (bf16_t*)xn);
     OMX_LAUNCH_CHECK();
     GemvArgs a = {};
@@ -1132,7 +1404,7 @@ extern "C" int omx_moe_route(uint32_t* inds_out, void* scores_out, const void* x
     OMX_REQUIRE(hidden > 0 && hidden % 64 == 0, "omx_moe_route: hidden=%d must be a multiple of 64", hidden);
     OMX_REQUIRE(mode == 0 || mode == 1, "omx_moe_route: mode must be 0 (Mixtral) or 1 (Qwen3-MoE)");
     if (n_tokens <= 0) return 0;
-    moe_router_kernel<<<n_tokens, router_threads(n_experts, hidden), 0, (hipStream_t)stream>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts,
+    moe_router_kernel<false><<<n_tokens, router_threads(n_experts, hidden), 0, (hipStream_t)stream>>>((const bf16_t*)x, (const bf16_t*)gate_w, hidden, n_experts,
                                                                  top_k, mode, norm_topk_prob, inds_out, (bf16_t*)scores_out);
     OMX_LAUNCH_CHECK();
     return 0;

@@ -81,4 +81,69 @@ __device__ __forceinline__ void route_from_logits(const float* s_logit, int t, i
     }
 }
 
+// mode 2 (DeepSeek-V2 family, MoEGate::route deepseek-ocr2-mlx/src/lib.rs:178-200): the logits arrive in float32 and nothing is
+// rounded to 16 bits on the way -- softmax over all experts, top-k (descending, ties to the lower index), optional division by
+// (sum of the selected + 1e-20) where k > 1, then the routed scaling factor.  The weights leave as float32.
+// inds has k + n_tail entries per token: the constant tail E, E + 1, ... names the shared MLP's pseudo-experts behind the routed stack.
+__device__ __forceinline__ void route_from_logits_f32(const float* s_logit, int t, int lane, int E, int k, int renorm, float scale,
+                                                      int n_tail, uint32_t* __restrict__ inds, float* __restrict__ weights) {
+    constexpr int PER = kMaxExperts / 64;
+    float v[PER];
+    bool taken[PER];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        const int e = lane + 64 * u;
+        v[u] = e < E ? s_logit[e] : -INFINITY;
+        taken[u] = e >= E;
+        mx = fmaxf(mx, v[u]);
+    }
+    mx = wave_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int u = 0; u < PER; ++u) {
+        v[u] = (lane + 64 * u < E) ? expf(v[u] - mx) : 0.f;
+        sum += v[u];
+    }
+    sum = wave_sum(sum);
+#pragma unroll
+    for (int u = 0; u < PER; ++u) v[u] = (lane + 64 * u < E) ? v[u] / sum : -INFINITY;
+    uint32_t sel[kMaxTopK];
+    float selv[kMaxTopK];
+    for (int j = 0; j < k; ++j) {   // the probabilities are >= 0: their bit patterns order like the values; key = (bits, ~index)
+        unsigned long long best = 0;
+#pragma unroll
+        for (int u = 0; u < PER; ++u) {
+            if (taken[u]) continue;
+            const unsigned long long key = ((unsigned long long)(__float_as_uint(v[u]) | 0x80000000u) << 32) | (uint32_t)~(uint32_t)(lane + 64 * u);
+            best = key > best ? key : best;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const unsigned long long other = __shfl_xor(best, o, 64);
+            best = other > best ? other : best;
+        }
+        const uint32_t e = ~(uint32_t)(best & 0xFFFFFFFFull);
+        sel[j] = e;
+        selv[j] = __uint_as_float((uint32_t)(best >> 32) & 0x7FFFFFFFu);
+#pragma unroll
+        for (int u = 0; u < PER; ++u)
+            if ((uint32_t)(lane + 64 * u) == e) taken[u] = true;
+    }
+    if (renorm && k > 1) {
+        float den = 0.f;
+        for (int j = 0; j < k; ++j) den += selv[j];
+        den += 1e-20f;
+        for (int j = 0; j < k; ++j) selv[j] = selv[j] / den;
+    }
+    if (lane == 0) {
+        const size_t stride = (size_t)(k + n_tail);
+        for (int j = 0; j < k; ++j) {
+            inds[(size_t)t * stride + j] = sel[j];
+            weights[(size_t)t * k + j] = selv[j] * scale;
+        }
+        for (int j = 0; j < n_tail; ++j) inds[(size_t)t * stride + k + j] = (uint32_t)(E + j);
+    }
+}
+
 }  // namespace omx

@@ -26,6 +26,11 @@ class Qwen3Config(ctypes.Structure):
                 ("float16_weights", c_int)]
 
 
+class DeepseekPlan(ctypes.Structure):
+    """omx_qwen3_deepseek_plan: the DeepSeek-V2 family layer plan that goes beside a mode-2 Qwen3Config (omx_qwen3_create_deepseek)."""
+    _fields_ = [("first_k_dense_replace", c_int), ("n_shared_experts", c_int), ("routed_scaling_factor", c_float)]
+
+
 class GemvEx(ctypes.Structure):
     """omx_gemv_ex: every field of one dense decode GEMV launch (omx_debug_gemv_ex); route_* are filled in by the call."""
     _fields_ = [("out", c_void_p), ("argmax_slot", c_void_p), ("argmax_slot_n", c_int),
@@ -91,6 +96,7 @@ ENGINE_SIGNATURES = {
     "omx_fill_uniform_2d": (c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                     ctypes.c_int64, c_uint32, c_float, c_float, c_int, c_void_p]),
     "omx_qwen3_create": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(Qwen3Config)]),
+    "omx_qwen3_create_deepseek": (c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(Qwen3Config), ctypes.POINTER(DeepseekPlan)]),
     "omx_qwen3_destroy": (c_int, [c_void_p]),
     "omx_qwen3_set_weight": (c_int, [c_void_p, ctypes.c_char_p, c_void_p, ctypes.c_size_t]),
     "omx_qwen3_synth_weights": (c_int, [c_void_p, c_uint32]),
@@ -272,10 +278,11 @@ def mixed_recipe_quantization(recipe: str, num_layers: int, tie_word_embeddings:
     return q
 
 
-def expected_shape(c: Qwen3Config, name: str, formats=None):
+def expected_shape(c: Qwen3Config, name: str, formats=None, plan=None):
     """Shape the engine will read for checkpoint tensor `name` on THIS rank (after the TP / EP slicing), or None for a
     name the forward does not use.  Mirrors resolve_weights in csrc/engine_weights.hip.  formats: {module path: (bits, group_size)} of
-    the matrices that have a format of their own (quant_formats); every other packed matrix has the config's base format."""
+    the matrices that have a format of their own (quant_formats); every other packed matrix has the config's base format.  plan: the
+    DeepseekPlan of a moe_mode "deepseek" model (None: every layer routes, no shared experts)."""
     tp, ep = max(c.tp_size, 1), max(c.ep_size, 1)
     hd, D = c.hidden_size, c.head_dim
     H, Hkv, I, V = c.num_attention_heads // tp, max(1, c.num_key_value_heads // tp), c.intermediate_size // tp, c.vocab_size
@@ -314,6 +321,18 @@ def expected_shape(c: Qwen3Config, name: str, formats=None):
     sub = ".".join(parts[3:])
     table = {"self_attn.q_proj": (H * D, hd), "self_attn.k_proj": (Hkv * D, hd), "self_attn.v_proj": (Hkv * D, hd),
              "self_attn.o_proj": (hd, H * D), "mlp.gate_proj": (I, hd), "mlp.up_proj": (I, hd), "mlp.down_proj": (hd, I)}
+    ds = E > 0 and c.moe_mode == MOE_MODES["deepseek"]
+    if ds:      # the per-layer plan: a dense prefix, then router + stacks + shared experts; a name its layer does not read has no shape
+        plan = plan or DeepseekPlan(0, 0, 1.0)
+        is_moe = int(parts[2]) >= plan.first_k_dense_replace
+        moe_name = sub == "mlp.gate" or sub.startswith("mlp.switch_mlp.") or sub.startswith("mlp.shared_experts.")
+        if (sub in ("mlp.gate_proj", "mlp.up_proj", "mlp.down_proj") and is_moe) or (moe_name and not is_moe):
+            return None
+        Ws = plan.n_shared_experts * Im
+        if Ws and sub in ("mlp.shared_experts.gate_proj", "mlp.shared_experts.up_proj"):
+            return lin(Ws, hd)
+        if Ws and sub == "mlp.shared_experts.down_proj":
+            return lin(hd, Ws)
     if sub in table:
         return lin(*table[sub])
     if sub in ("input_layernorm", "post_attention_layernorm"):
@@ -332,6 +351,9 @@ def expected_shape(c: Qwen3Config, name: str, formats=None):
     return None
 
 
+MOE_MODES = {"mixtral": 0, "qwen3_moe": 1, "deepseek": 2}
+
+
 class Model:
     """qwen3_mlx::Model (dense Qwen3) resident on one MI355X (or one TP shard of it)."""
 
@@ -341,13 +363,17 @@ class Model:
                  num_key_value_heads, head_dim, vocab_size, rms_norm_eps=1e-6, rope_theta=1e6,
                  tie_word_embeddings=False, rope_scaling=None, max_context=4096, tp_rank=0, tp_size=1, quantization=None,
                  num_experts=0, num_experts_per_tok=0, moe_intermediate_size=0, moe_mode="qwen3_moe", norm_topk_prob=False,
-                 qk_norm=True, ep_rank=0, ep_size=1, attention_bias=False, dtype="bfloat16", **_ignored):
+                 qk_norm=True, ep_rank=0, ep_size=1, attention_bias=False, dtype="bfloat16", first_k_dense_replace=0,
+                 n_shared_experts=0, routed_scaling_factor=1.0, **_ignored):
         """quantization: config.json's {"bits": 2|3|4|5|6|8, "group_size": 64} (model.rs:63) or None for a bf16 checkpoint (2, 3,
         5 and 6 bits: dense single-rank models only); nested entries {module path: {"bits", "group_size"}} give single matrices a
         format of their own (a mixed-precision MLX checkpoint; quant_formats; dense single-rank bf16-triplet models); + "scales_dtype":
         "float16" when the checkpoint's scales / biases are float16 (loader.load_model reads it off the tensors' dtype).
         num_experts > 0: sparse-MoE feed-forward in every layer -- moe_mode "qwen3_moe" (qwen3_moe.rs ModelArgs :60-87) or
         "mixtral" (mixtral-mlx ModelArgs :54-80, with qk_norm=False and moe_intermediate_size = intermediate_size).
+        moe_mode "deepseek" (deepseek-ocr2-mlx/src/lib.rs:70-130, the DeepSeek-V2 family): layers [0, first_k_dense_replace) are dense
+        MLPs of intermediate_size, the rest route in float32 over num_experts with routed_scaling_factor and add n_shared_experts
+        shared experts ("mlp.shared_experts.*" at n_shared_experts * moe_intermediate_size); bf16, one rank, qk_norm=False.
         dtype: the weight dtype of a dense (unquantised) checkpoint -- "bfloat16" (default) or "float16"; a float16 model runs in
         float16 end to end, like MLX runs a checkpoint saved in float16 (single rank, dense MLP, head_dim 128)."""
         require_device()
@@ -359,12 +385,17 @@ class Model:
                                rope_scale_from_config(rope_scaling), int(bool(tie_word_embeddings)), max_context,
                                tp_rank, tp_size, int(q.get("bits", 0)), int(q.get("group_size", 64 if q else 0)),
                                int(num_experts), int(num_experts_per_tok), int(moe_intermediate_size),
-                               {"mixtral": 0, "qwen3_moe": 1}[moe_mode], int(bool(norm_topk_prob)), int(not qk_norm),
+                               MOE_MODES[moe_mode], int(bool(norm_topk_prob)), int(not qk_norm),
                                int(ep_rank), int(ep_size), int(bool(attention_bias)),
                                int(str(q.get("scales_dtype", "bfloat16")).lower() in ("float16", "f16", "half")),
                                int(f16_weights))
         self._h = c_void_p()
-        check(lib.omx_qwen3_create(ctypes.byref(self._h), ctypes.byref(self.cfg)))
+        self.plan = None
+        if moe_mode == "deepseek" or first_k_dense_replace or n_shared_experts:      # (on another mode the engine refuses the plan by name)
+            self.plan = DeepseekPlan(int(first_k_dense_replace), int(n_shared_experts), float(routed_scaling_factor))
+            check(lib.omx_qwen3_create_deepseek(ctypes.byref(self._h), ctypes.byref(self.cfg), ctypes.byref(self.plan)))
+        else:
+            check(lib.omx_qwen3_create(ctypes.byref(self._h), ctypes.byref(self.cfg)))
         self._keep = []
         # per-matrix formats: what differs from the base goes to the engine (an entry that repeats the base changes nothing; a tied head
         # has the embedding's format, so a stray lm_head entry of a tied model names no matrix)
@@ -436,7 +467,7 @@ class Model:
             check(lib.omx_qwen3_set_weight(self._h, name.encode(), t.ptr, t.nbytes))
 
     def expected_shape(self, name: str):
-        return expected_shape(self.cfg, name, self.quant_table)
+        return expected_shape(self.cfg, name, self.quant_table, self.plan)
 
     def quant_format(self, prefix: str) -> tuple:
         """(bits, group_size) of the packed matrix at module path `prefix`: its own, or the base format (omx_qwen3_quant_format)."""

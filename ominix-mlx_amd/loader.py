@@ -114,10 +114,60 @@ def sanitize_weights(weights: Dict[str, np.ndarray], num_hidden_layers: int, num
     return out
 
 
+# DeepseekOCR2Config's serde defaults (deepseek-ocr2-mlx/src/lib.rs:111-130): a config.json may leave any of them out
+DEEPSEEK_OCR2_DEFAULTS = dict(hidden_size=1280, num_hidden_layers=12, num_attention_heads=10, num_key_value_heads=10, intermediate_size=6848,
+                              vocab_size=129280, rms_norm_eps=1e-6, rope_theta=10000.0, max_position_embeddings=8192,
+                              tie_word_embeddings=False, moe_intermediate_size=896, n_routed_experts=64, n_shared_experts=2,
+                              num_experts_per_tok=6, first_k_dense_replace=1, norm_topk_prob=False, routed_scaling_factor=1.0, n_group=1,
+                              topk_group=1, topk_method="greedy", use_mla=False, bos_token_id=0, eos_token_id=1)
+
+
+def deepseek_ocr2_config(c: dict) -> dict:
+    """config.json's dictionary with the reference's defaults filled in (unknown keys kept)"""
+    return dict(DEEPSEEK_OCR2_DEFAULTS, **{k: v for k, v in c.items() if v is not None})
+
+
+def deepseek_ocr2_args(c: dict) -> dict:
+    """-> keyword arguments of engine.Model for the DeepSeek-OCR-2 decoder (load_model, lib.rs:981-1100): MHA with head_dim =
+    hidden / heads, no q/k norm, non-traditional RoPE, greedy softmax routing (one group), no MLA"""
+    c = deepseek_ocr2_config(c)
+    if c["use_mla"] or c["topk_method"] != "greedy" or c["n_group"] != 1 or c["topk_group"] != 1:
+        raise ValueError("load_model: DeepSeek decoders with MLA or group-limited routing (use_mla, topk_method, n_group, topk_group) are not supported")
+    return dict(hidden_size=c["hidden_size"], num_hidden_layers=c["num_hidden_layers"], intermediate_size=c["intermediate_size"],
+                num_attention_heads=c["num_attention_heads"], num_key_value_heads=c["num_key_value_heads"],
+                head_dim=c["hidden_size"] // c["num_attention_heads"], vocab_size=c["vocab_size"], rms_norm_eps=c["rms_norm_eps"],
+                rope_theta=c["rope_theta"], tie_word_embeddings=c["tie_word_embeddings"], qk_norm=False, num_experts=c["n_routed_experts"],
+                num_experts_per_tok=c["num_experts_per_tok"], moe_intermediate_size=c["moe_intermediate_size"], moe_mode="deepseek",
+                norm_topk_prob=c["norm_topk_prob"], first_k_dense_replace=c["first_k_dense_replace"], n_shared_experts=c["n_shared_experts"],
+                routed_scaling_factor=c["routed_scaling_factor"])
+
+
+def stack_deepseek_experts(weights: Dict[str, np.ndarray], num_hidden_layers: int, n_routed_experts: int) -> Dict[str, np.ndarray]:
+    """`model.layers.{i}.mlp.experts.{e}.{gate,up,down}_proj.weight` stacked over e into `mlp.switch_mlp.*` (what sanitize_weights does for
+    Mixtral); layers without experts (the dense prefix) and already-stacked checkpoints pass through, `mlp.shared_experts.*` and the
+    vision towers' keys are left to their owners"""
+    out = dict(weights)
+    for layer in range(num_hidden_layers):
+        prefix = f"model.layers.{layer}.mlp"
+        for proj in ("gate_proj", "up_proj", "down_proj"):
+            if f"{prefix}.experts.0.{proj}.weight" not in out:
+                continue
+            parts = []
+            for e in range(n_routed_experts):
+                key = f"{prefix}.experts.{e}.{proj}.weight"
+                if key not in out:
+                    raise KeyError(f"WeightNotFound: {key}")
+                parts.append(out.pop(key))
+            out[f"{prefix}.switch_mlp.{proj}.weight"] = keep_kind(parts[0], np.stack(parts, 0))
+    return out
+
+
 def model_args(model_dir: str) -> dict:
     """config.json -> keyword arguments of engine.Model (ModelArgs, model.rs:47-64)."""
     with open(os.path.join(model_dir, "config.json")) as f:
         c = json.load(f)
+    if "n_routed_experts" in c or str(c.get("model_type", "")).lower().startswith("deepseek"):
+        return deepseek_ocr2_args(c)      # every field has a default there (lib.rs:111-130)
     head_dim = c.get("head_dim") or c["hidden_size"] // c["num_attention_heads"]
     args = dict(hidden_size=c["hidden_size"], num_hidden_layers=c["num_hidden_layers"], intermediate_size=c["intermediate_size"],
                 num_attention_heads=c["num_attention_heads"], num_key_value_heads=c.get("num_key_value_heads", c["num_attention_heads"]),
@@ -166,6 +216,9 @@ def load_model(model_dir: str, max_context: int = 4096, dtype=None, **overrides)
     args["dtype"] = dense_dtype(weights, args) if dtype is None else dtype
     if args.get("moe_mode") == "mixtral":
         weights = sanitize_weights(weights, args["num_hidden_layers"], args["num_experts"])
+    if args.get("moe_mode") == "deepseek":     # the decoder's tensors only: the vision towers have their own loader (deepseek_ocr2.py)
+        weights = stack_deepseek_experts({k: v for k, v in weights.items() if k.startswith(("model.layers.", "model.embed_tokens.", "model.norm.", "lm_head."))},
+                                         args["num_hidden_layers"], args["num_experts"])
     if args.get("quantization") is not None and any(k.endswith(".scales") and np.asarray(v).dtype == np.float16 for k, v in weights.items()):
         args["quantization"] = dict(args["quantization"], scales_dtype="float16")     # a float16 checkpoint's triplets (engine.Model)
     m = engine.Model(**args)
