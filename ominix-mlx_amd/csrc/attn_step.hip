@@ -284,6 +284,11 @@ __device__ __forceinline__ void gateup_reduce(const AttnStepArgs& a, const u32x4
 //     the watch: 361.22 (set 2) -- the rows in front of the optimistic pass delay it, and a miss costs a second pass;
 //   * E, row 0 left in front of hop four, on A / B / C: 362.51 / 367.09 / 365.62 (set 1), on B 364.35 (set 2) -- row 0 carries 1.2-1.5 of B's 10;
 //   * D, a third named down set through hop four: 256 VGPRs and 332 bytes of scratch -- not run.
+// The residual row's norm (EXPERIMENTS C-7): hipcc holds s_waitcnt vmcnt(4) / (3) / (3) between its barriers -- the norm weight was asked for
+// ahead of the rows, but across the join of the two arms the count is lost -- so the row is normalised when 21 of a wave's 24 row loads have
+// landed.  With the weight read from LDS (parked there by the launch's first round of loads) no wait is left in the norm: 368.55 against the
+// parent's 367.79 in one set, 366.43 against 366.71 in the other, +0.1 on top of hop three's publish-first form -- the rows land while the
+// norm runs either way.  Not in the tree.
 constexpr int kDnInter = 12288, kDnBlockRows = 16, kDnNV = kDnInter / 512 / 4, kDnUnits = kDnBlockRows / 2 * 4, kDnQRows = 3;
 // LDS of the phase, in the (dead) split-merge area at the front: the activation vector, the K-quarter partials, the parked activations
 constexpr int kDnPartOff = kDnInter * 2, kDnParkOff = kDnPartOff + kDnBlockRows * 4 * 4, kDnLdsBytes = kDnParkOff + kGuBlockPairs * 2;
@@ -507,13 +512,14 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
 }
 
 // Every wave of every block ends here.  `pub_rows` > 0: the block's O rows [pub_row0, + pub_rows) are parked in sm_pub (a block of O
-// waves holds an even number of rows from an even row on: whole granules).  Waves 1..7 ask for their first pair at once.  Wave 0 -- no
-// weight load in flight: a granule asked for behind 32 KB of weights would only arrive after them -- publishes the rows, watches, and
-// asks for the whole hidden row ONCE in straight-line code; right behind those 32 granule loads the block meets at an LDS-only barrier,
+// waves holds an even number of rows from an even row on: whole granules).  Waves 1..7 ask for their first pair at once (in the layer
+// launch's O blocks: behind the publish, see below).  Wave 0 -- no weight load in flight: a granule asked for behind 32 KB of weights would
+// only arrive after them -- publishes the rows, watches (not in the layer launch), and asks for the whole hidden row ONCE in straight-line
+// code; right behind those 32 granule loads the block meets at an LDS-only barrier,
 // wave 0 asks for its first pair and the others for their SECOND: all of it is queued behind the sweep -- it cannot delay it -- and
 // streams while the row makes its round trip and is normalised.  Wave 0 reads the tags behind a counted wait (hipcc counts loads exactly
 // in straight-line code only; the pair stays in flight); a tag that is not there yet (rare) sends it into the draining retry loop.
-// Every wave passes the same three barriers on every path, the give-up included.
+// Every wave passes the same three barriers (four in a block that publishes first) on every path, the give-up included.
 // Issue points measured at Qwen3-8B shapes, ctx 2 k:
 //   * (EXPERIMENTS C-2) first pair of waves 1..7 HERE, once their O rows are consumed: 343.4 tok/s against the parent's 337.7; right
 //     behind the O rows' own loads -- 57 MB more parked in front of the split merge and the attention vector's sweep -- 338.1: no gain;
@@ -521,11 +527,25 @@ __device__ __forceinline__ void down_qkv_phase(const AttnStepArgs& a, unsigned c
 //     0's first and the others' second pair behind the hidden row's sweep as well: 347.5; the first pair of waves 1..7 moved up behind
 //     the ATTENTION VECTOR's sweep on top of that: 343.9, slower than the parent -- that sweep feeds the O rows every block waits for;
 //   * wave 0's second pair asked for as soon as the row is in LDS instead of behind the norm: 342.7 against 346.4.
-template <bool TRACE, bool DN = false>
+// Hop three of the layer launch (DN; EXPERIMENTS C-7, mean tok/s of four runs; parent 367.79 in set 1, 366.71 in set 2).  An O block (PUB)
+// publishes FIRST, as down_qkv_phase does at hops four and five: wave 0 stores the block's O rows behind the barrier that follows their
+// parking, the block meets at a second LDS-only barrier, and only then do waves 1..7 ask for their first pair -- stored behind the 112 KB
+// they used to ask for ahead of the first barrier, the granules became visible late, and every block's sweep waits for the slowest block's.
+// And wave 0 does not watch: its optimistic pass goes out right behind the publish, a miss goes to the draining retry loop (hop five's form).
+//   * P, publish first, with the watch: 373.87 (set 1); P', without it, as here: 375.84 (set 1), 374.90 (set 2);
+//   * N, the hidden row's norm reading its weight from LDS (parked there by the launch's first round of loads), one arm per wave class from
+//     a pair's issue to its reduce -- no s_waitcnt vmcnt between the row's LDS write and the first reduce, which then waits for vmcnt(31)
+//     .. (16) with the second pair in flight: 364.72 against the parent's 367.79 (set 1), 363.04 against 366.71 with the weights parked
+//     behind the block's own chunk (set 2) -- SLOWER; with wave 0's second pair asked for as soon as the row is in LDS: 364.54 (set 1);
+//   * N5, the same norm in hop five: 368.55 (set 1), 366.43 (set 2, parked late) -- inside the parent's spread; P' + N5: 375.00 (set 2),
+//     P' + N + N5: 373.64, with the early second pair 372.66 -- neither N nor N5 is in the tree.
+// A consumer block (PUB false) publishes nothing here and keeps its early first pair.
+template <bool TRACE, bool DN = false, bool PUB = false>
 __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, float* red, int* sm_gu, const uint16_t* sm_pub, unsigned tag,
                                              int lane, int wave, int pub_row0, int pub_rows, unsigned long long* tr,
                                              unsigned char* sm_dn = nullptr) {
     typedef Act16<false> A;
+    constexpr bool PFIRST = DN && PUB;   // the layer launch's O blocks: the O rows leave before the block asks for anything
     const int pair0 = ((int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x) * kGuBlockPairs;
     uint16_t* park = DN ? reinterpret_cast<uint16_t*>(sm_dn + kDnParkOff) : nullptr;   // DN: the block's values by ticket
     constexpr int PV = kGuNV * 64 / 256;              // vectors of the row per thread of the first four waves
@@ -536,19 +556,31 @@ __device__ __forceinline__ void gateup_phase(const AttnStepArgs& a, u32x4* xs, f
     int tA = 0, tB;
     // (the two tickets a wave draws ahead of the norm are below kGuBlockPairs, no check: all sixteen are drawn before the barrier in front
     //  of it, and the tickets that are compared with kGuBlockPairs are drawn behind it)
-    if (wave != 0) {
+    if (!PFIRST && wave != 0) {
         tA = gateup_claim(sm_gu, lane);
         gateup_issue(a, wA, pair0 + tA, lane);
     }
     lds_barrier();   // every wave is done with the attention vector in `xs` and has parked its O rows
+    if constexpr (PFIRST) {
+        if (wave == 0 && lane < pub_rows / 2) st_granule_u32(a.hg + pub_row0 / 2 + lane, tag, reinterpret_cast<const unsigned*>(sm_pub)[lane]);
+        lds_barrier();   // the block's granules are in the CU's queue: what the block asks for now is behind them
+        if (wave != 0) {
+            tA = gateup_claim(sm_gu, lane);
+            gateup_issue(a, wA, pair0 + tA, lane);
+        }
+    }
     if (wave == 0) {
-        if (lane < pub_rows / 2) st_granule_u32(a.hg + pub_row0 / 2 + lane, tag, reinterpret_cast<const unsigned*>(sm_pub)[lane]);
+        if constexpr (!PFIRST) {
+            if (lane < pub_rows / 2) st_granule_u32(a.hg + pub_row0 / 2 + lane, tag, reinterpret_cast<const unsigned*>(sm_pub)[lane]);
+        }
         // (written out, not sweep_granules: the first pass is straight-line, its tags read behind a counted wait)
         constexpr int GPL = kGuHidden / 2 / 64;       // granules per lane
-        for (unsigned spins = 0; spins < kGranuleSpinLimit; ++spins) {   // politely: one granule of every eighth producer, a sleep between looks
-            const unsigned long long g = ld_granule(a.hg + (size_t)lane * GPL + (GPL - 1));
-            if (__all((unsigned)(g >> 32) == tag)) break;
-            __builtin_amdgcn_s_sleep(4);
+        if constexpr (!DN) {   // (the layer launch does not watch: see above)
+            for (unsigned spins = 0; spins < kGranuleSpinLimit; ++spins) {   // politely: one granule of every eighth producer, a sleep between looks
+                const unsigned long long g = ld_granule(a.hg + (size_t)lane * GPL + (GPL - 1));
+                if (__all((unsigned)(g >> 32) == tag)) break;
+                __builtin_amdgcn_s_sleep(4);
+            }
         }
         unsigned long long g[GPL];
 #pragma unroll
@@ -1021,7 +1053,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
             uint16_t* sm_pub = reinterpret_cast<uint16_t*>(sm_l);   // (the split merge is done with sm_m / sm_l: a block barrier ago)
             if (rows == 2) oproj_phase<NV, 2, true>(a, sm_x, tag, lane, wave, o_row0, otr, sm_pub, pub_row0);
             else oproj_phase<NV, 3, true>(a, sm_x, tag, lane, wave, o_row0, otr, sm_pub, pub_row0);
-            gateup_phase<TRACE, DN>(a, sm_x, sm_m, sm_gu, sm_pub, tag, lane, wave, pub_row0, pub_rows, otr, smem);
+            gateup_phase<TRACE, DN, true>(a, sm_x, sm_m, sm_gu, sm_pub, tag, lane, wave, pub_row0, pub_rows, otr, smem);
             return;
         } else
         if constexpr (QO) {
@@ -1054,7 +1086,7 @@ __global__ __launch_bounds__(kBlock, 1) void attn_step_kernel(const AttnStepArgs
     if constexpr (GU) {
         // the consumer blocks take their share of the pairs once their heads are merged and published (block-uniform: split < G here)
         lds_barrier();
-        gateup_phase<TRACE, DN>(a, sm_x, sm_m, sm_gu, nullptr, tag, lane, wave, 0, 0, TRACE ? tr : nullptr, smem);
+        gateup_phase<TRACE, DN, false>(a, sm_x, sm_m, sm_gu, nullptr, tag, lane, wave, 0, 0, TRACE ? tr : nullptr, smem);
     }
 }
 
